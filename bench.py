@@ -1,6 +1,6 @@
 """Benchmark of the GLIGEN denoising hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5]
+    python bench.py --gpus N --steps K --warmup W [--config C2|C3|C4|C5] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` with N > 1 and no WORLD_SIZE in the environment spawns its N ranks itself (re-executes under
@@ -18,7 +18,14 @@ Inputs (x_T, CLIP-shaped context, grounding features, seeded random weights of t
 resident in HBM before the timed region. N > 1: every rank runs the same batch size on its own GPU (weak scaling, no
 data-path collective); value = all images / max-over-ranks time.
 
-Beside the contract's keys the line carries what makes a number comparable across boxes and rounds:
+A plain run does only what the headline needs: set-up, warm-up, the timed steps, --dump-outputs if given, and a line with the
+contract's keys (metric, value, unit, higher_is_better, dtype, ms_per_step, ...). --dump-outputs DIR writes the images the
+last timed step returned (what a caller of the timed path receives) as DIR/images.npy, float32 [B, 512, 512, 3] in 0..255
+(DIR/images_rank<r>.npy per rank when N > 1); the inputs are seeded, so two builds can be compared output for output.
+
+--full adds everything else the benchmark measures, outside the timed region (the --no-* switches below thin it out):
+    unet_step_ms, value_one_lane, set_cond_ms, vae_decode_ms, launches_per_unet_eval, memory, gpu_clocks, roofline, cpu_baseline
+and what makes a number comparable across boxes and rounds:
     box_calibration   float4-copy GB/s, global->LDS DMA TB/s, sustained bf16 MFMA TFLOP/s of THIS box (gl_box_calibrate)
     ff_rows_ab        one-lane UNet evaluation ms with the row-local kernels (feed-forward chains and, since round 6, the projection +
                       LayerNorm + q,k,v^T launch) off / forced on / chosen by the engine's on-device timing (the default), and the timed
@@ -263,6 +270,21 @@ def spawn_ranks(n, argv):
     return subprocess.call(cmd, env=env)
 
 
+DUMP_BYTES = 64 * 2 ** 20   # all ranks' --dump-outputs files together
+
+
+def dump_outputs(folder, images, rank, world):
+    """--dump-outputs: the uint8 images [B, H, W, 3] of the last timed step as float32 DIR/images.npy (images_rank<r>.npy per rank
+    when N > 1). A batch beyond this rank's share of DUMP_BYTES is cut to a fixed, seeded choice of whole images."""
+    a = images.detach().cpu().numpy().astype(np.float32)
+    per_image = a[0].nbytes if len(a) else 1
+    keep = max(1, DUMP_BYTES // world // per_image)
+    if len(a) > keep:
+        a = a[np.sort(np.random.default_rng(0).choice(len(a), keep, replace=False))]
+    os.makedirs(folder, exist_ok=True)
+    np.save(os.path.join(folder, "images.npy" if world == 1 else f"images_rank{rank}.npy"), a)
+
+
 def stub_lanes(L, B):
     """--stub: the measurement protocol without the engine (CPU test of the N-rank launch path, tests/test_dist_cpu.py):
     a 'pass' sleeps 20 ms and returns a deterministic uint8 tensor of the real shape."""
@@ -283,12 +305,29 @@ def stub_main(args, cfg, gdist, rank, world, dist_world, dist_backend):
     gdist.barrier()
     elapsed = gdist.max_over_ranks(time.perf_counter() - t0)
     assert outs[-1].shape == (B, 512, 512, 3)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs[-1], rank, world)
     if rank == 0:
         print(json.dumps({"metric": "stub", "value": B * world * args.steps / elapsed, "unit": "images/s", "n_gpus": world, "steps": args.steps,
                           "warmup": args.warmup, "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak",
                           "vs_baseline": None, "dtype": "none", "data": "stub", "config": {"workload": "stub: " + cfg["desc"]},
                           "collective_world_size": dist_world, "collective_backend": dist_backend}), flush=True)
     gdist.shutdown()
+
+
+def headline(args, cfg, alpha_type, B, L, world, elapsed, dist_world, dist_backend):
+    """The keys of every result line: the metric of the timed steps and the configuration it was measured on."""
+    return {
+        "metric": "512x512 images/sec @ 50 PLMS steps, box+text (CFG 7.5), UNet step ms",
+        "value": B * world * args.steps / elapsed, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "bf16", "data": "synthetic",
+        "config": {"workload": cfg["desc"] + ", 512x512, 50 PLMS steps, CFG 7.5, bf16 storage / fp32 accumulate", "baseline_config": args.config,
+                   "images_per_gpu_per_step": B, "plms_steps": args.plms_steps, "unet_evals_per_image": 2 * (args.plms_steps + 1),
+                   "grounding_tokens": cfg["ng"], "alpha_type": alpha_type or [1, 0, 0], "hipgraph": not args.no_graph, "batches_in_flight": L,
+                   "weights": "seeded random init of the SD-1.4 GLIGEN architecture (966 tensors, 1.07 B params)"},
+        "collective_world_size": dist_world, "collective_backend": dist_backend,   # the RCCL world the barrier / max-over-ranks ran in
+    }
 
 
 def main():
@@ -312,6 +351,11 @@ def main():
     ap.add_argument("--alpha-type", default=None,
                     help="gate schedule 'on,decay,off' (fractions of the steps), e.g. 0.3,0,0.7 as in the reference's demo prompts; default: "
                          "None = fusers on at every step, the configuration the metric is quoted on (and the one with the most work)")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline: the row-local A/B, the one-lane reading, per-prompt set_cond, VAE decode, per-kernel profile "
+                         "and roofline, memory, clocks, box calibration, a training iteration and the CPU baseline (a plain run does none)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the images of the last timed step to DIR/images.npy (float32, 0..255)")
     ap.add_argument("--stub", action="store_true", help=argparse.SUPPRESS)   # protocol-only run without a GPU (CPU test of the launch path)
     args = ap.parse_args()
     alpha_type = [float(v) for v in args.alpha_type.split(",")] if args.alpha_type else None
@@ -385,7 +429,7 @@ def main():
     # on-device timing (the default, restored last; a policy change drops the captured graphs, so every lane re-captures below)
     eng0 = lanes[0][0].engine
     ff_ab = None
-    if not args.no_ff_ab:
+    if args.full and not args.no_ff_ab:
         ff_ab = {}
         for name, mode in (("off", 0), ("forced", 1)):
             eng0.set_ff_rows_policy(mode)
@@ -397,20 +441,29 @@ def main():
             one_pass(lane)
             torch.cuda.synchronize()
     # UNet evaluation time with the GPU to itself: one more untimed pass on lane 0 alone
-    one_pass(0)
-    torch.cuda.synchronize()
-    unet_ms, first_ms, n_evals = eng0.sampler_timing()
+    if args.full:
+        one_pass(0)
+        torch.cuda.synchronize()
+        unet_ms, first_ms, n_evals = eng0.sampler_timing()
     if ff_ab is not None:
         ff_ab["unet_step_ms_timed_choice"] = round(unet_ms, 4)
         ff_ab["timed_table"] = eng0.ff_rows_policy_report()
 
-    clocks = ClockSampler(local_rank)
+    clocks = ClockSampler(local_rank) if args.full else None
     gdist.barrier(); torch.cuda.synchronize()
-    clocks.start()
+    if clocks:
+        clocks.start()
     t0 = time.perf_counter()
     outs = [one_pass(i % L) for i in range(args.steps)]
     torch.cuda.synchronize(); gdist.barrier()
     elapsed = gdist.max_over_ranks(time.perf_counter() - t0, dev)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, outs[-1], rank, world)
+    if not args.full:
+        if rank == 0:
+            print(json.dumps(headline(args, cfg, alpha_type, B, L, world, elapsed, dist_world, dist_backend)), flush=True)
+        gdist.shutdown()
+        return
     clk = clocks.summary()
     # the strict BASELINE C2 reading -- one batch at a time on one context -- over the same number of steps, outside the timed
     # region above (what gligen_inference.run() delivers below 8 samples per GPU)
@@ -517,14 +570,7 @@ def main():
                                     {"GB/s": round(p["bytes"] / (p["ms"] * 1e-3) / 1e9, 1), "frac_of_6.3TB/s": round(p["bytes"] / (p["ms"] * 1e-3) / 6.3e12, 3)})}
                                 for p in prof[:14]]}
         line = {
-            "metric": "512x512 images/sec @ 50 PLMS steps, box+text (CFG 7.5), UNet step ms",
-            "value": value, "unit": "images/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": elapsed / args.steps * 1e3, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "bf16", "data": "synthetic",
-            "config": {"workload": cfg["desc"] + ", 512x512, 50 PLMS steps, CFG 7.5, bf16 storage / fp32 accumulate", "baseline_config": args.config,
-                       "images_per_gpu_per_step": B, "plms_steps": args.plms_steps, "unet_evals_per_image": 2 * (args.plms_steps + 1),
-                       "grounding_tokens": cfg["ng"], "alpha_type": alpha_type or [1, 0, 0], "hipgraph": not args.no_graph, "batches_in_flight": L,
-                       "weights": "seeded random init of the SD-1.4 GLIGEN architecture (966 tensors, 1.07 B params)"},
+            **headline(args, cfg, alpha_type, B, L, world, elapsed, dist_world, dist_backend),
             "unet_step_ms": unet_ms, "unet_step_desc": f"one [cond ; uncond] UNet evaluation at batch {2 * B} (hipGraph replay, HIP events on the engine stream, "
                                                        f"measured in an untimed pass with one batch in flight)",
             "vae_decode_ms": dec_ms,
@@ -537,7 +583,6 @@ def main():
             "ff_rows_ab": ff_ab,
             "train_step": train,
             "value_one_lane": (B * world * args.steps / elapsed_one) if elapsed_one else value,
-            "collective_world_size": dist_world, "collective_backend": dist_backend,   # the RCCL world the barrier / max-over-ranks ran in
             "gpu_clocks": clk,
             "roofline": roofline,
         }

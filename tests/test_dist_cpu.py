@@ -105,6 +105,25 @@ def test_bench_spawns_its_own_ranks():
     assert bad.returncode != 0 and "must agree" in (bad.stderr + bad.stdout)
 
 
+def test_bench_dump_outputs(tmp_path):
+    """`bench.py --dump-outputs DIR` writes the last timed step's images as float32 .npy files (one per rank when N > 1), and --steps
+    is the number of timed steps the line reports. --stub as above: the protocol and the writer are the real ones."""
+    import json
+    import numpy as np
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    for gpus, names in ((1, ["images.npy"]), (2, ["images_rank0.npy", "images_rank1.npy"])):
+        out = tmp_path / f"g{gpus}"
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(gpus), "--steps", "2", "--warmup", "0", "--stub",
+                            "--batch", "3", "--dump-outputs", str(out)], env=env, capture_output=True, text=True, timeout=300, cwd=ROOT)
+        assert r.returncode == 0, r.stderr[-3000:]
+        d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
+        assert d["steps"] == 2 and d["ms_per_step"] > 0
+        assert sorted(p.name for p in out.iterdir()) == names
+        for n in names:
+            a = np.load(out / n)
+            assert a.dtype == np.float32 and a.shape == (3, 512, 512, 3)
+
+
 # ---- the one exchange of the training path (SURVEY.md section 8 f4): the trainable set's gradients, gligen_amd.dist.GradBuckets
 GRAD_WORKER = textwrap.dedent("""
     import os, sys, json

@@ -2,7 +2,7 @@
 # Usage: gpurun -- 'bash tools/gpu_batch_sweep.sh'   -> gpurun_out/$GL_OUT/batch_sweep.txt
 export TMPDIR=/tmp
 O=gpurun_out/${GL_OUT:-r6_b8}; mkdir -p $O
-run() { name=$1; shift; ( timeout 700 python bench.py "$@" --no-cpu-baseline --no-train-step --no-ff-ab 2> $O/$name.err ) > $O/$name.json; python -c "import sys,json; d=json.loads(open('$O/$name.json').read().strip().splitlines()[-1]); print('$name value %.3f one_lane %.3f unet_step_ms %.3f ms_per_step %.1f' % (d['value'], d['value_one_lane'], d['unet_step_ms'], d['ms_per_step']))" | tee -a $O/batch_sweep.txt; }
+run() { name=$1; shift; ( timeout 700 python bench.py --full "$@" --no-cpu-baseline --no-train-step --no-ff-ab 2> $O/$name.err ) > $O/$name.json; python -c "import sys,json; d=json.loads(open('$O/$name.json').read().strip().splitlines()[-1]); print('$name value %.3f one_lane %.3f unet_step_ms %.3f ms_per_step %.1f' % (d['value'], d['value_one_lane'], d['unet_step_ms'], d['ms_per_step']))" | tee -a $O/batch_sweep.txt; }
 : > $O/batch_sweep.txt
 run b4_l2 --steps 4
 run b8_l1 --batch 8 --lanes 1 --steps 2
