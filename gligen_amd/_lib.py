@@ -61,6 +61,11 @@ class TrainUNetIn(C.Structure):   # = gl_train_unet_in
                [("fuser_scale", C.c_float)] + [(n, C.c_void_p) for n in ("text_masks", "image_masks", "image_embeddings")] + [("checkpoint", C.c_int), ("use_weight_cache", C.c_int)]
 
 
+class TrainSpatialIn(C.Structure):   # = gl_train_spatial_in
+    _fields_ = [("map", C.c_void_p)] + [(n, C.c_int) for n in ("map_channels", "map_h", "map_w")] + [("mask", C.c_void_p), ("extra", C.c_void_p)] + \
+               [(n, C.c_int) for n in ("extra_in_channels", "extra_h", "extra_w", "ds_resize", "ds_mode", "ds_n_in", "ds_mid")]
+
+
 class BoxCalibration(C.Structure):   # = gl_box_calibration
     _fields_ = [("hbm_copy_gbs", C.c_float), ("lds_dma_tbs", C.c_float), ("mfma_bf16_tflops", C.c_float)]
 
@@ -118,6 +123,8 @@ SYMBOLS = {
     "gl_op_resblock_train": (_I, [_P, _P, C.POINTER(_P), _P, _P, _P, _P, _P, _P, _P]),
     "gl_op_resample_train": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gl_unet_train_step": (_I, [_P, C.POINTER(UNetConfig), C.POINTER(TrainUNetIn), _I, C.POINTER(C.c_char_p), C.POINTER(_P), C.POINTER(_P), _P, _P, _P]),
+    "gl_unet_train_step_spatial": (_I, [_P, C.POINTER(UNetConfig), C.POINTER(TrainUNetIn), C.POINTER(TrainSpatialIn), _I, C.POINTER(C.c_char_p),
+                                        C.POINTER(_P), C.POINTER(_P), _P, _P, _P]),
     "gl_train_wait_grads": (_I, [_P, _I, _P]),
     "gl_train_weight_cache": (_I, [_P, _I, C.POINTER(C.c_size_t)]),
     "gl_op_adamw_step": (_I, [_P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _I, _P]),

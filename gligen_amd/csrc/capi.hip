@@ -693,6 +693,43 @@ int gl_unet_train_step(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_un
     GL_API_END
 }
 
+int gl_unet_train_step_spatial(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, const gl_train_spatial_in* sp, int n_params,
+                               const char* const* names, const float* const* params, float* const* grads, float* eps_out, float* loss, gl_stream s) {
+    NEED(ctx);
+    if (!cfg || !in || !sp || !names || !params || !grads || !loss || n_params <= 0) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial: null pointer");
+    if (cfg->inpaint_mode)
+        return gl::set_error(GL_ERR_UNSUPPORTED, "gl_unet_train_step_spatial: training an inpainting model (9-channel first conv) is not built");
+    if (cfg->grounding_kind != 3 || cfg->fuser_kind != 0)
+        return gl::set_error(GL_ERR_UNSUPPORTED, "gl_unet_train_step_spatial: built for a spatial-map tokenizer (grounding_kind 3) with gatedSA fusers");
+    if (cfg->tok_resize < 32 || cfg->tok_resize % 32 || cfg->extra_channels < 0)
+        return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial: tok_resize must be a positive multiple of 32");
+    if (in->boxes || in->masks || in->positive_embeddings || in->text_masks || in->image_masks || in->image_embeddings)
+        return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial: the box / embedding inputs of gl_train_unet_in are NULL for a spatial-map model");
+    if (!in->x || !in->timesteps || !in->context || !in->target || !sp->map || !sp->mask || ((cfg->extra_channels > 0) != (sp->extra != nullptr)))
+        return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial: null input (grounding_extra_input is given iff extra_channels > 0)");
+    const int Ng = (cfg->tok_resize / 32) * (cfg->tok_resize / 32);
+    if (in->Ng != Ng) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial: Ng = %d, the tokenizer makes (tok_resize / 32)^2 = %d tokens", in->Ng, Ng);
+    if (cfg->gr_out_dim != cfg->context_dim)
+        return gl::set_error(GL_ERR_UNSUPPORTED, "gl_unet_train_step_spatial: grounding out dim and context_dim are expected to be equal (768 in every shipped config)");
+    GL_API_BEGIN
+    Engine& eng = *ctx->eng;
+    eng.arena().reset();
+    gl::TrainUNetCfg c{};
+    c.in_channels = cfg->in_channels; c.out_channels = cfg->out_channels; c.model_channels = cfg->model_channels; c.num_res_blocks = cfg->num_res_blocks;
+    c.num_heads = cfg->num_heads; c.context_dim = cfg->context_dim; c.gr_dim = 768; c.grounding_kind = 3; c.n_mult = cfg->n_mult; c.n_attn = cfg->n_attn;
+    for (int i = 0; i < 8; ++i) { c.channel_mult[i] = cfg->channel_mult[i]; c.attention_resolutions[i] = cfg->attention_resolutions[i]; }
+    c.extra_channels = cfg->extra_channels; c.tok_resize = cfg->tok_resize; c.tok_in_dim = cfg->tok_in_dim;
+    gl::TrainUNetIn u{in->B, in->H, in->W, in->ctx_T, Ng, Ng, in->x, in->timesteps, in->context, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
+                      in->target, in->fuser_scale, in->checkpoint};
+    gl::TrainSpatialIn spi{sp->map, sp->map_channels, sp->map_h, sp->map_w, sp->mask, sp->extra, sp->extra_in_channels, sp->extra_h, sp->extra_w,
+                           sp->ds_resize, sp->ds_mode, sp->ds_n_in, sp->ds_mid};
+    int rc = gl::unet_train_step(eng.arena(), eng.splitk_ws(), eng.splitk_ws_bytes(), c, u, n_params, names, params, grads, k_train_block_names, eps_out, loss, S(s),
+                                 eng.train_events(), Engine::kTrainEvents, in->use_weight_cache ? eng.train_cache : nullptr, &spi);
+    if (rc != GL_OK) throw GlError(rc, gl::last_error());
+    eng.train_events_recorded = true;
+    GL_API_END
+}
+
 int gl_train_weight_cache(gl_ctx* ctx, int enable, size_t* bytes) {
     NEED(ctx);
     GL_API_BEGIN

@@ -57,8 +57,21 @@ int resample_train_step(Arena& ar, float* ws, size_t ws_bytes, int mode, int B, 
 // ---- the whole training iteration for a UNetModel with the text grounding tokenizer and gatedSA fusers (openaimodel.py:237-464)
 struct TrainUNetCfg {
     int in_channels, out_channels, model_channels, num_res_blocks, num_heads, context_dim, gr_dim;
-    int grounding_kind;                 // 0 text, 1 text+image (two MLPs, tokens concatenated), 2 keypoint (points in `boxes`, 17 tokens per person)
+    int grounding_kind;                 // 0 text, 1 text+image (two MLPs, tokens concatenated), 2 keypoint (points in `boxes`, 17 tokens per person),
+                                        // 3 spatial map (ConvNeXt-tiny tokenizer; TrainSpatialIn)
     int n_mult, channel_mult[8], n_attn, attention_resolutions[8];
+    int extra_channels;                 // grounding_kind 3: GroundingDownsampler output channels in front of the first conv (0: none)
+    int tok_resize, tok_in_dim;         // grounding_kind 3: PositionNet resize_input; channels of a semantic map (sem: in_conv first), else 0
+};
+// The spatial-map inputs of a training step (grounding_kind 3): the tokenizer's map and mask, grounding_extra_input and the
+// GroundingDownsampler's constants (canny / depth / normal / sem / hed_grounding_downsampler.py)
+struct TrainSpatialIn {
+    const float* map;                   // [B][Ct][Ht][Wt]
+    int Ct, Ht, Wt;
+    const float* mask;                  // [B]
+    const float* extra;                 // [B][Ce][He][We]; null iff extra_channels == 0
+    int Ce, He, We;
+    int ds_resize, ds_mode, ds_n_in, ds_mid;   // resize, 0 bicubic / 1 nearest, channels read, channels of the first conv (0: no layers)
 };
 struct TrainUNetIn {
     int B, H, W, ctx_T, Ng;             // Ng: grounding tokens per sample = Ng_boxes (text) or 2 * Ng_boxes (text+image)
@@ -87,10 +100,12 @@ void train_cache_destroy(TrainWeightCache* c);      // frees every cached copy
 size_t train_cache_bytes(const TrainWeightCache* c);
 int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& cfg, const TrainUNetIn& in, int n_params, const char* const* names,
                     const float* const* params, float* const* grads, const char* const* block_names, float* eps_out, float* loss, hipStream_t s,
-                    hipEvent_t* grad_events = nullptr, int n_grad_events = 0, TrainWeightCache* cache = nullptr);
+                    hipEvent_t* grad_events = nullptr, int n_grad_events = 0, TrainWeightCache* cache = nullptr, const TrainSpatialIn* spatial = nullptr);
 // grad_events (optional): event j is recorded on `s` when the backward of the j-th SpatialTransformer (module order) has written its
 // fuser gradients -- the backward runs from the last block to the first, so high j come early --, event [number of SpatialTransformers]
-// when position_net's (the last gradients of the step) are written
+// when position_net's, downsample_net's and the first conv's (the last gradients of the step) are written.
+// spatial: required for grounding_kind 3; the trainable set then also admits downsample_net.* and, with extra_channels > 0,
+// input_blocks.0.0.weight (trainer.py:189-194, 233)
 
 // One AdamW update of a flat fp32 parameter range, in place (torch.optim.AdamW semantics: trainer.py:245, :384 opt.step()); step = 1, 2, ...
 int adamw_step(float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps, double wd, int step, hipStream_t s);

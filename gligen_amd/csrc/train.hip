@@ -162,16 +162,16 @@ __global__ void __launch_bounds__(1024) colsum_kernel(const float* __restrict__ 
     }
 }
 
-// LayerNorm over C per row (eps 1e-5, nn.LayerNorm): one wave per row
+// LayerNorm over C per row (nn.LayerNorm: eps 1e-5 in the fusers, 1e-6 in ConvNeXt, convnext.py:29, 75, 80): one wave per row
 __global__ void ln_fwd_kernel(const float* __restrict__ x, const float* __restrict__ g, const float* __restrict__ b, int R, int Cc,
-                              float* __restrict__ y, float* __restrict__ xhat, float* __restrict__ rstd_out) {
+                              float* __restrict__ y, float* __restrict__ xhat, float* __restrict__ rstd_out, float eps) {
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= R) return;
     const float* xr = x + (size_t)row * Cc;
     float s = 0.f, ss = 0.f;
     for (int c = lane; c < Cc; c += 64) { const float v = xr[c]; s += v; ss += v * v; }
     s = wave_sum(s); ss = wave_sum(ss);
-    const float mean = s / Cc, var = fmaxf(ss / Cc - mean * mean, 0.f), rstd = rsqrtf(var + 1e-5f);
+    const float mean = s / Cc, var = fmaxf(ss / Cc - mean * mean, 0.f), rstd = rsqrtf(var + eps);
     for (int c = lane; c < Cc; c += 64) {
         const float h = (xr[c] - mean) * rstd;
         xhat[(size_t)row * Cc + c] = h;
@@ -598,6 +598,10 @@ __global__ void __launch_bounds__(64) attn_mfma_bwd_kv_kernel(APrep Q, APrep K, 
         }
 }
 
+// erf GELU (F.gelu default): gelu(g) = g Phi(g), gelu'(g) = Phi(g) + g phi(g)
+__device__ __forceinline__ float gelu_cdf(float g) { return 0.5f * (1.f + erff(g * 0.70710678118654752440f)); }
+__device__ __forceinline__ float gelu_pdf(float g) { return 0.3989422804014327f * __expf(-0.5f * g * g); }
+
 // GEGLU (attention.py:37-44): h = val * gelu(gate), u = [val | gate] of width 2 I (erf GELU, F.gelu default)
 __global__ void geglu_fwd_kernel(const float* __restrict__ u, int R, int I, float* __restrict__ h) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -611,8 +615,8 @@ __global__ void geglu_bwd_kernel(const float* __restrict__ dh, const float* __re
     if (idx >= (size_t)R * I) return;
     const size_t r = idx / I, c = idx % I;
     const float val = u[r * 2 * I + c], g = u[r * 2 * I + I + c], d = dh[idx];
-    const float Phi = 0.5f * (1.f + erff(g * 0.70710678118654752440f));
-    const float phi = 0.3989422804014327f * __expf(-0.5f * g * g);
+    const float Phi = gelu_cdf(g);
+    const float phi = gelu_pdf(g);
     du[r * 2 * I + c] = d * g * Phi;
     du[r * 2 * I + I + c] = d * val * (Phi + g * phi);
 }
@@ -961,9 +965,9 @@ struct Ctx {
         ar.release(mk);
     }
     struct LN { float* y; float* xhat; float* rstd; };
-    LN ln_fwd(const float* x, int R, int Cc, const float* g, const float* b) const {
+    LN ln_fwd(const float* x, int R, int Cc, const float* g, const float* b, float eps = 1e-5f) const {
         LN r{f32((size_t)R * Cc), f32((size_t)R * Cc), f32(R)};
-        hipLaunchKernelGGL(ln_fwd_kernel, dim3(cdiv(R, 4)), dim3(256), 0, s, x, g, b, R, Cc, r.y, r.xhat, r.rstd);
+        hipLaunchKernelGGL(ln_fwd_kernel, dim3(cdiv(R, 4)), dim3(256), 0, s, x, g, b, R, Cc, r.y, r.xhat, r.rstd, eps);
         return r;
     }
     void ln_bwd(const float* dy, const LN& f, const float* g, int R, int Cc, float* dx, bool accumulate, float* dgamma, float* dbeta) const {
@@ -1638,19 +1642,407 @@ struct Names {
     }
 };
 
+// ---- spatial-map models (grounding_kind 3: canny / depth / normal / hed / sem_grounding_net.py + *_grounding_downsampler.py): the
+// ConvNeXt-tiny tokenizer (convnext.py:36-50, 71-81, 108-112), the GroundingDownsampler and the 4 + k channel first conv, forward in
+// fp32 with every activation kept, and their backward. Matrix products go through the three-pass helpers of Ctx; the kernels below are
+// the rest. Every reduction is a fixed-order sum (colsum_kernel, the GEMMs, dwconv7_wgrad_kernel): no float atomics.
+// y = x + gamma h (gamma null: 1)   (Block.forward, convnext.py:47-50: layer scale, then the residual)
+__global__ void layer_scale_residual_kernel(const float* __restrict__ x, const float* __restrict__ h, const float* __restrict__ gamma, int Cc, size_t n,
+                                            float* __restrict__ y) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) y[i] = x[i] + (gamma ? gamma[i % Cc] : 1.f) * h[i];
+}
+// out = g gamma (per column)
+__global__ void scale_cols_kernel(const float* __restrict__ g, const float* __restrict__ gamma, int Cc, size_t n, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = g[i] * gamma[i % Cc];
+}
+__global__ void gelu_fwd_kernel(const float* __restrict__ u, size_t n, float* __restrict__ a) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) a[i] = u[i] * gelu_cdf(u[i]);
+}
+__global__ void gelu_bwd_kernel(const float* __restrict__ da, const float* __restrict__ u, size_t n, float* __restrict__ du) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const float g = u[i];
+    du[i] = da[i] * (gelu_cdf(g) + g * gelu_pdf(g));
+}
+// depthwise 7 x 7 conv, pad 3, over pixel rows [B][H][W][C] (convnext.py:38): y = bias + sum_taps w x. flip = 1: the taps rotated by
+// 180 degrees -- the data gradient of the same conv (bias null); accumulate: y +=
+__global__ void dwconv7_f32_kernel(const float* __restrict__ x, const float* __restrict__ w, const float* __restrict__ bias, int H, int W, int Cc, size_t n,
+                                   int flip, int accumulate, float* __restrict__ y) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % Cc), xw = (int)((i / Cc) % W), yh = (int)((i / ((size_t)Cc * W)) % H);
+    const size_t b = i / ((size_t)Cc * W * H);
+    const float* wc = w + (size_t)c * 49;
+    float acc = bias ? bias[c] : 0.f;
+    for (int ky = 0; ky < 7; ++ky) {
+        const int yy = yh + ky - 3;
+        if (yy < 0 || yy >= H) continue;
+        for (int kx = 0; kx < 7; ++kx) {
+            const int xx = xw + kx - 3;
+            if (xx < 0 || xx >= W) continue;
+            const int t = ky * 7 + kx;
+            acc = fmaf(x[((b * H + yy) * W + xx) * Cc + c], wc[flip ? 48 - t : t], acc);
+        }
+    }
+    y[i] = accumulate ? y[i] + acc : acc;
+}
+// depthwise weight gradient dw[c][tap] = sum over (b, y, x) of g[b][y][x][c] x[b][y + ky - 3][x + kx - 3][c]: grid (C / 64, 49), 64 channels
+// x 16 pixel lanes; each lane sums pixels ry, ry + 16, .. in order, the 16 partials are added in a fixed order
+__global__ void __launch_bounds__(1024) dwconv7_wgrad_kernel(const float* __restrict__ g, const float* __restrict__ x, int B, int H, int W, int Cc,
+                                                             float* __restrict__ dw) {
+    __shared__ float part[16][64];
+    const int tx = threadIdx.x & 63, ry = threadIdx.x >> 6, c = blockIdx.x * 64 + tx, tap = blockIdx.y, ky = tap / 7, kx = tap % 7;
+    const int P = B * H * W;
+    float s = 0.f;
+    if (c < Cc)
+        for (int p = ry; p < P; p += 16) {
+            const int xw = p % W, yh = (p / W) % H, b = p / (W * H);
+            const int yy = yh + ky - 3, xx = xw + kx - 3;
+            if (yy < 0 || yy >= H || xx < 0 || xx >= W) continue;
+            s = fmaf(g[(size_t)p * Cc + c], x[(((size_t)b * H + yy) * W + xx) * Cc + c], s);
+        }
+    part[ry][tx] = s;
+    __syncthreads();
+    if (ry == 0 && c < Cc) {
+        float t = 0.f;
+#pragma unroll
+        for (int i = 0; i < 16; ++i) t += part[i][tx];
+        dw[(size_t)c * 49 + tap] = t;
+    }
+}
+// im2col of a k x k conv (stride, pad) over an image addressed by strides (NCHW or pixel rows): out [B Ho Wo][Kp], column c k^2 + ky k + kx
+// (the OIHW order of the weight); zero for taps outside the image and for columns >= Cin k^2
+__global__ void im2col_f32_kernel(const float* __restrict__ x, int Cin, int H, int W, size_t sb, size_t sc, size_t sy, size_t sx, int k, int stride, int pad,
+                                  int Ho, int Wo, int Kp, size_t n, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int col = (int)(i % Kp);
+    const size_t m = i / Kp;
+    const int ox = (int)(m % Wo), oy = (int)((m / Wo) % Ho);
+    const size_t b = m / ((size_t)Wo * Ho);
+    float v = 0.f;
+    if (col < Cin * k * k) {
+        const int c = col / (k * k), t = col % (k * k);
+        const int iy = oy * stride - pad + t / k, ix = ox * stride - pad + t % k;
+        if (iy >= 0 && iy < H && ix >= 0 && ix < W) v = x[b * sb + (size_t)c * sc + (size_t)iy * sy + (size_t)ix * sx];
+    }
+    out[i] = v;
+}
+// the adjoint of a patchify (im2col with stride == k, no padding: a permutation): dx (addressed by strides) from dp [B Ho Wo][ldp]
+__global__ void unpatchify_kernel(const float* __restrict__ dp, int ldp, int Cin, int H, int W, int k, size_t sb, size_t sc, size_t sy, size_t sx, size_t n,
+                                  float* __restrict__ dx) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % Cin), xw = (int)((i / Cin) % W), yh = (int)((i / ((size_t)Cin * W)) % H);
+    const size_t b = i / ((size_t)Cin * W * H);
+    const int Ho = H / k, Wo = W / k;
+    dx[b * sb + (size_t)c * sc + (size_t)yh * sy + (size_t)xw * sx] =
+        dp[((b * Ho + yh / k) * Wo + xw / k) * ldp + (size_t)c * k * k + (yh % k) * k + xw % k];
+}
+// objs = feat m_b + null (1 - m_b) + pos   (canny_grounding_net.py:48-56), rows [B][T][C]
+__global__ void token_mix_f32_kernel(const float* __restrict__ feat, const float* __restrict__ mask, const float* __restrict__ null_feat,
+                                     const float* __restrict__ pos, int T, int Cc, size_t n, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int c = (int)(i % Cc), t = (int)((i / Cc) % T);
+    const float m = mask[i / ((size_t)Cc * T)];
+    out[i] = feat[i] * m + null_feat[c] * (1.f - m) + pos[(size_t)t * Cc + c];
+}
+// its backward: dfeat = g m_b; the per-row mask of null_grad_kernel; d pos[t][c] = sum_b g[b][t][c] (b in order)
+__global__ void mask_rows_kernel(const float* __restrict__ g, const float* __restrict__ mask, int T, int Cc, size_t n, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = g[i] * mask[i / ((size_t)T * Cc)];
+}
+__global__ void expand_mask_kernel(const float* __restrict__ mask, int T, int n, float* __restrict__ out) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) out[i] = mask[i / T];
+}
+__global__ void sum_batch_kernel(const float* __restrict__ g, int B, size_t n, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    float s = 0.f;
+    for (int b = 0; b < B; ++b) s += g[(size_t)b * n + i];
+    out[i] = s;
+}
+// h = cat([x, e], dim = 1) as pixel rows (openaimodel.py:442-444): x rows [B HW][C0], e NCHW [B][C1][HW] -> [B HW][C0 + C1]
+__global__ void cat_rows_nchw_kernel(const float* __restrict__ x, int C0, const float* __restrict__ e, int C1, int HW, size_t n, float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int C = C0 + C1, c = (int)(i % C);
+    const size_t r = i / C, p = r % HW, b = r / HW;
+    out[i] = c < C0 ? x[r * C0 + c] : e[(b * C1 + (c - C0)) * HW + p];
+}
+// data gradient of Conv2d(k 4, stride 2, pad 1) (GroundingDownsampler layers.2): g pixel rows [B][Ho Wo][Cout] -> dx NCHW [B][Cin][H][W]
+__global__ void conv4x4s2_dgrad_kernel(const float* __restrict__ g, const float* __restrict__ w, int Cin, int Cout, int H, int W, size_t n,
+                                       float* __restrict__ dx) {
+    const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int ix = (int)(i % W), iy = (int)((i / W) % H), ci = (int)((i / ((size_t)W * H)) % Cin);
+    const size_t b = i / ((size_t)W * H * Cin);
+    const int Ho = H / 2, Wo = W / 2;
+    float acc = 0.f;
+    for (int ky = 0; ky < 4; ++ky) {
+        const int ty = iy + 1 - ky;          // iy = 2 oy - 1 + ky
+        if (ty < 0 || (ty & 1) || (ty >> 1) >= Ho) continue;
+        for (int kx = 0; kx < 4; ++kx) {
+            const int tx = ix + 1 - kx;
+            if (tx < 0 || (tx & 1) || (tx >> 1) >= Wo) continue;
+            const float* gp = g + ((b * Ho + (ty >> 1)) * Wo + (tx >> 1)) * Cout;
+            for (int co = 0; co < Cout; ++co) acc = fmaf(gp[co], w[((size_t)co * Cin + ci) * 16 + ky * 4 + kx], acc);
+        }
+    }
+    dx[i] = acc;
+}
+
+struct Strides { size_t b, c, y, x; };
+Strides nchw(int Cc, int H, int W) { return {(size_t)Cc * H * W, (size_t)H * W, (size_t)W, 1}; }
+Strides pixel_rows(int Cc, int H, int W) { return {(size_t)H * W * Cc, 1, (size_t)W * Cc, (size_t)Cc}; }
+
+// dst [R][Kp] = src [R][K] zero-padded on the right
+float* pad_cols(const Ctx& c, const float* src, int R, int K, int Kp) {
+    float* d = c.f32((size_t)R * Kp);
+    hipLaunchKernelGGL(pad_cols_kernel, Ctx::g1((size_t)R * Kp), dim3(256), 0, c.s, src, K, Kp, (size_t)R * Kp, d);
+    return d;
+}
+// y = x W^T + b and dx = dy W for any contraction length: zero-padded to the GEMM's 64-step (ConvNeXt's first stage has C = 96)
+float* lin_fwd_any(const Ctx& c, const float* x, int M, int K, const float* W, const float* b, int N) {
+    if (K % 64 == 0) return c.lin_fwd(x, M, K, W, b, N);
+    const int Kp = round_up(K, 64);
+    return c.lin_fwd(pad_cols(c, x, M, K, Kp), M, Kp, pad_cols(c, W, N, K, Kp), b, N);
+}
+float* lin_dgrad_any(const Ctx& c, const float* dy, int M, int N, const float* W, int K) {
+    if (N % 64 == 0) return c.lin_dgrad(dy, M, N, W, K);
+    const int Np = round_up(N, 64);
+    float* Wp = c.f32((size_t)Np * K);
+    c.hip(hipMemsetAsync(Wp + (size_t)N * K, 0, (size_t)(Np - N) * K * 4, c.s), "hipMemsetAsync");
+    c.hip(hipMemcpyAsync(Wp, W, (size_t)N * K * 4, hipMemcpyDeviceToDevice, c.s), "hipMemcpyAsync");
+    return c.lin_dgrad(pad_cols(c, dy, M, N, Np), M, Np, Wp, K);
+}
+float* im2col(const Ctx& c, const float* x, int B, int Cin, int H, int W, Strides st, int k, int stride, int pad, int Ho, int Wo, int Kp) {
+    const size_t n = (size_t)B * Ho * Wo * Kp;
+    float* d = c.f32(n);
+    hipLaunchKernelGGL(im2col_f32_kernel, Ctx::g1(n), dim3(256), 0, c.s, x, Cin, H, W, st.b, st.c, st.y, st.x, k, stride, pad, Ho, Wo, Kp, n, d);
+    return d;
+}
+// weight (OIHW) and bias gradient of a k x k conv as an im2col of its input + lin_wgrad: x addressed by strides, dy pixel rows [B Ho Wo][Cout]
+void conv_wgrad(const Ctx& c, const float* x, int B, int Cin, int H, int W, Strides st, int k, int stride, int pad, int Ho, int Wo, const float* dy,
+                int Cout, float* dW, float* db) {
+    if (!dW && !db) return;
+    const int K = Cin * k * k, Kp = round_up(K, 64), M = B * Ho * Wo;
+    const size_t mk = c.ar.mark();
+    const float* col = dW ? im2col(c, x, B, Cin, H, W, st, k, stride, pad, Ho, Wo, Kp) : nullptr;
+    float* dWp = dW ? (Kp == K ? dW : c.f32((size_t)Cout * Kp)) : nullptr;
+    c.lin_wgrad(dy, col, M, Cout, Kp, dWp, db);
+    if (dW && dWp != dW) hipLaunchKernelGGL(split_kernel, Ctx::g1((size_t)Cout * K), dim3(256), 0, c.s, (const float*)dWp, Kp, 0, K, (size_t)Cout, dW, 0);
+    c.ar.release(mk);
+}
+
+const int kCnxDims[4] = {96, 192, 384, 768};       // ConvNeXt-tiny (convnext.py:203-207)
+const char* const kPN = "position_net.";
+const char* const kBB = "position_net.convnext_tiny_backbone.";
+struct CnxBlock { std::string p; const float* x; Ctx::LN n; float *u, *a, *h2; };
+struct CnxDown { std::string p; Ctx::LN l; float* col; int C, Cn; };
+struct SpatialSaved {
+    int R = 0, Cuse = 0, H = 0, M = 0;          // H: the last stage's grid side; M = B H H rows (B T tokens)
+    float *img = nullptr, *img3 = nullptr, *col0 = nullptr, *w0p = nullptr;
+    Ctx::LN stem_ln{};
+    CnxDown down[3];
+    std::vector<CnxBlock> blocks[4];
+    float* mix = nullptr;                         // the MLP's input rows [B T][768]
+};
+
+// PositionNet.forward up to the MLP (canny_grounding_net.py:38-56; sem: nearest resize + in_conv first, sem_grounding_net.py:40-49)
+SpatialSaved spatial_forward(const Ctx& c, const Names& nm, const TrainUNetCfg& cfg, const TrainSpatialIn& sp, int B) {
+    hipStream_t s = c.s;
+    const std::string PN = kPN, BB = kBB;
+    SpatialSaved t;
+    const int R = cfg.tok_resize;
+    t.R = R;
+    t.Cuse = cfg.tok_in_dim ? cfg.tok_in_dim : 3;
+    if (R < 32 || R % 32) throw GlError(GL_ERR_ARG, "unet_train_step: tok_resize must be a positive multiple of 32");
+    if (!sp.map || !sp.mask || sp.Ct < t.Cuse) throw GlError(GL_ERR_ARG, fmt("unet_train_step: the tokenizer reads %d map channels", t.Cuse));
+    t.img = c.f32((size_t)B * t.Cuse * R * R);
+    c.ck(resize_f32_launch(sp.map, t.img, B, sp.Ct, t.Cuse, sp.Ht, sp.Wt, R, 1, s));      // F.interpolate(x, resize_input): nearest
+    t.img3 = t.img;
+    if (cfg.tok_in_dim) {
+        t.img3 = c.f32((size_t)B * 3 * R * R);
+        c.ck(conv3x3_f32_launch(t.img, nm.w(PN + "in_conv.weight"), nm.w(PN + "in_conv.bias"), t.img3, B, t.Cuse, 3, R, R, s));
+    }
+    // stem: Conv2d(3, 96, 4, 4) as patches [B (R/4)^2][48 -> 64] times the OIHW weight as rows, then LayerNorm (convnext.py:71-74)
+    int H = R / 4, C = kCnxDims[0], M = B * H * H;
+    t.col0 = im2col(c, t.img3, B, 3, R, R, nchw(3, R, R), 4, 4, 0, H, H, 64);
+    t.w0p = pad_cols(c, nm.w(BB + "downsample_layers.0.0.weight"), C, 48, 64);
+    float* x = c.lin_fwd(t.col0, M, 64, t.w0p, nm.w(BB + "downsample_layers.0.0.bias"), C);
+    t.stem_ln = c.ln_fwd(x, M, C, nm.w(BB + "downsample_layers.0.1.weight"), nm.w(BB + "downsample_layers.0.1.bias"), 1e-6f);
+    x = t.stem_ln.y;
+    for (int st = 0; st < 4; ++st) {
+        if (st > 0) {     // LayerNorm + Conv2d(C, C', 2, 2) (convnext.py:76-81)
+            CnxDown& d = t.down[st - 1];
+            d.p = BB + fmt("downsample_layers.%d", st);
+            d.C = C;
+            d.Cn = kCnxDims[st];
+            d.l = c.ln_fwd(x, M, C, nm.w(d.p + ".0.weight"), nm.w(d.p + ".0.bias"), 1e-6f);
+            d.col = im2col(c, d.l.y, B, C, H, H, pixel_rows(C, H, H), 2, 2, 0, H / 2, H / 2, 4 * C);
+            H /= 2;
+            M /= 4;
+            x = c.lin_fwd(d.col, M, 4 * C, nm.w(d.p + ".1.weight"), nm.w(d.p + ".1.bias"), d.Cn);
+            C = d.Cn;
+        }
+        for (int j = 0; nm.has(BB + fmt("stages.%d.%d.dwconv.weight", st, j)); ++j) {      // Block.forward (convnext.py:36-50)
+            CnxBlock b;
+            b.p = BB + fmt("stages.%d.%d", st, j);
+            b.x = x;
+            const size_t n = (size_t)M * C;
+            float* dw = c.f32(n);
+            hipLaunchKernelGGL(dwconv7_f32_kernel, Ctx::g1(n), dim3(256), 0, s, (const float*)x, nm.w(b.p + ".dwconv.weight"), nm.w(b.p + ".dwconv.bias"), H, H, C,
+                               n, 0, 0, dw);
+            b.n = c.ln_fwd(dw, M, C, nm.w(b.p + ".norm.weight"), nm.w(b.p + ".norm.bias"), 1e-6f);
+            b.u = lin_fwd_any(c, b.n.y, M, C, nm.w(b.p + ".pwconv1.weight"), nm.w(b.p + ".pwconv1.bias"), 4 * C);
+            b.a = c.f32(4 * n);
+            hipLaunchKernelGGL(gelu_fwd_kernel, Ctx::g1(4 * n), dim3(256), 0, s, (const float*)b.u, 4 * n, b.a);
+            b.h2 = c.lin_fwd(b.a, M, 4 * C, nm.w(b.p + ".pwconv2.weight"), nm.w(b.p + ".pwconv2.bias"), C);
+            float* y = c.f32(n);
+            hipLaunchKernelGGL(layer_scale_residual_kernel, Ctx::g1(n), dim3(256), 0, s, (const float*)x, (const float*)b.h2,
+                               nm.has(b.p + ".gamma") ? nm.w(b.p + ".gamma") : (const float*)nullptr, C, n, y);
+            x = y;
+            t.blocks[st].push_back(b);
+        }
+        if (t.blocks[st].empty()) throw GlError(GL_ERR_MISSING, fmt("unet_train_step: ConvNeXt stage %d has no blocks", st));
+    }
+    t.H = H;
+    t.M = M;
+    t.mix = c.f32((size_t)M * C);
+    hipLaunchKernelGGL(token_mix_f32_kernel, Ctx::g1((size_t)M * C), dim3(256), 0, s, (const float*)x, sp.mask, nm.w(PN + "null_feature"), nm.w(PN + "pos_embedding"),
+                       H * H, C, (size_t)M * C, t.mix);
+    return t;
+}
+
+// g_mix: dL/d(the MLP's input rows) [B T][768] -> the gradients asked for among position_net.* (ConvNeXt, pos_embedding, null_feature,
+// in_conv). No gradient is formed for the map itself.
+void spatial_backward(const Ctx& c, const Names& nm, const TrainUNetCfg& cfg, const TrainSpatialIn& sp, int B, const SpatialSaved& t, const float* g_mix) {
+    hipStream_t s = c.s;
+    const std::string PN = kPN, BB = kBB;
+    int H = t.H, M = t.M, C = kCnxDims[3];
+    const int T = H * H;
+    if (float* gp = nm.g(PN + "pos_embedding")) hipLaunchKernelGGL(sum_batch_kernel, Ctx::g1((size_t)T * C), dim3(256), 0, s, g_mix, B, (size_t)T * C, gp);
+    if (float* gp = nm.g(PN + "null_feature")) {
+        float* mr = c.f32(M);
+        hipLaunchKernelGGL(expand_mask_kernel, Ctx::g1(M), dim3(256), 0, s, sp.mask, T, M, mr);
+        hipLaunchKernelGGL(null_grad_kernel, Ctx::g1(C), dim3(256), 0, s, g_mix, (const float*)mr, M, C, 0, C, gp, 0);
+    }
+    float* g = c.f32((size_t)M * C);
+    hipLaunchKernelGGL(mask_rows_kernel, Ctx::g1((size_t)M * C), dim3(256), 0, s, g_mix, sp.mask, T, C, (size_t)M * C, g);
+    for (int st = 3; st >= 0; --st) {
+        for (int j = (int)t.blocks[st].size() - 1; j >= 0; --j) {
+            const CnxBlock& b = t.blocks[st][j];
+            const size_t n = (size_t)M * C;
+            const float* gam = nm.has(b.p + ".gamma") ? nm.w(b.p + ".gamma") : nullptr;
+            const float* gh2 = g;
+            if (gam) {      // y = x + gamma h2: d gamma = sum_rows g h2, dh2 = g gamma
+                if (float* gg = nm.g(b.p + ".gamma"))
+                    hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, s, (const float*)g, (const float*)b.h2, M, C, gg);
+                float* t2 = c.f32(n);
+                hipLaunchKernelGGL(scale_cols_kernel, Ctx::g1(n), dim3(256), 0, s, (const float*)g, gam, C, n, t2);
+                gh2 = t2;
+            }
+            c.lin_wgrad(gh2, b.a, M, C, 4 * C, nm.g(b.p + ".pwconv2.weight"), nm.g(b.p + ".pwconv2.bias"));
+            float* ga = lin_dgrad_any(c, gh2, M, C, nm.w(b.p + ".pwconv2.weight"), 4 * C);
+            float* gu = c.f32(4 * n);
+            hipLaunchKernelGGL(gelu_bwd_kernel, Ctx::g1(4 * n), dim3(256), 0, s, (const float*)ga, (const float*)b.u, 4 * n, gu);
+            c.lin_wgrad(gu, b.n.y, M, 4 * C, C, nm.g(b.p + ".pwconv1.weight"), nm.g(b.p + ".pwconv1.bias"));
+            float* gn = c.lin_dgrad(gu, M, 4 * C, nm.w(b.p + ".pwconv1.weight"), C);
+            float* gdw = c.f32(n);
+            c.ln_bwd(gn, b.n, nm.w(b.p + ".norm.weight"), M, C, gdw, false, nm.g(b.p + ".norm.weight"), nm.g(b.p + ".norm.bias"));
+            if (float* gw = nm.g(b.p + ".dwconv.weight"))
+                hipLaunchKernelGGL(dwconv7_wgrad_kernel, dim3(cdiv(C, 64), 49), dim3(1024), 0, s, (const float*)gdw, b.x, B, H, H, C, gw);
+            if (float* gb = nm.g(b.p + ".dwconv.bias"))
+                hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, s, (const float*)gdw, (const float*)nullptr, M, C, gb);
+            // the residual's gradient g + the depthwise conv's data gradient (the same conv with the taps rotated by 180 degrees)
+            hipLaunchKernelGGL(dwconv7_f32_kernel, Ctx::g1(n), dim3(256), 0, s, (const float*)gdw, nm.w(b.p + ".dwconv.weight"), (const float*)nullptr, H, H, C, n,
+                               1, 1, g);
+        }
+        if (st > 0) {       // LayerNorm + 2 x 2 patch conv: wgrad / dgrad of the patch GEMM, un-patchify, LayerNorm backward
+            const CnxDown& d = t.down[st - 1];
+            c.lin_wgrad(g, d.col, M, d.Cn, 4 * d.C, nm.g(d.p + ".1.weight"), nm.g(d.p + ".1.bias"));
+            float* gcol = c.lin_dgrad(g, M, d.Cn, nm.w(d.p + ".1.weight"), 4 * d.C);
+            H *= 2;
+            M *= 4;
+            C = d.C;
+            const size_t n = (size_t)M * C;
+            float* gl = c.f32(n);
+            const Strides r = pixel_rows(C, H, H);
+            hipLaunchKernelGGL(unpatchify_kernel, Ctx::g1(n), dim3(256), 0, s, (const float*)gcol, 4 * C, C, H, H, 2, r.b, r.c, r.y, r.x, n, gl);
+            float* gx = c.f32(n);
+            c.ln_bwd(gl, d.l, nm.w(d.p + ".0.weight"), M, C, gx, false, nm.g(d.p + ".0.weight"), nm.g(d.p + ".0.bias"));
+            g = gx;
+        }
+    }
+    // stem: LayerNorm backward, then the patch GEMM's weight / bias gradient
+    const std::string s0 = BB + "downsample_layers.0.";
+    float* gs = c.f32((size_t)M * C);
+    c.ln_bwd(g, t.stem_ln, nm.w(s0 + "1.weight"), M, C, gs, false, nm.g(s0 + "1.weight"), nm.g(s0 + "1.bias"));
+    float* gw0 = nm.g(s0 + "0.weight");
+    float* gw0p = gw0 ? c.f32((size_t)C * 64) : nullptr;
+    c.lin_wgrad(gs, t.col0, M, C, 64, gw0p, nm.g(s0 + "0.bias"));
+    if (gw0) hipLaunchKernelGGL(split_kernel, Ctx::g1((size_t)C * 48), dim3(256), 0, s, (const float*)gw0p, 64, 0, 48, (size_t)C, gw0, 0);
+    if (cfg.tok_in_dim && (nm.g(PN + "in_conv.weight") || nm.g(PN + "in_conv.bias"))) {
+        // sem's in_conv (Conv2d(152, 3, 3, 1, 1), sem_grounding_net.py:21, 46): the stem's data gradient back to pixel rows [B R R][3],
+        // then im2col + lin_wgrad over the resized class planes
+        const int R = t.R;
+        float* gcol = lin_dgrad_any(c, gs, M, C, t.w0p, 64);
+        const size_t n = (size_t)B * R * R * 3;
+        float* g3 = c.f32(n);
+        const Strides r = pixel_rows(3, R, R);
+        hipLaunchKernelGGL(unpatchify_kernel, Ctx::g1(n), dim3(256), 0, s, (const float*)gcol, 64, 3, R, R, 4, r.b, r.c, r.y, r.x, n, g3);
+        conv_wgrad(c, t.img, B, t.Cuse, R, R, nchw(t.Cuse, R, R), 3, 1, 1, R, R, g3, 3, nm.g(PN + "in_conv.weight"), nm.g(PN + "in_conv.bias"));
+    }
+}
+
+// GroundingDownsampler.forward (canny_grounding_downsampler.py:21-29; hed: the resize only; sem: nearest, 152 -> 16 -> 8), NCHW fp32
+struct DsSaved { float *r = nullptr, *a1 = nullptr, *s1 = nullptr, *out = nullptr; };
+DsSaved downsampler_forward(const Ctx& c, const Names& nm, const TrainSpatialIn& sp, int B, int Ce, int H0, int W0) {
+    DsSaved d;
+    const int Rd = sp.ds_resize, ni = sp.ds_n_in, mid = sp.ds_mid;
+    if (!sp.extra || ni < 1 || sp.Ce < ni || Rd < 4) throw GlError(GL_ERR_ARG, "unet_train_step: grounding_extra_input / downsampler constants");
+    if (mid ? (Rd != 4 * H0 || Rd != 4 * W0) : (Rd != H0 || Rd != W0 || ni != Ce))
+        throw GlError(GL_ERR_ARG, fmt("unet_train_step: the downsampler (resize %d) does not match the %d x %d latent", Rd, H0, W0));
+    d.r = c.f32((size_t)B * ni * Rd * Rd);
+    c.ck(resize_f32_launch(sp.extra, d.r, B, sp.Ce, ni, sp.He, sp.We, Rd, sp.ds_mode == 1 ? 1 : 0, c.s));
+    d.out = d.r;
+    if (mid) {
+        const int Rh = Rd / 2;
+        const size_t nh = (size_t)B * mid * Rh * Rh;
+        d.a1 = c.f32(nh);           // the first conv's pre-activation: the SiLU backward reads it
+        c.ck(conv4x4s2_f32_launch(d.r, nm.w("downsample_net.layers.0.weight"), nm.w("downsample_net.layers.0.bias"), d.a1, B, ni, mid, Rd, Rd, 0, c.s));
+        d.s1 = c.f32(nh);
+        hipLaunchKernelGGL(silu_kernel, Ctx::g1(nh), dim3(256), 0, c.s, (const float*)d.a1, nh, d.s1);
+        d.out = c.f32((size_t)B * Ce * H0 * W0);
+        c.ck(conv4x4s2_f32_launch(d.s1, nm.w("downsample_net.layers.2.weight"), nm.w("downsample_net.layers.2.bias"), d.out, B, mid, Ce, Rh, Rh, 0, c.s));
+    }
+    return d;
+}
+
 }  // namespace
 
 int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& cfg, const TrainUNetIn& in, int n_params, const char* const* names,
                     const float* const* params, float* const* grads, const char* const* block_names, float* eps_out, float* loss, hipStream_t s, hipEvent_t* grad_events, int n_grad_events,
-                    TrainWeightCache* cache) {
+                    TrainWeightCache* cache, const TrainSpatialIn* spatial) {
     try {
         Names nm;
         nm.params = params;
         nm.grads = grads;
         for (int i = 0; i < n_params; ++i) nm.idx[names[i]] = i;
+        // trainer.py:217-242: fuser.*, position_net.*, and for a model with a grounding downsampler downsample_net.* and the first conv's
+        // weight (input_conv_train, :189-194, 233; its bias stays frozen)
+        const bool ds_model = cfg.grounding_kind == 3 && cfg.extra_channels > 0;
         for (int i = 0; i < n_params; ++i)
-            if (grads[i] && !(strstr(names[i], ".fuser.") || !strncmp(names[i], "position_net.", 13)))
+            if (grads[i] && !(strstr(names[i], ".fuser.") || !strncmp(names[i], "position_net.", 13) ||
+                              (ds_model && (!strncmp(names[i], "downsample_net.", 15) || !strcmp(names[i], "input_blocks.0.0.weight")))))
                 throw GlError(GL_ERR_ARG, fmt("unet_train_step: a gradient was asked for '%s', which the reference keeps frozen", names[i]));
+        if (cfg.grounding_kind == 3 && !spatial) throw GlError(GL_ERR_ARG, "unet_train_step: a spatial-map model needs its TrainSpatialIn");
         Ctx c{ar, ws, ws_bytes, s};
         std::unordered_set<const void*> frozen;
         if (cache) {
@@ -1667,7 +2059,9 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
         // keypoint tokenizer (points, 2 coords; the embedding is person + keypoint table rows), two MLPs (text, image) whose tokens are
         // concatenated along the token axis for text+image (text_grounding_net.py:30-52, text_image_grounding_net.py:41-70,
         // keypoint_grounding_net.py:34-58)
-        const int GK = cfg.grounding_kind, NB = in.Ng_boxes, MRB = B * NB, NC = GK == 2 ? 2 : 4, PWr = cfg.gr_dim + 16 * NC, PW = round_up(PWr, 64);
+        // (spatial-map tokenizers, GK 3: the same MLP over the ConvNeXt features mixed with null_feature and pos_embedding, K = 768)
+        const int GK = cfg.grounding_kind, NB = in.Ng_boxes, MRB = B * NB, NC = GK == 2 ? 2 : 4;
+        const int PWr = GK == 3 ? kCnxDims[3] : cfg.gr_dim + 16 * NC, PW = round_up(PWr, 64);
         const int NBR = GK == 1 ? 2 : 1;
         if (Ng != NB * NBR || (GK == 2 && NB % 17)) throw GlError(GL_ERR_ARG, "unet_train_step: Ng must be the box count (text), twice it (text+image), 17 per person (keypoint)");
         const int MR = B * Ng;
@@ -1679,13 +2073,21 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
                            {"position_net.linears_image", "position_net.null_image_feature", in.image_embeddings, in.image_masks, nullptr, nullptr, nullptr, nullptr,
                             nullptr, nullptr, nullptr}};
         float* objs = NBR == 1 ? nullptr : c.f32((size_t)MR * KD);
+        SpatialSaved tok;
         for (int r = 0; r < NBR; ++r) {
             PosBranch& p = pb[r];
-            if ((!p.emb && GK != 2) || !p.emb_mask) throw GlError(GL_ERR_ARG, "unet_train_step: null grounding input");
-            p.pcat = c.f32((size_t)MRB * PW);
-            hipLaunchKernelGGL(posnet_input_kernel_f32, dim3(MRB), dim3(256), 0, s, in.boxes, NC, in.masks, p.emb_mask, p.emb,
-                               GK == 2 ? nm.w("position_net.person_embeddings") : (const float*)nullptr,
-                               GK == 2 ? nm.w("position_net.keypoint_embeddings") : (const float*)nullptr, NB, nm.w(p.null_emb), nm.w(null_pos), cfg.gr_dim, PW, p.pcat);
+            if (GK == 3) {
+                tok = spatial_forward(c, nm, cfg, *spatial, B);
+                if (tok.M != MRB) throw GlError(GL_ERR_ARG, "unet_train_step: Ng must be (tok_resize / 32)^2 for a spatial-map tokenizer");
+                p.pcat = tok.mix;
+            } else {
+                if ((!p.emb && GK != 2) || !p.emb_mask) throw GlError(GL_ERR_ARG, "unet_train_step: null grounding input");
+                p.pcat = c.f32((size_t)MRB * PW);
+                hipLaunchKernelGGL(posnet_input_kernel_f32, dim3(MRB), dim3(256), 0, s, in.boxes, NC, in.masks, p.emb_mask, p.emb,
+                                   GK == 2 ? nm.w("position_net.person_embeddings") : (const float*)nullptr,
+                                   GK == 2 ? nm.w("position_net.keypoint_embeddings") : (const float*)nullptr, NB, nm.w(p.null_emb), nm.w(null_pos), cfg.gr_dim, PW,
+                                   p.pcat);
+            }
             const float* w0 = nm.w(p.lin + ".0.weight");
             if (PW != PWr) {        // the first Linear's K (800 for the keypoint tokenizer) padded to the GEMM's 64-step with zero columns
                 p.w0p = c.f32((size_t)512 * PW);
@@ -1749,12 +2151,21 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
             }
             return l;
         };
-        const int Cx = cfg.in_channels;
+        const int Cx = cfg.in_channels, Ce = GK == 3 ? cfg.extra_channels : 0, Cin0 = Cx + Ce;
         const size_t M0 = (size_t)B * H0 * W0;
-        // conv_in (frozen, in front of every trainable parameter: forward only)
+        // conv_in: frozen for the discrete models (forward only); for a model with a grounding downsampler its input is
+        // cat(x, downsample_net(grounding_extra_input)) (openaimodel.py:442-444) and its weight is trainable
+        DsSaved dsv;
+        const float* xin = in.x;
+        if (Ce) {
+            dsv = downsampler_forward(c, nm, *spatial, B, Ce, H0, W0);
+            float* cat0 = c.f32(M0 * Cin0);
+            hipLaunchKernelGGL(cat_rows_nchw_kernel, Ctx::g1(M0 * Cin0), dim3(256), 0, s, in.x, Cx, (const float*)dsv.out, Ce, H0 * W0, M0 * Cin0, cat0);
+            xin = cat0;
+        }
         float* h0 = c.f32(M0 * mc);
-        hipLaunchKernelGGL(conv3x3_direct_kernel, Ctx::g1(M0 * mc), dim3(256), 0, s, in.x, nm.w("input_blocks.0.0.weight"), nm.w("input_blocks.0.0.bias"), H0, W0,
-                           Cx, mc, M0 * mc, h0);
+        hipLaunchKernelGGL(conv3x3_direct_kernel, Ctx::g1(M0 * mc), dim3(256), 0, s, xin, nm.w("input_blocks.0.0.weight"), nm.w("input_blocks.0.0.bias"), H0, W0,
+                           Cin0, mc, M0 * mc, h0);
         Act h{h0, mc, H0, W0};
         std::vector<Act> hs{h};
         std::vector<int> hs_layer{-1};          // which layer produced each skip (-1: conv_in)
@@ -1870,7 +2281,15 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
         int n_st_layers = 0;
         for (size_t i = 0; i < L.size(); ++i)
             if (L[i].kind == K_ST) st_ordinal[i] = n_st_layers++;
-        for (int i = (int)L.size() - 1; i >= 0 && i >= first_st; --i) {
+        // a trainable first conv (or downsampler) needs dL/d(conv_in output): the loop then runs through the layers in front of the first
+        // fuser too and keeps conv_in's skip gradient (hs_layer -1, the last output block's concat)
+        bool ds_grads = false;
+        for (const char* k : {"downsample_net.layers.0.weight", "downsample_net.layers.0.bias", "downsample_net.layers.2.weight", "downsample_net.layers.2.bias"})
+            ds_grads = ds_grads || nm.g(k);
+        const bool in_grad = Ce > 0 && (nm.g("input_blocks.0.0.weight") || ds_grads);
+        const int stop = in_grad ? 0 : first_st;
+        float* skip0 = nullptr;
+        for (int i = (int)L.size() - 1; i >= 0 && i >= stop; --i) {
             Layer& l = L[i];
             const size_t rows = (size_t)B * l.H * l.W;
             if (skip_grad[i]) {     // this layer's output also went into a skip connection (l.H, l.W are its INPUT size)
@@ -1881,10 +2300,11 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
                 float* gh = c.f32(rows * l.C0);
                 hipLaunchKernelGGL(split_kernel, Ctx::g1(rows * l.C0), dim3(256), 0, s, (const float*)g, l.Cin, 0, l.C0, rows, gh, 0);
                 const int C1 = l.Cin - l.C0;
-                if (l.skip_idx >= first_st) {       // (a skip produced in front of the first fuser carries no gradient anybody needs)
+                if (in_grad || l.skip_idx >= first_st) {   // (without in_grad a skip produced in front of the first fuser carries no gradient anybody needs)
                     float* gs = c.f32(rows * C1);
                     hipLaunchKernelGGL(split_kernel, Ctx::g1(rows * C1), dim3(256), 0, s, (const float*)g, l.Cin, l.C0, C1, rows, gs, 0);
-                    skip_grad[l.skip_idx] = gs;
+                    if (l.skip_idx < 0) skip0 = gs;
+                    else skip_grad[l.skip_idx] = gs;
                 }
                 g = gh;
             } else if (l.kind == K_RES) {
@@ -1916,8 +2336,35 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
                 g = resample_backward(c, 1, B, l.H, l.W, l.Cin, l.P[0], g);
             }
         }
+        if (in_grad) {
+            // ---- the first conv and the GroundingDownsampler (trainer.py:189-194, 229-236). g = dL/d(conv_in output) through
+            // input_blocks.1, plus the skip into the last output block's concat
+            if (skip0) c.add(g, skip0, M0 * mc);
+            if (float* gw = nm.g("input_blocks.0.0.weight"))
+                conv_wgrad(c, xin, B, Cin0, H0, W0, pixel_rows(Cin0, H0, W0), 3, 1, 1, H0, W0, g, mc, gw, nullptr);
+            if (spatial->ds_mid && ds_grads) {
+                // the first conv's data gradient for the k downsampler channels only: rows Cx .. Cx + k of the flipped / transposed filter
+                float* wt = c.f32((size_t)Cin0 * mc * 9);
+                hipLaunchKernelGGL(conv_dgrad_weight_kernel, Ctx::g1((size_t)Cin0 * mc * 9), dim3(256), 0, s, nm.w("input_blocks.0.0.weight"), mc, Cin0, wt);
+                float* gds = c.f32(M0 * Ce);
+                hipLaunchKernelGGL(conv3x3_direct_kernel, Ctx::g1(M0 * Ce), dim3(256), 0, s, (const float*)g, (const float*)(wt + (size_t)Cx * mc * 9),
+                                   (const float*)nullptr, H0, W0, mc, Ce, M0 * Ce, gds);
+                const int Rd = spatial->ds_resize, Rh = Rd / 2, mid = spatial->ds_mid, ni = spatial->ds_n_in;
+                conv_wgrad(c, dsv.s1, B, mid, Rh, Rh, nchw(mid, Rh, Rh), 4, 2, 1, H0, W0, gds, Ce, nm.g("downsample_net.layers.2.weight"),
+                           nm.g("downsample_net.layers.2.bias"));
+                const size_t nh = (size_t)B * mid * Rh * Rh;
+                float* gs1 = c.f32(nh);
+                hipLaunchKernelGGL(conv4x4s2_dgrad_kernel, Ctx::g1(nh), dim3(256), 0, s, (const float*)gds, nm.w("downsample_net.layers.2.weight"), mid, Ce, Rh, Rh,
+                                   nh, gs1);
+                float* ga1 = c.f32(nh);
+                hipLaunchKernelGGL(silu_bwd_kernel, Ctx::g1(nh), dim3(256), 0, s, (const float*)gs1, (const float*)dsv.a1, nh, ga1);
+                const float* ga1r = im2col(c, ga1, B, mid, Rh, Rh, nchw(mid, Rh, Rh), 1, 1, 0, Rh, Rh, mid);     // NCHW -> pixel rows
+                conv_wgrad(c, dsv.r, B, ni, Rd, Rd, nchw(ni, Rd, Rd), 4, 2, 1, Rh, Rh, ga1r, mid, nm.g("downsample_net.layers.0.weight"),
+                           nm.g("downsample_net.layers.0.bias"));
+            }
+        }
         // ---- position_net backward (Linear, SiLU, Linear, SiLU, Linear per branch; the learnable null embeddings: the position one is
-        // shared by the branches; the keypoint tokenizer's person / keypoint embedding tables)
+        // shared by the branches; the keypoint tokenizer's person / keypoint embedding tables; GK 3: token mix + ConvNeXt)
         for (int r = 0; r < NBR; ++r) {
             const PosBranch& p = pb[r];
             const float* go = NBR == 1 ? g_objs : c.slice_rows(g_objs, B, Ng, r * NB, NB, KD);
@@ -1938,6 +2385,10 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
                 if (gw0) hipLaunchKernelGGL(split_kernel, Ctx::g1((size_t)512 * PWr), dim3(256), 0, s, (const float*)gw0p, PW, 0, PWr, (size_t)512, gw0, 0);
             }
             float* g_cat = c.lin_dgrad(g_l0, MRB, 512, p.w0p ? p.w0p : nm.w(p.lin + ".0.weight"), PW);
+            if (GK == 3) {
+                spatial_backward(c, nm, cfg, *spatial, B, tok, g_cat);
+                continue;
+            }
             if (float* gp = nm.g(p.null_emb))
                 hipLaunchKernelGGL(null_grad_kernel, Ctx::g1(cfg.gr_dim), dim3(256), 0, s, (const float*)g_cat, p.emb_mask, MRB, PW, 0, cfg.gr_dim, gp, 0);
             if (float* gp = nm.g(null_pos))

@@ -30,6 +30,32 @@ def _f32(t: torch.Tensor, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+SPATIAL_MAP_KEYS = dict(canny="canny_edge", hed="hed_edge", depth="depth", normal="normal", sem="sem")
+
+
+def spatial_train_config(cfg: Mapping) -> Optional[dict]:
+    """What the training step needs to know of a spatial-map model, from its UNetModel kwargs (None for the discrete tokenizers):
+    the modality and the batch key of its map (the five *_grounding_net targets), the tokenizer's resize_input and semantic-map
+    channels, and the GroundingDownsampler's resize / mode / channels -- read off the same classes the model is built from
+    (ldm/modules/diffusionmodules/_spatial.py), so a config's `params` and the class defaults both apply."""
+    import inspect
+    from ldm.util import get_obj_from_str, instantiate_from_config
+    tok = cfg.get("grounding_tokenizer") or {}
+    mod = tok.get("target", "").rsplit(".", 2)
+    modality = mod[-2][:-len("_grounding_net")] if len(mod) == 3 and mod[-2].endswith("_grounding_net") else None
+    if modality not in SPATIAL_MAP_KEYS:
+        return None
+    defaults = {k: p.default for k, p in inspect.signature(get_obj_from_str(tok["target"]).__init__).parameters.items()}
+    params = dict(tok.get("params") or {})
+    out = dict(modality=modality, map_key=SPATIAL_MAP_KEYS[modality], tok_resize=int(params.get("resize_input", defaults["resize_input"])),
+               tok_in_dim=int(params.get("in_dim", defaults.get("in_dim")) or 0), ds=None)
+    if cfg.get("grounding_downsampler"):
+        ds = instantiate_from_config(cfg["grounding_downsampler"])      # a few small convs: only its constants are read
+        out["ds"] = dict(resize=int(ds.resize_input), mode={"bicubic": 0, "nearest": 1}[ds.mode], n_in=int(ds.n_in),
+                         mid=int(ds.c_mid) if ds.has_layers else 0, out=int(ds.out_dim))
+    return out
+
+
 class TrainResDims(C.Structure):   # = gl_train_resblock_dims
     _fields_ = [(n, C.c_int) for n in ("B", "H", "W", "Cin", "Cout", "emb_dim")]
 
@@ -465,8 +491,11 @@ class Engine:
         """One training iteration of the reference (trainer.py:353-392: model(input), mse_loss(model_output, noise), backward) on the
         device (gl_unet_train_step). cfg: UNetModel kwargs (text tokenizer, gatedSA); state_dict: the model's parameters (fp32, on this
         device: they are used in place); batch: x [B, 4, H, W] (noised latent), timesteps [B], context [B, 77, 768], boxes, masks,
-        positive_embeddings (or, for the text+image tokenizer, text_embeddings, image_embeddings, text_masks, image_masks), target [B, 4, H, W] (the noise). Returns (loss, eps [B, 4, H, W], grads) with grads over the reference's
-        trainable set (trainer.py:217-245: '*.fuser.*' and 'position_net.*' keys) or the `trainable` names given; `grads`: buffers to
+        positive_embeddings (or, for the text+image tokenizer, text_embeddings, image_embeddings, text_masks, image_masks), target [B, 4, H, W] (the noise).
+        A spatial-map model (cfg["grounding_tokenizer"] one of the five *_grounding_net targets; gl_unet_train_step_spatial) takes the map
+        under the reference's key (canny_edge, hed_edge, depth, normal, sem), mask [B] and grounding_extra_input instead of the boxes.
+        Returns (loss, eps [B, 4, H, W], grads) with grads over the reference's
+        trainable set (train.trainable_names: trainer.py:189-245) or the `trainable` names given; `grads`: buffers to
         write into instead of fresh ones (every entry is overwritten); `checkpoint`: keep only block inputs / outputs and recompute each block's
         forward in its backward (the same gradients bit for bit, a fraction of the arena); `use_weight_cache`: keep / reuse the bf16
         operand copies of the tensors no gradient is asked for (train_weight_cache: only when those tensors never change)."""
@@ -480,15 +509,20 @@ class Engine:
         c.n_attn = len(cfg["attention_resolutions"])
         for i, v in enumerate(cfg["attention_resolutions"]):
             c.attention_resolutions[i] = int(v)
-        ti = "image_embeddings" in batch        # the text+image tokenizer (text_image_grounding_net.py)
-        kp = "points" in batch                  # the keypoint tokenizer (keypoint_grounding_net.py); else the text tokenizer
-        c.grounding_kind, c.fuser_kind = (1 if ti else 2 if kp else 0), 0
+        sp = spatial_train_config(cfg)          # a spatial-map tokenizer (canny / depth / normal / hed / sem_grounding_net.py)?
+        ti = sp is None and "image_embeddings" in batch     # the text+image tokenizer (text_image_grounding_net.py)
+        kp = sp is None and "points" in batch               # the keypoint tokenizer (keypoint_grounding_net.py); else the text tokenizer
+        c.grounding_kind, c.fuser_kind = (3 if sp else 1 if ti else 2 if kp else 0), 0
         c.max_persons = int(batch["points"].shape[1]) // 17 if kp else 0
         c.gr_in_dim = c.gr_out_dim = 768
+        if sp:
+            c.extra_channels = sp["ds"]["out"] if sp["ds"] else 0
+            c.tok_resize, c.tok_in_dim = sp["tok_resize"], sp["tok_in_dim"]
         names = [k for k in state_dict.keys()]
         params = [_f32(state_dict[k], dev) for k in names]
         if trainable is None:
-            trainable = [k for k in names if ".fuser." in k or k.startswith("position_net.")]
+            from .train import trainable_names
+            trainable = trainable_names(state_dict, cfg)
         if grads is None:
             grads = {k: torch.zeros_like(p) for k, p in zip(names, params) if k in set(trainable)}
         else:       # caller-owned gradient buffers (gligen_amd.dist.GradBuckets.views: the backward writes straight into the flat buckets)
@@ -497,6 +531,28 @@ class Engine:
         x, target = batch["x"], batch["target"]
         B, Cx, H, W = x.shape
         rows = lambda t: _f32(t, dev).permute(0, 2, 3, 1).reshape(B, H * W, t.shape[1]).contiguous()
+        n = len(names)
+        narr = (C.c_char_p * n)(*[k.encode() for k in names])
+        parr = (C.c_void_p * n)(*[p.data_ptr() for p in params])
+        garr = (C.c_void_p * n)(*[(grads[k].data_ptr() if k in grads else None) for k in names])
+        eps = torch.empty((B, H * W, c.out_channels), device=dev, dtype=torch.float32)
+        loss = torch.zeros(1, device=dev, dtype=torch.float32)
+        if sp:      # batch: the map under the reference's key, mask, grounding_extra_input (gl_unet_train_step_spatial)
+            keep = dict(x=rows(x), t=_f32(batch["timesteps"], dev), ctx=_f32(batch["context"], dev), target=rows(target),
+                        map=_f32(batch[sp["map_key"]], dev), mask=_f32(batch["mask"].reshape(-1), dev))
+            if keep["mask"].shape[0] != B:
+                raise ValueError("unet_train_step: one mask value per sample")
+            ds = sp["ds"]
+            extra = _f32(batch["grounding_extra_input"], dev) if ds else None
+            u = _lib.TrainUNetIn(int(B), int(H), int(W), int(keep["ctx"].shape[1]), (sp["tok_resize"] // 32) ** 2, keep["x"].data_ptr(), keep["t"].data_ptr(),
+                                 keep["ctx"].data_ptr(), None, None, None, keep["target"].data_ptr(), float(fuser_scale), None, None, None,
+                                 int(bool(checkpoint)), int(bool(use_weight_cache)))
+            m = keep["map"]
+            s = _lib.TrainSpatialIn(m.data_ptr(), int(m.shape[1]), int(m.shape[2]), int(m.shape[3]), keep["mask"].data_ptr(),
+                                    extra.data_ptr() if ds else None, *((int(extra.shape[1]), int(extra.shape[2]), int(extra.shape[3])) if ds else (0, 0, 0)),
+                                    ds["resize"] if ds else 0, ds["mode"] if ds else 0, ds["n_in"] if ds else 0, ds["mid"] if ds else 0)
+            check(self.lib.gl_unet_train_step_spatial(self._ctx, C.byref(c), C.byref(u), C.byref(s), n, narr, parr, garr, _ptr(eps), _ptr(loss), _stream(dev)))
+            return loss, eps.reshape(B, H, W, c.out_channels).permute(0, 3, 1, 2).contiguous(), grads
         keep = dict(x=rows(x), t=_f32(batch["timesteps"], dev), ctx=_f32(batch["context"], dev), boxes=_f32(batch["points" if kp else "boxes"], dev),
                     masks=_f32(batch["masks"], dev), pe=None if kp else _f32(batch["text_embeddings" if ti else "positive_embeddings"], dev), target=rows(target))
         if ti:
@@ -505,12 +561,6 @@ class Engine:
                              keep["ctx"].data_ptr(), keep["boxes"].data_ptr(), keep["masks"].data_ptr(), None if kp else keep["pe"].data_ptr(), keep["target"].data_ptr(),
                              float(fuser_scale), keep["tm"].data_ptr() if ti else None, keep["im"].data_ptr() if ti else None,
                              keep["ie"].data_ptr() if ti else None, int(bool(checkpoint)), int(bool(use_weight_cache)))
-        n = len(names)
-        narr = (C.c_char_p * n)(*[k.encode() for k in names])
-        parr = (C.c_void_p * n)(*[p.data_ptr() for p in params])
-        garr = (C.c_void_p * n)(*[(grads[k].data_ptr() if k in grads else None) for k in names])
-        eps = torch.empty((B, H * W, c.out_channels), device=dev, dtype=torch.float32)
-        loss = torch.zeros(1, device=dev, dtype=torch.float32)
         check(self.lib.gl_unet_train_step(self._ctx, C.byref(c), C.byref(u), n, narr, parr, garr, _ptr(eps), _ptr(loss), _stream(dev)))
         return loss, eps.reshape(B, H, W, c.out_channels).permute(0, 3, 1, 2).contiguous(), grads
 

@@ -8,9 +8,9 @@ Everything numeric runs in the library: forward + backward in gl_unet_train_step
 the bookkeeping the reference leaves to torch.optim / DDP: the trainable parameters and their gradients are views into a few flat
 fp32 buffers (gligen_amd.dist.GradBuckets), so the backward writes the gradients where the collective reads them, one
 reduce-scatter + all-gather pair per bucket goes over RCCL, and AdamW is one launch per bucket over the flat range.
-The step is built for the three discrete grounding tokenizers with gatedSA fusers (what the spatial-map modalities
-need); the batch dict carries boxes + masks + positive_embeddings (text), + text_embeddings / image_embeddings / text_masks / image_masks
-(text+image), or points + masks (keypoint)."""
+The step is built for the three discrete grounding tokenizers and the five spatial-map ones with gatedSA fusers; the batch dict carries
+boxes + masks + positive_embeddings (text), + text_embeddings / image_embeddings / text_masks / image_masks (text+image), points + masks
+(keypoint), or the map under the reference's key (canny_edge, hed_edge, depth, normal, sem) + mask + grounding_extra_input."""
 from __future__ import annotations
 
 import math
@@ -22,7 +22,12 @@ import torch.distributed as tdist
 
 from .dist import GradBuckets
 
-GROUNDING_KEYS = ("boxes", "masks", "positive_embeddings", "text_embeddings", "image_embeddings", "text_masks", "image_masks", "points")
+GROUNDING_KEYS = ("boxes", "masks", "positive_embeddings", "text_embeddings", "image_embeddings", "text_masks", "image_masks", "points",
+                  # the spatial-map tokenizers' map and mask (grounding_input/*_grounding_tokinzer_input.py); grounding_extra_input, the
+                  # GroundingDownsampler's input, is not part of the drop (openaimodel.py:428-429 replaces the tokenizer's input only).
+                  # The bare "mask" is the spatial tokenizers' key alone: the discrete batches carry "masks", the inpainting mask
+                  # never travels as a batch key (tests/test_train_spatial_cpu.py holds the discrete batches to that)
+                  "canny_edge", "hed_edge", "depth", "normal", "sem", "mask")
 
 
 def warmup_schedule(base_lr: float, warmup_steps: int, total_iters: Optional[int] = None) -> Callable[[int], float]:
@@ -45,9 +50,22 @@ def null_grounding(batch: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]
     return {k: (torch.zeros_like(v) if k in GROUNDING_KEYS else v) for k, v in batch.items()}
 
 
-def trainable_names(state_dict: Mapping[str, torch.Tensor]):
-    """trainer.py:217-245: 'transformer_blocks' + 'fuser' in the name, or 'position_net'."""
-    return [k for k in state_dict if ".fuser." in k or k.startswith("position_net.")]
+def has_grounding_downsampler(state_dict: Mapping[str, torch.Tensor], cfg: Optional[Mapping] = None) -> bool:
+    """Whether the model feeds a GroundingDownsampler's output into its first conv (openaimodel.py:288-305): the config's
+    `grounding_downsampler` when a config is given (TrainStep and Engine.unet_train_step pass it). Without a config it is a
+    heuristic read off the state_dict: downsample_net.* weights, or a ConvNeXt tokenizer -- every spatial-map config the reference
+    ships pairs its tokenizer with a downsampler (hed's has no parameters), but a custom config need not."""
+    if cfg is not None:
+        return bool(cfg.get("grounding_downsampler"))
+    return any(k.startswith("downsample_net.") or k.startswith("position_net.convnext_tiny_backbone.") for k in state_dict)
+
+
+def trainable_names(state_dict: Mapping[str, torch.Tensor], cfg: Optional[Mapping] = None):
+    """trainer.py:217-245: 'transformer_blocks' + 'fuser' in the name, 'position_net', 'downsample_net', and the first conv's weight
+    when additional channels come from a grounding downsampler (trainer.py:189-194, 233: input_conv_train; the bias stays frozen)."""
+    conv_train = has_grounding_downsampler(state_dict, cfg)
+    return [k for k in state_dict if ".fuser." in k or k.startswith("position_net.") or k.startswith("downsample_net.")
+            or (conv_train and k == "input_blocks.0.0.weight")]
 
 
 def _block_order(prefix: str):
@@ -65,8 +83,8 @@ def gradient_milestones(names):
     """For every trainable tensor the milestone of gl_unet_train_step behind which its gradient is final (gl_train_wait_grads): a fuser
     tensor's is the number of its SpatialTransformer in MODULE order (input_blocks .., middle_block, output_blocks .., by the numeric
     index in the path -- not the iteration order of the dict handed in: a re-sorted state_dict puts input_blocks.10 before
-    input_blocks.2 and would point a bucket at the wrong event), position_net's is the number of SpatialTransformers -- the end of the
-    backward. The backward walks the blocks from the last to the first, so milestone j is reached before milestone j - 1."""
+    input_blocks.2 and would point a bucket at the wrong event), every other tensor's (position_net, downsample_net, the first conv)
+    is the number of SpatialTransformers -- the end of the backward. The backward walks the blocks from the last to the first, so milestone j is reached before milestone j - 1."""
     blocks = sorted({k.split(".transformer_blocks.")[0] for k in names if ".fuser." in k}, key=_block_order)
     index = {b: i for i, b in enumerate(blocks)}
     return {k: (index[k.split(".transformer_blocks.")[0]] if ".fuser." in k else len(blocks)) for k in names}
@@ -104,7 +122,7 @@ class TrainStep:
         self.wd, self.betas, self.eps = float(weight_decay), tuple(betas), float(eps)
         self.drop_prob, self.rng = float(drop_prob), rng or random.Random()
         self.checkpoint = bool(checkpoint)       # activation checkpointing per block (the reference: use_checkpoint=True in every shipped config)
-        names = trainable_names(state_dict)
+        names = trainable_names(state_dict, self.cfg)
         self.milestone = gradient_milestones(names)
         n_blocks = max(self.milestone.values(), default=0)
         # the engine numbers SpatialTransformers by walking the config; both counts must agree or bucket_ready waits on the wrong events

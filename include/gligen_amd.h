@@ -358,6 +358,27 @@ typedef struct gl_train_unet_in {
 int gl_unet_train_step(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, int n_params, const char* const* names,
                        const float* const* params, float* const* grads, float* eps_out, float* loss, gl_stream s);
 
+/* The same training iteration for a spatial-map model (canny / depth / normal / hed / sem: the ConvNeXt-tiny tokenizer,
+ * canny_grounding_net.py:38-62, and the GroundingDownsampler in front of a 4 + k channel first conv, openaimodel.py:442-444):
+ * cfg->grounding_kind = 3 with extra_channels, tok_resize and tok_in_dim set, fuser_kind 0, no inpainting. in->boxes, masks and the
+ * embedding pointers are NULL and in->Ng = (tok_resize / 32)^2. The trainable set (trainer.py:189-245) is every "*.fuser.*" key,
+ * "position_net.*" (the whole ConvNeXt backbone included), "downsample_net.*" and, with extra_channels > 0,
+ * "input_blocks.0.0.weight" -- its bias stays frozen; any other non-NULL grads entry is rejected. The tokenizer's and the
+ * downsampler's gradients are the step's last (gl_train_wait_grads milestone = number of SpatialTransformers). */
+typedef struct gl_train_spatial_in {
+    const float* map;                   /* the tokenizer's map [B][map_channels][map_h][map_w] (canny_edge, hed_edge, depth, normal, sem) */
+    int map_channels, map_h, map_w;
+    const float* mask;                  /* [B] */
+    const float* extra;                 /* grounding_extra_input [B][extra_in_channels][extra_h][extra_w]; NULL iff extra_channels == 0 */
+    int extra_in_channels, extra_h, extra_w;
+    int ds_resize;                      /* the downsampler's resize_input (hed: 64) */
+    int ds_mode;                        /* 0 bicubic, 1 nearest (sem) */
+    int ds_n_in;                        /* channels of grounding_extra_input it reads (1 grey maps, 3 normal, 152 sem) */
+    int ds_mid;                         /* channels of its first 4x4 stride-2 conv (4, sem 16); 0: no layers (hed) */
+} gl_train_spatial_in;
+int gl_unet_train_step_spatial(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, const gl_train_spatial_in* sp, int n_params,
+                               const char* const* names, const float* const* params, float* const* grads, float* eps_out, float* loss, gl_stream s);
+
 /* Operand copies of the FROZEN parameters across training steps (reference trainer.py:217-245: only fuser.* / position_net.* are ever
  * updated). gl_unet_train_step multiplies every fp32 weight as (hi | hi | lo) bf16 operands -- rows for the forward, transposes for the
  * data gradient, packed / flipped filters for the convs --, built per product. With the cache enabled those copies are built once for every

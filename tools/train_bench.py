@@ -1,6 +1,8 @@
 """Wall time of one training iteration (gl_unet_train_step: forward + loss + backward) of the correctness path, per configuration:
 small UNet at a 16 x 16 latent, the shipped topology at 16 x 16 and at the real 64 x 64 latent. Synthetic inputs, seeded weights.
-   PYTHONPATH=. python tools/train_bench.py [--full64]"""
+--spatial MODALITY: the shipped topology with that spatial-map tokenizer (ConvNeXt-tiny, resize 256: 64 tokens) and grounding
+downsampler instead (gl_unet_train_step_spatial), B = 4, 64 x 64 latent, checkpoint=True.
+   PYTHONPATH=. python tools/train_bench.py [--full64] [--spatial {canny,depth,normal,hed,sem}]"""
 import json
 import sys
 import time
@@ -38,7 +40,47 @@ def run(name, cfg, B, hw, reps, eng, checkpoint=False, cache=False):
         eng.train_weight_cache(False)
 
 
+def run_spatial(modality, B, hw, reps, checkpoint=True):
+    """The shipped topology (syn.UNET_CFG) with a spatial-map tokenizer and its downsampler (configs/cc3m_canny.yaml etc.)."""
+    from ldm.modules.diffusionmodules.openaimodel import UNetModel
+    from gligen_amd.engine import SPATIAL_MAP_KEYS
+    from gligen_amd.train import trainable_names
+    ds_params = dict(out_dim=1) if modality == "hed" else dict(resize_input=4 * hw, out_dim=8)
+    tk_params = dict(resize_input=256, out_dim=768)
+    if modality == "sem":
+        ds_params["in_dim"], tk_params["in_dim"] = 152, 152
+    cfg = dict(syn.UNET_CFG, grounding_downsampler=dict(target=f"ldm.modules.diffusionmodules.{modality}_grounding_downsampler.GroundingDownsampler", params=ds_params),
+               grounding_tokenizer=dict(target=f"ldm.modules.diffusionmodules.{modality}_grounding_net.PositionNet", params=tk_params))
+    m = UNetModel(**dict(cfg, inpaint_mode=False))
+    shapes = {k: tuple(v.shape) for k, v in m.state_dict().items()}
+    del m
+    eng = Engine(0, arena_gb=160.0)
+    sd = {k: v.float().to(eng.device).contiguous() for k, v in syn.seeded_state_dict(shapes, 1234).items()}
+    img = syn.make_spatial_map(modality, B, 256, seed=3)
+    batch = {SPATIAL_MAP_KEYS[modality]: img, "mask": torch.ones(B, 1), "grounding_extra_input": img, "x": syn.make_latent(B, 4, hw, hw, seed=6),
+             "timesteps": torch.tensor([981, 441, 300, 77][:B]).float(), "context": syn.make_context(B, seed=6), "target": syn.make_latent(B, 4, hw, hw, seed=7)}
+    grads = {k: torch.zeros_like(sd[k]) for k in trainable_names(sd, cfg)}
+    eng.unet_train_step(cfg, sd, batch, grads=grads, checkpoint=checkpoint)     # warm-up (GEMM tile selection)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    for _ in range(reps):
+        loss, _, _ = eng.unet_train_step(cfg, sd, batch, grads=grads, checkpoint=checkpoint)
+    torch.cuda.synchronize()
+    dt = (time.time() - t0) / reps
+    print(json.dumps(dict(config=f"shipped topology, {modality} tokenizer + downsampler", B=B, latent=hw, tok_resize=256, checkpoint=bool(checkpoint),
+                          s_per_iteration=round(dt, 4), loss=float(loss), arena_high_water_gb=round(eng.arena_high_water() / 2 ** 30, 2),
+                          trainable_values=sum(int(g.numel()) for g in grads.values()))), flush=True)
+
+
 if __name__ == "__main__":
+    if "--spatial" in sys.argv:
+        modality = sys.argv[sys.argv.index("--spatial") + 1]
+        if "--full64" in sys.argv:
+            run("shipped topology", syn.UNET_CFG, 4, 64, 1, Engine(0, arena_gb=1.0), checkpoint=True)     # the text model's line, same box
+            run_spatial(modality, 4, 64, 1)
+        else:
+            run_spatial(modality, 1, 16, 2)
+        sys.exit(0)
     eng = Engine(0, arena_gb=160.0)
     if "--b4only" in sys.argv:          # the profiled line (tools/gpu_run.sh train with TRAIN_PROF=1): the bench line's train_step shape
         run("shipped topology", syn.UNET_CFG, 4, 64, 2, eng, checkpoint=True)
