@@ -35,6 +35,10 @@ class VaeConfig(C.Structure):
     ]
 
 
+class ClipTextConfig(C.Structure):   # = gl_clip_text_config
+    _fields_ = [(n, C.c_int) for n in ("vocab", "width", "heads", "layers", "intermediate", "max_positions")] + [("ln_eps", C.c_float)]
+
+
 class Grounding(C.Structure):
     _fields_ = [
         ("n", C.c_int),
@@ -91,6 +95,8 @@ SYMBOLS = {
     "gl_vae_configure": (_I, [_P, C.POINTER(VaeConfig)]),
     "gl_weight_upload": (_I, [_P, C.c_char_p, _P, _I, C.POINTER(C.c_int64), _I]),
     "gl_finalize": (_I, [_P]),
+    "gl_clip_text_configure": (_I, [_P, C.POINTER(ClipTextConfig)]),
+    "gl_clip_text_encode": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
     "gl_unet_set_cond": (_I, [_P, _I, _P, _I, C.POINTER(Grounding), _P]),
     "gl_unet_set_fuser_scale": (_I, [_P, C.c_float, _P]),
     "gl_unet_set_fuser_scales": (_I, [_P, C.POINTER(C.c_float), _I, _P]),

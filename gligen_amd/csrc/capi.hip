@@ -131,6 +131,21 @@ int gl_finalize(gl_ctx* ctx) {
     GL_API_END
 }
 
+int gl_clip_text_configure(gl_ctx* ctx, const gl_clip_text_config* cfg) {
+    NEED(ctx);
+    if (!cfg) return gl::set_error(GL_ERR_ARG, "null config");
+    GL_API_BEGIN
+    ctx->eng->configure_clip_text(*cfg);
+    GL_API_END
+}
+
+int gl_clip_text_encode(gl_ctx* ctx, const int32_t* ids, const int32_t* eos_index, int n_seq, int n_tok, float* last_hidden, float* pooled, gl_stream s) {
+    NEED(ctx);
+    GL_API_BEGIN
+    ctx->eng->clip_text_encode(ids, eos_index, n_seq, n_tok, last_hidden, pooled, S(s));
+    GL_API_END
+}
+
 int gl_unet_set_cond(gl_ctx* ctx, int Beff, const float* context, int n_ctx_tokens, const gl_grounding* g, gl_stream s) {
     NEED(ctx);
     if (!context || !g) return gl::set_error(GL_ERR_ARG, "null context/grounding");

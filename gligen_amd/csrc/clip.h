@@ -1,0 +1,25 @@
+// CLIP text tower (transformers CLIPTextModel, the reference's FrozenCLIPEmbedder: ldm/modules/encoders/modules.py:144-173): the
+// kernels around the bf16 GEMMs -- embedding gather, residual add + LayerNorm on the fp32 residual stream, causal attention at
+// head dim 64, EOS-row pooling. The layer schedule is Engine::clip_text_encode (engine.hip).
+#pragma once
+#include "common.h"
+
+namespace gl {
+
+constexpr int kClipMaxTokens = 96;   // clip_attn_kernel keeps a whole head (three 32-token tiles) in LDS
+constexpr int kClipHeadDim = 64;
+constexpr int kClipMaxWidth = 2048;  // clip_add_ln_kernel: one wave per row, at most 8 float4 per lane
+
+// h[row][:] = token_embedding[ids[row]] + position_embedding[row % T] (fp32). An id outside [0, vocab) reads row 0 / vocab - 1
+// instead and is counted in *bad (device counter, may be null).
+int clip_embed_launch(const int32_t* ids, const float* tok, const float* pos, float* h, int rows, int T, int width, int vocab, unsigned* bad,
+                      hipStream_t stream);
+// h += delta (delta may be null), then y = LayerNorm(h; gamma, beta): bf16 rows (ybf, the next GEMM's operand) or fp32 rows (yf32)
+int clip_add_ln_launch(float* h, const float* delta, const float* gamma, const float* beta, float eps, bf16* ybf, float* yf32, int rows, int width,
+                       hipStream_t stream);
+// o[s][t][h * 64 ..] = softmax(q k^T / 8 (+ causal mask)) v per (sequence, head); qkv [S * T][3 * heads * 64] bf16 rows = [q | k | v]
+int clip_attn_launch(const bf16* qkv, bf16* o, int S, int T, int heads, int causal, hipStream_t stream);
+// pooled[s][:] = x[s * T + clamp(eos[s], 0, T - 1)][:]
+int clip_pool_launch(const float* x, const int32_t* eos, float* pooled, int S, int T, int width, hipStream_t stream);
+
+}  // namespace gl

@@ -62,6 +62,10 @@ __device__ __forceinline__ bf16 f2bf(float v) { return (bf16)v; }
 __device__ __forceinline__ float silu_f(float v) {
     return v * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(v * -1.4426950408889634f));
 }
+// CLIP's "quick_gelu": x * sigmoid(1.702 x); the same exp2 + hardware-reciprocal form as silu_f
+__device__ __forceinline__ float quick_gelu_f(float v) {
+    return v * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(v * (-1.702f * 1.4426950408889634f)));
+}
 // erf GELU, as torch F.gelu default (reference ldm/modules/attention.py:44). erf by Abramowitz & Stegun
 // 7.1.26 (|abs error| <= 1.5e-7, far below the bf16 output's 4e-3 relative step): 2 transcendental +
 // ~10 plain VALU ops instead of libm erff's ~30 on the GEGLU epilogue's critical path.

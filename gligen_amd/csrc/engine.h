@@ -11,6 +11,7 @@
 #include <vector>
 
 #include "attention.h"
+#include "clip.h"
 #include "common.h"
 #include "convnext.h"
 #include "ffn.h"
@@ -166,6 +167,7 @@ class Engine {
     void upload(const std::string& key, const void* src, int ndim, const int64_t* shape, bool is_device);
     void configure_unet(const gl_unet_config& c);
     void configure_vae(const gl_vae_config& c);
+    void configure_clip_text(const gl_clip_text_config& c);
     void finalize();
     bool finalized() const { return finalized_; }
 
@@ -185,6 +187,9 @@ class Engine {
     void vae_decode(int B, int h, int w, const float* z, float* out, hipStream_t s);
     void vae_encode(int B, int H, int W, const float* img, const float* noise, float* z, hipStream_t s);
     bool has_vae_encoder() const { return has_venc_; }
+    // CLIPTextModel.forward (reference ldm/modules/encoders/modules.py:144-173): ids [S][T] int32, eos_index [S] (the row HF pools)
+    // -> last_hidden fp32 [S][T][width], pooled fp32 [S][width] (may be null). S is chunked to what the arena holds.
+    void clip_text_encode(const int32_t* ids, const int32_t* eos_index, int S, int T, float* last_hidden, float* pooled, hipStream_t s);
     void sample_plms(const gl_plms_args& a, hipStream_t s);
     void sampler_timing(float* avg_ms, float* first_ms, int* n);
 
@@ -396,6 +401,21 @@ class Engine {
     const float* qc_w_ = nullptr;
     const float* qc_b_ = nullptr;
     void build_vae_encoder();
+
+    // ---- CLIP text tower (pre-LN transformer: LN1 -> q,k,v -> causal attention -> out + residual -> LN2 -> fc1 quick-GELU -> fc2 + residual).
+    // The layer routine takes width / heads / tokens / causal from here and from its arguments, not from constants.
+    struct ClipLayerW { NormW ln1, ln2; LinW qkv, out, fc1, fc2; };
+    bool has_clip_ = false;
+    gl_clip_text_config ccfg_{};
+    const float* clip_tok_ = nullptr;      // [vocab][width] fp32, as uploaded
+    const float* clip_pos_ = nullptr;      // [max_positions][width] fp32
+    std::vector<ClipLayerW> clip_layers_;
+    NormW clip_final_ln_;
+    unsigned* clip_bad_ids_ = nullptr;     // device counter: ids outside [0, vocab) met (and clamped) by clip_embed_kernel
+    void build_clip_text();
+    // one pre-LN transformer stack over M = S * T rows of the fp32 residual stream `h` (tmp: fp32 [M][width] scratch); leaves the
+    // last sub-layer's output in tmp, still to be added: returns it (the final LayerNorm's launch does the add)
+    const float* clip_layers_run(float* h, float* tmp, int S, int T, bool causal, hipStream_t s);
 
     // ---- sampler state
     struct Sampler {

@@ -302,6 +302,140 @@ void Engine::configure_vae(const gl_vae_config& c) {
     has_vae_ = true;
 }
 
+// ---------------------------------------------------------------- CLIP text tower
+void Engine::configure_clip_text(const gl_clip_text_config& c) {
+    if (c.vocab < 1 || c.layers < 1 || c.heads < 1 || c.width < 1 || c.intermediate < 1 || c.max_positions < 1 || !(c.ln_eps > 0.f))
+        throw GlError(GL_ERR_ARG, fmt("clip text config: vocab %d, width %d, heads %d, layers %d, intermediate %d, max_positions %d, ln_eps %g must all be positive",
+                                      c.vocab, c.width, c.heads, c.layers, c.intermediate, c.max_positions, c.ln_eps));
+    if (c.width % c.heads || c.width / c.heads != kClipHeadDim)
+        throw GlError(GL_ERR_UNSUPPORTED, fmt("clip text tower: head dim %d (width %d / %d heads) is not supported: clip_attn_kernel is built for head dim %d",
+                                              c.width / c.heads, c.width, c.heads, kClipHeadDim));
+    if (c.width > kClipMaxWidth) throw GlError(GL_ERR_UNSUPPORTED, fmt("clip text tower: width %d exceeds %d", c.width, kClipMaxWidth));
+    if (c.intermediate % 64) throw GlError(GL_ERR_UNSUPPORTED, fmt("clip text tower: intermediate size %d is not a multiple of 64", c.intermediate));
+    if (c.max_positions > kClipMaxTokens)
+        throw GlError(GL_ERR_UNSUPPORTED, fmt("clip text tower: max_positions %d exceeds the %d tokens clip_attn_kernel holds", c.max_positions, kClipMaxTokens));
+    ccfg_ = c;
+    has_clip_ = true;
+}
+
+// Weights under "text_encoder/" + the checkpoint's key (transformers 4.x layout: transformer.text_model.*)
+void Engine::build_clip_text() {
+    const gl_clip_text_config& c = ccfg_;
+    const std::string P = "text_encoder/transformer.text_model.";
+    auto expect = [&](const std::string& key, int64_t d0, int64_t d1) {
+        const RawTensor& t = raw(key);
+        const int64_t a = t.shape.empty() ? 0 : t.shape[0], b = t.shape.size() > 1 ? t.shape[1] : 0;
+        if (a != d0 || (d1 && b != d1))
+            throw GlError(GL_ERR_ARG, fmt("'%s' has shape [%lld, %lld], the configuration expects [%lld, %lld]", key.c_str(), (long long)a, (long long)b, (long long)d0, (long long)d1));
+    };
+    expect(P + "embeddings.token_embedding.weight", c.vocab, c.width);
+    expect(P + "embeddings.position_embedding.weight", c.max_positions, c.width);
+    clip_tok_ = FK(P + "embeddings.token_embedding.weight");
+    clip_pos_ = FK(P + "embeddings.position_embedding.weight");
+    clip_layers_.clear();
+    for (int l = 0; l < c.layers; ++l) {
+        const std::string L = P + "encoder.layers." + std::to_string(l) + ".";
+        ClipLayerW w;
+        w.ln1 = norm(L + "layer_norm1");
+        w.ln2 = norm(L + "layer_norm2");
+        for (const char* n : {"q_proj", "k_proj", "v_proj", "out_proj"}) {
+            expect(L + "self_attn." + n + ".weight", c.width, c.width);
+            expect(L + "self_attn." + n + ".bias", c.width, 0);
+        }
+        expect(L + "mlp.fc1.weight", c.intermediate, c.width);
+        expect(L + "mlp.fc2.weight", c.width, c.intermediate);
+        if (w.ln1.C != c.width || w.ln2.C != c.width) throw GlError(GL_ERR_ARG, "'" + L + "layer_norm*' does not match the configured width");
+        // [q_proj ; k_proj ; v_proj] rows: one GEMM writes the rows [q | k | v] that clip_attn_kernel slices per head
+        w.qkv.w = cast_rows({L + "self_attn.q_proj.weight", L + "self_attn.k_proj.weight", L + "self_attn.v_proj.weight"});
+        w.qkv.N = 3 * c.width;
+        w.qkv.K = c.width;
+        float* b3 = reinterpret_cast<float*>(persist((size_t)3 * c.width * sizeof(float), false));
+        const char* names[3] = {"q_proj", "k_proj", "v_proj"};
+        for (int i = 0; i < 3; ++i)
+            HIPCK(hipMemcpy(b3 + (size_t)i * c.width, F(L + "self_attn." + names[i] + ".bias"), (size_t)c.width * sizeof(float), hipMemcpyDeviceToDevice));
+        w.qkv.b = b3;
+        w.out = linear(L + "self_attn.out_proj");
+        w.fc1 = linear(L + "mlp.fc1");
+        w.fc2 = linear(L + "mlp.fc2");
+        clip_layers_.push_back(w);
+    }
+    clip_final_ln_ = norm(P + "final_layer_norm");
+    if (clip_final_ln_.C != c.width) throw GlError(GL_ERR_ARG, "'" + P + "final_layer_norm' does not match the configured width");
+    clip_bad_ids_ = reinterpret_cast<unsigned*>(persist(sizeof(unsigned), true));
+}
+
+// Seven launches per layer. The residual stream stays in fp32 (torch's autocast, the yardstick of the parity tests, adds bf16 linear
+// outputs into an fp32 residual): the out-projection and fc2 write fp32 rows (bias included) that the NEXT LayerNorm's launch adds
+// into the stream before it normalises -- clip_add_ln_kernel reads and writes the stream once per sub-layer. That is why the
+// LayerNorms are not folded into the GEMMs behind them here (gemm.h: the folded form takes its row statistics from the bf16 GEMM
+// that produced the rows).
+const float* Engine::clip_layers_run(float* h, float* tmp, int S, int T, bool causal, hipStream_t s) {
+    const gl_clip_text_config& c = ccfg_;
+    const int M = S * T, W = c.width, I = c.intermediate;
+    const size_t Mp = (size_t)round_up(M, 256);   // (whole GEMM tiles of rows exist behind every operand)
+    bf16* xn = arena_.get<bf16>(Mp * W);
+    bf16* qkv = arena_.get<bf16>(Mp * 3 * W);
+    bf16* ao = arena_.get<bf16>(Mp * W);
+    bf16* f1 = arena_.get<bf16>(Mp * I);
+    auto lin = [&](const bf16* x, const LinW& L, void* out, bool f32, int act) {
+        AOperand A;
+        aoperand_rows(A, x, L.K, L.K);
+        Epilogue E;
+        epilogue_defaults(E);
+        E.out = out; E.ldo = L.N; E.out_f32 = f32 ? 1 : 0; E.bias = L.b; E.act = act;
+        gemm(A, L.w, M, L.N, L.K, E, s);
+    };
+    const float* delta = nullptr;
+    for (const ClipLayerW& w : clip_layers_) {
+        CK(clip_add_ln_launch(h, delta, w.ln1.g, w.ln1.b, c.ln_eps, xn, nullptr, M, W, s));
+        lin(xn, w.qkv, qkv, false, ACT_NONE);
+        {
+            ProfScope ps(this, s, "clip_attn_kernel", 4.0 * S * c.heads * (double)T * T * kClipHeadDim, 0.0);
+            CK(clip_attn_launch(qkv, ao, S, T, c.heads, causal ? 1 : 0, s));
+        }
+        lin(ao, w.out, tmp, true, ACT_NONE);
+        CK(clip_add_ln_launch(h, tmp, w.ln2.g, w.ln2.b, c.ln_eps, xn, nullptr, M, W, s));
+        lin(xn, w.fc1, f1, false, ACT_QUICK_GELU);
+        lin(f1, w.fc2, tmp, true, ACT_NONE);
+        delta = tmp;
+        n_launches += 3;   // two add + LayerNorm launches, one attention (gemm() counts its own)
+    }
+    return delta;
+}
+
+void Engine::clip_text_encode(const int32_t* ids, const int32_t* eos_index, int S, int T, float* last_hidden, float* pooled, hipStream_t s) {
+    if (!has_clip_ || !finalized_) throw GlError(GL_ERR_STATE, "clip text tower not configured / finalized");
+    if (!ids || !last_hidden || (pooled && !eos_index)) throw GlError(GL_ERR_ARG, "clip_text_encode: null ids / output (pooled needs eos_index)");
+    const gl_clip_text_config& c = ccfg_;
+    if (S < 1 || T < 1 || T > c.max_positions)
+        throw GlError(GL_ERR_ARG, fmt("clip_text_encode: %d sequences of %d tokens (1 <= tokens <= max_positions %d)", S, T, c.max_positions));
+    const int W = c.width;
+    // activation bytes of one chunk of Sc sequences: fp32 stream + fp32 scratch + bf16 [LN | q,k,v | attention | fc1] rows, row count
+    // rounded up to whole GEMM tiles, + the allocator's alignment
+    auto need = [&](int Sc) { return (size_t)round_up(Sc * T, 256) * ((size_t)W * (4 + 4 + 2 + 6 + 2) + (size_t)c.intermediate * 2) + 8 * 256; };
+    const size_t mk = arena_.mark();
+    const size_t avail = arena_.capacity() - std::min(arena_.capacity(), (mk + 255) & ~size_t(255));
+    int Sc = S;
+    while (Sc > 1 && need(Sc) > avail) Sc = (Sc + 1) / 2;
+    if (need(Sc) > avail) throw GlError(GL_ERR_STATE, fmt("clip_text_encode: the arena (%zu bytes free) does not hold one sequence (%zu bytes)", avail, need(1)));
+    for (int s0 = 0; s0 < S; s0 += Sc) {
+        const int n = std::min(Sc, S - s0), M = n * T;
+        const size_t Mp = (size_t)round_up(M, 256);
+        float* h = arena_.get<float>(Mp * W);
+        float* tmp = arena_.get<float>(Mp * W);
+        CK(clip_embed_launch(ids + (size_t)s0 * T, clip_tok_, clip_pos_, h, M, T, W, c.vocab, clip_bad_ids_, s));
+        const float* delta = clip_layers_run(h, tmp, n, T, true, s);
+        float* out = last_hidden + (size_t)s0 * T * W;
+        CK(clip_add_ln_launch(h, delta, clip_final_ln_.g, clip_final_ln_.b, c.ln_eps, nullptr, out, M, W, s));
+        n_launches += 2;
+        if (pooled) {
+            CK(clip_pool_launch(out, eos_index + s0, pooled + (size_t)s0 * W, n, T, W, s));
+            ++n_launches;
+        }
+        arena_.release(mk);
+    }
+}
+
 // ---------------------------------------------------------------- weight packing
 NormW Engine::norm(const std::string& p) {
     NormW n;
@@ -968,6 +1102,7 @@ void Engine::finalize() {
     if (has_unet_) build_unet();
     if (has_vae_) build_vae();
     if (has_vae_ && has("vae/encoder.conv_in.weight")) build_vae_encoder();
+    if (has_clip_) build_clip_text();
     HIPCK(hipDeviceSynchronize());
     for (void* p : fold_tmps_) (void)hipFree(p);   // fp32 W * gamma / b + W beta temporaries of the folded LayerNorms
     fold_tmps_.clear();

@@ -94,6 +94,9 @@ __device__ __forceinline__ void epi_finish4(const Epilogue& E, int m, int n0, fl
     } else if (E.act == ACT_GELU) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = gelu_erf_f(v[i]);
+    } else if (E.act == ACT_QUICK_GELU) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = quick_gelu_f(v[i]);
     }
     switch (E.mode) {
         case EPI_ROWMAJOR: {
@@ -162,6 +165,9 @@ __device__ __forceinline__ void epi_store4(const Epilogue& E, int m, int n0, flo
     } else if (WITH_GELU && E.act == ACT_GELU) {
 #pragma unroll
         for (int i = 0; i < 4; ++i) v[i] = gelu_erf_f(v[i]);
+    } else if (WITH_GELU && E.act == ACT_QUICK_GELU) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) v[i] = quick_gelu_f(v[i]);
     }
     switch (E.mode) {
         case EPI_ROWMAJOR: {
@@ -1290,7 +1296,7 @@ gemm_u_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Epilo
     constexpr int EPW = 16 * RS;                   // bytes per wave
     static_assert(WMW * 2 * (EPW + 16 * LPR * 8) <= STAGE, "epilogue staging (+ row-statistics scratch) does not fit one ring slot");
     auto epilogue_staged = [&](int tm, int tn, int slot_done) -> bool {
-        if (wd.splits > 1 || E.mode != EPI_ROWMAJOR || E.out_f32 || (N & 7) || (E.act == ACT_GEGLU && (TN & 1)) || E.act == ACT_GELU) return false;
+        if (wd.splits > 1 || E.mode != EPI_ROWMAJOR || E.out_f32 || (N & 7) || (E.act == ACT_GEGLU && (TN & 1)) || E.act == ACT_GELU || E.act == ACT_QUICK_GELU) return false;
         if (E.res && E.act == ACT_SILU) return false;   // (no caller combines them; the fragment-layout epilogue handles it)
         unsigned char* ep = smem + slot_done * STAGE + wave * EPW;
         if constexpr ((TN & 1) == 0) {
@@ -1561,7 +1567,7 @@ splitk_reduce_kernel(const float* __restrict__ ws, int splits, int M, int N, Epi
             // Row-major bf16 outputs (every split-K conv and projection of the UNet): bias, per-sample bias, residual and gate are
             // requested BEFORE the slabs, unconditionally (an absent operand reads the slab area and is never used -- behind
             // `if (E.res)` hipcc would unpack inside the branch and wait there); they arrive while the slabs are summed
-            const bool fast = E.mode == EPI_ROWMAJOR && !E.out_f32 && !E.remap_in && E.act != ACT_GELU && !E.ln_stats;
+            const bool fast = E.mode == EPI_ROWMAJOR && !E.out_f32 && !E.remap_in && E.act != ACT_GELU && E.act != ACT_QUICK_GELU && !E.ln_stats;
             // (no `if (fast)` around the loads either: a value that is "loaded or zero" is the pattern that gets waited for in place)
             const float4 pb = *reinterpret_cast<const float4*>((fast && E.bias) ? E.bias + n0 : ws);
             const float4 pb2 = *reinterpret_cast<const float4*>((fast && E.bias2) ? E.bias2 + (size_t)div_rpb(E, m) * E.bias2_ld + n0 : ws);
@@ -2818,7 +2824,7 @@ int gemm_p_launch(const AOperand& A, const bf16* W, int M, int N, int K, const E
         // row statistics for a folded LayerNorm downstream: only the staged row-major epilogue of gemm_u_kernel produces them
         // (one partial per row and wave column block of tn * 16 columns)
         g_last_stats_nb = (E.stats_out && use_u && wd.splits == 1 && A.mode == A_ROWS && E.mode == EPI_ROWMAJOR && !E.out_f32 && E.act != ACT_GEGLU &&
-                           E.act != ACT_GELU && !(E.res && E.act == ACT_SILU) /* (epilogue_staged does not take that combination) */ &&
+                           E.act != ACT_GELU && E.act != ACT_QUICK_GELU && !(E.res && E.act == ACT_SILU) /* (epilogue_staged does not take that combination) */ &&
                            N % (tn * 16) == 0 && N / (tn * 16) <= E.stats_ld)
                               ? N / (tn * 16) : 0;
         if (E.ln_stats && (!use_u || A.mode != A_ROWS || wd.splits > 1 || (tm == 4 && tn == 5) || (E.mode != EPI_QKV_HEADS && E.mode != EPI_QK_HEADS)))
@@ -3052,8 +3058,8 @@ int gemm_launch(const AOperand& A, const bf16* W, int M, int N, int K, const Epi
     }
     if (A.mode == A_CONV3 && (E.gate || E.remap_in))
         return set_error(GL_ERR_UNSUPPORTED, "conv3x3: the gated residual and the row remap are row-GEMM epilogues");
-    if (E.act == ACT_GELU && (E.res || E.bias2 || A.mode != A_ROWS))
-        return set_error(GL_ERR_UNSUPPORTED, "gemm: the GELU epilogue has no residual / broadcast-bias form");
+    if ((E.act == ACT_GELU || E.act == ACT_QUICK_GELU) && (E.res || E.bias2 || A.mode != A_ROWS))
+        return set_error(GL_ERR_UNSUPPORTED, "gemm: the GELU / quick-GELU epilogues have no residual / broadcast-bias form");
     if (E.act == ACT_GEGLU && (N % 32 != 0 || E.mode != EPI_ROWMAJOR))
         return set_error(GL_ERR_ARG, "gemm: GEGLU epilogue needs packed N %% 32 == 0 (N=%d)", N);
     if (E.act == ACT_GEGLU && E.geglu16 != gemm_geglu_layout())

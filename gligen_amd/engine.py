@@ -79,6 +79,7 @@ class Engine:
         check(self.lib.gl_ctx_create(self.device.index, C.c_size_t(int(arena_gb * (1 << 30))), C.byref(self._ctx)))
         self.unet_cfg: Optional[dict] = None
         self.vae_cfg: Optional[dict] = None
+        self.clip_cfg: Optional[dict] = None
         self._keep: list = []
 
     def fork(self, arena_gb: Optional[float] = None) -> "Engine":
@@ -147,6 +148,30 @@ class Engine:
         cfg.scale_factor = float(scale_factor)
         check(self.lib.gl_vae_configure(self._ctx, C.byref(cfg)))
         self.vae_cfg = dict(out_ch=out_ch, z_channels=z_channels, n_up=len(ch_mult) - 1)
+
+    def configure_clip_text(self, *, vocab, width, heads, layers, intermediate, max_positions, ln_eps=1e-5) -> None:
+        """The CLIP text tower (transformers CLIPTextConfig: vocab_size, hidden_size, num_attention_heads, num_hidden_layers,
+        intermediate_size, max_position_embeddings, layer_norm_eps); weights go under the namespace 'text_encoder'."""
+        cfg = _lib.ClipTextConfig()
+        cfg.vocab, cfg.width, cfg.heads, cfg.layers = int(vocab), int(width), int(heads), int(layers)
+        cfg.intermediate, cfg.max_positions, cfg.ln_eps = int(intermediate), int(max_positions), float(ln_eps)
+        check(self.lib.gl_clip_text_configure(self._ctx, C.byref(cfg)))
+        self.clip_cfg = dict(vocab=int(vocab), width=int(width), max_positions=int(max_positions))
+
+    def clip_text_encode(self, ids: torch.Tensor, eos_index: torch.Tensor):
+        """ids [S, T] integer token ids, eos_index [S] (the position HF pools) -> (last_hidden [S, T, width], pooled [S, width]), fp32."""
+        if ids.dim() != 2 or eos_index.shape != (ids.shape[0],):
+            raise ValueError("clip_text_encode: ids [S, T] and one eos index per sequence")
+        S, T = int(ids.shape[0]), int(ids.shape[1])
+        host = ids.detach().cpu()
+        if S == 0 or int(host.min()) < 0 or int(host.max()) >= self.clip_cfg["vocab"]:
+            raise ValueError(f"clip_text_encode: token ids must lie in [0, {self.clip_cfg['vocab']})")
+        ids = ids.to(device=self.device, dtype=torch.int32).contiguous()
+        eos = eos_index.to(device=self.device, dtype=torch.int32).contiguous()
+        hidden = torch.empty((S, T, self.clip_cfg["width"]), device=self.device, dtype=torch.float32)
+        pooled = torch.empty((S, self.clip_cfg["width"]), device=self.device, dtype=torch.float32)
+        check(self.lib.gl_clip_text_encode(self._ctx, _ptr(ids), _ptr(eos), S, T, _ptr(hidden), _ptr(pooled), _stream(self.device)))
+        return hidden, pooled
 
     def upload(self, namespace: str, state_dict: Mapping[str, torch.Tensor], prefix_filter: Optional[str] = None) -> int:
         """Upload fp32 parameters under '<namespace>/<reference state_dict key>'."""

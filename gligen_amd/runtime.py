@@ -71,6 +71,57 @@ def build_unet_engine(model, arena_gb: float = 12.0) -> Engine:
     return eng
 
 
+CLIP_TEXT_PREFIX = "transformer.text_model."
+
+
+def clip_text_keys(layers: int):
+    """The text tower's tensors under the key names GLIGEN checkpoints carry (transformers 4.x: 4 + 16 per layer)."""
+    keys = [CLIP_TEXT_PREFIX + "embeddings.token_embedding.weight", CLIP_TEXT_PREFIX + "embeddings.position_embedding.weight"]
+    for l in range(layers):
+        p = f"{CLIP_TEXT_PREFIX}encoder.layers.{l}."
+        for m in ("self_attn.k_proj", "self_attn.v_proj", "self_attn.q_proj", "self_attn.out_proj", "layer_norm1", "mlp.fc1", "mlp.fc2", "layer_norm2"):
+            keys += [p + m + ".weight", p + m + ".bias"]
+    return keys + [CLIP_TEXT_PREFIX + "final_layer_norm.weight", CLIP_TEXT_PREFIX + "final_layer_norm.bias"]
+
+
+def clip_text_upload_dict(state_dict: Mapping[str, torch.Tensor], layers: int) -> Dict[str, torch.Tensor]:
+    """What the engine is given for a FrozenCLIPEmbedder state_dict in either key layout (transformers 4.x wraps the tower in
+    `.text_model`, 5.x does not): the checkpoint's names, `position_ids` (a buffer of old versions) dropped, strictly -- a missing
+    or an unknown tensor raises."""
+    seen = {}
+    for k, v in state_dict.items():
+        if k.endswith("position_ids"):
+            continue
+        if k.startswith("transformer.") and not k.startswith(CLIP_TEXT_PREFIX):
+            k = CLIP_TEXT_PREFIX + k[len("transformer."):]
+        seen[k] = v
+    want = clip_text_keys(layers)
+    missing = [k for k in want if k not in seen]
+    extra = sorted(set(seen) - set(want))
+    if missing or extra:
+        raise KeyError(f"text encoder state_dict does not match a {layers}-layer CLIP text tower: missing {missing[:4]}, unexpected {extra[:4]}")
+    return {k: seen[k] for k in want}
+
+
+def build_clip_text_engine(embedder, arena_gb: float = 0.25) -> Engine:
+    """The native text tower of a FrozenCLIPEmbedder: its own engine with a small arena (32 sequences of 77 tokens need ~50 MB)."""
+    dev = module_device(embedder)
+    tower = getattr(embedder.transformer, "text_model", embedder.transformer)
+    cfg = embedder.transformer.config
+    eng = Engine(dev, arena_gb=arena_gb)
+    try:
+        eng.configure_clip_text(vocab=cfg.vocab_size, width=cfg.hidden_size, heads=cfg.num_attention_heads, layers=len(tower.encoder.layers),
+                                intermediate=cfg.intermediate_size, max_positions=cfg.max_position_embeddings, ln_eps=cfg.layer_norm_eps)
+        if cfg.hidden_act != "quick_gelu":
+            raise NotImplementedError(f"CLIP text tower with hidden_act={cfg.hidden_act!r}: the native path implements quick_gelu")
+        eng.upload("text_encoder", clip_text_upload_dict(embedder.state_dict(), len(tower.encoder.layers)))
+        eng.finalize()
+    except Exception:
+        eng.close()
+        raise
+    return eng
+
+
 def build_vae_engine(ae, arena_gb: float = 8.0) -> Engine:
     dev = module_device(ae)
     eng = Engine(dev, arena_gb=arena_gb)

@@ -173,13 +173,27 @@ def batch_to_device(batch, dev):
 
 
 @torch.no_grad()
-def prepare_batch(meta, batch=1, max_objs=30):
+def prepare_batch(meta, batch=1, max_objs=30, text_encoder=None):
+    """text_encoder (run() with native_clip): the phrase features are the pooled rows of the checkpoint's own text tower, one
+    batched call -- the same openai/clip-vit-large-patch14 tower get_clip_feature reads them from; CLIPModel is then loaded only
+    for image-grounded phrases."""
     phrases, images = meta.get("phrases"), meta.get("images")
     n = len(meta["locations"])
     images = [None] * n if images is None else images
     phrases = [None] * n if phrases is None else phrases
     text_features, image_features = meta.get("text_embeddings"), meta.get("image_embeddings")
-    if text_features is None and image_features is None:  # the reference path: encode with CLIP ViT-L/14
+    if text_features is None and image_features is None and text_encoder is not None:
+        said = [i for i, p in enumerate(phrases) if p is not None]
+        text_features = [None] * n
+        if said:
+            pooled = text_encoder.encode([phrases[i] for i in said], return_pooler_output=True)[1]
+            for j, i in enumerate(said):
+                text_features[i] = pooled[j]
+        image_features = [None] * n
+        if any(im is not None for im in images):
+            model, processor = _clip()
+            image_features = [get_clip_feature(model, processor, im, is_image=True) for im in images]
+    elif text_features is None and image_features is None:  # the reference path: encode with CLIP ViT-L/14
         model, processor = _clip()
         text_features = [get_clip_feature(model, processor, p, is_image=False) for p in phrases]
         image_features = [get_clip_feature(model, processor, im, is_image=True) for im in images]
@@ -532,7 +546,13 @@ def run(meta, config, starting_noise=None, models=None):
         gdist.barrier()
         return torch.empty((0, 3, 8 * model.image_size, 8 * model.image_size))
     prepare = next((fn for key, fn in _PREPARE_BY_NAME if key in meta["ckpt"]), prepare_batch)
-    batch = {k: _shard(v, lo, hi) for k, v in prepare(meta, B).items()}
+    native_clip = bool(args.get("native_clip"))
+    if native_clip:      # the text tower on the HIP path (FrozenCLIPEmbedder backend="hip"); it never falls back to torch
+        text_encoder.backend = "hip"
+    if native_clip and prepare is prepare_batch:
+        batch = {k: _shard(v, lo, hi) for k, v in prepare_batch(meta, B, text_encoder=text_encoder).items()}
+    else:
+        batch = {k: _shard(v, lo, hi) for k, v in prepare(meta, B).items()}
     if "grounding_tokens" in meta:   # spatial-map modalities: ConvNeXt tokens computed elsewhere (like precomputed CLIP features)
         batch["tokens"] = _shard(meta["grounding_tokens"].to(device), lo, hi)
     if "context" in meta:  # precomputed CLIP last_hidden_state (B,77,768)
@@ -705,6 +725,7 @@ def main(argv=None):
     parser.add_argument("--synthetic", type=str, default=None, choices=["text", "text_image", "keypoint"],
                         help="run with seeded random weights and features (no checkpoint / CLIP needed)")
     parser.add_argument("--inpaint", action="store_true", help="with --synthetic text: the inpainting model (9-channel first conv, encode + blend)")
+    parser.add_argument("--native_clip", action="store_true", help="run the checkpoint's CLIP text tower (prompt, negative prompt, phrases) in the native HIP engine instead of transformers")
     parser.add_argument("--ckpt", type=str, default=None, help="run only the meta_list entries whose checkpoint path contains this string")
     parser.add_argument("--seed", type=int, default=None, help="seed of x_T (one draw for the whole batch, sliced across ranks)")
     parser.add_argument("--lanes", type=int, default=None, help="with --repeat: whole batches in flight (default 3, the bench's schedule); without: per-GPU batches of 32 and more run as two half-batches in flight unless this is 1")

@@ -73,6 +73,14 @@ typedef struct gl_grounding {
     const float* tokens;         /* [Beff][n][out_dim] grounding tokens  (kind 3) */
 } gl_grounding;
 
+/* CLIPTextConfig of the text tower inside every GLIGEN checkpoint (reference ldm/modules/encoders/modules.py:144-173,
+ * openai/clip-vit-large-patch14: 49408, 768, 12, 12, 3072, 77, 1e-5). Supported: width = heads * 64, intermediate a multiple of
+ * 64, max_positions <= 96; anything else is refused with a message that names the offending value. */
+typedef struct gl_clip_text_config {
+    int vocab, width, heads, layers, intermediate, max_positions;
+    float ln_eps;
+} gl_clip_text_config;
+
 /* One PLMS run (reference ldm/models/diffusion/plms.py:65-162): schedule arrays are host
  * pointers of length n_steps, in sampling order (time descending). */
 typedef struct gl_plms_args {
@@ -127,6 +135,17 @@ int gl_vae_configure(gl_ctx* ctx, const gl_vae_config* cfg);
  * reference state_dict key; data is fp32, host or device. */
 int gl_weight_upload(gl_ctx* ctx, const char* key, const void* data, int ndim, const int64_t* shape, int is_device);
 int gl_finalize(gl_ctx* ctx);
+
+/* FrozenCLIPEmbedder (reference ldm/modules/encoders/modules.py:144-173): transformers' CLIPTextModel -- token + position embedding,
+ * pre-LN transformer layers with a causal mask and quick-GELU MLPs, final LayerNorm. Weights: key = "text_encoder/" + the
+ * checkpoint's key (transformers 4.x names: transformer.text_model.embeddings.token_embedding.weight, ...encoder.layers.N.self_attn.
+ * {q,k,v,out}_proj.{weight,bias}, ...layer_norm{1,2}.*, ...mlp.fc{1,2}.*, ...final_layer_norm.*), packed by the finalize call.
+ * Encode: ids int32 [S][T] (device, T <= max_positions; an id outside the vocabulary is clamped), eos_index int32 [S] (device: the
+ * token whose row is pooled, i.e. the first EOS; may be NULL when pooled is) -> last_hidden fp32 [S][T][width] = last_hidden_state,
+ * pooled fp32 [S][width] = pooler_output (may be NULL). bf16 operands, fp32 accumulation, fp32 residual stream, LayerNorm and
+ * softmax. S is processed in chunks when the arena is small. */
+int gl_clip_text_configure(gl_ctx* ctx, const gl_clip_text_config* cfg);
+int gl_clip_text_encode(gl_ctx* ctx, const int32_t* ids, const int32_t* eos_index, int S, int T, float* last_hidden, float* pooled, gl_stream s);
 
 /* Step-invariant part of UNetModel.forward: position_net(**grounding_input) (openaimodel.py:433),
  * fuser.linear(objs) (attention.py:239) and attn2.to_k/to_v(context) (attention.py:130-131). */
