@@ -16,7 +16,13 @@ struct AttnParams {
     int nqb;             // query blocks (128 rows) per (b,h); filled by attn_launch
     float scale_log2e;   // d^-0.5 * log2(e)
     int vt_layout;       // attn_vt_layout() of the vt buffer: 0 = [DPV of attn_dims][Tk_pad], tokens permuted in 16s; 1 = DPV 48, permuted in 32s
+    // Test-only instrument (gl_attn_regime_counters): a device block of ATTN_CTR_N words that attn3_kernel's counting instantiation adds
+    // to, or nullptr (every production caller: the struct is filled field by field) for the kernel as shipped
+    unsigned* counters = nullptr;
 };
+enum { ATTN_CTR_LAZY_MOVES = 0,   // one per wave per execution of the lazy-move block (d = 40)
+       ATTN_CTR_RERUNS = 1,       // one per workgroup that runs its tiles again with the exact per-tile maximum
+       ATTN_CTR_N = 2 };
 
 // padded head dims used by the q/k (DP) and v^T (DPV) buffers for a real head dim d
 int attn_dims(int d, int* DP, int* DPV);

@@ -675,7 +675,9 @@ __device__ __forceinline__ void lds_rd_v16(bf16x8 (&d)[N], unsigned a) {
 }
 // DP / DPV: padded head dims of the q,k / v^T buffers (48 / 48 at d = 40, 80 / 96 at d = 80); BIAS: the stabiliser rides in the free Q column
 // (d = 40), else it is subtracted in front of the exps. The ones row of V^T is row d (P.d) in both.
-template <int DP, int DPV, bool BIAS, int NW>
+// COUNT (tests only, gl_attn_regime_counters): add to the regime counters of AttnParams::counters. Production is COUNT = false: the
+// statements outside `if constexpr (COUNT)`, i.e. the kernel as it was before the counters existed.
+template <int DP, int DPV, bool BIAS, int NW, bool COUNT>
 __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) attn3_kernel(AttnParams P) {
     static_assert(DP % 16 == 0 && DPV % 16 == 0 && DPV > DP - 8, "tile geometry");
     constexpr int KS = DP / 16;            // k-steps of S^T = K Q^T
@@ -804,6 +806,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) attn3_kernel(AttnPar
                 // the denominators accumulated through tile j - 2 (their MFMAs retired an iteration ago: no wait here): row d of O^T, lanes 16 OG ..
                 const bool big = g4 == OG && (ot[0][OB][ORR] > __builtin_ldexpf(1.f, LAZY_LOG2) || ot[1][OB][ORR] > __builtin_ldexpf(1.f, LAZY_LOG2));
                 if (__builtin_amdgcn_ballot_w64(big) != 0) {
+                    if constexpr (COUNT) { if (lane == 0) atomicAdd(P.counters + ATTN_CTR_LAZY_MOVES, 1u); }
                     const float la = __shfl(ot[0][OB][ORR], 16 * OG + l15, 64), lb = __shfl(ot[1][OB][ORR], 16 * OG + l15, 64);
                     const float lq = lrow < 16 ? la : lb;                        // this lane's query = lane & 31
                     overshoot |= !(lq < 1.0e30f);      // (sticky: the move below brings l back into range, not an O^T entry that has overflowed)
@@ -1011,6 +1014,7 @@ __global__ void __launch_bounds__(NW * 64, NW == 4 ? 2 : 1) attn3_kernel(AttnPar
         __builtin_amdgcn_s_waitcnt(0xC07F);
         __builtin_amdgcn_s_barrier();                       // (the flags are read before the rerun's DMA overwrites them)
         if (any_bad) {
+            if constexpr (COUNT) { if (t == 0) atomicAdd(P.counters + ATTN_CTR_RERUNS, 1u); }
 #pragma unroll
             for (int qh = 0; qh < 2; ++qh)
 #pragma unroll
@@ -1061,7 +1065,8 @@ static int launch_attn3(const AttnParams& P, int B, hipStream_t stream) {
     AttnParams Q = P;
     Q.nqb = cdiv(P.Nq, NW * 32);
     dim3 grid(Q.nqb * P.H * B);
-    hipLaunchKernelGGL((attn3_kernel<DP, DPV, BIAS, NW>), grid, dim3(NW * 64), lds, stream, Q);
+    if (P.counters) hipLaunchKernelGGL((attn3_kernel<DP, DPV, BIAS, NW, true>), grid, dim3(NW * 64), lds, stream, Q);
+    else hipLaunchKernelGGL((attn3_kernel<DP, DPV, BIAS, NW, false>), grid, dim3(NW * 64), lds, stream, Q);
     GL_LAUNCH_CHECK();
     return GL_OK;
 }
@@ -1148,6 +1153,7 @@ int attn_vt_layout(int d, int Nk, int* DPV) {
 }
 
 const char* attn_kernel_name(int d, int Nk, int vt_layout) {
+    // (profile labels: attn3_kernel keeps the four-parameter form that profiles/*/ are keyed by; its COUNT parameter is false there)
     int v2 = attn_use_v2(d, Nk) ? attn_v2_mode() : 0;
     if (vt_layout == 0 && v2 >= 3) v2 = 1;     // a caller whose V^T buffer is in the 16-token form gets the kernel that reads it
     if (d == 40) return v2 == 0 ? "attn_kernel<48, 64, true>" : v2 == 1 ? "attn2_kernel<48, 64, true, 4>" : v2 == 2 ? "attn2_kernel<48, 64, true, 8>" : "attn3_kernel<48, 48, true, 4>";

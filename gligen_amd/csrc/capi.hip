@@ -922,7 +922,19 @@ int gl_op_attention(gl_ctx* ctx, const void* xq, const void* xkv, int B, int Nq,
     P.q = bufs.q; P.k = bufs.k; P.vt = bufs.vt; P.o = (bf16*)o; P.H = H; P.d = d; P.Nq = Nq; P.Nk = Nk;
     P.Tq_pad = bufs.Tq_pad; P.Tk_pad = bufs.Tk_pad; P.ldo = C; P.o_rows_per_b = Nq; P.vt_layout = vt_layout;
     P.scale_log2e = (float)(1.4426950408889634 / std::sqrt((double)d));
+    P.counters = eng.attn_counters();     // nullptr unless gl_attn_regime_counters switched counting on
     ck(attn_launch(P, B, S(s)));
+    GL_API_END
+}
+
+int gl_attn_regime_counters(gl_ctx* ctx, int enable, unsigned* lazy_moves, unsigned* reruns) {
+    NEED(ctx);
+    if (!lazy_moves || !reruns) return gl::set_error(GL_ERR_ARG, "gl_attn_regime_counters: null pointer");
+    GL_API_BEGIN
+    unsigned c[ATTN_CTR_N];
+    ctx->eng->attn_regime_counters(enable, c);
+    *lazy_moves = c[ATTN_CTR_LAZY_MOVES];
+    *reruns = c[ATTN_CTR_RERUNS];
     GL_API_END
 }
 

@@ -200,6 +200,10 @@ class Engine {
     void* persist(size_t bytes, bool zero);
     void init_workspace();
     AttnBufs& attn_bufs(int B, int H, int d, int Tq, int Tk, int dpv_layout = 0, int slot = 0);   // dpv_layout: V^T rows when not attn_dims' (attn_vt_layout)
+    // Regime counters of the attention kernel (gl_attn_regime_counters, tests only): out[ATTN_CTR_N] := the counts since the last call,
+    // the device block is zeroed, and gl_op_attention counts from here on iff enable. Nothing else ever passes the block to a kernel.
+    void attn_regime_counters(int enable, unsigned* out);
+    unsigned* attn_counters() const { return attn_counting_ ? attn_ctr_ : nullptr; }
 
     // GroupNorm32 -> SiLU -> conv3x3 (stride 1, pad 1); out = nullptr: from the arena. GroupNorm-apply + SiLU run inside the conv's
     // loader where conv_halo_kernel takes the problem (gn_prologue_), as a separate pass elsewhere
@@ -373,6 +377,8 @@ class Engine {
 
     typedef std::array<int, 7> AttnKey;            // B, H, d, Tq_pad, Tk_pad, dpv, slot
     std::map<AttnKey, AttnBufs> attn_bufs_;
+    unsigned* attn_ctr_ = nullptr;      // device, ATTN_CTR_N words (allocated by the first attn_regime_counters call)
+    bool attn_counting_ = false;
     std::vector<hipEvent_t> train_events_;
 
     // ---- VAE decoder

@@ -206,6 +206,14 @@ void Engine::init_workspace() {
     ws_ = reinterpret_cast<float*>(persist(ws_bytes_, false));
 }
 
+void Engine::attn_regime_counters(int enable, unsigned* out) {
+    HIPCK(hipDeviceSynchronize());      // every attention launch that counted has finished
+    if (!attn_ctr_) attn_ctr_ = reinterpret_cast<unsigned*>(persist(ATTN_CTR_N * sizeof(unsigned), true));
+    HIPCK(hipMemcpy(out, attn_ctr_, ATTN_CTR_N * sizeof(unsigned), hipMemcpyDeviceToHost));
+    HIPCK(hipMemset(attn_ctr_, 0, ATTN_CTR_N * sizeof(unsigned)));
+    attn_counting_ = enable != 0;
+}
+
 void* Engine::persist(size_t bytes, bool zero) {
     void* p = nullptr;
     HIPCK(hipMalloc(&p, std::max<size_t>(bytes, 256)));
@@ -230,6 +238,8 @@ std::shared_ptr<Engine> Engine::fork(const std::shared_ptr<Engine>& parent, size
     e.ws_bytes_ = 0;
     e.cond_ = Cond{};
     e.attn_bufs_.clear();
+    e.attn_ctr_ = nullptr;
+    e.attn_counting_ = false;
     e.smp_ = Sampler{};
     e.train_events_.clear();
     e.fuser_kv_.clear();

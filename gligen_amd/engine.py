@@ -758,3 +758,10 @@ class Engine:
         check(self.lib.gl_op_attention(self._ctx, _ptr(xq), _ptr(xkv), B, Nq, Nk, Cc, Ck, heads, _ptr(wq), _ptr(wk), _ptr(wv),
                                        _ptr(o), _stream(self.device)))
         return o
+
+    def attn_regime_counters(self, enable):
+        """(lazy_moves, reruns) counted by op_attention since the last call (gl_attn_regime_counters): the counts are reset, and
+        counting is on afterwards iff `enable`. A test instrument: d = 40 only, 0 elsewhere."""
+        lazy, reruns = C.c_uint(0), C.c_uint(0)
+        check(self.lib.gl_attn_regime_counters(self._ctx, 1 if enable else 0, C.byref(lazy), C.byref(reruns)))
+        return lazy.value, reruns.value

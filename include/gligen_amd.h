@@ -448,6 +448,13 @@ int gl_op_layernorm(gl_ctx* ctx, const void* x, const void* x2, int B, int N1, i
  * xq [B][Nq][C], xkv [B][Nk][Ck] bf16, Wq [C][C], Wk/Wv [C][Ck] fp32 (no bias), heads H -> o [B][Nq][C] bf16 */
 int gl_op_attention(gl_ctx* ctx, const void* xq, const void* xkv, int B, int Nq, int Nk, int C, int Ck, int H,
                     const float* wq, const float* wk, const float* wv, void* o, gl_stream s);
+/* Test instrument: which softmax-stabiliser regime the pipelined attention kernel ran. Waits for the device, returns the counts
+ * gathered on this context since the previous call, zeroes them, and switches counting on (enable != 0) or off for the
+ * gl_op_attention calls that follow. *lazy_moves: executions of the lazy stabiliser move (head dim 40), one per wave;
+ * *reruns: workgroups that ran their key tiles a second time with the exact per-tile maximum. Counting runs a separate
+ * instantiation of the kernel; while it is off (the default, and always inside the engine's forward passes) the kernel receives no
+ * counter block. Head dims other than 40 have neither regime: both counts stay 0. */
+int gl_attn_regime_counters(gl_ctx* ctx, int enable, unsigned* lazy_moves, unsigned* reruns);
 
 /* A projection, the LayerNorm behind it and the self-attention behind that, as the engine runs them at the 64 x 64 level (reference
  * ldm/modules/attention.py:366-368 SpatialTransformer.proj_in -> :335 norm1 -> attn1, and :183-186 attn1.to_out + residual ->

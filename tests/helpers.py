@@ -212,3 +212,147 @@ def _fabricated_clip(tmp_path, hidden=768, proj=768):
     torch.manual_seed(0)
     model = CLIPModel(CLIPConfig(text_config=tcfg.to_dict(), vision_config=vcfg.to_dict(), projection_dim=proj)).eval()
     return model, CLIPProcessor(image_processor=CLIPImageProcessor(), tokenizer=tok), tok
+
+
+# ---- attention with a spike channel: inputs that put chosen rows into a chosen softmax-stabiliser regime --------------------------
+# Identity wq / wk and, per head, one reserved channel (channel 0 of the head: zero in xq, in xkv and in the matching columns of wv,
+# so V never sees it). a_i in the reserved channel of query i and b_j in that of key j add exactly a_i b_j d^-0.5 log2(e) log2 units
+# to the score (i, j) of that head: a rank-one bump that leaves every row with a_i = 0 bit-for-bit alone, unlike xkv[j] = gain * xq[i],
+# which moves every query's score against key j. a is a power of two (16 by default) and b is rounded to bf16: exact operands.
+# Key i carries the features of query i (self-attention's diagonal: ordinary rows have a dominant key somewhere along the row).
+SPIKE_A = 16.0
+# bump sizes in log2 units (at a = 16), and the band of log2(l / 2^stabiliser) each regime needs at the jump. From attn3_kernel's
+# constants: the lazy move at l > 2^40, the rerun at l >= 1e30 = 2^99.7, exp2 overflow at 2^128 -- with a margin of a few units for
+# the row's ordinary scores and for the bf16 roundings of b and of q * scale.
+SPIKE_UNITS = {"quiet": 20.0, "lazy": 75.0, "overshoot": 122.0, "overflow": 360.0}
+SPIKE_BANDS = {"quiet": (-1e9, 36.0), "lazy": (48.0, 90.0), "overshoot": (105.0, 120.0), "overflow": (140.0, 1e9)}
+SPIKE_ROW, SPIKE_HEAD = 37, 3        # the grid's bump row: wave 1 of query block 0; its own key (37) lies in tile 0
+
+
+def spike_attention_case(B, Nq, Nk, C, H, bumps=(), rows=None, device="cpu", seed=1):
+    """bumps: [(sample, head, query rows, {key or (first key, end key): bump in log2 units}[, a])]. The rows of an entry see its
+    bumps times a / 16; entries of one (sample, head) share their keys (the bump is rank one: every bumped row sees every bumped key).
+    rows: the query rows to build the reference for (default: all). Returns the tensors op_attention takes, the float64 reference
+    [B][len(rows)][C] of the softmax in float64 on the same bf16 inputs, and the score statistics of the regime checks."""
+    import math
+    from types import SimpleNamespace
+    d = C // H
+    c = d ** -0.5 * math.log2(math.e)
+    g = torch.Generator().manual_seed(seed)
+    base = torch.randn(B, max(Nq, Nk), C, generator=g).to(torch.bfloat16)
+    wv = torch.randn(C, C, generator=g) * C ** -0.5
+    ch0 = torch.arange(H) * d
+    base[:, :, ch0] = 0
+    wv[:, ch0] = 0
+    xq, xkv = base[:, :Nq].clone(), base[:, :Nk].clone()
+    bumped = torch.zeros(B, H, Nq, dtype=torch.bool)
+    for item in bumps:
+        b, h, qrows, keys = item[:4]
+        a = item[4] if len(item) > 4 else SPIKE_A
+        assert math.log2(a) == int(math.log2(a)), "a is a power of two"
+        xq[b, list(qrows), h * d] = a
+        bumped[b, h, list(qrows)] = True
+        for key, units in keys.items():
+            k0, k1 = key if isinstance(key, tuple) else (key, key + 1)
+            assert 0 <= k0 < k1 <= Nk
+            val = torch.tensor(units / (SPIKE_A * c)).to(torch.bfloat16)
+            old = xkv[b, k0:k1, h * d]
+            assert bool(((old == 0) | (old == val)).all()), "two entries disagree about a key's bump"
+            xkv[b, k0:k1, h * d] = val
+    rows_t = torch.arange(Nq) if rows is None else torch.as_tensor(sorted(set(rows)))
+    pos = {int(r): i for i, r in enumerate(rows_t.tolist())}
+    R = len(rows_t)
+    out = SimpleNamespace(B=B, Nq=Nq, Nk=Nk, C=C, H=H, d=d, rows=rows_t, xq=xq.to(device), xkv=xkv.to(device),
+                          wq=torch.eye(C, device=device), wk=torch.eye(C, device=device), wv=wv.to(device))
+    q = out.xq[:, rows_t.to(device)].double()
+    k = out.xkv.double()
+    v = k @ out.wv.to(torch.bfloat16).double().t()
+    ref = torch.empty(B, R, C, dtype=torch.float64, device=device)
+    excess0 = torch.empty(B, H, R, dtype=torch.float64, device=device)   # log2 sum_j 2^(s_j - max over tile 0)
+    smin, smax = float("inf"), float("-inf")
+    info = []
+    for b in range(B):
+        for h in range(H):
+            hs = slice(h * d, (h + 1) * d)
+            s = (q[b, :, hs] @ k[b, :, hs].t()) * c             # [R][Nk], log2 units
+            m = s.max(1).values
+            p = torch.exp2(s - m[:, None])
+            l = p.sum(1)
+            ref[b, :, hs] = (p @ v[b, :, hs]) / l[:, None]
+            lse = m + torch.log2(l)
+            excess0[b, h] = lse - s[:, :64].max(1).values
+            ordinary = ~bumped[b, h][rows_t].to(device)
+            if bool(ordinary.any()):
+                smin, smax = min(smin, float(s[ordinary].min())), max(smax, float(s[ordinary].max()))
+            for item in bumps:
+                if item[0] != b or item[1] != h:
+                    continue
+                # the jump: the first tile that holds a key bumped upwards (downward bumps make the tiles after them jump)
+                ups = [(key if isinstance(key, tuple) else (key, key + 1)) for key, u in item[3].items() if u > 0]
+                downs = [(key if isinstance(key, tuple) else (key, key + 1)) for key, u in item[3].items() if u < 0]
+                jt = min([k0 // 64 for k0, _ in ups] + [(k1 + 63) // 64 for _, k1 in downs if k1 < Nk] + [1 << 30])
+                for r in item[2]:
+                    if r not in pos:
+                        continue
+                    i = pos[r]
+                    before = float(s[i, : 64 * jt].max()) if 0 < jt < (1 << 30) else None
+                    info.append(dict(b=b, h=h, q=r, i=i, tile=jt if jt < (1 << 30) else None, a=item[4] if len(item) > 4 else SPIKE_A,
+                                     excess0=float(excess0[b, h, i]),
+                                     excess_before=None if before is None else float(lse[i]) - before))
+    out.ref, out.excess0, out.bump_rows, out.bumped = ref, excess0, info, bumped
+    out.ordinary_span = (smin, smax)
+    return out
+
+
+def spike_attention_metrics(case, y):
+    """The figures every spike case is judged by (y: what op_attention returned for case.xq ...): all finite; max |y - ref| over all rows
+    / max |ref| over the ordinary rows (no bump in any head); mean |y - ref| / mean |ref|; per bumped (row, head), max |y - ref| over
+    that head's slice of the row / its own max |ref| -- the worst of them."""
+    dev = case.ref.device
+    rows = case.rows.to(dev)
+    yy = y.to(dev).double()[:, rows]
+    err = (yy - case.ref).abs()
+    ordinary = ~case.bumped.any(1)[:, case.rows].to(dev)            # [B][R]
+    d = case.d
+    worst_row = 0.0
+    for br in case.bump_rows:
+        hs = slice(br["h"] * d, (br["h"] + 1) * d)
+        worst_row = max(worst_row, float(err[br["b"], br["i"], hs].max() / case.ref[br["b"], br["i"], hs].abs().max()))
+    return dict(finite=bool(torch.isfinite(yy).all()),
+                max_rel=float(err.max() / case.ref[ordinary].abs().max()),
+                mean_rel=float(err.mean() / case.ref.abs().mean()),
+                row_rel=worst_row)
+
+
+def spike_positions(Nk):
+    """{position name: (key, tile)} of the jump positions: tile 0, tile 1, a middle tile (31 where the row has it), the tile before the
+    last full tile, the last full tile, and a key inside the ragged tail where there is one. Positions that fall on the same tile
+    are listed once."""
+    nt = (Nk + 63) // 64
+    full = Nk // 64
+    want = [("tile0", 0), ("tile1", 1), ("mid", 31 if nt > 34 else nt // 2), ("before_last_full", full - 2), ("last_full", full - 1)]
+    out, seen = {}, set()
+    for name, t in want:
+        if 0 <= t < full and t not in seen:
+            seen.add(t)
+            out[name] = (64 * t + 20, t)
+    if Nk % 64:
+        out["ragged_tail"] = (64 * full + (Nk % 64) // 2, full)
+    return out
+
+
+SPIKE_GRID_SHAPES = {40: [(1, 4096, 4096, 320), (1, 4096, 4126, 320), (1, 256, 160, 320)],
+                     80: [(1, 1024, 1054, 640), (1, 4096, 4126, 640)]}
+
+
+def spike_grid(d):
+    """[(id, (B, Nq, Nk, C), regime, position name, tile, bumps)]: every jump position x {lazy, finite overshoot, overflow} at d = 40,
+    x {lazy, overflow} at d = 80 (H = 8), one bumped row (SPIKE_ROW of head SPIKE_HEAD)."""
+    out = []
+    for shape in SPIKE_GRID_SHAPES[d]:
+        B, Nq, Nk, C = shape
+        for pname, (key, tile) in spike_positions(Nk).items():
+            for regime in (("lazy", "overshoot", "overflow") if d == 40 else ("lazy", "overflow")):
+                bumps = [(0, SPIKE_HEAD, [SPIKE_ROW], {key: SPIKE_UNITS[regime]})]
+                out.append((f"d{d}-{Nq}x{Nk}-{pname}-{regime}", shape, regime, pname, tile, bumps))
+    return out

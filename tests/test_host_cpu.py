@@ -1008,3 +1008,50 @@ def test_ctypes_structs_match_the_c_header(tmp_path):
     out = dict(l.split() for l in subprocess.run([str(exe)], capture_output=True, text=True, check=True).stdout.splitlines())
     for name, ct in pairs.items():
         assert int(out[name]) == C.sizeof(ct), (name, out[name], C.sizeof(ct))
+
+
+def _spike_grid_params():
+    import helpers
+    return [pytest.param(*g, id=g[0]) for d in (40, 80) for g in helpers.spike_grid(d)]
+
+
+@pytest.mark.parametrize("name,shape,regime,pname,tile,bumps", _spike_grid_params())
+def test_spike_attention_builder_lands_in_its_regime(name, shape, regime, pname, tile, bumps):
+    """The inputs of tests/test_attention_regimes_gpu.py, checked from their float64 scores (bump row + a sample of ordinary rows):
+    the bump row's log2 sum_j 2^(s_j - stabiliser) lies inside its regime's band, for the stabiliser the kernel holds at the jump (the
+    maximum over tile 0) and for the maximum over every key in front of the jump tile; every ordinary row stays quiet (below 2^36
+    over its tile-0 maximum: no lazy move); float32 and float64 references agree below 1e-5; rows without a bump are identical
+    with and without the bumps."""
+    import helpers
+    B, Nq, Nk, C = shape
+    H = 8
+    sample = [r for r in (0, 1, 31, 63, 64, 100, 127, 128, 255, 777, 1023, 2048, 3000, 4095) if r < Nq]
+    case = helpers.spike_attention_case(B, Nq, Nk, C, H, bumps, rows=sample + [helpers.SPIKE_ROW])
+    plain = helpers.spike_attention_case(B, Nq, Nk, C, H, (), rows=sample + [helpers.SPIKE_ROW])
+    (br,) = case.bump_rows
+    lo, hi = helpers.SPIKE_BANDS[regime]
+    assert br["tile"] == tile
+    if tile == 0:
+        # the first tile's maximum is the stabiliser: whatever the bump's size, the row is quiet from there on
+        assert br["excess0"] < 36.0, br
+    else:
+        assert lo <= br["excess0"] <= hi, br
+        assert lo <= br["excess_before"] <= hi, br
+    bumped = case.bumped[:, :, case.rows]                              # [B][H][R]
+    assert float(case.excess0[~bumped].max()) < 36.0
+    # float32 reference of the same rows (softmax in float32, as tests/test_ops_gpu.py attn_ref)
+    d = C // H
+    q = case.xq[:, case.rows].float().view(B, -1, H, d).transpose(1, 2)
+    k = case.xkv.float().view(B, Nk, H, d).transpose(1, 2)
+    v = (case.xkv.float() @ case.wv.to(torch.bfloat16).float().t()).view(B, Nk, H, d).transpose(1, 2)
+    ref32 = (((q @ k.transpose(-1, -2)) * d ** -0.5).softmax(-1) @ v).transpose(1, 2).reshape(B, -1, C)
+    assert float((ref32.double() - case.ref).abs().max() / case.ref.abs().max()) < 1e-5
+    ordinary = ~bumped.any(1)                                          # [B][R]
+    assert int(ordinary.sum()) == len(sample)
+    assert torch.equal(case.ref[ordinary], plain.ref[ordinary])
+    # a row that overflows the lazy pass is its dominant key's value row
+    if regime == "overflow":
+        key = next(iter(bumps[0][3]))
+        hs = slice(helpers.SPIKE_HEAD * d, (helpers.SPIKE_HEAD + 1) * d)
+        vrow = (case.xkv[0, key].double() @ case.wv.to(torch.bfloat16).double().t())[hs]
+        assert float((case.ref[0, br["i"], hs] - vrow).abs().max()) < 1e-12

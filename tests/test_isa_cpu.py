@@ -226,7 +226,7 @@ def test_attn3_loop_puts_pv_on_16x16x32(attn_asm):
     steady-state loop (two per trip, the score sets swap roles): 6 MFMAs 32x32x16 for S^T, 12 MFMAs 16x16x32 for P V, the 8
     v_permlane16_swap that turn the 32x32 accumulators into the 16-query B operands, 6 + 6 fragment reads, K / V^T by LDS-DMA
     (at most 4 pieces per wave), one vmcnt wait + one barrier; no scratch, fewer registers than attn2 (O^T is 24, not 32)."""
-    name = re.search(r"^(_ZN2gl12attn3_kernelILi48ELi48ELb1ELi4EE[^:\s]*):", attn_asm, re.M).group(1)
+    name = re.search(r"^(_ZN2gl12attn3_kernelILi48ELi48ELb1ELi4ELb0EE[^:\s]*):", attn_asm, re.M).group(1)
     a = attn_asm.index(name + ":")
     body = attn_asm[a:attn_asm.index(".Lfunc_end", a)].split("\n")
     meta = attn_asm[attn_asm.index(".name:           " + name):]
@@ -256,7 +256,7 @@ def test_attn3_loop_puts_pv_on_16x16x32(attn_asm):
     assert worst_v <= 22 and worst_m <= 8, (worst_v, worst_m)   # (round 6: no row maximum between the six MFMAs of the second P V half any more)
     # d = 80 (attn3_kernel<80, 96, false, 4>, the LATE_V form): the steady-state loop fits 256 registers without scratch traffic
     # (the once-only first / last iterations may spill a few accumulator tuples across their merges: bounded here)
-    name80 = re.search(r"^(_ZN2gl12attn3_kernelILi80ELi96ELb0ELi4EE[^:\s]*):", attn_asm, re.M).group(1)
+    name80 = re.search(r"^(_ZN2gl12attn3_kernelILi80ELi96ELb0ELi4ELb0EE[^:\s]*):", attn_asm, re.M).group(1)
     a = attn_asm.index(name80 + ":")
     body = attn_asm[a:attn_asm.index(".Lfunc_end", a)].split("\n")
     meta = attn_asm[attn_asm.index(".name:           " + name80):]
