@@ -39,6 +39,10 @@ class ClipTextConfig(C.Structure):   # = gl_clip_text_config
     _fields_ = [(n, C.c_int) for n in ("vocab", "width", "heads", "layers", "intermediate", "max_positions")] + [("ln_eps", C.c_float)]
 
 
+class ClipVisionConfig(C.Structure):   # = gl_clip_vision_config
+    _fields_ = [(n, C.c_int) for n in ("image_size", "patch", "width", "heads", "layers", "intermediate", "projection_dim")] + [("ln_eps", C.c_float)]
+
+
 class Grounding(C.Structure):
     _fields_ = [
         ("n", C.c_int),
@@ -97,6 +101,9 @@ SYMBOLS = {
     "gl_finalize": (_I, [_P]),
     "gl_clip_text_configure": (_I, [_P, C.POINTER(ClipTextConfig)]),
     "gl_clip_text_encode": (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
+    "gl_clip_vision_configure": (_I, [_P, C.POINTER(ClipVisionConfig)]),
+    "gl_clip_vision_encode": (_I, [_P, _P, _I, _P, _P, _P, _P]),
+    "gl_op_clip_attention": (_I, [_P, _P, _P, _I, _I, _I, _I, _P]),
     "gl_unet_set_cond": (_I, [_P, _I, _P, _I, C.POINTER(Grounding), _P]),
     "gl_unet_set_fuser_scale": (_I, [_P, C.c_float, _P]),
     "gl_unet_set_fuser_scales": (_I, [_P, C.POINTER(C.c_float), _I, _P]),

@@ -146,6 +146,30 @@ int gl_clip_text_encode(gl_ctx* ctx, const int32_t* ids, const int32_t* eos_inde
     GL_API_END
 }
 
+int gl_clip_vision_configure(gl_ctx* ctx, const gl_clip_vision_config* cfg) {
+    NEED(ctx);
+    if (!cfg) return gl::set_error(GL_ERR_ARG, "null config");
+    GL_API_BEGIN
+    ctx->eng->configure_clip_vision(*cfg);
+    GL_API_END
+}
+
+int gl_clip_vision_encode(gl_ctx* ctx, const float* pixel_values, int n_img, float* last_hidden, float* pooled, float* image_embeds, gl_stream s) {
+    NEED(ctx);
+    GL_API_BEGIN
+    ctx->eng->clip_vision_encode(pixel_values, n_img, last_hidden, pooled, image_embeds, S(s));
+    GL_API_END
+}
+
+int gl_op_clip_attention(gl_ctx* ctx, const void* qkv, void* out, int n_seq, int n_tok, int heads, int causal, gl_stream s) {
+    NEED(ctx);
+    if (!qkv || !out) return gl::set_error(GL_ERR_ARG, "null qkv/out");
+    GL_API_BEGIN
+    int r = clip_attn_launch((const bf16*)qkv, (bf16*)out, n_seq, n_tok, heads, causal, S(s));
+    if (r != GL_OK) throw GlError(r, gl::last_error());
+    GL_API_END
+}
+
 int gl_unet_set_cond(gl_ctx* ctx, int Beff, const float* context, int n_ctx_tokens, const gl_grounding* g, gl_stream s) {
     NEED(ctx);
     if (!context || !g) return gl::set_error(GL_ERR_ARG, "null context/grounding");

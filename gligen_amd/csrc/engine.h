@@ -168,6 +168,7 @@ class Engine {
     void configure_unet(const gl_unet_config& c);
     void configure_vae(const gl_vae_config& c);
     void configure_clip_text(const gl_clip_text_config& c);
+    void configure_clip_vision(const gl_clip_vision_config& c);
     void finalize();
     bool finalized() const { return finalized_; }
 
@@ -190,6 +191,12 @@ class Engine {
     // CLIPTextModel.forward (reference ldm/modules/encoders/modules.py:144-173): ids [S][T] int32, eos_index [S] (the row HF pools)
     // -> last_hidden fp32 [S][T][width], pooled fp32 [S][width] (may be null). S is chunked to what the arena holds.
     void clip_text_encode(const int32_t* ids, const int32_t* eos_index, int S, int T, float* last_hidden, float* pooled, hipStream_t s);
+    // CLIPVisionModelWithProjection.forward (the image features of reference gligen_inference.py:104-128): pixel_values fp32
+    // [S][3][image_size][image_size] -> last_hidden fp32 [S][T][width] (= last_hidden_state, T = 1 + patches), pooled fp32 [S][width] =
+    // post_layernorm(last_hidden[:, 0]), image_embeds fp32 [S][projection_dim] = pooled visual_projection^T (not normalised); each may
+    // be null. S is chunked to what the arena holds.
+    void clip_vision_encode(const float* pixel_values, int S, float* last_hidden, float* pooled, float* image_embeds, hipStream_t s);
+    int clip_vision_tokens() const { const int g = vcfg_clip_.patch ? vcfg_clip_.image_size / vcfg_clip_.patch : 0; return g * g + 1; }
     void sample_plms(const gl_plms_args& a, hipStream_t s);
     void sampler_timing(float* avg_ms, float* first_ms, int* n);
 
@@ -419,9 +426,24 @@ class Engine {
     NormW clip_final_ln_;
     unsigned* clip_bad_ids_ = nullptr;     // device counter: ids outside [0, vocab) met (and clamped) by clip_embed_kernel
     void build_clip_text();
+    // the 16 tensors of layers [0, n) under P + "encoder.layers.N.", shapes checked against (width, intermediate)
+    void build_clip_layers(const std::string& P, int n, int width, int intermediate, std::vector<ClipLayerW>& out);
     // one pre-LN transformer stack over M = S * T rows of the fp32 residual stream `h` (tmp: fp32 [M][width] scratch); leaves the
-    // last sub-layer's output in tmp, still to be added: returns it (the final LayerNorm's launch does the add)
-    const float* clip_layers_run(float* h, float* tmp, int S, int T, bool causal, hipStream_t s);
+    // last sub-layer's output in tmp, still to be added: returns it (the next LayerNorm's launch does the add). Both towers.
+    struct ClipStack { int width, heads, intermediate; float ln_eps; };
+    const float* clip_layers_run(const std::vector<ClipLayerW>& layers, const ClipStack& c, float* h, float* tmp, int S, int T, bool causal, hipStream_t s);
+
+    // ---- CLIP vision tower: patch rows -> GEMM -> [class ; patches] + positions -> pre_layrnorm (overwrites the stream) -> the same
+    // stack, not causal -> post_layernorm of the class rows -> visual_projection
+    bool has_clip_vision_ = false;
+    gl_clip_vision_config vcfg_clip_{};
+    const float* clipv_cls_ = nullptr;     // [width] fp32
+    const float* clipv_pos_ = nullptr;     // [tokens][width] fp32
+    LinW clipv_patch_;                     // [width][(c, ky, kx) zero-padded to a multiple of 64] bf16, no bias
+    NormW clipv_pre_ln_, clipv_post_ln_;
+    LinW clipv_proj_;                      // visual_projection: [projection_dim][width], no bias
+    std::vector<ClipLayerW> clipv_layers_;
+    void build_clip_vision();
 
     // ---- sampler state
     struct Sampler {

@@ -328,22 +328,16 @@ void Engine::configure_clip_text(const gl_clip_text_config& c) {
     has_clip_ = true;
 }
 
-// Weights under "text_encoder/" + the checkpoint's key (transformers 4.x layout: transformer.text_model.*)
-void Engine::build_clip_text() {
-    const gl_clip_text_config& c = ccfg_;
-    const std::string P = "text_encoder/transformer.text_model.";
+void Engine::build_clip_layers(const std::string& P, int n, int width, int intermediate, std::vector<ClipLayerW>& out) {
+    struct { int width, intermediate; } c{width, intermediate};
     auto expect = [&](const std::string& key, int64_t d0, int64_t d1) {
         const RawTensor& t = raw(key);
         const int64_t a = t.shape.empty() ? 0 : t.shape[0], b = t.shape.size() > 1 ? t.shape[1] : 0;
         if (a != d0 || (d1 && b != d1))
             throw GlError(GL_ERR_ARG, fmt("'%s' has shape [%lld, %lld], the configuration expects [%lld, %lld]", key.c_str(), (long long)a, (long long)b, (long long)d0, (long long)d1));
     };
-    expect(P + "embeddings.token_embedding.weight", c.vocab, c.width);
-    expect(P + "embeddings.position_embedding.weight", c.max_positions, c.width);
-    clip_tok_ = FK(P + "embeddings.token_embedding.weight");
-    clip_pos_ = FK(P + "embeddings.position_embedding.weight");
-    clip_layers_.clear();
-    for (int l = 0; l < c.layers; ++l) {
+    out.clear();
+    for (int l = 0; l < n; ++l) {
         const std::string L = P + "encoder.layers." + std::to_string(l) + ".";
         ClipLayerW w;
         w.ln1 = norm(L + "layer_norm1");
@@ -367,8 +361,25 @@ void Engine::build_clip_text() {
         w.out = linear(L + "self_attn.out_proj");
         w.fc1 = linear(L + "mlp.fc1");
         w.fc2 = linear(L + "mlp.fc2");
-        clip_layers_.push_back(w);
+        out.push_back(w);
     }
+}
+
+// Weights under "text_encoder/" + the checkpoint's key (transformers 4.x layout: transformer.text_model.*)
+void Engine::build_clip_text() {
+    const gl_clip_text_config& c = ccfg_;
+    const std::string P = "text_encoder/transformer.text_model.";
+    auto expect = [&](const std::string& key, int64_t d0, int64_t d1) {
+        const RawTensor& t = raw(key);
+        const int64_t a = t.shape.empty() ? 0 : t.shape[0], b = t.shape.size() > 1 ? t.shape[1] : 0;
+        if (a != d0 || (d1 && b != d1))
+            throw GlError(GL_ERR_ARG, fmt("'%s' has shape [%lld, %lld], the configuration expects [%lld, %lld]", key.c_str(), (long long)a, (long long)b, (long long)d0, (long long)d1));
+    };
+    expect(P + "embeddings.token_embedding.weight", c.vocab, c.width);
+    expect(P + "embeddings.position_embedding.weight", c.max_positions, c.width);
+    clip_tok_ = FK(P + "embeddings.token_embedding.weight");
+    clip_pos_ = FK(P + "embeddings.position_embedding.weight");
+    build_clip_layers(P, c.layers, c.width, c.intermediate, clip_layers_);
     clip_final_ln_ = norm(P + "final_layer_norm");
     if (clip_final_ln_.C != c.width) throw GlError(GL_ERR_ARG, "'" + P + "final_layer_norm' does not match the configured width");
     clip_bad_ids_ = reinterpret_cast<unsigned*>(persist(sizeof(unsigned), true));
@@ -379,8 +390,8 @@ void Engine::build_clip_text() {
 // into the stream before it normalises -- clip_add_ln_kernel reads and writes the stream once per sub-layer. That is why the
 // LayerNorms are not folded into the GEMMs behind them here (gemm.h: the folded form takes its row statistics from the bf16 GEMM
 // that produced the rows).
-const float* Engine::clip_layers_run(float* h, float* tmp, int S, int T, bool causal, hipStream_t s) {
-    const gl_clip_text_config& c = ccfg_;
+const float* Engine::clip_layers_run(const std::vector<ClipLayerW>& layers, const ClipStack& c, float* h, float* tmp, int S, int T, bool causal,
+                                     hipStream_t s) {
     const int M = S * T, W = c.width, I = c.intermediate;
     const size_t Mp = (size_t)round_up(M, 256);   // (whole GEMM tiles of rows exist behind every operand)
     bf16* xn = arena_.get<bf16>(Mp * W);
@@ -396,11 +407,12 @@ const float* Engine::clip_layers_run(float* h, float* tmp, int S, int T, bool ca
         gemm(A, L.w, M, L.N, L.K, E, s);
     };
     const float* delta = nullptr;
-    for (const ClipLayerW& w : clip_layers_) {
+    const char* attn_name = T <= kClipMaxTokens ? "clip_attn_kernel" : "clip_attn_long_kernel";
+    for (const ClipLayerW& w : layers) {
         CK(clip_add_ln_launch(h, delta, w.ln1.g, w.ln1.b, c.ln_eps, xn, nullptr, M, W, s));
         lin(xn, w.qkv, qkv, false, ACT_NONE);
         {
-            ProfScope ps(this, s, "clip_attn_kernel", 4.0 * S * c.heads * (double)T * T * kClipHeadDim, 0.0);
+            ProfScope ps(this, s, attn_name, 4.0 * S * c.heads * (double)T * T * kClipHeadDim, 0.0);
             CK(clip_attn_launch(qkv, ao, S, T, c.heads, causal ? 1 : 0, s));
         }
         lin(ao, w.out, tmp, true, ACT_NONE);
@@ -434,13 +446,124 @@ void Engine::clip_text_encode(const int32_t* ids, const int32_t* eos_index, int 
         float* h = arena_.get<float>(Mp * W);
         float* tmp = arena_.get<float>(Mp * W);
         CK(clip_embed_launch(ids + (size_t)s0 * T, clip_tok_, clip_pos_, h, M, T, W, c.vocab, clip_bad_ids_, s));
-        const float* delta = clip_layers_run(h, tmp, n, T, true, s);
+        const float* delta = clip_layers_run(clip_layers_, ClipStack{c.width, c.heads, c.intermediate, c.ln_eps}, h, tmp, n, T, true, s);
         float* out = last_hidden + (size_t)s0 * T * W;
         CK(clip_add_ln_launch(h, delta, clip_final_ln_.g, clip_final_ln_.b, c.ln_eps, nullptr, out, M, W, s));
         n_launches += 2;
         if (pooled) {
             CK(clip_pool_launch(out, eos_index + s0, pooled + (size_t)s0 * W, n, T, W, s));
             ++n_launches;
+        }
+        arena_.release(mk);
+    }
+}
+
+// ---------------------------------------------------------------- CLIP vision tower
+void Engine::configure_clip_vision(const gl_clip_vision_config& c) {
+    if (c.image_size < 1 || c.patch < 1 || c.layers < 1 || c.heads < 1 || c.width < 1 || c.intermediate < 1 || c.projection_dim < 1 || !(c.ln_eps > 0.f))
+        throw GlError(GL_ERR_ARG, fmt("clip vision config: image_size %d, patch %d, width %d, heads %d, layers %d, intermediate %d, projection_dim %d, ln_eps %g must all be positive",
+                                      c.image_size, c.patch, c.width, c.heads, c.layers, c.intermediate, c.projection_dim, c.ln_eps));
+    if (c.width % c.heads || c.width / c.heads != kClipHeadDim)
+        throw GlError(GL_ERR_UNSUPPORTED, fmt("clip vision tower: head dim %d (width %d / %d heads) is not supported: the attention kernels are built for head dim %d",
+                                              c.width / c.heads, c.width, c.heads, kClipHeadDim));
+    if (c.width > kClipMaxWidth) throw GlError(GL_ERR_UNSUPPORTED, fmt("clip vision tower: width %d exceeds %d", c.width, kClipMaxWidth));
+    if (c.intermediate % 64) throw GlError(GL_ERR_UNSUPPORTED, fmt("clip vision tower: intermediate size %d is not a multiple of 64", c.intermediate));
+    if (c.image_size % c.patch)
+        throw GlError(GL_ERR_UNSUPPORTED, fmt("clip vision tower: image_size %d is not a multiple of the patch size %d", c.image_size, c.patch));
+    const int64_t g = c.image_size / c.patch, tokens = g * g + 1;
+    if (tokens > kClipLongMaxTokens)
+        throw GlError(GL_ERR_UNSUPPORTED, fmt("clip vision tower: %lld tokens (image_size %d / patch %d) exceed the %d clip_attn_long_kernel holds", (long long)tokens,
+                                              c.image_size, c.patch, kClipLongMaxTokens));
+    vcfg_clip_ = c;
+    has_clip_vision_ = true;
+}
+
+// Weights under "clip_vision/" + the transformers key (CLIPModel / CLIPVisionModelWithProjection: vision_model.*, visual_projection.weight)
+void Engine::build_clip_vision() {
+    const gl_clip_vision_config& c = vcfg_clip_;
+    const std::string R = "clip_vision/", P = R + "vision_model.";
+    const int tokens = clip_vision_tokens();
+    auto expect = [&](const std::string& key, std::vector<int64_t> want) {
+        const RawTensor& t = raw(key);
+        if (t.shape != want) {
+            auto str = [](const std::vector<int64_t>& v) { std::string o = "["; for (size_t i = 0; i < v.size(); ++i) o += (i ? ", " : "") + std::to_string(v[i]); return o + "]"; };
+            throw GlError(GL_ERR_ARG, "'" + key + "' has shape " + str(t.shape) + ", the configuration expects " + str(want));
+        }
+    };
+    expect(P + "embeddings.class_embedding", {c.width});
+    expect(P + "embeddings.patch_embedding.weight", {c.width, 3, c.patch, c.patch});
+    expect(P + "embeddings.position_embedding.weight", {tokens, c.width});
+    expect(R + "visual_projection.weight", {c.projection_dim, c.width});
+    clipv_cls_ = FK(P + "embeddings.class_embedding");
+    clipv_pos_ = FK(P + "embeddings.position_embedding.weight");
+    clipv_patch_ = linear(P + "embeddings.patch_embedding", false);    // [width][3 p p], K zero-padded to a multiple of 64 (588 -> 640)
+    clipv_pre_ln_ = norm(P + "pre_layrnorm");                          // (sic: the transformers key)
+    clipv_post_ln_ = norm(P + "post_layernorm");
+    if (clipv_pre_ln_.C != c.width) throw GlError(GL_ERR_ARG, "'" + P + "pre_layrnorm' does not match the configured width");
+    if (clipv_post_ln_.C != c.width) throw GlError(GL_ERR_ARG, "'" + P + "post_layernorm' does not match the configured width");
+    build_clip_layers(P, c.layers, c.width, c.intermediate, clipv_layers_);
+    clipv_proj_ = linear(R + "visual_projection", false);
+}
+
+void Engine::clip_vision_encode(const float* pixel_values, int S, float* last_hidden, float* pooled, float* image_embeds, hipStream_t s) {
+    if (!has_clip_vision_ || !finalized_) throw GlError(GL_ERR_STATE, "clip vision tower not configured / finalized");
+    if (!pixel_values || (!last_hidden && !pooled && !image_embeds)) throw GlError(GL_ERR_ARG, "clip_vision_encode: null pixel_values / no output");
+    if (S < 1) throw GlError(GL_ERR_ARG, fmt("clip_vision_encode: %d images", S));
+    const gl_clip_vision_config& c = vcfg_clip_;
+    const int W = c.width, T = clip_vision_tokens(), NP = T - 1, Kp = clipv_patch_.K, D = c.projection_dim;
+    const ClipStack stack{c.width, c.heads, c.intermediate, c.ln_eps};
+    // activation bytes of one chunk of Sc images: what clip_text_encode counts + the bf16 patch rows (the fp32 patch embeddings use
+    // the scratch rows) + the bf16 pooled rows the projection reads, row counts rounded up to whole GEMM tiles
+    auto need = [&](int Sc) {
+        return (size_t)round_up(Sc * T, 256) * ((size_t)W * (4 + 4 + 2 + 6 + 2) + (size_t)c.intermediate * 2) + (size_t)round_up(Sc * NP, 256) * Kp * 2 +
+               (size_t)round_up(Sc, 256) * W * 2 + 10 * 256;
+    };
+    const size_t mk = arena_.mark();
+    const size_t avail = arena_.capacity() - std::min(arena_.capacity(), (mk + 255) & ~size_t(255));
+    int Sc = S;
+    while (Sc > 1 && need(Sc) > avail) Sc = (Sc + 1) / 2;
+    if (need(Sc) > avail) throw GlError(GL_ERR_STATE, fmt("clip_vision_encode: the arena (%zu bytes free) does not hold one image (%zu bytes)", avail, need(1)));
+    const size_t image_elems = (size_t)3 * c.image_size * c.image_size;
+    // no K split in this tower's GEMMs: a row's sums are then the same whatever the number of images, so an image's feature does
+    // not depend on the batch it came in (nor on the chunking above)
+    struct NoSplit { NoSplit() { gemm_set_no_split(1); } ~NoSplit() { gemm_set_no_split(0); } } no_split;
+    for (int s0 = 0; s0 < S; s0 += Sc) {
+        const int n = std::min(Sc, S - s0), M = n * T;
+        const size_t Mp = (size_t)round_up(M, 256);
+        float* h = arena_.get<float>(Mp * W);
+        float* tmp = arena_.get<float>(Mp * W);
+        bf16* rows = arena_.get<bf16>((size_t)round_up(n * NP, 256) * Kp);
+        bf16* pooled_bf = arena_.get<bf16>((size_t)round_up(n, 256) * W);
+        CK(clip_patch_rows_launch(pixel_values + (size_t)s0 * image_elems, rows, n, c.image_size, c.patch, Kp, s));
+        {
+            AOperand A;
+            aoperand_rows(A, rows, Kp, Kp);
+            Epilogue E;
+            epilogue_defaults(E);
+            E.out = tmp; E.ldo = W; E.out_f32 = 1;
+            gemm(A, clipv_patch_.w, n * NP, W, Kp, E, s);
+        }
+        CK(clip_vision_embed_launch(tmp, clipv_cls_, clipv_pos_, h, n, T, W, s));
+        CK(clip_ln_rows_launch(h, nullptr, W, clipv_pre_ln_.g, clipv_pre_ln_.b, c.ln_eps, h, nullptr, W, M, W, s));   // in place
+        n_launches += 3;
+        const float* delta = clip_layers_run(clipv_layers_, stack, h, tmp, n, T, false, s);
+        if (last_hidden) {
+            CK(clip_add_launch(h, delta, last_hidden + (size_t)s0 * T * W, (int64_t)M * W, s));
+            ++n_launches;
+        }
+        if (pooled || image_embeds) {
+            // post_layernorm of the class rows (h + delta)[s * T]: a row stride of T * width, no gather
+            CK(clip_ln_rows_launch(h, delta, (int64_t)T * W, clipv_post_ln_.g, clipv_post_ln_.b, c.ln_eps, pooled ? pooled + (size_t)s0 * W : nullptr,
+                                   image_embeds ? pooled_bf : nullptr, W, n, W, s));
+            ++n_launches;
+        }
+        if (image_embeds) {
+            AOperand A;
+            aoperand_rows(A, pooled_bf, W, W);
+            Epilogue E;
+            epilogue_defaults(E);
+            E.out = image_embeds + (size_t)s0 * D; E.ldo = D; E.out_f32 = 1;
+            gemm(A, clipv_proj_.w, n, D, clipv_proj_.K, E, s);
         }
         arena_.release(mk);
     }
@@ -1113,6 +1236,7 @@ void Engine::finalize() {
     if (has_vae_) build_vae();
     if (has_vae_ && has("vae/encoder.conv_in.weight")) build_vae_encoder();
     if (has_clip_) build_clip_text();
+    if (has_clip_vision_) build_clip_vision();
     HIPCK(hipDeviceSynchronize());
     for (void* p : fold_tmps_) (void)hipFree(p);   // fp32 W * gamma / b + W beta temporaries of the folded LayerNorms
     fold_tmps_.clear();

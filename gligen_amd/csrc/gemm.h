@@ -107,6 +107,10 @@ int gemm_geglu_layout();
 void gemm_force_cfg(int tm, int tn, int splits);   // 0,0,0 = automatic
 void gemm_force_grid(int blocks);                  // 0 = automatic (512)
 void gemm_set_autotune(int on);                    // 1 (default): time candidates at the first eager launch of a problem
+// 1: the row GEMMs this THREAD launches from now on take no K split (and tune / look up their tile under a key of their own). Every
+// output element is then one sequential fp32 accumulation over K whatever M is, so a row of the result does not depend on how
+// many other rows the call carries (the CLIP vision tower: an image's feature must not depend on the batch it was encoded in).
+void gemm_set_no_split(int on);
 void gemm_last_cfg(int* tm, int* tn, int* splits);
 const char* gemm_last_kernel_name();  // kernel symbol (template arguments included) of the most recent gemm_launch
 bool gemm_gn_prologue_supported(const AOperand& A, int M, int N, int K, const Epilogue& E);   // may this launch take AOperand::gn?

@@ -2745,6 +2745,8 @@ static std::unordered_map<std::string, TunedCfg> g_tuned;   // process-wide, gua
 static std::mutex g_tune_mu;
 static int g_autotune = -1;
 void gemm_set_autotune_impl(int on) { g_autotune = on; }
+static thread_local int t_no_split = 0;
+void gemm_set_no_split_impl(int on) { t_no_split = on; }
 
 // Does this problem go to conv_halo_kernel? (one predicate for the launcher and for gemm_gn_prologue_supported)
 // eligible 3x3 convs with M >= 256 * GL_CONV_HALO (default 8; 0 = never) go to the halo kernel: at M = 512 (the 8 x 8 level) its
@@ -2790,7 +2792,7 @@ int gemm_p_launch(const AOperand& A, const bf16* W, int M, int N, int K, const E
         if (E.act == ACT_GEGLU && (tn & 1)) return false;
         if (E.mode == EPI_QKV_HEADS && (sp > 1 || (2 * E.C) % (tn * 32) || (tm == 4 && tn == 5))) return false;   // an item must not straddle the k | v boundary
         if (E.mode == EPI_QK_HEADS && E.ln_stats && (sp > 1 || (tm == 4 && tn == 5))) return false;                   // (same kernel family, no V third)
-        if (sp > 1 && (!ws || nk / sp < 2 || (size_t)sp * M * N * sizeof(float) > ws_bytes)) return false;
+        if (sp > 1 && (t_no_split || !ws || nk / sp < 2 || (size_t)sp * M * N * sizeof(float) > ws_bytes)) return false;
         const int kps = cdiv(nk, sp);
         sp = cdiv(nk, kps);
         return true;
@@ -2890,7 +2892,7 @@ int gemm_p_launch(const AOperand& A, const bf16* W, int M, int N, int K, const E
     char key[160];
     snprintf(key, sizeof key, "%d,%d,%d|%d,%d,%d,%d,%d,%d,%d|%d,%d,%d,%d,%d,%d|%d%s", M, N, K, A.mode, A.C0, A.C1, A.stride, A.ups, A.Win,
              A.Hin, E.mode, E.act, E.res != nullptr, E.bias2 != nullptr, E.out_f32, E.gate != nullptr, (int)use_u,
-             (E.mode == EPI_QK_HEADS && E.ln_stats) ? "|ln" : "");   // (q-only projection behind a folded LayerNorm: another kernel family)
+             (E.mode == EPI_QK_HEADS && E.ln_stats) ? "|ln" : t_no_split ? "|ns" : "");   // (q-only projection behind a folded LayerNorm: another kernel family; "|ns": gemm_set_no_split)
     std::unique_lock<std::mutex> tune_lock(g_tune_mu);
     if (g_tuned.empty() && use_u && !dev_env("GL_GEMM_NO_TABLE")) {
         // shipped choices for the problems of the benchmark configurations (generated by tools/make_tuned_table.py from an
@@ -3013,6 +3015,7 @@ int gemm_p_launch(const AOperand& A, const bf16* W, int M, int N, int K, const E
 }  // namespace
 
 void gemm_set_autotune(int on) { gemm_set_autotune_impl(on); }
+void gemm_set_no_split(int on) { gemm_set_no_split_impl(on); }
 
 // AOperand::gn (GroupNorm-apply + SiLU inside the conv's loader) exists in conv_halo_kernel only, for tiles that lie inside one
 // image (H W a multiple of 256: the tile's 256 pixels share one sample's coefficients)
@@ -3091,7 +3094,7 @@ int gemm_launch(const AOperand& A, const bf16* W, int M, int N, int K, const Epi
     const int tiles = cdiv(M, cf.bm) * cdiv(N, cf.bn);
     const int nk = K / 64;
     int splits = 1;
-    if (ws && tiles < 256 && nk >= 8) {
+    if (ws && !t_no_split && tiles < 256 && nk >= 8) {
         splits = min(min(cdiv(512, tiles), nk / 4), 16);
         while (splits > 1 && (size_t)splits * M * N * sizeof(float) > ws_bytes) --splits;
     }

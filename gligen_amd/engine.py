@@ -80,6 +80,7 @@ class Engine:
         self.unet_cfg: Optional[dict] = None
         self.vae_cfg: Optional[dict] = None
         self.clip_cfg: Optional[dict] = None
+        self.clip_vision_cfg: Optional[dict] = None
         self._keep: list = []
 
     def fork(self, arena_gb: Optional[float] = None) -> "Engine":
@@ -172,6 +173,45 @@ class Engine:
         pooled = torch.empty((S, self.clip_cfg["width"]), device=self.device, dtype=torch.float32)
         check(self.lib.gl_clip_text_encode(self._ctx, _ptr(ids), _ptr(eos), S, T, _ptr(hidden), _ptr(pooled), _stream(self.device)))
         return hidden, pooled
+
+    def configure_clip_vision(self, *, image_size, patch, width, heads, layers, intermediate, projection_dim, ln_eps=1e-5) -> None:
+        """The CLIP vision tower and visual_projection (transformers CLIPVisionConfig: image_size, patch_size, hidden_size,
+        num_attention_heads, num_hidden_layers, intermediate_size, projection_dim, layer_norm_eps); weights go under the namespace
+        'clip_vision'."""
+        cfg = _lib.ClipVisionConfig()
+        cfg.image_size, cfg.patch, cfg.width, cfg.heads, cfg.layers = int(image_size), int(patch), int(width), int(heads), int(layers)
+        cfg.intermediate, cfg.projection_dim, cfg.ln_eps = int(intermediate), int(projection_dim), float(ln_eps)
+        check(self.lib.gl_clip_vision_configure(self._ctx, C.byref(cfg)))
+        self.clip_vision_cfg = dict(image_size=int(image_size), width=int(width), projection_dim=int(projection_dim),
+                                    tokens=(int(image_size) // int(patch)) ** 2 + 1)
+
+    def clip_vision_encode(self, pixel_values: torch.Tensor):
+        """pixel_values [S, 3, image_size, image_size] (preprocessed) -> (last_hidden [S, T, width], pooled [S, width] after
+        post_layernorm, image_embeds [S, projection_dim], not normalised), fp32."""
+        c = self.clip_vision_cfg
+        if c is None:
+            raise _lib.GligenAmdError("clip_vision_encode: the CLIP vision tower is not configured")
+        if pixel_values.dim() != 4 or tuple(pixel_values.shape[1:]) != (3, c["image_size"], c["image_size"]) or pixel_values.shape[0] < 1:
+            raise ValueError(f"clip_vision_encode: pixel_values {tuple(pixel_values.shape)}, expected [S >= 1, 3, {c['image_size']}, {c['image_size']}]")
+        S = int(pixel_values.shape[0])
+        px = pixel_values.to(device=self.device, dtype=torch.float32).contiguous()
+        hidden = torch.empty((S, c["tokens"], c["width"]), device=self.device, dtype=torch.float32)
+        pooled = torch.empty((S, c["width"]), device=self.device, dtype=torch.float32)
+        embeds = torch.empty((S, c["projection_dim"]), device=self.device, dtype=torch.float32)
+        check(self.lib.gl_clip_vision_encode(self._ctx, _ptr(px), S, _ptr(hidden), _ptr(pooled), _ptr(embeds), _stream(self.device)))
+        return hidden, pooled, embeds
+
+    def op_clip_attention(self, qkv: torch.Tensor, S: int, T: int, heads: int, causal: bool = False, out: Optional[torch.Tensor] = None):
+        """The CLIP towers' attention launch: qkv bf16 [>= S * T, 3 * heads * 64] rows [q | k | v] -> bf16 [S * T, heads * 64] (written
+        into `out` when given: rows >= S * T of it are left alone)."""
+        if qkv.dtype != torch.bfloat16 or qkv.dim() != 2 or qkv.shape[1] != 3 * heads * 64 or qkv.shape[0] < S * T or not qkv.is_contiguous():
+            raise ValueError("op_clip_attention: qkv must be contiguous bf16 [>= S * T, 3 * heads * 64]")
+        if out is None:
+            out = torch.empty((S * T, heads * 64), device=self.device, dtype=torch.bfloat16)
+        elif out.dtype != torch.bfloat16 or out.dim() != 2 or out.shape[1] != heads * 64 or out.shape[0] < S * T or not out.is_contiguous():
+            raise ValueError("op_clip_attention: out must be contiguous bf16 [>= S * T, heads * 64]")
+        check(self.lib.gl_op_clip_attention(self._ctx, _ptr(qkv), _ptr(out), int(S), int(T), int(heads), int(bool(causal)), _stream(self.device)))
+        return out
 
     def upload(self, namespace: str, state_dict: Mapping[str, torch.Tensor], prefix_filter: Optional[str] = None) -> int:
         """Upload fp32 parameters under '<namespace>/<reference state_dict key>'."""

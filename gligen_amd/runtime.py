@@ -122,6 +122,70 @@ def build_clip_text_engine(embedder, arena_gb: float = 0.25) -> Engine:
     return eng
 
 
+CLIP_VISION_PREFIXES = ("vision_model.", "visual_projection.")
+
+
+def clip_vision_keys(layers: int):
+    """The vision tower's tensors and visual_projection under their transformers keys (8 + 16 per layer)."""
+    v = "vision_model."
+    keys = [v + "embeddings.class_embedding", v + "embeddings.patch_embedding.weight", v + "embeddings.position_embedding.weight",
+            v + "pre_layrnorm.weight", v + "pre_layrnorm.bias"]
+    for l in range(layers):
+        p = f"{v}encoder.layers.{l}."
+        for m in ("self_attn.k_proj", "self_attn.v_proj", "self_attn.q_proj", "self_attn.out_proj", "layer_norm1", "mlp.fc1", "mlp.fc2", "layer_norm2"):
+            keys += [p + m + ".weight", p + m + ".bias"]
+    return keys + [v + "post_layernorm.weight", v + "post_layernorm.bias", "visual_projection.weight"]
+
+
+def clip_vision_upload_dict(state_dict: Mapping[str, torch.Tensor], layers: int) -> Dict[str, torch.Tensor]:
+    """What the engine is given for a CLIPModel state_dict (the text side -- text_model.*, text_projection.*, logit_scale -- is not
+    the vision tower's and is ignored) or a CLIPVisionModelWithProjection one: `position_ids` dropped, strictly otherwise -- a missing
+    or an unknown vision tensor raises."""
+    seen = {k: v for k, v in state_dict.items() if k.startswith(CLIP_VISION_PREFIXES) and not k.endswith("position_ids")}
+    other = sorted(k for k in state_dict if not k.startswith(CLIP_VISION_PREFIXES + ("text_model.", "text_projection.")) and k != "logit_scale")
+    want = clip_vision_keys(layers)
+    missing = [k for k in want if k not in seen]
+    extra = sorted(set(seen) - set(want)) + other
+    if missing or extra:
+        raise KeyError(f"state_dict does not match a {layers}-layer CLIP vision tower with projection: missing {missing[:4]}, unexpected {extra[:4]}")
+    return {k: seen[k] for k in want}
+
+
+def clip_vision_arena_gb(images: int = 8, tokens: int = 257, width: int = 1024, intermediate: int = 4096, patch_k: int = 640) -> float:
+    """The activation bytes Engine::clip_vision_encode needs for `images` at once (its need() formula), with 25 % on top: 8 images of
+    ViT-L/14 are 2304 rows x 26.6 KB + patch rows = 64 MB -> 0.08."""
+    up = lambda n: -(-n // 256) * 256
+    need = up(images * tokens) * (width * 18 + intermediate * 2) + up(images * (tokens - 1)) * patch_k * 2 + up(images) * width * 2 + 10 * 256
+    return 1.25 * need / 2 ** 30
+
+
+def build_clip_vision_engine(clip_model, arena_gb: Optional[float] = None) -> Engine:
+    """The native vision tower + visual_projection of a transformers CLIPModel or CLIPVisionModelWithProjection: its own engine, the
+    arena sized for 8 images at once by default (more are encoded in chunks)."""
+    dev = module_device(clip_model)
+    cfg = getattr(clip_model.config, "vision_config", clip_model.config)
+    layers = len(clip_model.vision_model.encoder.layers)
+    projection_dim = int(clip_model.visual_projection.weight.shape[0])
+    if cfg.hidden_act != "quick_gelu":
+        raise NotImplementedError(f"CLIP vision tower with hidden_act={cfg.hidden_act!r}: the native path implements quick_gelu")
+    if cfg.num_channels != 3:
+        raise NotImplementedError(f"CLIP vision tower with num_channels={cfg.num_channels}: the native path reads 3-channel pixel_values")
+    if arena_gb is None:
+        kpad = -(-3 * cfg.patch_size ** 2 // 64) * 64
+        tokens = (cfg.image_size // max(cfg.patch_size, 1)) ** 2 + 1
+        arena_gb = max(clip_vision_arena_gb(8, tokens, cfg.hidden_size, cfg.intermediate_size, kpad), 0.03)
+    eng = Engine(dev, arena_gb=arena_gb)
+    try:
+        eng.configure_clip_vision(image_size=cfg.image_size, patch=cfg.patch_size, width=cfg.hidden_size, heads=cfg.num_attention_heads, layers=layers,
+                                  intermediate=cfg.intermediate_size, projection_dim=projection_dim, ln_eps=cfg.layer_norm_eps)
+        eng.upload("clip_vision", clip_vision_upload_dict(clip_model.state_dict(), layers))
+        eng.finalize()
+    except Exception:
+        eng.close()
+        raise
+    return eng
+
+
 def build_vae_engine(ae, arena_gb: float = 8.0) -> Engine:
     dev = module_device(ae)
     eng = Engine(dev, arena_gb=arena_gb)

@@ -136,12 +136,52 @@ def _clip():
     return _CLIP["model"], _CLIP["processor"]
 
 
+def _clip_vision():
+    """The native vision tower of _clip()'s model (the checkpoint has no vision weights: CLIPModel supplies them and the processor),
+    built once and kept next to the model."""
+    model, processor = _clip()
+    if "vision" not in _CLIP:
+        from gligen_amd.runtime import build_clip_vision_engine
+        _CLIP["vision"] = build_clip_vision_engine(model)
+    return model, processor, _CLIP["vision"]
+
+
+def _drop_clip():
+    """Forget the cached CLIPModel, its processor and the native vision engine built from it."""
+    eng = _CLIP.pop("vision", None)
+    if eng is not None:
+        eng.close()
+    _CLIP.clear()
+
+
 @torch.no_grad()
-def get_clip_feature(model, processor, input, is_image=False):
+def get_clip_image_features(model, processor, paths, vision):
+    """get_clip_feature(..., is_image=True) for a list of image files (None kept in place): ONE preprocess and ONE
+    vision.clip_vision_encode for all of them. The tail is the reference's: image_embeds re-projected with `projection_matrix`, unit
+    norm x 28.7 (normalising image_embeds first, as CLIPModel does, cancels in that norm)."""
+    given = [i for i, p in enumerate(paths) if p is not None]
+    out = [None] * len(paths)
+    if not given:
+        return out
+    images = [Image.open(paths[i]).convert("RGB") for i in given]
+    pixel_values = processor(images=images, return_tensors="pt", padding=True)["pixel_values"]
+    embeds = vision.clip_vision_encode(pixel_values)[2]
+    feature = project(embeds, torch.load("projection_matrix").to(embeds.device).T)
+    feature = feature / feature.norm(dim=-1, keepdim=True) * 28.7
+    for j, i in enumerate(given):
+        out[i] = feature[j:j + 1]
+    return out
+
+
+@torch.no_grad()
+def get_clip_feature(model, processor, input, is_image=False, vision=None):
     """Text: pooler_output before projection. Image: image_embeds re-projected with the text
-    projection matrix and scaled to norm 28.7 (reference gligen_inference.py:104-128)."""
+    projection matrix and scaled to norm 28.7 (reference gligen_inference.py:104-128). vision (an engine with the native CLIP vision
+    tower, gligen_amd.runtime.build_clip_vision_engine): the image runs through it instead of `model`, without the dummy text pass."""
     if input is None:
         return None
+    if is_image and vision is not None:
+        return get_clip_image_features(model, processor, [input], vision)[0]
     if is_image:
         image = Image.open(input).convert("RGB")
         inputs = processor(images=[image], return_tensors="pt", padding=True)
@@ -176,7 +216,8 @@ def batch_to_device(batch, dev):
 def prepare_batch(meta, batch=1, max_objs=30, text_encoder=None):
     """text_encoder (run() with native_clip): the phrase features are the pooled rows of the checkpoint's own text tower, one
     batched call -- the same openai/clip-vit-large-patch14 tower get_clip_feature reads them from; CLIPModel is then loaded only
-    for image-grounded phrases."""
+    for image-grounded phrases, for its vision weights and its processor: the images run through the native vision tower
+    (get_clip_image_features), one batched call, and the model's own forward is not used."""
     phrases, images = meta.get("phrases"), meta.get("images")
     n = len(meta["locations"])
     images = [None] * n if images is None else images
@@ -191,8 +232,8 @@ def prepare_batch(meta, batch=1, max_objs=30, text_encoder=None):
                 text_features[i] = pooled[j]
         image_features = [None] * n
         if any(im is not None for im in images):
-            model, processor = _clip()
-            image_features = [get_clip_feature(model, processor, im, is_image=True) for im in images]
+            model, processor, vision = _clip_vision()
+            image_features = get_clip_image_features(model, processor, images, vision)
     elif text_features is None and image_features is None:  # the reference path: encode with CLIP ViT-L/14
         model, processor = _clip()
         text_features = [get_clip_feature(model, processor, p, is_image=False) for p in phrases]
@@ -725,7 +766,7 @@ def main(argv=None):
     parser.add_argument("--synthetic", type=str, default=None, choices=["text", "text_image", "keypoint"],
                         help="run with seeded random weights and features (no checkpoint / CLIP needed)")
     parser.add_argument("--inpaint", action="store_true", help="with --synthetic text: the inpainting model (9-channel first conv, encode + blend)")
-    parser.add_argument("--native_clip", action="store_true", help="run the checkpoint's CLIP text tower (prompt, negative prompt, phrases) in the native HIP engine instead of transformers")
+    parser.add_argument("--native_clip", action="store_true", help="run CLIP in the native HIP engine instead of transformers: the checkpoint's text tower (prompt, negative prompt, phrases) and, for image-grounded phrases, the ViT-L/14 vision tower")
     parser.add_argument("--ckpt", type=str, default=None, help="run only the meta_list entries whose checkpoint path contains this string")
     parser.add_argument("--seed", type=int, default=None, help="seed of x_T (one draw for the whole batch, sliced across ranks)")
     parser.add_argument("--lanes", type=int, default=None, help="with --repeat: whole batches in flight (default 3, the bench's schedule); without: per-GPU batches of 32 and more run as two half-batches in flight unless this is 1")

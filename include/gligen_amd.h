@@ -81,6 +81,15 @@ typedef struct gl_clip_text_config {
     float ln_eps;
 } gl_clip_text_config;
 
+/* CLIPVisionConfig of the vision tower the image-grounded phrases are encoded with (reference gligen_inference.py:104-128 reads
+ * image_embeds of openai/clip-vit-large-patch14: 224, 14, 1024, 16, 24, 4096, 768, 1e-5). Supported: three channels, width =
+ * heads * 64 <= 2048, intermediate a multiple of 64, image_size a multiple of patch, 1 + (image_size / patch)^2 <= 288 tokens;
+ * anything else is refused with a message that names the offending value. */
+typedef struct gl_clip_vision_config {
+    int image_size, patch, width, heads, layers, intermediate, projection_dim;
+    float ln_eps;
+} gl_clip_vision_config;
+
 /* One PLMS run (reference ldm/models/diffusion/plms.py:65-162): schedule arrays are host
  * pointers of length n_steps, in sampling order (time descending). */
 typedef struct gl_plms_args {
@@ -146,6 +155,21 @@ int gl_finalize(gl_ctx* ctx);
  * softmax. S is processed in chunks when the arena is small. */
 int gl_clip_text_configure(gl_ctx* ctx, const gl_clip_text_config* cfg);
 int gl_clip_text_encode(gl_ctx* ctx, const int32_t* ids, const int32_t* eos_index, int S, int T, float* last_hidden, float* pooled, gl_stream s);
+
+/* The CLIP vision tower with its projection (transformers CLIPVisionModelWithProjection; CLIPModel's vision side). Configure before
+ * gl_finalize and upload the tensors under "clip_vision/" + the transformers key: vision_model.embeddings.{class_embedding,
+ * patch_embedding.weight, position_embedding.weight}, vision_model.pre_layrnorm.*, vision_model.encoder.layers.N.* (the 16 tensors per
+ * layer of the text tower), vision_model.post_layernorm.*, visual_projection.weight. Encode: pixel_values fp32 [S][3][image_size]
+ * [image_size] (device, already resized / cropped / normalised) -> last_hidden fp32 [S][T][width] = last_hidden_state (T = 1 +
+ * (image_size / patch)^2), pooled fp32 [S][width] = post_layernorm(last_hidden[:, 0]), image_embeds fp32 [S][projection_dim] =
+ * pooled visual_projection^T, NOT normalised (the caller normalises). Each output may be NULL (not all three). Numerics as the text
+ * tower; S is processed in chunks when the arena is small. */
+int gl_clip_vision_configure(gl_ctx* ctx, const gl_clip_vision_config* cfg);
+int gl_clip_vision_encode(gl_ctx* ctx, const float* pixel_values, int S, float* last_hidden, float* pooled, float* image_embeds, gl_stream s);
+/* The towers' attention launch on its own (operator tests): qkv bf16 rows [S * T][3 * heads * 64] = [q | k | v] -> out bf16
+ * [S * T][heads * 64] = softmax(q k^T / 8 (+ causal mask)) v per (sequence, head). T <= 96: the text tower's kernel; 96 < T <= 288,
+ * not causal: the vision tower's. Anything else is refused with a message that names the value. */
+int gl_op_clip_attention(gl_ctx* ctx, const void* qkv, void* out, int S, int T, int heads, int causal, gl_stream s);
 
 /* Step-invariant part of UNetModel.forward: position_net(**grounding_input) (openaimodel.py:433),
  * fuser.linear(objs) (attention.py:239) and attn2.to_k/to_v(context) (attention.py:130-131). */
