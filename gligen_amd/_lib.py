@@ -1,4 +1,4 @@
-"""ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h).
+"""ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h and include/gligen_amd_image.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -41,6 +41,11 @@ class ClipTextConfig(C.Structure):   # = gl_clip_text_config
 
 class ClipVisionConfig(C.Structure):   # = gl_clip_vision_config
     _fields_ = [(n, C.c_int) for n in ("image_size", "patch", "width", "heads", "layers", "intermediate", "projection_dim")] + [("ln_eps", C.c_float)]
+
+
+class ImageDesc(C.Structure):   # = gl_image_desc
+    _fields_ = [("pixels", C.c_void_p)] + [(n, C.c_int) for n in ("width", "height", "row_stride", "resized_w", "resized_h",
+                                                                  "crop_x", "crop_y", "crop_w", "crop_h")]
 
 
 class Grounding(C.Structure):
@@ -152,6 +157,12 @@ SYMBOLS = {
     "gl_op_proj_attention": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, C.POINTER(_I), _P]),
 }
 
+# every symbol include/gligen_amd_image.h declares (the image front end)
+IMAGE_SYMBOLS = {
+    "gl_op_image_resample": (_I, [_P, C.POINTER(ImageDesc), _I, _I, _I, C.POINTER(C.c_float), _P, _P]),
+    "gl_image_resample_coeffs": (_I, [_I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_I), _I]),
+}
+
 _lib = None
 
 
@@ -169,7 +180,7 @@ def load() -> C.CDLL:
     # torch.cuda.is_available() is True) -- seen with build() called before the first `import torch` of the process.
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in SYMBOLS.items():
+    for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -1,5 +1,6 @@
 // extern "C" surface of libgligen_amd.so (see include/gligen_amd.h). Nothing throws across it.
 #include "engine.h"
+#include "image.h"
 #include "train.h"
 
 #include <cstdlib>
@@ -11,6 +12,7 @@ using namespace gl;
 struct gl_ctx {
     std::shared_ptr<Engine> holder;   // forks (gl_ctx_fork) keep the context whose weights they share alive
     Engine* eng;
+    ImageStage image_stage;           // gl_op_image_resample's pinned staging block
 };
 
 #define GL_API_BEGIN try {
@@ -70,7 +72,7 @@ int gl_ctx_create(int device, size_t arena_bytes, gl_ctx** out) {
     std::shared_ptr<Engine> eng(new Engine(device));
     eng->arena().init(arena_bytes ? arena_bytes : (size_t(8) << 30));
     eng->init_workspace();
-    *out = new gl_ctx{eng, eng.get()};
+    *out = new gl_ctx{eng, eng.get(), {}};
     GL_API_END
 }
 
@@ -79,7 +81,7 @@ int gl_ctx_fork(gl_ctx* parent, size_t arena_bytes, gl_ctx** out) {
     if (!out) return gl::set_error(GL_ERR_ARG, "null out pointer");
     GL_API_BEGIN
     std::shared_ptr<Engine> e = Engine::fork(parent->holder, arena_bytes);
-    *out = new gl_ctx{e, e.get()};
+    *out = new gl_ctx{e, e.get(), {}};
     GL_API_END
 }
 
@@ -167,6 +169,43 @@ int gl_op_clip_attention(gl_ctx* ctx, const void* qkv, void* out, int n_seq, int
     GL_API_BEGIN
     int r = clip_attn_launch((const bf16*)qkv, (bf16*)out, n_seq, n_tok, heads, causal, S(s));
     if (r != GL_OK) throw GlError(r, gl::last_error());
+    GL_API_END
+}
+
+int gl_op_image_resample(gl_ctx* ctx, const gl_image_desc* images, int n_img, int filter, int out_kind, const float* lut_host, void* out, gl_stream s) {
+    NEED(ctx);
+    GL_API_BEGIN
+    ImagePlan plan;
+    GL_TRY(image_resample_plan(images, n_img, filter, out_kind, lut_host, out, &plan));
+    gl::Arena& ar = ctx->eng->arena();
+    const size_t mk = ar.mark();
+    struct Release {
+        gl::Arena& ar;
+        size_t mk;
+        ~Release() { ar.release(mk); }   // stream-ordered reuse, as every operator's workspace
+    } release{ar, mk};
+    void* work = ar.alloc(plan.work_bytes);
+    GL_TRY(image_resample_run(ctx->image_stage, plan, work, S(s)));
+    ctx->eng->n_launches += 2;
+    GL_API_END
+}
+
+int gl_image_resample_coeffs(int in_size, int out_size, int filter, int* ksize, int* bounds, int bounds_cap, int* coeffs, int coeffs_cap) {
+    if (!ksize) return gl::set_error(GL_ERR_ARG, "gl_image_resample_coeffs: null ksize");
+    GL_API_BEGIN
+    std::shared_ptr<const ResampleAxis> t;
+    GL_TRY(resample_axis(in_size, out_size, filter, &t));
+    *ksize = t->ksize;
+    if (bounds) {
+        if (bounds_cap < (int)t->bounds.size())
+            return gl::set_error(GL_ERR_ARG, "gl_image_resample_coeffs: bounds holds %d ints, 2 * out_size = %d are needed", bounds_cap, (int)t->bounds.size());
+        std::copy(t->bounds.begin(), t->bounds.end(), bounds);
+    }
+    if (coeffs) {
+        if ((int64_t)coeffs_cap < (int64_t)t->kk.size())
+            return gl::set_error(GL_ERR_ARG, "gl_image_resample_coeffs: coeffs holds %d ints, out_size * ksize = %zu are needed", coeffs_cap, t->kk.size());
+        std::copy(t->kk.begin(), t->kk.end(), coeffs);
+    }
     GL_API_END
 }
 

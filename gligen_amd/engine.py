@@ -30,6 +30,24 @@ def _f32(t: torch.Tensor, device) -> torch.Tensor:
     return t.to(device=device, dtype=torch.float32).contiguous()
 
 
+IMAGE_FILTERS = {"bicubic": 0, "bilinear": 1}      # gl_op_image_resample's filter argument
+
+
+def clip_resize_size(width: int, height: int, shortest_edge: int):
+    """(width, height) after CLIP's resize: the short side becomes `shortest_edge`, the long one int(shortest_edge * long / short)
+    (transformers get_resize_output_image_size with default_to_square=False)."""
+    short, long = (width, height) if width <= height else (height, width)
+    new_long = int(shortest_edge * long / short)
+    return (shortest_edge, new_long) if width <= height else (new_long, shortest_edge)
+
+
+def normalise_lut(mean, std) -> np.ndarray:
+    """[3, 256] float32: (float32(v) / float32(255) - float32(mean_c)) / float32(std_c), each operation rounded to float32 -- what
+    rescale by 1 / 255 followed by normalize gives for a u8 sample v."""
+    v = np.arange(256, dtype=np.float32)[None, :] / np.float32(255)
+    return ((v - np.asarray(mean, dtype=np.float32)[:, None]) / np.asarray(std, dtype=np.float32)[:, None]).astype(np.float32)
+
+
 SPATIAL_MAP_KEYS = dict(canny="canny_edge", hed="hed_edge", depth="depth", normal="normal", sem="sem")
 
 
@@ -200,6 +218,57 @@ class Engine:
         embeds = torch.empty((S, c["projection_dim"]), device=self.device, dtype=torch.float32)
         check(self.lib.gl_clip_vision_encode(self._ctx, _ptr(px), S, _ptr(hidden), _ptr(pooled), _ptr(embeds), _stream(self.device)))
         return hidden, pooled, embeds
+
+    def image_resample(self, images, sizes, crops=None, filter: str = "bicubic", lut=None):
+        """PIL.Image.resize + crop of 8-bit RGB images, bit for bit, for a batch of different sizes in two launches
+        (gl_op_image_resample). images: u8 [H, W, 3] tensors or arrays (host ones are uploaded; a device tensor may be a view with a
+        row stride); sizes: (width, height) each image is resized to; crops: (x, y, width, height) inside the resized image, None = all
+        of it. Returns the list of u8 [ch, cw, 3] device tensors, or, with lut (float32 [3, 256]: sample v of channel c becomes
+        lut[c, v]; all crops equal), one float32 [S, 3, ch, cw] tensor."""
+        if filter not in IMAGE_FILTERS:
+            raise ValueError(f"image_resample: filter {filter!r}; the resampler has {', '.join(IMAGE_FILTERS)}")
+        S = len(images)
+        if S < 1 or len(sizes) != S or (crops is not None and len(crops) != S):
+            raise ValueError("image_resample: one size (and one crop) per image, at least one image")
+        descs = (_lib.ImageDesc * S)()
+        keep = []
+        for i, im in enumerate(images):
+            t = im if isinstance(im, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(im))
+            if t.dtype != torch.uint8 or t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+                raise ValueError(f"image_resample: image {i} is {t.dtype} {tuple(t.shape)}; 3 interleaved u8 channels [H, W, 3] are read")
+            t = t.to(self.device)
+            if t.stride(2) != 1 or t.stride(1) != 3 or (t.shape[0] > 1 and t.stride(0) < 3 * t.shape[1]):
+                t = t.contiguous()
+            keep.append(t)
+            w, h = (int(v) for v in sizes[i])
+            x, y, cw, ch = (0, 0, w, h) if crops is None or crops[i] is None else (int(v) for v in crops[i])
+            d = descs[i]
+            d.pixels, d.width, d.height = t.data_ptr(), int(t.shape[1]), int(t.shape[0])
+            d.row_stride = int(t.stride(0)) if t.shape[0] > 1 else 3 * int(t.shape[1])
+            d.resized_w, d.resized_h, d.crop_x, d.crop_y, d.crop_w, d.crop_h = w, h, x, y, cw, ch
+        if lut is None:
+            outs = [torch.empty((max(d.crop_h, 0), max(d.crop_w, 0), 3), device=self.device, dtype=torch.uint8) for d in descs]
+            out = (C.c_void_p * S)(*[o.data_ptr() for o in outs])
+            check(self.lib.gl_op_image_resample(self._ctx, descs, S, IMAGE_FILTERS[filter], 0, None, out, _stream(self.device)))
+            return outs
+        table = np.ascontiguousarray(lut, dtype=np.float32)
+        if table.shape != (3, 256):
+            raise ValueError(f"image_resample: lut {table.shape}; one float32 row of 256 values per channel, [3, 256]")
+        px = torch.empty((S, 3, max(descs[0].crop_h, 0), max(descs[0].crop_w, 0)), device=self.device, dtype=torch.float32)
+        check(self.lib.gl_op_image_resample(self._ctx, descs, S, IMAGE_FILTERS[filter], 1, table.ctypes.data_as(C.POINTER(C.c_float)),
+                                            _ptr(px), _stream(self.device)))
+        return px
+
+    def clip_vision_preprocess(self, images, size: int, crop: int, mean, std, filter: str = "bicubic") -> torch.Tensor:
+        """transformers' CLIPImageProcessor on the device: resize the short side to `size` (clip_resize_size), centre crop `crop` x
+        `crop`, (v / 255 - mean) / std. images: u8 [H, W, 3] tensors or arrays of any sizes -> pixel_values float32 [S, 3, crop, crop]
+        on the device, the input of clip_vision_encode, bit for bit the processor's (Pillow backend)."""
+        size, crop = int(size), int(crop)
+        if crop > size:
+            raise ValueError(f"clip_vision_preprocess: crop {crop} larger than the resized short side {size} (the processor would pad)")
+        sizes = [clip_resize_size(int(im.shape[1]), int(im.shape[0]), size) for im in images]
+        crops = [((w - crop) // 2, (h - crop) // 2, crop, crop) for w, h in sizes]
+        return self.image_resample(images, sizes, crops, filter, normalise_lut(mean, std))
 
     def op_clip_attention(self, qkv: torch.Tensor, S: int, T: int, heads: int, causal: bool = False, out: Optional[torch.Tensor] = None):
         """The CLIP towers' attention launch: qkv bf16 [>= S * T, 3 * heads * 64] rows [q | k | v] -> bf16 [S * T, heads * 64] (written

@@ -186,6 +186,52 @@ def build_clip_vision_engine(clip_model, arena_gb: Optional[float] = None) -> En
     return eng
 
 
+def clip_preprocess_settings(image_processor, image_size: Optional[int] = None) -> dict:
+    """The arguments of Engine.clip_vision_preprocess read from a transformers CLIPImageProcessor: dict(size, crop, mean, std,
+    filter). Supported: do_resize with size.shortest_edge, resample BICUBIC or BILINEAR, do_center_crop with a square crop_size (equal
+    to the tower's image_size when that is given), do_rescale with rescale_factor 1 / 255, do_normalize with any mean and std.
+    Anything else raises NotImplementedError naming the field. Host only."""
+    ip = image_processor
+
+    def refuse(field, what):
+        raise NotImplementedError(f"native CLIP image preprocessing does not cover {field} {what}")
+
+    def entry(d, k):
+        return None if d is None else d.get(k) if isinstance(d, Mapping) else getattr(d, k, None)
+
+    if not getattr(ip, "do_resize", False):
+        refuse("do_resize", "= False (the images are resized to size.shortest_edge)")
+    size = getattr(ip, "size", None)
+    if entry(size, "shortest_edge") is None or any(entry(size, k) is not None for k in ("height", "width", "longest_edge", "max_height", "max_width")):
+        refuse("size", f"= {size!r} (only shortest_edge is implemented)")
+    resample = getattr(ip, "resample", None)
+    filters = {3: "bicubic", 2: "bilinear"}       # PIL.Image.Resampling
+    if resample is None or int(resample) not in filters:
+        refuse("resample", f"= {resample!r} (BICUBIC and BILINEAR are implemented)")
+    if not getattr(ip, "do_center_crop", False):
+        refuse("do_center_crop", "= False (the tower reads a square centre crop)")
+    crop = getattr(ip, "crop_size", None)
+    ch, cw = entry(crop, "height"), entry(crop, "width")
+    if ch is None or ch != cw or (image_size is not None and int(ch) != int(image_size)):
+        refuse("crop_size", f"= {crop!r} (a square crop" + (f" of the tower's image_size {image_size})" if image_size is not None else ")"))
+    if int(ch) > int(entry(size, "shortest_edge")):
+        refuse("crop_size", f"= {crop!r} larger than size.shortest_edge = {entry(size, 'shortest_edge')} (the processor would pad)")
+    if getattr(ip, "do_pad", None):
+        refuse("do_pad", "= True")
+    if not getattr(ip, "do_rescale", False):
+        refuse("do_rescale", "= False (samples are scaled by 1 / 255)")
+    if getattr(ip, "rescale_factor", None) != 1 / 255:
+        refuse("rescale_factor", f"= {getattr(ip, 'rescale_factor', None)!r} (1 / 255 is implemented)")
+    mean, std = getattr(ip, "image_mean", None), getattr(ip, "image_std", None)
+    if not getattr(ip, "do_normalize", False):
+        refuse("do_normalize", "= False")
+    for name, v in (("image_mean", mean), ("image_std", std)):
+        if not isinstance(v, (list, tuple)) or len(v) != 3 or (name == "image_std" and any(float(x) == 0 for x in v)):
+            refuse(name, f"= {v!r} (three values, one per channel)")
+    return dict(size=int(entry(size, "shortest_edge")), crop=int(ch), mean=tuple(float(x) for x in mean), std=tuple(float(x) for x in std),
+                filter=filters[int(resample)])
+
+
 def build_vae_engine(ae, arena_gb: float = 8.0) -> Engine:
     dev = module_device(ae)
     eng = Engine(dev, arena_gb=arena_gb)

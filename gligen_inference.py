@@ -154,17 +154,47 @@ def _drop_clip():
     _CLIP.clear()
 
 
+def _native_preprocess_settings(processor, vision, preprocess):
+    """The settings of the native image front end (gligen_amd.runtime.clip_preprocess_settings) when it is to be used, else None:
+    "processor" never uses it; "auto" uses it when `vision` offers clip_vision_preprocess and the processor carries an image processor
+    with supported settings; "native" insists, and raises NotImplementedError naming what stands in the way. Host only."""
+    if preprocess not in ("auto", "native", "processor"):
+        raise ValueError(f"preprocess = {preprocess!r}: 'auto', 'native' or 'processor'")
+    if preprocess == "processor":
+        return None
+    strict = preprocess == "native"
+    ip = getattr(processor, "image_processor", None)
+    if not hasattr(vision, "clip_vision_preprocess") or ip is None:
+        if strict:
+            raise NotImplementedError("native CLIP image preprocessing needs an engine with clip_vision_preprocess and a processor with an image_processor")
+        return None
+    from gligen_amd.runtime import clip_preprocess_settings
+    try:
+        return clip_preprocess_settings(ip, (getattr(vision, "clip_vision_cfg", None) or {}).get("image_size"))
+    except NotImplementedError:
+        if strict:
+            raise
+        return None
+
+
 @torch.no_grad()
-def get_clip_image_features(model, processor, paths, vision):
+def get_clip_image_features(model, processor, paths, vision, preprocess="auto"):
     """get_clip_feature(..., is_image=True) for a list of image files (None kept in place): ONE preprocess and ONE
-    vision.clip_vision_encode for all of them. The tail is the reference's: image_embeds re-projected with `projection_matrix`, unit
+    vision.clip_vision_encode for all of them. preprocess: "auto" resizes, crops and normalises on the device
+    (vision.clip_vision_preprocess, bit for bit the processor's pixel_values) when the engine and the processor's settings allow it and
+    calls the processor otherwise; "processor" always calls the processor; "native" raises NotImplementedError where "auto" would fall
+    back. The tail is the reference's: image_embeds re-projected with `projection_matrix`, unit
     norm x 28.7 (normalising image_embeds first, as CLIPModel does, cancels in that norm)."""
+    settings = _native_preprocess_settings(processor, vision, preprocess)
     given = [i for i, p in enumerate(paths) if p is not None]
     out = [None] * len(paths)
     if not given:
         return out
     images = [Image.open(paths[i]).convert("RGB") for i in given]
-    pixel_values = processor(images=images, return_tensors="pt", padding=True)["pixel_values"]
+    if settings is not None:
+        pixel_values = vision.clip_vision_preprocess([np.array(im) for im in images], **settings)
+    else:
+        pixel_values = processor(images=images, return_tensors="pt", padding=True)["pixel_values"]
     embeds = vision.clip_vision_encode(pixel_values)[2]
     feature = project(embeds, torch.load("projection_matrix").to(embeds.device).T)
     feature = feature / feature.norm(dim=-1, keepdim=True) * 28.7
@@ -174,14 +204,15 @@ def get_clip_image_features(model, processor, paths, vision):
 
 
 @torch.no_grad()
-def get_clip_feature(model, processor, input, is_image=False, vision=None):
+def get_clip_feature(model, processor, input, is_image=False, vision=None, preprocess="auto"):
     """Text: pooler_output before projection. Image: image_embeds re-projected with the text
     projection matrix and scaled to norm 28.7 (reference gligen_inference.py:104-128). vision (an engine with the native CLIP vision
-    tower, gligen_amd.runtime.build_clip_vision_engine): the image runs through it instead of `model`, without the dummy text pass."""
+    tower, gligen_amd.runtime.build_clip_vision_engine): the image runs through it instead of `model`, without the dummy text pass,
+    preprocessed as get_clip_image_features' `preprocess` says."""
     if input is None:
         return None
     if is_image and vision is not None:
-        return get_clip_image_features(model, processor, [input], vision)[0]
+        return get_clip_image_features(model, processor, [input], vision, preprocess)[0]
     if is_image:
         image = Image.open(input).convert("RGB")
         inputs = processor(images=[image], return_tensors="pt", padding=True)

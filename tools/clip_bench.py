@@ -8,8 +8,12 @@ Line 3: 8 image features (ViT-L/14, 257 tokens) -- parent: get_clip_feature(...,
 call per image, each with its dummy four-token text pass; native: get_clip_image_features, one batched call through the native
 vision tower. The pixel tensors are prepared beforehand (the processor and Image.open are stand-ins that hand them out), so PIL is in
 neither arm; both read `projection_matrix` as the functions do. Also the time of one clip_attn_long_kernel launch at S = 8, T = 257.
+Line 4: the image preprocessing in front of line 3, for eight 640 x 480 and for eight 1920 x 1080 u8 images -- host: transformers'
+CLIPImageProcessor on PIL images (what get_clip_image_features(..., preprocess="processor") calls), its pixel_values left on the host
+as the processor returns them; native: Engine.clip_vision_preprocess on the same pixels as host arrays, i.e. INCLUDING the
+host-to-device copy of the u8 pixels, pixel_values left on the device where the tower reads them. native_GBps = source bytes / time.
 
-    PYTHONPATH=. python tools/clip_bench.py [--reps 20] [--warmup 3] [--no-phrases] [--no-images]
+    PYTHONPATH=. python tools/clip_bench.py [--reps 20] [--warmup 3] [--no-phrases] [--no-images] [--no-preprocess] [--preprocess-only]
 """
 import argparse
 import importlib.util
@@ -48,6 +52,28 @@ def alternate(a, b, dev, warmup, reps):
     return statistics.median(ta), statistics.median(tb)
 
 
+def bench_preprocess(dev, warmup, reps):
+    import numpy as np
+    import transformers
+    from PIL import Image
+    from gligen_amd.runtime import clip_preprocess_settings, scratch_engine
+    proc = transformers.CLIPImageProcessor()
+    kw = clip_preprocess_settings(proc, 224)
+    eng = scratch_engine(dev)
+    rec = dict(bench="image_preprocess", images=8, reps=reps)
+    for name, (w, h) in (("640x480", (640, 480)), ("1920x1080", (1920, 1080))):
+        arrays = [np.random.RandomState(i).randint(0, 256, (h, w, 3), dtype=np.uint8) for i in range(8)]
+        pils = [Image.fromarray(a) for a in arrays]
+        host = lambda: proc(images=pils, return_tensors="pt")["pixel_values"]
+        native = lambda: eng.clip_vision_preprocess(arrays, **kw)
+        equal = bool(torch.equal(host(), native().cpu()))
+        t_host, t_nat = alternate(host, native, dev, warmup, reps)
+        src = sum(a.nbytes for a in arrays)
+        rec[name] = dict(processor_host_ms=round(t_host, 3), native_ms=round(t_nat, 3), speedup=round(t_host / t_nat, 2), source_MB=round(src / 1e6, 2),
+                         native_GBps=round(src / t_nat / 1e6, 2), bit_equal=equal)
+    print(json.dumps(rec))
+
+
 @torch.no_grad()
 def main():
     ap = argparse.ArgumentParser()
@@ -55,7 +81,11 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no-phrases", action="store_true")
     ap.add_argument("--no-images", action="store_true")
+    ap.add_argument("--no-preprocess", action="store_true")
+    ap.add_argument("--preprocess-only", action="store_true")
     a = ap.parse_args()
+    if a.preprocess_only:
+        return bench_preprocess(torch.device("cuda:0"), a.warmup, a.reps)
     from ldm.modules.encoders.modules import FrozenCLIPEmbedder
     import gligen_inference as gi
     dev = torch.device("cuda:0")
@@ -163,6 +193,8 @@ def main():
     print(json.dumps(dict(bench="image_features", images=8, tokens=257, reps=a.reps, hf_clipmodel_ms=round(t_par, 3), hip_ms=round(t_nat, 3),
                           speedup=round(t_par / t_nat, 3), launches=launches, hip_tflops=round(gf / t_nat, 2), rel_mse_vs_hf_fp32_device=rel,
                           attn_long_us_per_launch_S8_T257_H16=round(1e3 * t_attn, 2))))
+    if not a.no_preprocess:
+        bench_preprocess(dev, a.warmup, a.reps)
 
 
 if __name__ == "__main__":
