@@ -16,7 +16,8 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 INCLUDE = HERE.parent / "include"
 LIB = HERE / "libgligen_amd.so"
-SOURCES = ["gemm.hip", "ffn.hip", "attention.hip", "clip.hip", "norm.hip", "misc.hip", "image.hip", "convnext.hip", "train.hip", "engine.hip", "capi.hip"]
+SOURCES = ["gemm.hip", "ffn.hip", "attention.hip", "clip.hip", "norm.hip", "misc.hip", "image.hip", "convnext.hip", "train.hip",
+           "engine.hip", "engine_unet.hip", "engine_policy.hip", "engine_vae.hip", "engine_clip.hip", "engine_spatial.hip", "engine_sampler.hip", "capi.hip"]
 # attention: keep MFMA accumulators in VGPRs (gfx950 has one unified register file); the default AGPR
 # form costs a v_accvgpr_read/write pair per accumulator per KV tile around the softmax rescale
 # ffn: the GEGLU micro-steps of the row-local feed-forward are plain fp32 on purpose (packed fp32 is dearer beside MFMAs): no SLP packing
@@ -56,7 +57,7 @@ def build_native(force: bool = False, verbose: bool = False) -> Path:
             print(r.stderr, file=sys.stderr)
         return obj
 
-    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 4)) as ex:
+    with ThreadPoolExecutor(max_workers=min(len(SOURCES), os.cpu_count() or 4, 16)) as ex:
         objs = list(ex.map(compile_one, SOURCES))
     cmd = [hipcc, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", str(LIB), *map(str, objs)]
     r = subprocess.run(cmd, capture_output=True, text=True)

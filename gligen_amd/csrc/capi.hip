@@ -1,5 +1,5 @@
 // extern "C" surface of libgligen_amd.so (see include/gligen_amd.h). Nothing throws across it.
-#include "engine.h"
+#include "engine_impl.h"
 #include "image.h"
 #include "train.h"
 
@@ -421,12 +421,9 @@ int gl_op_linear(gl_ctx* ctx, const void* x, const void* w, const float* bias, c
                  int M, int N, int K, int act, int out_f32, gl_stream s) {
     NEED(ctx);
     GL_API_BEGIN
-    AOperand A;
-    aoperand_rows(A, (const bf16*)x, K, K);
-    Epilogue E;
-    epilogue_defaults(E);
-    E.out = y; E.ldo = N; E.out_f32 = out_f32; E.bias = bias; E.act = act; E.res = (const bf16*)res; E.ldres = N;
-    int r = gemm_launch(A, (const bf16*)w, M, N, K, E, ctx->eng->splitk_ws(), ctx->eng->splitk_ws_bytes(), S(s));
+    Epilogue E = e_rows_res(y, N, bias, (const bf16*)res);
+    E.out_f32 = out_f32; E.act = act;
+    int r = gemm_launch(a_rows((const bf16*)x, K), (const bf16*)w, M, N, K, E, ctx->eng->splitk_ws(), ctx->eng->splitk_ws_bytes(), S(s));
     if (r != GL_OK) throw GlError(r, gl::last_error());
     GL_API_END
 }
@@ -441,12 +438,9 @@ int gl_op_geglu(gl_ctx* ctx, const void* x, const float* w_f32, const float* b_f
     const int layout = gl::gemm_geglu_layout();
     int r = pack_geglu_launch(w_f32, b_f32, wp, bp, inner, K, layout, S(s));
     if (r != GL_OK) throw GlError(r, gl::last_error());
-    AOperand A;
-    aoperand_rows(A, (const bf16*)x, K, K);
-    Epilogue E;
-    epilogue_defaults(E);
-    E.act = ACT_GEGLU; E.geglu16 = layout; E.out = y; E.ldo = inner; E.bias = bp;
-    r = gemm_launch(A, wp, M, 2 * inner, K, E, ctx->eng->splitk_ws(), ctx->eng->splitk_ws_bytes(), S(s));
+    Epilogue E = e_rows(y, inner, bp);
+    E.act = ACT_GEGLU; E.geglu16 = layout;
+    r = gemm_launch(a_rows((const bf16*)x, K), wp, M, 2 * inner, K, E, ctx->eng->splitk_ws(), ctx->eng->splitk_ws_bytes(), S(s));
     if (r != GL_OK) throw GlError(r, gl::last_error());
     GL_API_END
 }
@@ -469,13 +463,9 @@ int gl_op_ln_linear(gl_ctx* ctx, const void* a, int M, int K0, const float* w0, 
     const int ld = C / 32;
     float2* stats = ar.get<float2>((size_t)M * ld);
     {
-        AOperand A;
-        aoperand_rows(A, (const bf16*)a, K0, K0);
-        Epilogue E;
-        epilogue_defaults(E);
-        E.out = x_out; E.ldo = C; E.bias = b0; E.res = (const bf16*)res; E.ldres = C;
+        Epilogue E = e_rows_res(x_out, C, b0, (const bf16*)res);
         E.stats_out = stats; E.stats_ld = ld;
-        ck(gemm_launch(A, w0b, M, C, K0, E, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s)));
+        ck(gemm_launch(a_rows((const bf16*)a, K0), w0b, M, C, K0, E, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s)));
     }
     const int nb = gemm_last_stats_nb();
     // ---- the consumer's folded weights: W1 * gamma, b1 + W1 beta, csum of the packed rows
@@ -507,7 +497,7 @@ int gl_op_ln_linear(gl_ctx* ctx, const void* a, int M, int K0, const float* w0, 
     const bool fold = nb > 0 && gemm_ln_fold_supported(A, M, N1, C, E);
     *used_fold = fold ? 1 : 0;
     if (fold) {
-        E.ln_stats = stats; E.ln_nb = nb; E.ln_ld = ld; E.ln_csum = cs; E.ln_inv_c = 1.f / (float)C; E.ln_eps = 1e-5f;
+        e_fold_ln(E, RowStats{stats, nb, ld}, cs, C);
     } else {   // the fallback the engine takes where no statistics exist: ln_kernel without affine, same folded weights
         bf16* xn = ar.get<bf16>((size_t)M * C);
         LNParams P{};
@@ -568,18 +558,12 @@ int gl_op_feedforward(gl_ctx* ctx, const void* x, int M, int C, const float* gam
         bf16* w2b = ar.get<bf16>((size_t)C * 4 * C);
         ck(cast_f32_bf16_launch(w2, w2b, (int64_t)C * 4 * C, S(s)));
         bf16* hid = ar.get<bf16>((size_t)M * 4 * C);
-        AOperand A;
-        aoperand_rows(A, in, C, C);
-        Epilogue E;
-        epilogue_defaults(E);
-        E.act = ACT_GEGLU; E.geglu16 = layout; E.out = hid; E.ldo = 4 * C; E.bias = bp;
-        ck(gemm_launch(A, wp, M, 8 * C, C, E, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s)));
-        AOperand A2;
-        aoperand_rows(A2, hid, 4 * C, 4 * C);
-        Epilogue E2;
-        epilogue_defaults(E2);
-        E2.out = y; E2.ldo = C; E2.bias = b2; E2.res = (const bf16*)res; E2.ldres = C; E2.gate = gate;
-        ck(gemm_launch(A2, w2b, M, C, 4 * C, E2, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s)));
+        Epilogue E = e_rows(hid, 4 * C, bp);
+        E.act = ACT_GEGLU; E.geglu16 = layout;
+        ck(gemm_launch(a_rows(in, C), wp, M, 8 * C, C, E, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s)));
+        Epilogue E2 = e_rows_res(y, C, b2, (const bf16*)res);
+        E2.gate = gate;
+        ck(gemm_launch(a_rows(hid, 4 * C), w2b, M, C, 4 * C, E2, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s)));
     }
     GL_API_END
 }
@@ -950,29 +934,16 @@ int gl_op_attention(gl_ctx* ctx, const void* xq, const void* xkv, int B, int Nq,
         ck(cast_f32_bf16_launch(wq, wqkv, (int64_t)C * C, S(s)));
         ck(cast_f32_bf16_launch(wk, wqkv + (size_t)C * C, (int64_t)C * C, S(s)));
         ck(cast_f32_bf16_launch(wv, wqkv + (size_t)2 * C * C, (int64_t)C * C, S(s)));
-        AOperand A;
-        aoperand_rows(A, xqp, C, C);
-        Epilogue E;
-        epilogue_defaults(E);
-        E.mode = EPI_QKV_HEADS; E.q = bufs.q; E.k = bufs.k; E.vt = bufs.vt; E.C = C; E.H = H; E.d = d; E.DP = dp; E.DPV = dpv; E.T = Tq; E.vt_perm32 = vt_layout;
-        E.Tpad_q = bufs.Tq_pad; E.Tpad_k = bufs.Tk_pad;
-        ck(gemm_launch(A, wqkv, B * Tq, 3 * C, C, E, nullptr, 0, S(s)));
+        Epilogue E = e_heads(EPI_QKV_HEADS, bufs.q, bufs.k, C, H, d, dp, Tq, bufs.Tq_pad, bufs.Tk_pad);
+        E.vt = bufs.vt; E.DPV = dpv; E.vt_perm32 = vt_layout;
+        ck(gemm_launch(a_rows(xqp, C), wqkv, B * Tq, 3 * C, C, E, nullptr, 0, S(s)));
     } else {
+        ck(gemm_launch(a_rows(xqp, C), wqb, B * Tq, C, C, e_heads(EPI_QK_HEADS, bufs.q, nullptr, C, H, d, dp, Tq, bufs.Tq_pad, 0), eng.splitk_ws(),
+                       eng.splitk_ws_bytes(), S(s)));
         {
-            AOperand A;
-            aoperand_rows(A, xqp, C, C);
-            Epilogue E;
-            epilogue_defaults(E);
-            E.mode = EPI_QK_HEADS; E.q = bufs.q; E.C = C; E.H = H; E.d = d; E.DP = dp; E.T = Tq; E.Tpad_q = bufs.Tq_pad;
-            ck(gemm_launch(A, wqb, B * Tq, C, C, E, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s)));
-        }
-        {
-            AOperand A;
-            aoperand_rows(A, xkp, Ck, Ck);
-            Epilogue E;
-            epilogue_defaults(E);
-            E.mode = EPI_QK_HEADS; E.q = bufs.k; E.q_tiled = 1; E.C = C; E.H = H; E.d = d; E.DP = dp; E.T = Tk; E.Tpad_q = bufs.Tk_pad;
-            ck(gemm_launch(A, wkb, B * Tk, C, Ck, E, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s)));
+            Epilogue E = e_heads(EPI_QK_HEADS, bufs.k, nullptr, C, H, d, dp, Tk, bufs.Tk_pad, 0);
+            E.q_tiled = 1;
+            ck(gemm_launch(a_rows(xkp, Ck), wkb, B * Tk, C, Ck, E, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s)));
         }
         {
             Epilogue E;
@@ -981,10 +952,7 @@ int gl_op_attention(gl_ctx* ctx, const void* xq, const void* xkv, int B, int Nq,
             ck(gemm_launch_t(wvb, C, xkp, B * Tk, Ck, E, S(s)));
         }
     }
-    AttnParams P{};
-    P.q = bufs.q; P.k = bufs.k; P.vt = bufs.vt; P.o = (bf16*)o; P.H = H; P.d = d; P.Nq = Nq; P.Nk = Nk;
-    P.Tq_pad = bufs.Tq_pad; P.Tk_pad = bufs.Tk_pad; P.ldo = C; P.o_rows_per_b = Nq; P.vt_layout = vt_layout;
-    P.scale_log2e = (float)(1.4426950408889634 / std::sqrt((double)d));
+    AttnParams P = attn_params(bufs.q, bufs.k, bufs.vt, (bf16*)o, H, d, Nq, Nk, bufs.Tq_pad, bufs.Tk_pad, vt_layout);
     P.counters = eng.attn_counters();     // nullptr unless gl_attn_regime_counters switched counting on
     ck(attn_launch(P, B, S(s)));
     GL_API_END
@@ -1047,30 +1015,17 @@ int gl_op_proj_attention(gl_ctx* ctx, const void* x, int B, int N, int C, int H,
         bf16* pw = ar.get<bf16>((size_t)C * C);
         ck(cast_f32_bf16_launch(pre_w, pw, (int64_t)C * C, S(s)));
         {
-            AOperand A;
-            aoperand_rows(A, (const bf16*)x, C, C);
-            Epilogue E;
-            epilogue_defaults(E);
-            E.out = mid; E.ldo = C; E.bias = pre_b; E.res = (const bf16*)pre_res; E.ldres = C;
-            ck(gemm_launch(A, pw, M, C, C, E, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s)));
+            ck(gemm_launch(a_rows((const bf16*)x, C), pw, M, C, C, e_rows_res(mid, C, pre_b, (const bf16*)pre_res), eng.splitk_ws(), eng.splitk_ws_bytes(), S(s)));
         }
         bf16* xn = ar.get<bf16>((size_t)M * C);
         LNParams L{};
         L.x = (const bf16*)mid; L.B = 1; L.N1 = M; L.N2 = 0; L.Tpad = M; L.C = C; L.eps = 1e-5f; L.y = xn;
         ck(layernorm_launch(L, S(s)));
-        AOperand A;
-        aoperand_rows(A, xn, C, C);
-        Epilogue E;
-        epilogue_defaults(E);
-        E.mode = EPI_QKV_HEADS; E.q = bufs.q; E.k = bufs.k; E.vt = bufs.vt; E.C = C; E.H = H; E.d = d; E.DP = dp; E.DPV = dpv; E.T = N; E.vt_perm32 = vt_layout;
-        E.Tpad_q = bufs.Tq_pad; E.Tpad_k = bufs.Tk_pad; E.bias = bias;
-        ck(gemm_launch(A, wqkv, M, 3 * C, C, E, nullptr, 0, S(s)));
+        Epilogue E = e_heads(EPI_QKV_HEADS, bufs.q, bufs.k, C, H, d, dp, N, bufs.Tq_pad, bufs.Tk_pad);
+        E.vt = bufs.vt; E.DPV = dpv; E.vt_perm32 = vt_layout; E.bias = bias;
+        ck(gemm_launch(a_rows(xn, C), wqkv, M, 3 * C, C, E, nullptr, 0, S(s)));
     }
-    AttnParams P{};
-    P.q = bufs.q; P.k = bufs.k; P.vt = bufs.vt; P.o = (bf16*)o; P.H = H; P.d = d; P.Nq = N; P.Nk = N;
-    P.Tq_pad = bufs.Tq_pad; P.Tk_pad = bufs.Tk_pad; P.ldo = C; P.o_rows_per_b = N; P.vt_layout = vt_layout;
-    P.scale_log2e = (float)(1.4426950408889634 / std::sqrt((double)d));
-    ck(attn_launch(P, B, S(s)));
+    ck(attn_launch(attn_params(bufs.q, bufs.k, bufs.vt, (bf16*)o, H, d, N, N, bufs.Tq_pad, bufs.Tk_pad, vt_layout), B, S(s)));
     GL_API_END
 }
 

@@ -1,6 +1,6 @@
 // CLIP towers. Text (transformers CLIPTextModel, the reference's FrozenCLIPEmbedder: ldm/modules/encoders/modules.py:144-173): the
 // kernels around the bf16 GEMMs -- embedding gather, residual add + LayerNorm on the fp32 residual stream, causal attention at
-// head dim 64, EOS-row pooling. The layer schedule is Engine::clip_text_encode (engine.hip).
+// head dim 64, EOS-row pooling. The layer schedule is Engine::clip_text_encode (engine_clip.hip).
 #pragma once
 #include "common.h"
 

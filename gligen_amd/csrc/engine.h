@@ -1,5 +1,7 @@
 // gligen_amd engine: owns packed weights + workspace for one device and runs the GLIGEN
 // denoising path (UNet forward, CFG + PLMS loop, VAE decode) as sequences of HIP kernels.
+// One class, one source file per concern: engine.hip (core: arena, contexts, weight builders, primitive launches), engine_unet.hip,
+// engine_policy.hip, engine_vae.hip, engine_clip.hip, engine_spatial.hip, engine_sampler.hip. The state below is grouped the same way.
 #pragma once
 #include <array>
 #include <map>
@@ -64,7 +66,8 @@ class Arena {
 
 struct NormW { const float* g = nullptr; const float* b = nullptr; int C = 0; };
 struct LinW { const bf16* w = nullptr; const float* b = nullptr; int K = 0, N = 0; };
-struct ConvW { const bf16* w = nullptr; const float* b = nullptr; int Cin = 0, Cout = 0, Npad = 0; };
+// Kpad: the small-channel im2col form (conv3_small / conv3x3_small): w is [Cout][Kpad], K = 9 * Cin zero-padded to a multiple of 64
+struct ConvW { const bf16* w = nullptr; const float* b = nullptr; int Cin = 0, Cout = 0, Npad = 0, Kpad = 0; };
 
 struct ResW {
     int Cin = 0, Cout = 0;
@@ -148,9 +151,12 @@ struct AttnBufs {  // persistent, zero-initialised head-layout buffers for one a
 // channel-concat view of up to two NHWC bf16 tensors
 struct TRef { const bf16* p0 = nullptr; int C0 = 0; const bf16* p1 = nullptr; int C1 = 0; int C() const { return C0 + C1; } };
 
-// row-local feed-forward kernel or two GEMMs (engine.hip ff_policy): -1 = by on-device timing (default), 0 = never, 1 = wherever it exists
+// row-local kernels or GEMMs (engine_policy.hip ff_policy): -1 = by on-device timing (default), 0 = never, 1 = wherever they exist,
+// 2 = by the static rule on the row count
 int ff_rows_policy_set(int mode);
 int ff_rows_policy_report(char* buf, size_t cap);
+// the attention kernel's arguments over q / k / v^T in their head layouts, o [B][Nq][H * d]
+AttnParams attn_params(const bf16* q, const bf16* k, const bf16* vt, bf16* o, int H, int d, int Nq, int Nk, int Tq_pad, int Tk_pad, int vt_layout);
 
 class Engine {
    public:
@@ -175,11 +181,11 @@ class Engine {
     void set_cond(int Beff, const float* context, int n_ctx, const gl_grounding& g, hipStream_t s);
     void set_fuser_scale(float v, hipStream_t s);
     void set_fuser_scales(const float* scales_host, int n, hipStream_t s);
-    int n_fusers() const { return (int)st_.size(); }
+    int n_fusers() const { return (int)unet_.st.size(); }
     void grounding_tokens(float* out, hipStream_t s);
     // PositionNet.forward of the spatial-map tokenizers: image [B][C][H][W] fp32, mask [B] -> out fp32 [B][tokens][gr_out_dim]
     void spatial_tokens(int B, const float* image, int C, int H, int W, const float* mask, float* out, hipStream_t s);
-    int spatial_token_count() const { return cnx_.tokens; }  // [Beff][Ng][gr_out_dim] fp32: objs of openaimodel.py:433 for the current conditioning
+    int spatial_token_count() const { return unet_.cnx.tokens; }  // [Beff][Ng][gr_out_dim] fp32: objs of openaimodel.py:433 for the current conditioning
     void restore_first_conv(const float* w, const float* b, hipStream_t s);
     // emb_row (the sampler): the step's emb_layers outputs [sum Cout] fp32, the same for every sample -- the time-embedding MLP and
     // the concatenated emb_layers GEMM are then not launched (emb_table_build computed them for the whole schedule)
@@ -187,7 +193,7 @@ class Engine {
                       int extraB, float* eps, hipStream_t s, const float* emb_row = nullptr);
     void vae_decode(int B, int h, int w, const float* z, float* out, hipStream_t s);
     void vae_encode(int B, int H, int W, const float* img, const float* noise, float* z, hipStream_t s);
-    bool has_vae_encoder() const { return has_venc_; }
+    bool has_vae_encoder() const { return vae_.enc.present; }
     // CLIPTextModel.forward (reference ldm/modules/encoders/modules.py:144-173): ids [S][T] int32, eos_index [S] (the row HF pools)
     // -> last_hidden fp32 [S][T][width], pooled fp32 [S][width] (may be null). S is chunked to what the arena holds.
     void clip_text_encode(const int32_t* ids, const int32_t* eos_index, int S, int T, float* last_hidden, float* pooled, hipStream_t s);
@@ -196,7 +202,7 @@ class Engine {
     // post_layernorm(last_hidden[:, 0]), image_embeds fp32 [S][projection_dim] = pooled visual_projection^T (not normalised); each may
     // be null. S is chunked to what the arena holds.
     void clip_vision_encode(const float* pixel_values, int S, float* last_hidden, float* pooled, float* image_embeds, hipStream_t s);
-    int clip_vision_tokens() const { const int g = vcfg_clip_.patch ? vcfg_clip_.image_size / vcfg_clip_.patch : 0; return g * g + 1; }
+    int clip_vision_tokens() const { const int g = clipv_.cfg.patch ? clipv_.cfg.image_size / clipv_.cfg.patch : 0; return g * g + 1; }
     void sample_plms(const gl_plms_args& a, hipStream_t s);
     void sampler_timing(float* avg_ms, float* first_ms, int* n);
 
@@ -236,6 +242,7 @@ class Engine {
     std::vector<ProfRec> profile_end(hipStream_t s);
 
    private:
+    // ---- core (engine.hip): profiling, uploaded tensors, weight-descriptor builders, primitive launches
     struct ProfEvt { std::string name; double flops, bytes; hipEvent_t e0, e1; };
     bool profiling_ = false;
     std::vector<ProfEvt> prof_;
@@ -257,6 +264,7 @@ class Engine {
     NormW norm(const std::string& prefix);
     LinW linear(const std::string& prefix, bool bias = true);
     ConvW conv3(const std::string& prefix, int Npad = 0);
+    ConvW conv3_small(const std::string& prefix, int Cout);
     LinW conv1(const std::string& prefix);
     const bf16* cast_rows(const std::vector<std::string>& weight_keys);
     // pre_key / post_key: weights of the C x C projections chained in front of / behind this feed-forward ("" = none)
@@ -267,14 +275,8 @@ class Engine {
     struct FoldTmp { float* w = nullptr; float* b = nullptr; int N = 0, K = 0; };
     FoldTmp fold_ln(const std::string& weight_key, const float* bias, const NormW& n);
     std::vector<void*> fold_tmps_;
-    bool ln_fold_ = false;       // LayerNorms folded into their consumers (GL_LN_FOLD=0: off)
-    bool ff_rows_ = true;        // row-local feed-forward kernel where it exists (GL_FF_ROWS=0: off)
-    int ff_chain_ = 2;           // its chained forms: 1 = attn2.to_out -> ff -> proj_out, 2 = also fuser.attn.to_out -> fuser.ff (GL_FF_CHAIN)
     ResW resw(const std::string& prefix, int Cin, int Cout, bool unet);
-    void build_unet();
-    void build_vae();
 
-    // execution helpers
     void gemm(const AOperand& A, const bf16* W, int M, int N, int K, const Epilogue& E, hipStream_t s);
     bf16* linear_rows(const bf16* x, int M, const LinW& L, int act, const bf16* res, const float* gate, hipStream_t s, RowStats* stats = nullptr);
     bf16* layernorm_plain(const bf16* x, int B, int N, int C, bool pad64, hipStream_t s);   // (x - mean) * rstd, no affine
@@ -282,22 +284,97 @@ class Engine {
     bf16* layernorm(const bf16* x, int B, int N, int C, const NormW& n, bool pad64, hipStream_t s);
     bf16* conv3x3(const TRef& x, int B, int Hin, int Win, const ConvW& c, int stride, int ups, int pad_lo,
                   const float* bias2, int bias2_ld, const bf16* res, hipStream_t s);
+    bf16* conv3x3_small(const ConvW& c, Im2colParams P, int reps, hipStream_t s);
+    void gn_silu_conv3x3_nchw(const bf16* x, int C, int B, int H, int W, const NormW& n, float eps, const ConvW& c, int n_real, float* out, hipStream_t s);
     bf16* resblock(const ResW& r, const TRef& x, int B, int H, int W, const float* embout, int emb_ld, float eps, hipStream_t s);
+    // one attention launch over q / k / v^T in their head layouts (profile scope, launch log, launch counter)
+    void attention(const bf16* q, const bf16* k, const bf16* vt, bf16* o, int B, int H, int d, int Nq, int Nk, int Tq_pad, int Tk_pad, int vt_layout,
+                   hipStream_t s);
+
+    Engine(const Engine&) = default;       // (fork() copies the weight descriptors member by member, then resets the per-context state)
+    Engine& operator=(const Engine&) = delete;
+    std::shared_ptr<Engine> parent_;       // fork: the context that owns the shared weights
+    size_t persist_bytes_ = 0;
+    int device_;
+    bool finalized_ = false;
+    std::unordered_map<std::string, RawTensor> raw_;   // (a fork sees the parent's tensors, it does not own them)
+    std::vector<void*> owned_;  // persistent device allocations
+    Arena arena_;
+    float* ws_ = nullptr;
+    size_t ws_bytes_ = 0;
+    typedef std::array<int, 7> AttnKey;            // B, H, d, Tq_pad, Tk_pad, dpv, slot
+    std::map<AttnKey, AttnBufs> attn_bufs_;
+    unsigned* attn_ctr_ = nullptr;      // device, ATTN_CTR_N words (allocated by the first attn_regime_counters call)
+    bool attn_counting_ = false;
+    std::vector<hipEvent_t> train_events_;
+
+    // ---- UNet (engine_unet.hip): packed weights, shared by forks
+    struct Unet {
+        bool present = false;
+        gl_unet_config cfg{};
+        LinW te0, te2;
+        LinW embcat;  // all ResBlock emb_layers concatenated: [sumCout][4*mc]
+        ConvW conv_in_small;  // [mc][Kpad] via small im2col (a fork holds its own copy: restorable)
+        std::vector<ResW> res;
+        std::vector<STW> st;
+        std::vector<ConvW> updown;
+        std::vector<UNetBlock> in_blocks, out_blocks;
+        UNetBlock mid_block;
+        NormW out_norm;
+        ConvW out_conv;
+        const float* const* alpha_ptrs = nullptr;  // device array [2*n_st]
+        // grounding tokenizer
+        int gkind = 0;
+        LinW pn[2][3];
+        const float* pn_null_feat[2] = {nullptr, nullptr};
+        const float* pn_null_pos = nullptr;
+        const float* kp_table = nullptr;  // keypoint: person+keypoint embedding table [P*17][out]
+        CnxNet cnx;   // (engine_spatial.hip)
+    } unet_;
+    bool ln_fold_ = false;       // LayerNorms folded into their consumers (GL_LN_FOLD=0: off)
+    bool ff_rows_ = true;        // row-local feed-forward kernel where it exists (GL_FF_ROWS=0: off)
+    int ff_chain_ = 2;           // its chained forms: 1 = attn2.to_out -> ff -> proj_out, 2 = also fuser.attn.to_out -> fuser.ff (GL_FF_CHAIN)
+    int qkv_rows_ = 1;           // GL_QKV_ROWS (developer A/B): 0 = off, 1 = by the timed policy (default), 2 = wherever the kernel exists
+    bool fuser_hoist_ = true;    // GL_FUSER_KV_HOIST=0 (developer A/B): the [x ; objs] concat LayerNorm + projection over all rows every step
+    void build_unet();
+    // ---- UNet, per context: gates, conditioning cache, fuser keys
+    float* gates_ = nullptr;                    // device [2*n_st]: (attn, dense) per transformer
+    float* fuser_scale_ = nullptr;              // device [n_st]: the fusers' external gate multipliers
+    bool fuser_off_ = false;                    // host mirror of "scale == 0": the fuser branches are then skipped outright
+    struct Cond {
+        int Beff = 0, Ng = 0, ctx_T = 0, ctx_Tpad = 0, obj_Tpad = 0;
+        bf16* tokens = nullptr;     // position_net output [Beff][obj_stride][gr_out_dim] (kept for gl_unet_grounding_tokens)
+        int obj_stride = 0;
+        std::vector<bf16*> objs;    // per transformer: [Beff*Ng][C]
+        std::vector<bf16*> obj_k;   // gatedCA, per transformer: [Beff*H][obj_Tpad][DP]   (K of the grounding tokens)
+        std::vector<bf16*> obj_vt;  // gatedCA, per transformer: [Beff*H][DPV][obj_Tpad]
+        std::vector<bf16*> ctx_k;   // per transformer: [Beff*H][ctx_Tpad][DP]
+        std::vector<bf16*> ctx_vt;  // per transformer: [Beff*H][DPV][ctx_Tpad]
+        std::vector<void*> allocs;
+    } cond_;
+    // GatedSelfAttentionDense (attention.py:236-244): the K / V rows of the grounding tokens linear(objs) do not depend on the step.
+    // They are projected ONCE per prompt into the tail (tokens HW .. HW + Ng - 1) of this block's own K / V^T buffers; per step only
+    // the HW visual rows go through the (LayerNorm-folded) q,k,v^T projection -- no [x ; objs] concat LayerNorm pass.
+    void fuser_kv_fill(const STW& t, int B, int HW, hipStream_t s);
+    void ensure_fuser_kv(const STW& t, int B, int HW, hipStream_t s);
+    struct FuserKV { uint64_t epoch = 0; int B = 0, HW = 0; };
+    std::vector<FuserKV> fuser_kv_;
+    uint64_t cond_epoch_ = 0;
+
+    // ---- UNet, the transformer block (engine_unet.hip)
     bf16* transformer(const STW& t, const bf16* x, int B, int H, int W, hipStream_t s);
     // in_stats: `ln` holds RAW rows whose statistics are in_stats (folded LayerNorm applied by the GEMM); out_stats: statistics of the result
     // raw_rows: with a folded LayerNorm, `ln` may be the RAW rows (no in_stats needed) when ff_rows(f, M) says the row-local kernel runs
     // use_rows: run the row-local kernel (the caller asked ff_rows_for)
     bf16* feedforward(const FFW& f, const bf16* ln, int M, const bf16* res, const float* gate, hipStream_t s, const RowStats* in_stats = nullptr,
                       RowStats* out_stats = nullptr, bool raw_rows = false, bool use_rows = false);
-    // Row-local kernel or LayerNorm + two GEMMs (+ the separate projections) for the feed-forward `which` (1 = fuser.ff, 2 = ff) of
-    // block t at B x HW rows: decided once per (shape, chain form) by TIMING both forms on this device at the first eager launch
-    // (ff_policy.* below, gl_set_ff_rows_policy); under a stream capture an undecided shape takes the static rule
-    bool ff_rows_for(const STW& t, int which, int B, int HW, hipStream_t s);
     // fuser.attn.to_out (+ gated residual) -> LayerNorm -> fuser.ff (+ gated residual)  [gatedSA, attention.py:236-244]
     // q_done (optional, out): the launch also projected attn2.to_q(norm2(.)) into the cross-attention's q buffer (chain_q_stream)
     bf16* fuser_ff_tail(const STW& t, const bf16* o, const bf16* t1, int B, int HW, bool rows, hipStream_t s, RowStats* st3, bool* q_done = nullptr);
+    AttnBufs& to_q_heads(const LinW& q, const bf16* ln, int B, int Tp, int C, int d, int Tk_pad, const RowStats* st, const float* csum, hipStream_t s);
     // attn2.to_q(norm2(rows)) by GEMM into the cross-attention's q buffer (st: the rows' statistics, if their producer wrote any)
     void cross_q_gemm(const STW& t, const bf16* rows, const RowStats& st, int B, int HW, hipStream_t s);
+    bf16* concat_layernorm(const STW& t, const bf16* x, int B, int HW, int Tf, hipStream_t s);
     // attn2.to_out (+ residual) -> LayerNorm -> ff (+ residual) -> proj_out + x_in  [attention.py:337-338, 374-376]
     void block_ff_tail(const STW& t, const bf16* o, const bf16* t3, const bf16* x, bf16* out, int B, int HW, bool rows, hipStream_t s);
     bf16* ff_behind(const FFW& f, const NormW& nw, const bf16* rows_in, RowStats& st_in, int B, int HW, const float* gate, bool rows, hipStream_t s,
@@ -315,137 +392,86 @@ class Engine {
     // The row-local projection launch (ffn.h QkvRowsParams): mid = pre_res + (x Wpre^T + pre_b) -> LayerNorm in registers -> q, k, v^T
     // of attention `a` into its head-layout buffers; T tokens per sample, Nk keys decide the V^T form (attn_vt_layout)
     bool qkv_rows_ok(const SelfAttnW& a, int B, int T, int Nk, int C, int d) const;
-    bool qkv_rows_for(const STW& t, int which, int B, int HW, int Nk, hipStream_t s);   // the timed choice (ff_policy), which: 0 = attn1, 1 = fuser.attn
     void qkv_project_gemm(const SelfAttnW& a, const bf16* ln, int B, int T, int Nk, int C, int d, hipStream_t s, const RowStats* in_stats, int Tbuf, int slot);
     void qkv_rows_project(const SelfAttnW& a, const bf16* x, int B, int T, int Nk, int C, int d, const LinW& pre, const bf16* pre_res, bf16* mid,
                           RowStats* mid_stats, int Tbuf, int slot, hipStream_t s);
-    int qkv_rows_ = 1;           // GL_QKV_ROWS (developer A/B): 0 = off, 1 = by the timed policy (default), 2 = wherever the kernel exists
-    // GatedSelfAttentionDense (attention.py:236-244): the K / V rows of the grounding tokens linear(objs) do not depend on the step.
-    // They are projected ONCE per prompt into the tail (tokens HW .. HW + Ng - 1) of this block's own K / V^T buffers; per step only
-    // the HW visual rows go through the (LayerNorm-folded) q,k,v^T projection -- no [x ; objs] concat LayerNorm pass.
-    void fuser_kv_fill(const STW& t, int B, int HW, hipStream_t s);
-    struct FuserKV { uint64_t epoch = 0; int B = 0, HW = 0; };
-    std::vector<FuserKV> fuser_kv_;
-    uint64_t cond_epoch_ = 0;
-    bool fuser_hoist_ = true;    // GL_FUSER_KV_HOIST=0 (developer A/B): the [x ; objs] concat LayerNorm + projection over all rows every step
-    bf16* vae_attn(const VaeAttnW& a, const bf16* x, int B, int HW, hipStream_t s);
+    // time_embed + every ResBlock's emb_layers (openaimodel.py:436-437, 220-221) depend on the timestep alone, and a sampling run knows
+    // its timesteps: one batched pass over the whole schedule at the start of gl_sample_plms instead of 4 tiny GEMM chains per evaluation
+    float* emb_rows(const int64_t* t_dev, int R, float* out, hipStream_t s);
+    void emb_table_build(const int64_t* t_host, int R, hipStream_t s);
+    float* emb_table_ = nullptr;     // [rows][embcat.N]
+    float* emb_cur_ = nullptr;       // [embcat.N]: the row of the evaluation in flight (what the captured graph reads)
+    int64_t* emb_t_dev_ = nullptr;
+    int emb_table_cap_ = 0;
+    std::vector<int64_t> emb_t_cache_;
 
-    Engine(const Engine&) = default;       // (fork() copies the weight descriptors member by member, then resets the per-context state)
-    Engine& operator=(const Engine&) = delete;
-    std::shared_ptr<Engine> parent_;       // fork: the context that owns the shared weights
-    size_t persist_bytes_ = 0;
-    int device_;
-    bool finalized_ = false;
-    std::unordered_map<std::string, RawTensor> raw_;   // (a fork sees the parent's tensors, it does not own them)
-    std::vector<void*> owned_;  // persistent device allocations
-    Arena arena_;
-    float* ws_ = nullptr;
-    size_t ws_bytes_ = 0;
+    // ---- the kernel-form policy (engine_policy.hip)
+    // Row-local kernel or LayerNorm + two GEMMs (+ the separate projections) for the feed-forward `which` (1 = fuser.ff, 2 = ff) of
+    // block t at B x HW rows: decided once per (shape, chain form) by TIMING both forms on this device at the first eager launch
+    // (ff_policy.*, gl_set_ff_rows_policy); under a stream capture an undecided shape takes the static rule
+    bool ff_rows_for(const STW& t, int which, int B, int HW, hipStream_t s);
+    bool qkv_rows_for(const STW& t, int which, int B, int HW, int Nk, hipStream_t s);   // the timed choice (ff_policy), which: 0 = attn1, 1 = fuser.attn
+    template <class Run>
+    bool timed_form(uint64_t key, int M, int C, int n_zero, const char* name, int form, hipStream_t s, Run&& run);
 
-    // ---- UNet
-    bool has_unet_ = false;
-    gl_unet_config ucfg_{};
-    LinW te0_, te2_;
-    LinW embcat_;  // all ResBlock emb_layers concatenated: [sumCout][4*mc]
-    ConvW conv_in_small_;  // [mc][Kpad] via small im2col
-    int conv_in_kpad_ = 0;
-    std::vector<ResW> res_;
-    std::vector<STW> st_;
-    std::vector<ConvW> updown_;
-    std::vector<UNetBlock> in_blocks_, out_blocks_;
-    UNetBlock mid_block_;
-    NormW out_norm_;
-    ConvW out_conv_;
-    const float* const* alpha_ptrs_ = nullptr;  // device array [2*n_st]
-    float* gates_ = nullptr;                    // device [2*n_st]: (attn, dense) per transformer
-    float* fuser_scale_ = nullptr;              // device [n_st]: the fusers' external gate multipliers
-    bool fuser_off_ = false;                    // host mirror of "scale == 0": the fuser branches are then skipped outright
-    // grounding tokenizer
-    int gkind_ = 0;
-    LinW pn_[2][3];
-    const float* pn_null_feat_[2] = {nullptr, nullptr};
-    const float* pn_null_pos_ = nullptr;
-    const float* kp_table_ = nullptr;  // keypoint: person+keypoint embedding table [P*17][out]
-    CnxNet cnx_;
+    // ---- spatial-map tokenizer (engine_spatial.hip)
     void build_convnext(const std::string& PN);
 
-    // ---- conditioning cache
-    struct Cond {
-        int Beff = 0, Ng = 0, ctx_T = 0, ctx_Tpad = 0, obj_Tpad = 0;
-        bf16* tokens = nullptr;     // position_net output [Beff][obj_stride][gr_out_dim] (kept for gl_unet_grounding_tokens)
-        int obj_stride = 0;
-        std::vector<bf16*> objs;    // per transformer: [Beff*Ng][C]
-        std::vector<bf16*> obj_k;   // gatedCA, per transformer: [Beff*H][obj_Tpad][DP]   (K of the grounding tokens)
-        std::vector<bf16*> obj_vt;  // gatedCA, per transformer: [Beff*H][DPV][obj_Tpad]
-        std::vector<bf16*> ctx_k;   // per transformer: [Beff*H][ctx_Tpad][DP]
-        std::vector<bf16*> ctx_vt;  // per transformer: [Beff*H][DPV][ctx_Tpad]
-        std::vector<void*> allocs;
-    } cond_;
-
-    typedef std::array<int, 7> AttnKey;            // B, H, d, Tq_pad, Tk_pad, dpv, slot
-    std::map<AttnKey, AttnBufs> attn_bufs_;
-    unsigned* attn_ctr_ = nullptr;      // device, ATTN_CTR_N words (allocated by the first attn_regime_counters call)
-    bool attn_counting_ = false;
-    std::vector<hipEvent_t> train_events_;
-
-    // ---- VAE decoder
-    bool has_vae_ = false;
-    gl_vae_config vcfg_{};
-    const float* pq_w_ = nullptr;
-    const float* pq_b_ = nullptr;
-    ConvW vae_in_small_;
-    int vae_in_kpad_ = 0;
-    ResW vmid1_, vmid2_;
-    VaeAttnW vattn_;
-    struct VaeUp { std::vector<ResW> blocks; bool has_up = false; ConvW up; };
-    std::vector<VaeUp> vup_;  // index = level (0 = full resolution)
-    NormW vnorm_out_;
-    ConvW vconv_out_;
-    // ---- VAE encoder (inpainting configuration; built when the encoder.* / quant_conv.* weights were uploaded)
-    bool has_venc_ = false;
-    ConvW venc_in_small_;
-    int venc_in_kpad_ = 0;
-    struct VaeDown { std::vector<ResW> blocks; bool has_down = false; ConvW down; };
-    std::vector<VaeDown> vdown_;
-    ResW vemid1_, vemid2_;
-    VaeAttnW veattn_;
-    NormW venorm_out_;
-    ConvW veconv_out_;
-    const float* qc_w_ = nullptr;
-    const float* qc_b_ = nullptr;
+    // ---- VAE (engine_vae.hip): the decoder and the encoder (inpainting configuration; built when the encoder.* / quant_conv.* weights
+    // were uploaded) mirror each other
+    struct VaeLevel { std::vector<ResW> blocks; bool has_resample = false; ConvW resample; };   // decoder: upsample behind the blocks, encoder: downsample
+    struct VaeHalf {
+        bool present = false;       // decoder: configured; encoder: its weights were uploaded
+        ConvW in_small;
+        ResW mid1, mid2;
+        VaeAttnW attn;
+        std::vector<VaeLevel> levels;  // index = level (0 = full resolution)
+        NormW norm_out;
+        ConvW conv_out;
+        const float* quant_w = nullptr;   // decoder: post_quant_conv, encoder: quant_conv (fp32, 1x1)
+        const float* quant_b = nullptr;
+    };
+    struct Vae { gl_vae_config cfg{}; VaeHalf dec, enc; } vae_;
+    void build_vae();
     void build_vae_encoder();
+    void build_vae_mid(VaeHalf& h, const std::string& prefix, int C);
+    bf16* vae_attn(const VaeAttnW& a, const bf16* x, int B, int HW, hipStream_t s);
 
-    // ---- CLIP text tower (pre-LN transformer: LN1 -> q,k,v -> causal attention -> out + residual -> LN2 -> fc1 quick-GELU -> fc2 + residual).
+    // ---- CLIP (engine_clip.hip). Text tower: pre-LN transformer: LN1 -> q,k,v -> causal attention -> out + residual -> LN2 -> fc1 quick-GELU -> fc2 + residual.
     // The layer routine takes width / heads / tokens / causal from here and from its arguments, not from constants.
     struct ClipLayerW { NormW ln1, ln2; LinW qkv, out, fc1, fc2; };
-    bool has_clip_ = false;
-    gl_clip_text_config ccfg_{};
-    const float* clip_tok_ = nullptr;      // [vocab][width] fp32, as uploaded
-    const float* clip_pos_ = nullptr;      // [max_positions][width] fp32
-    std::vector<ClipLayerW> clip_layers_;
-    NormW clip_final_ln_;
-    unsigned* clip_bad_ids_ = nullptr;     // device counter: ids outside [0, vocab) met (and clamped) by clip_embed_kernel
+    struct ClipText {
+        bool present = false;
+        gl_clip_text_config cfg{};
+        const float* tok = nullptr;      // [vocab][width] fp32, as uploaded
+        const float* pos = nullptr;      // [max_positions][width] fp32
+        std::vector<ClipLayerW> layers;
+        NormW final_ln;
+        unsigned* bad_ids = nullptr;     // device counter: ids outside [0, vocab) met (and clamped) by clip_embed_kernel
+    } clipt_;
     void build_clip_text();
+    void clip_expect_shape(const std::string& key, int64_t d0, int64_t d1) const;
     // the 16 tensors of layers [0, n) under P + "encoder.layers.N.", shapes checked against (width, intermediate)
     void build_clip_layers(const std::string& P, int n, int width, int intermediate, std::vector<ClipLayerW>& out);
     // one pre-LN transformer stack over M = S * T rows of the fp32 residual stream `h` (tmp: fp32 [M][width] scratch); leaves the
     // last sub-layer's output in tmp, still to be added: returns it (the next LayerNorm's launch does the add). Both towers.
     struct ClipStack { int width, heads, intermediate; float ln_eps; };
     const float* clip_layers_run(const std::vector<ClipLayerW>& layers, const ClipStack& c, float* h, float* tmp, int S, int T, bool causal, hipStream_t s);
-
-    // ---- CLIP vision tower: patch rows -> GEMM -> [class ; patches] + positions -> pre_layrnorm (overwrites the stream) -> the same
+    // Vision tower: patch rows -> GEMM -> [class ; patches] + positions -> pre_layrnorm (overwrites the stream) -> the same
     // stack, not causal -> post_layernorm of the class rows -> visual_projection
-    bool has_clip_vision_ = false;
-    gl_clip_vision_config vcfg_clip_{};
-    const float* clipv_cls_ = nullptr;     // [width] fp32
-    const float* clipv_pos_ = nullptr;     // [tokens][width] fp32
-    LinW clipv_patch_;                     // [width][(c, ky, kx) zero-padded to a multiple of 64] bf16, no bias
-    NormW clipv_pre_ln_, clipv_post_ln_;
-    LinW clipv_proj_;                      // visual_projection: [projection_dim][width], no bias
-    std::vector<ClipLayerW> clipv_layers_;
+    struct ClipVision {
+        bool present = false;
+        gl_clip_vision_config cfg{};
+        const float* cls = nullptr;     // [width] fp32
+        const float* pos = nullptr;     // [tokens][width] fp32
+        LinW patch;                     // [width][(c, ky, kx) zero-padded to a multiple of 64] bf16, no bias
+        NormW pre_ln, post_ln;
+        LinW proj;                      // visual_projection: [projection_dim][width], no bias
+        std::vector<ClipLayerW> layers;
+    } clipv_;
     void build_clip_vision();
 
-    // ---- sampler state
+    // ---- sampler (engine_sampler.hip), per context
     struct Sampler {
         int B = 0, h = 0, w = 0;
         float* x2 = nullptr;
@@ -470,14 +496,6 @@ class Engine {
     } smp_;
     void sampler_release_graph();
     void sampler_wait_idle();
-    // time_embed + every ResBlock's emb_layers (openaimodel.py:436-437, 220-221) depend on the timestep alone, and a sampling run knows
-    // its timesteps: one batched pass over the whole schedule at the start of gl_sample_plms instead of 4 tiny GEMM chains per evaluation
-    void emb_table_build(const int64_t* t_host, int R, hipStream_t s);
-    float* emb_table_ = nullptr;     // [rows][embcat_.N]
-    float* emb_cur_ = nullptr;       // [embcat_.N]: the row of the evaluation in flight (what the captured graph reads)
-    int64_t* emb_t_dev_ = nullptr;
-    int emb_table_cap_ = 0;
-    std::vector<int64_t> emb_t_cache_;
 };
 
 }  // namespace gl

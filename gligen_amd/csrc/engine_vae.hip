@@ -1,0 +1,180 @@
+// gligen_amd engine -- AutoencoderKL: decoder and encoder
+#include "engine_impl.h"
+#include <cmath>
+
+namespace gl {
+
+void Engine::configure_vae(const gl_vae_config& c) {
+    if (c.n_mult < 1 || c.n_mult > 8) throw GlError(GL_ERR_ARG, "bad vae config");
+    vae_.cfg = c;
+    vae_.dec.present = true;
+}
+
+// mid.block_1 -> mid.attn_1 -> mid.block_2 of either half (model.py:409-415, 500-506)
+void Engine::build_vae_mid(VaeHalf& h, const std::string& p, int C) {
+    h.mid1 = resw(p + ".block_1", C, C, false);
+    h.mid2 = resw(p + ".block_2", C, C, false);
+    h.attn.gn = norm(p + ".attn_1.norm");
+    h.attn.q = conv1(p + ".attn_1.q");
+    h.attn.k = conv1(p + ".attn_1.k");
+    h.attn.v = conv1(p + ".attn_1.v");
+    h.attn.proj = conv1(p + ".attn_1.proj_out");
+}
+
+void Engine::build_vae() {
+    const gl_vae_config& c = vae_.cfg;
+    const std::string V = "vae/";
+    vae_.dec.quant_w = F(V + "post_quant_conv.weight");
+    vae_.dec.quant_b = F(V + "post_quant_conv.bias");
+    const int block_in0 = c.ch * c.ch_mult[c.n_mult - 1];
+    vae_.dec.in_small = conv3_small(V + "decoder.conv_in", block_in0);
+    build_vae_mid(vae_.dec, V + "decoder.mid", block_in0);
+    vae_.dec.levels.assign(c.n_mult, VaeLevel{});
+    int block_in = block_in0;
+    for (int level = c.n_mult - 1; level >= 0; --level) {
+        const int block_out = c.ch * c.ch_mult[level];
+        for (int i = 0; i <= c.num_res_blocks; ++i) {
+            vae_.dec.levels[level].blocks.push_back(resw(V + fmt("decoder.up.%d.block.%d", level, i), block_in, block_out, false));
+            block_in = block_out;
+        }
+        if (level != 0) {
+            vae_.dec.levels[level].has_resample = true;
+            vae_.dec.levels[level].resample = conv3(V + fmt("decoder.up.%d.upsample.conv", level));
+        }
+    }
+    vae_.dec.norm_out = norm(V + "decoder.norm_out");
+    vae_.dec.conv_out = conv3(V + "decoder.conv_out", 32);
+}
+
+// Encoder of AutoencoderKL (reference model.py:368-459)
+void Engine::build_vae_encoder() {
+    const gl_vae_config& c = vae_.cfg;
+    const std::string V = "vae/";
+    vae_.enc.in_small = conv3_small(V + "encoder.conv_in", c.ch);
+    vae_.enc.levels.assign(c.n_mult, VaeLevel{});
+    int block_in = c.ch;
+    for (int level = 0; level < c.n_mult; ++level) {
+        const int block_out = c.ch * c.ch_mult[level];
+        for (int i = 0; i < c.num_res_blocks; ++i) {
+            vae_.enc.levels[level].blocks.push_back(resw(V + fmt("encoder.down.%d.block.%d", level, i), block_in, block_out, false));
+            block_in = block_out;
+        }
+        if (level != c.n_mult - 1) {
+            vae_.enc.levels[level].has_resample = true;
+            vae_.enc.levels[level].resample = conv3(V + fmt("encoder.down.%d.downsample.conv", level));
+        }
+    }
+    build_vae_mid(vae_.enc, V + "encoder.mid", block_in);
+    vae_.enc.norm_out = norm(V + "encoder.norm_out");
+    vae_.enc.conv_out = conv3(V + "encoder.conv_out", 32);
+    if (vae_.enc.conv_out.Cout != 2 * c.z_channels) throw GlError(GL_ERR_ARG, "encoder.conv_out must produce 2 * z_channels moments");
+    const RawTensor& q = raw(V + "quant_conv.weight");
+    if (q.shape[0] != 2 * c.z_channels || q.shape[1] != 2 * c.z_channels)
+        throw GlError(GL_ERR_UNSUPPORTED, "quant_conv must map 2*z_channels -> 2*z_channels (embed_dim == z_channels)");
+    vae_.enc.quant_w = F(V + "quant_conv.weight");
+    vae_.enc.quant_b = F(V + "quant_conv.bias");
+    vae_.enc.present = true;
+}
+
+// ---------------------------------------------------------------- VAE
+// AttnBlock.forward (model.py:177-202): single head over HW tokens, scale C^-0.5
+bf16* Engine::vae_attn(const VaeAttnW& a, const bf16* x, int B, int HW, hipStream_t s) {
+    const int C = a.gn.C, M = B * HW;
+    if (HW % 64 != 0) throw GlError(GL_ERR_UNSUPPORTED, "VAE attention needs h*w to be a multiple of 64");
+    bf16* out = arena_.get<bf16>((size_t)M * C);
+    const size_t mk = arena_.mark();
+    bf16* n = groupnorm(TRef{x, C, nullptr, 0}, B, HW, a.gn, 1e-6f, false, s);
+    bf16* q = linear_rows(n, M, a.q, ACT_NONE, nullptr, nullptr, s);
+    bf16* k = linear_rows(n, M, a.k, ACT_NONE, nullptr, nullptr, s);
+    bf16* o = arena_.get<bf16>((size_t)M * C);
+    for (int b = 0; b < B; ++b) {
+        const size_t mb = arena_.mark();
+        // v^T [C][HW] = Wv n_b^T  (bias folded into the P v product: rows of P sum to 1)
+        bf16* vT = arena_.get<bf16>((size_t)C * HW);
+        {
+            gemm(a_rows(a.v.w, C), n + (size_t)b * HW * C, C, HW, C, e_rows(vT, HW), s);
+        }
+        float* S = arena_.get<float>((size_t)HW * HW);
+        {
+            Epilogue E = e_rows(S, HW);
+            E.out_f32 = 1;
+            gemm(a_rows(q + (size_t)b * HW * C, C), k + (size_t)b * HW * C, HW, HW, C, E, s);
+        }
+        bf16* Pm = arena_.get<bf16>((size_t)HW * HW);
+        CK(softmax_rows_launch(S, Pm, HW, HW, 1.f / std::sqrt((float)C), s));
+        ++n_launches;
+        {
+            gemm(a_rows(Pm, HW), vT, HW, C, HW, e_rows(o + (size_t)b * HW * C, C, a.v.b), s);
+        }
+        arena_.release(mb);
+    }
+    gemm(a_rows(o, C), a.proj.w, M, C, C, e_rows_res(out, C, a.proj.b, x), s);
+    arena_.release(mk);
+    return out;
+}
+
+// AutoencoderKL.decode (autoencoder.py:40-44) -> Decoder.forward (model.py:535-568)
+void Engine::vae_decode(int B, int h, int w, const float* z, float* out, hipStream_t s) {
+    if (!vae_.dec.present || !finalized_) throw GlError(GL_ERR_STATE, "vae not finalized");
+    const gl_vae_config& c = vae_.cfg;
+    arena_.reset();
+    int H = h, W = w;
+    int C = vae_.dec.in_small.Cout;
+    Im2colParams P{};
+    P.x0 = z; P.C0 = c.z_channels; P.B = B; P.H = H; P.W = W;
+    P.pre_w = vae_.dec.quant_w; P.pre_b = vae_.dec.quant_b; P.pre_scale = 1.f / c.scale_factor;   // post_quant_conv and 1 / scale_factor ride in the gather
+    bf16* cur = conv3x3_small(vae_.dec.in_small, P, 1, s);
+    const float eps = 1e-6f;
+    cur = resblock(vae_.dec.mid1, TRef{cur, C, nullptr, 0}, B, H, W, nullptr, 0, eps, s);
+    cur = vae_attn(vae_.dec.attn, cur, B, H * W, s);
+    cur = resblock(vae_.dec.mid2, TRef{cur, C, nullptr, 0}, B, H, W, nullptr, 0, eps, s);
+    for (int level = c.n_mult - 1; level >= 0; --level) {
+        for (const ResW& r : vae_.dec.levels[level].blocks) {
+            cur = resblock(r, TRef{cur, C, nullptr, 0}, B, H, W, nullptr, 0, eps, s);
+            C = r.Cout;
+        }
+        if (vae_.dec.levels[level].has_resample) {
+            cur = conv3x3(TRef{cur, C, nullptr, 0}, B, H, W, vae_.dec.levels[level].resample, 1, 1, 1, nullptr, 0, nullptr, s);
+            H *= 2;
+            W *= 2;
+        }
+    }
+    gn_silu_conv3x3_nchw(cur, C, B, H, W, vae_.dec.norm_out, eps, vae_.dec.conv_out, c.out_ch, out, s);
+}
+
+// AutoencoderKL.encode (autoencoder.py:34-38) -> Encoder.forward (model.py:434-459) -> quant_conv -> posterior sample
+void Engine::vae_encode(int B, int H, int W, const float* img, const float* noise, float* z, hipStream_t s) {
+    if (!vae_.enc.present || !finalized_) throw GlError(GL_ERR_STATE, "vae encoder weights were not uploaded / not finalized");
+    const gl_vae_config& c = vae_.cfg;
+    const int total_stride = 1 << (c.n_mult - 1);
+    if (H % total_stride || W % total_stride) throw GlError(GL_ERR_ARG, "vae_encode: image size must be divisible by the encoder stride");
+    arena_.reset();
+    int C = vae_.enc.in_small.Cout;
+    Im2colParams P{};
+    P.x0 = img; P.C0 = vae_.enc.in_small.Cin; P.B = B; P.H = H; P.W = W;
+    P.pre_scale = 1.f;
+    bf16* cur = conv3x3_small(vae_.enc.in_small, P, 1, s);
+    const float eps = 1e-6f;
+    for (int level = 0; level < c.n_mult; ++level) {
+        for (const ResW& r : vae_.enc.levels[level].blocks) {
+            cur = resblock(r, TRef{cur, C, nullptr, 0}, B, H, W, nullptr, 0, eps, s);
+            C = r.Cout;
+        }
+        if (vae_.enc.levels[level].has_resample) {
+            // Downsample: F.pad(x, (0,1,0,1)) + conv3x3 stride 2 padding 0 (model.py:72-76) = pad_lo 0 in the gather
+            cur = conv3x3(TRef{cur, C, nullptr, 0}, B, H, W, vae_.enc.levels[level].resample, 2, 0, 0, nullptr, 0, nullptr, s);
+            H /= 2;
+            W /= 2;
+        }
+    }
+    cur = resblock(vae_.enc.mid1, TRef{cur, C, nullptr, 0}, B, H, W, nullptr, 0, eps, s);
+    cur = vae_attn(vae_.enc.attn, cur, B, H * W, s);
+    cur = resblock(vae_.enc.mid2, TRef{cur, C, nullptr, 0}, B, H, W, nullptr, 0, eps, s);
+    const int HW = H * W;
+    float* moments = arena_.get<float>((size_t)B * 2 * c.z_channels * HW);
+    gn_silu_conv3x3_nchw(cur, C, B, H, W, vae_.enc.norm_out, eps, vae_.enc.conv_out, 2 * c.z_channels, moments, s);
+    CK(vae_posterior_launch(moments, vae_.enc.quant_w, vae_.enc.quant_b, noise, z, B, c.z_channels, HW, c.scale_factor, s));
+    ++n_launches;
+}
+
+}  // namespace gl

@@ -4,7 +4,7 @@ Class names, constructor signatures and state_dict keys follow the reference's
 ldm/modules/attention.py so checkpoints and `set_alpha_scale` keep working; the arithmetic
 (attention.py:37-64 GEGLU, :127-149 cross-attention, :167-186 self-attention, :236-244 gated
 self-attention, :333-338 block order, :366-376 SpatialTransformer) runs inside
-UNetModel.forward as fused HIP kernels (gligen_amd/csrc/engine.hip: Engine::transformer).
+UNetModel.forward as fused HIP kernels (gligen_amd/csrc/engine_unet.hip: Engine::transformer).
 """
 import torch
 from torch import nn

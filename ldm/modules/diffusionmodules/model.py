@@ -2,7 +2,7 @@
 ResnetBlock 82-141, AttnBlock 150-202, Up/Downsample 42-79, Encoder 368-459, Decoder 462-568).
 
 State_dict keys match the reference (248 tensors for the SD-1.4 KL-f8 autoencoder). The decoder
-is executed by Engine::vae_decode (gligen_amd/csrc/engine.hip); nothing here runs torch ops.
+is executed by Engine::vae_decode (gligen_amd/csrc/engine_vae.hip); nothing here runs torch ops.
 """
 import numpy as np
 import torch

@@ -4,7 +4,7 @@ Drop-in for the reference's ldm/modules/diffusionmodules/openaimodel.py: same cl
 constructor kwargs (openaimodel.py:238-259), attributes, state_dict keys (966 tensors for the
 shipped configs) and `forward(input: dict) -> eps` contract (openaimodel.py:420-464). The
 sub-modules only hold parameters; `UNetModel.forward` hands the whole evaluation to the native
-MI355X engine (gligen_amd/csrc/engine.hip: Engine::unet_forward) — no torch operator runs.
+MI355X engine (gligen_amd/csrc/engine_unet.hip: Engine::unet_forward) — no torch operator runs.
 """
 import torch
 import torch.nn as nn

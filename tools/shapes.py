@@ -1,5 +1,5 @@
 """Enumerate the kernel launches of one UNetModel.forward / AutoencoderKL.decode as the engine
-schedules them (gligen_amd/csrc/engine.hip), grouped by distinct shape, for gligen_amd/build/kbench.
+schedules them (gligen_amd/csrc/engine_unet.hip, engine_vae.hip), grouped by distinct shape, for gligen_amd/build/kbench.
 
 Line formats (count = launches per forward):
   gemm  M N K epi count        epi: 0 plain+bias(+res)  1 GEGLU  2 qk-heads  3 vt-heads (transposed launch)  4 fused q,k,v^T heads
