@@ -1,4 +1,4 @@
-"""ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h and include/gligen_amd_image.h).
+"""ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h and include/gligen_amd_maps.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -46,6 +46,10 @@ class ClipVisionConfig(C.Structure):   # = gl_clip_vision_config
 class ImageDesc(C.Structure):   # = gl_image_desc
     _fields_ = [("pixels", C.c_void_p)] + [(n, C.c_int) for n in ("width", "height", "row_stride", "resized_w", "resized_h",
                                                                   "crop_x", "crop_y", "crop_w", "crop_h")]
+
+
+class ClassMapDesc(C.Structure):   # = gl_class_map_desc
+    _fields_ = [("pixels", C.c_void_p)] + [(n, C.c_int) for n in ("width", "height", "row_stride", "box_x", "box_y", "box_w", "box_h")]
 
 
 class Grounding(C.Structure):
@@ -163,6 +167,14 @@ IMAGE_SYMBOLS = {
     "gl_image_resample_coeffs": (_I, [_I, _I, _I, C.POINTER(_I), C.POINTER(_I), _I, C.POINTER(_I), _I]),
 }
 
+# every symbol include/gligen_amd_maps.h declares (semantic maps as class indices)
+MAP_SYMBOLS = {
+    "gl_op_class_map_resize": (_I, [_P, C.POINTER(ClassMapDesc), _I, _I, _I, _P, _P]),
+    "gl_class_map_index_table": (_I, [_I, _I, _I, C.POINTER(_I), _I]),
+    "gl_op_spatial_tokens_classes": (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
+    "gl_op_grounding_downsample_classes": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P]),
+}
+
 _lib = None
 
 
@@ -180,7 +192,7 @@ def load() -> C.CDLL:
     # torch.cuda.is_available() is True) -- seen with build() called before the first `import torch` of the process.
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

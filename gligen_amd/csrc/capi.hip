@@ -1,4 +1,5 @@
 // extern "C" surface of libgligen_amd.so (see include/gligen_amd.h). Nothing throws across it.
+#include "classmap.h"
 #include "engine_impl.h"
 #include "image.h"
 #include "train.h"
@@ -12,7 +13,7 @@ using namespace gl;
 struct gl_ctx {
     std::shared_ptr<Engine> holder;   // forks (gl_ctx_fork) keep the context whose weights they share alive
     Engine* eng;
-    ImageStage image_stage;           // gl_op_image_resample's pinned staging block
+    ImageStage image_stage;           // the pinned staging block of gl_op_image_resample and gl_op_class_map_resize
 };
 
 #define GL_API_BEGIN try {
@@ -261,6 +262,68 @@ int gl_op_grounding_downsample(gl_ctx* ctx, const float* img, int B, int Cimg, i
         ar.release(mk);
         if (rc != GL_OK) return rc;
     }
+    GL_API_END
+}
+
+// ---- include/gligen_amd_maps.h: semantic maps as class indices
+int gl_op_class_map_resize(gl_ctx* ctx, const gl_class_map_desc* maps_host, int n_maps, int out_w, int out_h, uint8_t* out, gl_stream s) {
+    NEED(ctx);
+    GL_API_BEGIN
+    ClassMapPlan plan;
+    GL_TRY(class_map_resize_plan(maps_host, n_maps, out_w, out_h, out, &plan));
+    gl::Arena& ar = ctx->eng->arena();
+    const size_t mk = ar.mark();
+    struct Release {
+        gl::Arena& ar;
+        size_t mk;
+        ~Release() { ar.release(mk); }   // stream-ordered reuse, as every operator's workspace
+    } release{ar, mk};
+    void* work = ar.alloc(plan.block.size());
+    GL_TRY(class_map_resize_run(ctx->image_stage, plan, work, out, S(s)));
+    ++ctx->eng->n_launches;
+    GL_API_END
+}
+
+int gl_class_map_index_table(int box0, int box_len, int out_size, int* idx_host, int cap) {
+    if (!idx_host) return gl::set_error(GL_ERR_ARG, "gl_class_map_index_table: null table");
+    if (out_size >= 1 && cap < out_size) return gl::set_error(GL_ERR_ARG, "gl_class_map_index_table: the table holds %d ints, out_size = %d are needed", cap, out_size);
+    GL_API_BEGIN
+    GL_TRY(class_map_index_table(box0, box_len, out_size, idx_host));
+    GL_API_END
+}
+
+int gl_op_spatial_tokens_classes(gl_ctx* ctx, const uint8_t* cls, int B, int H, int W, const float* mask, float* tokens, gl_stream s) {
+    NEED(ctx);
+    if (!cls || !mask || !tokens) return gl::set_error(GL_ERR_ARG, "spatial_tokens_classes: null class map / mask / tokens");
+    GL_API_BEGIN
+    ctx->eng->spatial_tokens_classes(B, cls, H, W, mask, tokens, S(s));
+    GL_API_END
+}
+
+int gl_op_grounding_downsample_classes(gl_ctx* ctx, const uint8_t* cls, int B, int H, int W, int n_classes, int R,
+                                       const float* w1, const float* b1, int c_mid, const float* w2, const float* b2, int c_out,
+                                       float* out, gl_stream s) {
+    NEED(ctx);
+    if (!cls || !out || !w1 || !b1 || !w2 || !b2) return gl::set_error(GL_ERR_ARG, "grounding_downsample_classes: null class map / weights / out");
+    if (R <= 0 || R % 4) return gl::set_error(GL_ERR_ARG, "grounding_downsample_classes: resize_input %d; two stride-2 convs need a positive multiple of 4", R);
+    if (c_out <= 0) return gl::set_error(GL_ERR_ARG, "grounding_downsample_classes: %d output channels", c_out);
+    GL_API_BEGIN
+    gl::Arena& ar = ctx->eng->arena();
+    const size_t mk = ar.mark();
+    int rc = GL_OK;
+    if (n_classes < 1 || n_classes > kClassMaxClasses || c_mid < 4 || c_mid % 4 || B < 1)
+        rc = gl::set_error(GL_ERR_UNSUPPORTED, "grounding_downsample_classes: %d samples, %d classes, %d middle channels; at least one sample, 1 .. %d classes and a multiple of 4 middle channels are needed",
+                           B, n_classes, c_mid, kClassMaxClasses);
+    if (rc == GL_OK) {
+        float* g = ar.get<float>((size_t)n_classes * 16 * c_mid);
+        float* h1 = ar.get<float>((size_t)B * c_mid * (R / 2) * (R / 2));
+        rc = class_conv_weight_relayout_launch(w1, g, c_mid, n_classes, S(s));
+        if (rc == GL_OK) rc = class_conv4x4s2_launch(cls, g, b1, h1, B, H, W, n_classes, c_mid, R, 1, S(s));
+        if (rc == GL_OK) rc = gl::conv4x4s2_f32_launch(h1, w2, b2, out, B, c_mid, c_out, R / 2, R / 2, 0, S(s));
+        if (rc == GL_OK) ctx->eng->n_launches += 3;
+    }
+    ar.release(mk);
+    if (rc != GL_OK) return rc;
     GL_API_END
 }
 

@@ -185,6 +185,8 @@ class Engine {
     void grounding_tokens(float* out, hipStream_t s);
     // PositionNet.forward of the spatial-map tokenizers: image [B][C][H][W] fp32, mask [B] -> out fp32 [B][tokens][gr_out_dim]
     void spatial_tokens(int B, const float* image, int C, int H, int W, const float* mask, float* out, hipStream_t s);
+    // the same from the class map u8 [B][H][W] of a semantic-map tokenizer (in_dim one-hot planes), bit for bit
+    void spatial_tokens_classes(int B, const uint8_t* cls, int H, int W, const float* mask, float* out, hipStream_t s);
     int spatial_token_count() const { return unet_.cnx.tokens; }  // [Beff][Ng][gr_out_dim] fp32: objs of openaimodel.py:433 for the current conditioning
     void restore_first_conv(const float* w, const float* b, hipStream_t s);
     // emb_row (the sampler): the step's emb_layers outputs [sum Cout] fp32, the same for every sample -- the time-embedding MLP and
@@ -290,6 +292,8 @@ class Engine {
     // one attention launch over q / k / v^T in their head layouts (profile scope, launch log, launch counter)
     void attention(const bf16* q, const bf16* k, const bf16* vt, bf16* o, int B, int H, int d, int Nq, int Nk, int Tq_pad, int Tk_pad, int vt_layout,
                    hipStream_t s);
+    // spatial_tokens behind its input stage: ConvNeXt-tiny on img fp32 [B][3][resize][resize] and the token head (engine_spatial.hip)
+    void spatial_tokens_tail(int B, const float* img, const float* mask, float* out, hipStream_t s);
 
     Engine(const Engine&) = default;       // (fork() copies the weight descriptors member by member, then resets the per-context state)
     Engine& operator=(const Engine&) = delete;

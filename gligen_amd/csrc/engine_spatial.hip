@@ -1,4 +1,5 @@
 // gligen_amd engine -- the ConvNeXt tokenizer of the spatial-map modalities
+#include "classmap.h"
 #include "engine_impl.h"
 
 namespace gl {
@@ -78,6 +79,28 @@ void Engine::spatial_tokens(int B, const float* image, int Cimg, int H, int W, c
         CK(conv3x3_f32_launch(img, n.inconv_w, n.inconv_b, img3, B, n.in_dim, 3, R, R, s));
         img = img3;
     }
+    spatial_tokens_tail(B, img, mask, out, s);
+    arena_.release(mk);
+}
+
+// The same tokens from the class map of a semantic-map tokenizer: the nearest resize and in_conv over its one-hot planes are one gather
+// launch (classmap.h), which leaves the bits the two launches of spatial_tokens leave.
+void Engine::spatial_tokens_classes(int B, const uint8_t* cls, int H, int W, const float* mask, float* out, hipStream_t s) {
+    if (!unet_.present || !finalized_ || !unet_.cnx.present) throw GlError(GL_ERR_STATE, "no spatial-map tokenizer (ConvNeXt weights) in this engine");
+    const CnxNet& n = unet_.cnx;
+    if (!n.in_dim) throw GlError(GL_ERR_ARG, "spatial_tokens_classes: this tokenizer has no in_conv (in_dim 0): only a semantic-map tokenizer reads class maps");
+    const size_t mk = arena_.mark();
+    float* img = arena_.get<float>((size_t)B * 3 * n.resize * n.resize);
+    CK(class_inconv_launch(cls, n.inconv_w, n.inconv_b, img, B, H, W, n.in_dim, n.resize, s));
+    ++n_launches;
+    spatial_tokens_tail(B, img, mask, out, s);
+    arena_.release(mk);
+}
+
+// ConvNeXt-tiny on img fp32 [B][3][R][R], null-feature mixing, position embedding, MLP
+void Engine::spatial_tokens_tail(int B, const float* img, const float* mask, float* out, hipStream_t s) {
+    const CnxNet& n = unet_.cnx;
+    const int R = n.resize;
     auto ln_rows = [&](const bf16* x, int M, int C, int ld, const NormW& w) {
         bf16* y = arena_.get<bf16>((size_t)M * ld);
         LNParams P{};
@@ -132,7 +155,6 @@ void Engine::spatial_tokens(int B, const float* image, int Cimg, int H, int W, c
     bf16* h2 = linear_rows(h1, M, n.mlp[1], ACT_SILU, nullptr, nullptr, s);
     bf16* objs = linear_rows(h2, M, n.mlp[2], ACT_NONE, nullptr, nullptr, s);
     CK(bf16_rows_to_f32_launch(objs, out, B, n.tokens, n.tokens, n.mlp[2].N, s));
-    arena_.release(mk);
 }
 
 }  // namespace gl

@@ -58,6 +58,9 @@ struct ImageStage {
     bool pending = false;
     ~ImageStage();
 };
+// Copies `bytes` of host memory to `dst` on `stream` through the staging memory (grown as needed). Waits, on the host, only for the
+// previous call's copy to have left the staging memory; the device is never waited for.
+int image_stage_upload(ImageStage& stage, const void* block, size_t bytes, void* dst, hipStream_t stream);
 
 // Validates the call (gl_op_image_resample's arguments) and lays it out. Host only: touches no device.
 int image_resample_plan(const gl_image_desc* images, int S, int filter, int out_kind, const float* lut_host, void* out, ImagePlan* plan);

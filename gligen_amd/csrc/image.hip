@@ -290,9 +290,7 @@ int image_resample_plan(const gl_image_desc* images, int S, int filter, int out_
     return GL_OK;
 }
 
-int image_resample_run(ImageStage& stage, ImagePlan& plan, void* work, hipStream_t stream) {
-    if (!work || (reinterpret_cast<uintptr_t>(work) & 255)) return set_error(GL_ERR_ARG, "image resample: the workspace must be 256-byte aligned");
-    const size_t bytes = plan.block.size();
+int image_stage_upload(ImageStage& stage, const void* block, size_t bytes, void* dst, hipStream_t stream) {
     if (!stage.copied) GL_HIP(hipEventCreateWithFlags(&stage.copied, hipEventDisableTiming));
     if (stage.pending) {   // the previous call's copy out of the staging memory (long over by now; never the kernels behind it)
         GL_HIP(hipEventSynchronize(stage.copied));
@@ -305,6 +303,15 @@ int image_resample_run(ImageStage& stage, ImagePlan& plan, void* work, hipStream
         GL_HIP(hipHostMalloc(&stage.host, cap, hipHostMallocDefault));
         stage.cap = cap;
     }
+    memcpy(stage.host, block, bytes);
+    GL_HIP(hipMemcpyAsync(dst, stage.host, bytes, hipMemcpyHostToDevice, stream));
+    GL_HIP(hipEventRecord(stage.copied, stream));
+    stage.pending = true;
+    return GL_OK;
+}
+
+int image_resample_run(ImageStage& stage, ImagePlan& plan, void* work, hipStream_t stream) {
+    if (!work || (reinterpret_cast<uintptr_t>(work) & 255)) return set_error(GL_ERR_ARG, "image resample: the workspace must be 256-byte aligned");
     ImageJob* jobs = reinterpret_cast<ImageJob*>(plan.block.data());
     const uintptr_t b = reinterpret_cast<uintptr_t>(work);
     for (int i = 0; i < plan.S; ++i) {
@@ -315,11 +322,8 @@ int image_resample_run(ImageStage& stage, ImagePlan& plan, void* work, hipStream
         j.vk = reinterpret_cast<const int*>(b + reinterpret_cast<uintptr_t>(j.vk));
         j.mid = reinterpret_cast<uint8_t*>(b + reinterpret_cast<uintptr_t>(j.mid));
     }
-    memcpy(stage.host, plan.block.data(), bytes);
+    GL_TRY(image_stage_upload(stage, plan.block.data(), plan.block.size(), work, stream));
     plan.block.clear();   // the addresses are in: a plan runs once
-    GL_HIP(hipMemcpyAsync(work, stage.host, bytes, hipMemcpyHostToDevice, stream));
-    GL_HIP(hipEventRecord(stage.copied, stream));
-    stage.pending = true;
     const ImageJob* djobs = static_cast<const ImageJob*>(work);
     const float* dlut = reinterpret_cast<const float*>(static_cast<const char*>(work) + plan.lut_off);
     hipLaunchKernelGGL(image_resample_h_kernel, dim3(plan.hblocks), dim3(256), 0, stream, djobs, plan.S);

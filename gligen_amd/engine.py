@@ -365,6 +365,64 @@ class Engine:
                                                   _ptr(w2), _ptr(b2), int(w2.shape[0]), _ptr(out), _stream(self.device)))
         return out
 
+    # ---- semantic maps as class indices (include/gligen_amd_maps.h) ---------------
+    def _class_map(self, cls: torch.Tensor, what: str) -> torch.Tensor:
+        if cls.dtype != torch.uint8 or cls.dim() not in (3, 4) or (cls.dim() == 4 and cls.shape[1] != 1) or cls.numel() == 0:
+            raise ValueError(f"{what}: the class map is {cls.dtype} {tuple(cls.shape)}; u8 [B, 1, H, W] or [B, H, W] is read")
+        return cls.reshape(cls.shape[0], cls.shape[-2], cls.shape[-1]).to(self.device).contiguous()
+
+    def class_map_resize(self, maps, size, boxes=None) -> torch.Tensor:
+        """PIL.Image.crop(box).resize(size, Image.NEAREST) of single-channel u8 images of different sizes in one launch, byte for byte
+        (gl_op_class_map_resize). maps: u8 [H, W] tensors or arrays (host ones are uploaded; a device tensor may be a view with a row
+        stride); size: (width, height) of every result; boxes: (x, y, width, height) inside each map, None = all of it. Returns the
+        u8 [S, height, width] device tensor."""
+        S = len(maps)
+        if S < 1 or (boxes is not None and len(boxes) != S):
+            raise ValueError("class_map_resize: at least one map, and one box per map")
+        w, h = (int(v) for v in size)
+        descs = (_lib.ClassMapDesc * S)()
+        keep = []
+        for i, m in enumerate(maps):
+            t = m if isinstance(m, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(m))
+            if t.dtype != torch.uint8 or t.dim() != 2 or t.shape[0] < 1 or t.shape[1] < 1:
+                raise ValueError(f"class_map_resize: map {i} is {t.dtype} {tuple(t.shape)}; one u8 channel [H, W] is read")
+            t = t.to(self.device)
+            if t.stride(1) != 1 or (t.shape[0] > 1 and t.stride(0) < t.shape[1]):
+                t = t.contiguous()
+            keep.append(t)
+            d = descs[i]
+            d.pixels, d.width, d.height = t.data_ptr(), int(t.shape[1]), int(t.shape[0])
+            d.row_stride = int(t.stride(0)) if t.shape[0] > 1 else int(t.shape[1])
+            d.box_x, d.box_y, d.box_w, d.box_h = (0, 0, d.width, d.height) if boxes is None or boxes[i] is None else (int(v) for v in boxes[i])
+        out = torch.empty((S, max(h, 0), max(w, 0)), device=self.device, dtype=torch.uint8)
+        check(self.lib.gl_op_class_map_resize(self._ctx, descs, S, w, h, _ptr(out), _stream(self.device)))
+        return out
+
+    def spatial_tokens_classes(self, cls: torch.Tensor, mask: torch.Tensor) -> torch.Tensor:
+        """spatial_tokens of a semantic-map tokenizer from the class map u8 [B, 1, H, W] (a value >= in_dim: no class) instead of its
+        in_dim one-hot planes: the same tokens, bit for bit (gl_op_spatial_tokens_classes)."""
+        cls = self._class_map(cls, "spatial_tokens_classes")
+        mask = _f32(mask.reshape(-1), self.device)
+        B, H, W = cls.shape
+        if mask.shape[0] != B:
+            raise ValueError("spatial_tokens_classes: one mask value per map")
+        out = torch.empty((B, self.unet_cfg["tok_tokens"], self.unet_cfg["gr_out_dim"]), device=self.device, dtype=torch.float32)
+        check(self.lib.gl_op_spatial_tokens_classes(self._ctx, _ptr(cls), int(B), int(H), int(W), _ptr(mask), _ptr(out), _stream(self.device)))
+        return out
+
+    def grounding_downsample_classes(self, cls: torch.Tensor, n_classes: int, resize: int, convs) -> torch.Tensor:
+        """grounding_downsample(one-hot planes of cls, n_classes, resize, "nearest", convs) from the class map u8 [B, 1, H, W] itself:
+        -> [B, out, resize/4, resize/4], bit for bit (gl_op_grounding_downsample_classes)."""
+        cls = self._class_map(cls, "grounding_downsample_classes")
+        B, H, W = cls.shape
+        w1, b1, w2, b2 = (_f32(t.detach(), self.device) for t in convs)
+        if w1.shape[1] != n_classes:
+            raise ValueError(f"grounding_downsample_classes: the first conv reads {w1.shape[1]} channels, the map has {n_classes} classes")
+        out = torch.empty((B, w2.shape[0], resize // 4, resize // 4), device=self.device, dtype=torch.float32)
+        check(self.lib.gl_op_grounding_downsample_classes(self._ctx, _ptr(cls), int(B), int(H), int(W), int(n_classes), int(resize), _ptr(w1), _ptr(b1),
+                                                          int(w1.shape[0]), _ptr(w2), _ptr(b2), int(w2.shape[0]), _ptr(out), _stream(self.device)))
+        return out
+
     def set_fuser_scale(self, scale: float) -> None:
         check(self.lib.gl_unet_set_fuser_scale(self._ctx, C.c_float(float(scale)), _stream(self.device)))
 

@@ -323,36 +323,86 @@ def _pil_to_unit_tensor(image):
     return (torch.from_numpy(arr.copy()).permute(2, 0, 1).float() / 255 - 0.5) / 0.5
 
 
-def _prepare_batch_map(meta, batch, meta_key, batch_key):
+def _unit_lut():
+    """[3, 256] float32: what _pil_to_unit_tensor makes of each u8 level, computed by the same torch expression."""
+    return ((torch.arange(256, dtype=torch.uint8).float() / 255 - 0.5) / 0.5).unsqueeze(0).repeat(3, 1).numpy()
+
+
+def _native_rgb_512(path, centre_crop):
+    """_pil_to_unit_tensor(image.resize((512, 512))) of an RGB file, optionally behind crop_and_resize's centre crop, on the device:
+    only the decoding stays on the host; Pillow's bicubic resize (its default for RGB) and the scaling to [-1, 1] run in
+    Engine.image_resample, bit for bit. -> float32 [3, 512, 512] on the device."""
+    from gligen_amd import runtime as _rt
+    t = torch.from_numpy(np.asarray(Image.open(path).convert("RGB")).copy()).to(device)
+    if centre_crop:
+        h, w = t.shape[:2]
+        c = min(w, h)
+        left, top = int(round((w - c) / 2.0)), int(round((h - c) / 2.0))
+        t = t[top:top + c, left:left + c]      # a row-strided view: the crop is not copied
+    return _rt.scratch_engine(device).image_resample([t], [(512, 512)], None, "bicubic", _unit_lut())[0]
+
+
+def load_inpaint_image(path, native=False):
+    """The inpainting input as run() encodes it (reference gligen_inference.py:402-404): RGB, resized to 512 x 512 without a crop,
+    in [-1, 1], float32 [1, 3, 512, 512] on the device. native=True resizes on the device (the same bits)."""
+    if native:
+        return _native_rgb_512(path, centre_crop=False).unsqueeze(0)
+    img = torch.from_numpy(np.asarray(Image.open(path).convert("RGB").resize((512, 512)))).permute(2, 0, 1)
+    return (img.float().unsqueeze(0).to(device) / 255 - 0.5) / 0.5
+
+
+def _prepare_batch_map(meta, batch, meta_key, batch_key, native=False):
     """prepare_batch_hed / _canny / _depth / _normal (reference gligen_inference.py:221-300): the map as an RGB image in
-    [-1, 1], repeated over the batch, mask = 1. meta[meta_key] is a file name or an already-loaded tensor [3,512,512]."""
+    [-1, 1], repeated over the batch, mask = 1. meta[meta_key] is a file name or an already-loaded tensor [3,512,512].
+    native=True: a file is cropped, resized and scaled on the device (the same bits; only decoding stays on the host)."""
     src = meta[meta_key]
-    img = src.float() if torch.is_tensor(src) else _pil_to_unit_tensor(crop_and_resize(Image.open(src).convert("RGB")))
+    if native and not torch.is_tensor(src):
+        img = _native_rgb_512(src, centre_crop=True)
+    else:
+        img = src.float() if torch.is_tensor(src) else _pil_to_unit_tensor(crop_and_resize(Image.open(src).convert("RGB")))
     out = {batch_key: img.unsqueeze(0).repeat(batch, 1, 1, 1), "mask": torch.ones(batch, 1)}
     return batch_to_device(out, device)
 
 
-def prepare_batch_hed(meta, batch=1):
-    return _prepare_batch_map(meta, batch, "hed_image", "hed_edge")
+def prepare_batch_hed(meta, batch=1, native=False):
+    return _prepare_batch_map(meta, batch, "hed_image", "hed_edge", native)
 
 
-def prepare_batch_canny(meta, batch=1):
-    return _prepare_batch_map(meta, batch, "canny_image", "canny_edge")
+def prepare_batch_canny(meta, batch=1, native=False):
+    return _prepare_batch_map(meta, batch, "canny_image", "canny_edge", native)
 
 
-def prepare_batch_depth(meta, batch=1):
-    return _prepare_batch_map(meta, batch, "depth", "depth")
+def prepare_batch_depth(meta, batch=1, native=False):
+    return _prepare_batch_map(meta, batch, "depth", "depth", native)
 
 
-def prepare_batch_normal(meta, batch=1):
-    return _prepare_batch_map(meta, batch, "normal", "normal")
+def prepare_batch_normal(meta, batch=1, native=False):
+    return _prepare_batch_map(meta, batch, "normal", "normal", native)
+
+
+SEM_CLASSES = 152
 
 
 @torch.no_grad()
-def prepare_batch_sem(meta, batch=1):
+def prepare_batch_sem(meta, batch=1, native=False):
     """ADE class-index image -> 152 one-hot planes at 512 x 512, nearest resize (reference gligen_inference.py:318-338;
-    the colour visualisation it also writes is a side effect, not an input of the model)."""
+    the colour visualisation it also writes is a side effect, not an input of the model).
+    native=True: the class map itself, uint8 [batch, 1, 512, 512] on the device, cropped and resized there (Engine.class_map_resize);
+    the tokenizer and the downsampler read it in place of the planes and give the same bits."""
     src = meta["sem"]
+    if native:
+        from gligen_amd import runtime as _rt
+        if torch.is_tensor(src):
+            sem = src.to(device=device, dtype=torch.uint8).unsqueeze(0)
+        else:
+            a = np.asarray(Image.open(src).convert("L"))
+            if int(a.max()) >= SEM_CLASSES:      # the reference's scatter_ raises on such a file as well
+                raise ValueError(f"{src}: class value {int(a.max())} in a semantic map of {SEM_CLASSES} classes (0 .. {SEM_CLASSES - 1})")
+            h, w = a.shape
+            c = min(w, h)
+            left, top = int(round((w - c) / 2.0)), int(round((h - c) / 2.0))
+            sem = _rt.scratch_engine(device).class_map_resize([torch.from_numpy(a.copy())], (512, 512), [(left, top, c, c)])
+        return batch_to_device({"sem": sem.unsqueeze(1).repeat(batch, 1, 1, 1), "mask": torch.ones(batch, 1)}, device)
     if torch.is_tensor(src):
         sem = src.long()
     else:
@@ -370,6 +420,9 @@ def prepare_batch_sem(meta, batch=1):
 # run() picks the batch builder by checkpoint-name substring, in this order (reference gligen_inference.py:363-376)
 _PREPARE_BY_NAME = (("keypoint", prepare_batch_kp), ("hed", prepare_batch_hed), ("canny", prepare_batch_canny), ("depth", prepare_batch_depth),
                     ("normal", prepare_batch_normal), ("sem", prepare_batch_sem))
+
+
+_NATIVE_PREPARE = (prepare_batch_hed, prepare_batch_canny, prepare_batch_depth, prepare_batch_normal, prepare_batch_sem)   # take native=
 
 
 def draw_masks_from_boxes(boxes, size):
@@ -619,12 +672,14 @@ def run(meta, config, starting_noise=None, models=None):
         return torch.empty((0, 3, 8 * model.image_size, 8 * model.image_size))
     prepare = next((fn for key, fn in _PREPARE_BY_NAME if key in meta["ckpt"]), prepare_batch)
     native_clip = bool(args.get("native_clip"))
+    native_inputs = bool(args.get("native_inputs"))   # conditioning maps and the inpainting image: crop / resize / scale on the device
     if native_clip:      # the text tower on the HIP path (FrozenCLIPEmbedder backend="hip"); it never falls back to torch
         text_encoder.backend = "hip"
     if native_clip and prepare is prepare_batch:
         batch = {k: _shard(v, lo, hi) for k, v in prepare_batch(meta, B, text_encoder=text_encoder).items()}
     else:
-        batch = {k: _shard(v, lo, hi) for k, v in prepare(meta, B).items()}
+        kw = dict(native=True) if native_inputs and prepare in _NATIVE_PREPARE else {}
+        batch = {k: _shard(v, lo, hi) for k, v in prepare(meta, B, **kw).items()}
     if "grounding_tokens" in meta:   # spatial-map modalities: ConvNeXt tokens computed elsewhere (like precomputed CLIP features)
         batch["tokens"] = _shard(meta["grounding_tokens"].to(device), lo, hi)
     if "context" in meta:  # precomputed CLIP last_hidden_state (B,77,768)
@@ -657,8 +712,7 @@ def run(meta, config, starting_noise=None, models=None):
         if "z0" in meta:
             z0 = meta["z0"].to(device)
         else:
-            img = torch.from_numpy(np.asarray(Image.open(meta["input_image"]).convert("RGB").resize((512, 512)))).permute(2, 0, 1)
-            z0 = autoencoder.encode((img.float().unsqueeze(0).to(device) / 255 - 0.5) / 0.5)
+            z0 = autoencoder.encode(load_inpaint_image(meta["input_image"], native=native_inputs))
     grounding_extra_input = None
     if grounding_downsampler_input is not None:
         grounding_extra_input = grounding_downsampler_input.prepare(batch)
@@ -798,6 +852,7 @@ def main(argv=None):
                         help="run with seeded random weights and features (no checkpoint / CLIP needed)")
     parser.add_argument("--inpaint", action="store_true", help="with --synthetic text: the inpainting model (9-channel first conv, encode + blend)")
     parser.add_argument("--native_clip", action="store_true", help="run CLIP in the native HIP engine instead of transformers: the checkpoint's text tower (prompt, negative prompt, phrases) and, for image-grounded phrases, the ViT-L/14 vision tower")
+    parser.add_argument("--native_inputs", action="store_true", help="prepare the conditioning inputs on the device: crop, resize and scaling of the spatial maps and of the inpainting image in HIP (the same bits as Pillow), and semantic maps as uint8 class indices in place of 152 one-hot planes; only file decoding stays on the host")
     parser.add_argument("--ckpt", type=str, default=None, help="run only the meta_list entries whose checkpoint path contains this string")
     parser.add_argument("--seed", type=int, default=None, help="seed of x_T (one draw for the whole batch, sliced across ranks)")
     parser.add_argument("--lanes", type=int, default=None, help="with --repeat: whole batches in flight (default 3, the bench's schedule); without: per-GPU batches of 32 and more run as two half-batches in flight unless this is 1")

@@ -37,7 +37,8 @@ class _GroundingNetInputBase:
 
 class _SpatialNetInputBase:
     """Spatial-map tokenizers (reference grounding_input/{canny,hed,depth,normal,sem}_grounding_tokinzer_input.py): prepare()
-    forwards (image, mask); the null input is an all-zero image of the last seen batch and a zero mask."""
+    forwards (image, mask); the null input is an all-zero image of the last seen batch and a zero mask. For a uint8 class map
+    (semantic maps as class indices) the all-zero image is the map filled with 255, "no class", and the mask is float32."""
 
     image_key = None
 
@@ -56,6 +57,9 @@ class _SpatialNetInputBase:
         batch = self.batch if batch is None else batch
         device = self.device if device is None else device
         dtype = self.dtype if dtype is None else dtype
+        if self.dtype == th.uint8:   # a semantic class map: 255 is "no class", the class map of all-zero planes
+            return {self.image_key: th.full((self.batch, self.C, self.H, self.W), 255, dtype=th.uint8, device=device),
+                    "mask": th.zeros(batch, dtype=th.float32, device=device)}
         # as in the reference: the zero image keeps the batch seen by prepare(), only the mask follows `batch`
         return {self.image_key: th.zeros(self.batch, self.C, self.H, self.W).type(dtype).to(device),
                 "mask": th.zeros(batch).type(dtype).to(device)}

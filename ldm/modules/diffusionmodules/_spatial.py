@@ -39,7 +39,13 @@ class SpatialPositionNet(_EngineOnly):
             return grounding_input["tokens"]
         if engine is None:
             raise RuntimeError(f"{type(self).__module__}.PositionNet runs inside UNetModel on the MI355X engine (no CPU implementation)")
-        return engine.spatial_tokens(grounding_input[self.image_key], grounding_input["mask"])
+        image = grounding_input[self.image_key]
+        if image.dtype == torch.uint8:   # a class map [B,1,H,W] stands for its in_dim one-hot planes (gl_op_spatial_tokens_classes)
+            if self.in_dim is None:
+                raise ValueError(f"{type(self).__module__}.PositionNet: '{self.image_key}' is a uint8 class map, but this tokenizer has no in_dim "
+                                 "(only the semantic-map tokenizer reads class indices); pass the float map")
+            return engine.spatial_tokens_classes(image, grounding_input["mask"])
+        return engine.spatial_tokens(image, grounding_input["mask"])
 
 
 class SpatialDownsampler(nn.Module):
@@ -54,7 +60,7 @@ class SpatialDownsampler(nn.Module):
 
     def __init__(self, resize_input=256, out_dim=8, in_dim=None):
         super().__init__()
-        self.resize_input, self.out_dim = resize_input, out_dim
+        self.resize_input, self.out_dim, self.in_dim = resize_input, out_dim, in_dim
         if in_dim is not None:
             self.n_in = in_dim
         if self.has_layers:
@@ -67,6 +73,12 @@ class SpatialDownsampler(nn.Module):
         if not x.is_cuda:
             raise RuntimeError("GroundingDownsampler runs on the MI355X engine only (no CPU implementation)")
         eng = engine if engine is not None else _rt.scratch_engine(x.device)
+        if x.dtype == torch.uint8:   # a class map [B,1,H,W] stands for its n_in one-hot planes (gl_op_grounding_downsample_classes)
+            if self.in_dim is None or not self.has_layers or self.mode != "nearest":
+                raise ValueError(f"{type(self).__module__}.GroundingDownsampler: grounding_extra_input is a uint8 class map, but this downsampler "
+                                 "does not read one-hot class planes (only the semantic-map downsampler does); pass the float map")
+            c1, c2 = self.layers[0], self.layers[2]
+            return eng.grounding_downsample_classes(x, self.n_in, self.resize_input, (c1.weight, c1.bias, c2.weight, c2.bias))
         if self.has_layers:
             c1, c2 = self.layers[0], self.layers[2]
             return eng.grounding_downsample(x, self.n_in, self.resize_input, self.mode, (c1.weight, c1.bias, c2.weight, c2.bias))
