@@ -1074,36 +1074,20 @@ static int launch_attn3(const AttnParams& P, int B, hipStream_t stream) {
 template <int DP, int DPV, bool BIAS, int NW>
 static int launch_attn2(const AttnParams& P, int B, hipStream_t stream) {
     const size_t lds = 2 * ((DP / 8) * 1024 + (DPV / 8) * 1024);
-    auto kfn = attn2_kernel<DP, DPV, BIAS, NW>;
-    static bool attr_done = false;  // once per instantiation; never inside a stream capture
-    if (!attr_done && lds > 48 * 1024) {
-        GL_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
     AttnParams Q = P;
     Q.nqb = cdiv(P.Nq, NW * 32);
     dim3 grid(Q.nqb * P.H * B);
-    hipLaunchKernelGGL(kfn, grid, dim3(NW * 64), lds, stream, Q);
-    GL_LAUNCH_CHECK();
-    return GL_OK;
+    return launch_lds<attn2_kernel<DP, DPV, BIAS, NW>>(grid, dim3(NW * 64), lds, stream, Q);
 }
 
 template <int DP, int DPV, bool ONES>
 static int launch_attn(const AttnParams& P, int B, hipStream_t stream) {
     constexpr int KROW = DP * 2 + 16, VROW = 144;
     size_t lds = 2 * (64 * KROW + DPV * VROW);
-    auto kfn = attn_kernel<DP, DPV, ONES>;
-    static bool attr_done = false;  // once per instantiation; never inside a stream capture
-    if (!attr_done && lds > 48 * 1024) {
-        GL_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-        attr_done = true;
-    }
     AttnParams Q = P;
     Q.nqb = cdiv(P.Nq, 128);
     dim3 grid(Q.nqb * P.H * B);
-    hipLaunchKernelGGL(kfn, grid, dim3(256), lds, stream, Q);
-    GL_LAUNCH_CHECK();
-    return GL_OK;
+    return launch_lds<attn_kernel<DP, DPV, ONES>>(grid, dim3(256), lds, stream, Q);
 }
 
 int attn_dims(int d, int* DP, int* DPV) {

@@ -50,6 +50,20 @@ inline const char* dev_env(const char* name) {
     return on ? getenv(name) : nullptr;
 }
 
+// Launch a kernel that may need more than the default 48 KiB of dynamic LDS: the attribute is set once per kernel (per
+// instantiation), by its first launch -- which is an eager one everywhere in this library, never inside a stream capture.
+template <auto KFN, class... Args>
+int launch_lds(dim3 grid, dim3 block, size_t lds_bytes, hipStream_t stream, const Args&... args) {
+    static bool attr_done = false;
+    if (!attr_done && lds_bytes > 48 * 1024) {
+        GL_HIP(hipFuncSetAttribute((const void*)KFN, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes));
+        attr_done = true;
+    }
+    hipLaunchKernelGGL(KFN, grid, block, lds_bytes, stream, args...);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int round_up(int a, int b) { return cdiv(a, b) * b; }

@@ -1135,24 +1135,12 @@ int ff_rows_launch(const FFRowsParams& p, int C, hipStream_t s) {
     if (p.pre && (!p.normalize || !p.pre_b || !p.pre_res || !p.mid_out || p.ld_pre_res % 4 || p.ld_mid % 4))
         return set_error(GL_ERR_ARG, "ff_rows: the leading projection needs normalize = 1, its bias, residual and the buffer for its result");
     if (p.post == 1 && (!p.post_b || !p.post_res || p.ld_post_res % 4)) return set_error(GL_ERR_ARG, "ff_rows: the trailing projection needs its bias and residual");
-    // once per process and kernel; never inside a stream capture (the first call of each form is an eager one)
-#define FF_LAUNCH(PRE_, POST_)                                                                                               \
-    do {                                                                                                                     \
-        auto kfn = ff_rows_kernel<320, 0, PRE_, POST_>;                                                                      \
-        static bool attr_done = false;                                                                                       \
-        if (!attr_done) {                                                                                                    \
-            GL_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, G::LDS_BYTES));         \
-            attr_done = true;                                                                                                \
-        }                                                                                                                    \
-        hipLaunchKernelGGL(kfn, dim3(p.M / 128), dim3(256), G::LDS_BYTES, s, p);                                             \
-    } while (0)
-    if (p.pre && p.post == 2) FF_LAUNCH(true, 2);
-    else if (p.pre && p.post) FF_LAUNCH(true, 1);
-    else if (p.pre) FF_LAUNCH(true, 0);
-    else FF_LAUNCH(false, 0);
-#undef FF_LAUNCH
-    GL_LAUNCH_CHECK();
-    return GL_OK;
+    // (132 KB of LDS, above the 48 KiB default: launch_lds sets the attribute at the first launch of each form, as before)
+    const dim3 grid(p.M / 128), block(256);
+    if (p.pre && p.post == 2) return launch_lds<ff_rows_kernel<320, 0, true, 2>>(grid, block, G::LDS_BYTES, s, p);
+    if (p.pre && p.post) return launch_lds<ff_rows_kernel<320, 0, true, 1>>(grid, block, G::LDS_BYTES, s, p);
+    if (p.pre) return launch_lds<ff_rows_kernel<320, 0, true, 0>>(grid, block, G::LDS_BYTES, s, p);
+    return launch_lds<ff_rows_kernel<320, 0, false, 0>>(grid, block, G::LDS_BYTES, s, p);
 }
 
 
@@ -1179,23 +1167,12 @@ int qkv_rows_launch(const QkvRowsParams& p, int C, hipStream_t s) {
     if (p.pre && (!p.pre_b || !p.mid_out || p.ld_mid % 4 || (p.pre_res && p.ld_pre_res % 4))) return set_error(GL_ERR_ARG, "qkv_rows: the leading projection needs its bias and the buffer for its result");
     using G = FFGeom<320>;
     constexpr int LDS = 3 * G::PJ_BLK * 1024 + 4 * 320 * (int)sizeof(float);
-#define QKV_LAUNCH(PRE_, NP_)                                                                                                \
-    do {                                                                                                                     \
-        auto kfn = qkv_rows_kernel<320, 40, PRE_, NP_>;                                                                      \
-        static bool attr_done = false;                                                                                       \
-        if (!attr_done) {                                                                                                    \
-            GL_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, LDS));                  \
-            attr_done = true;                                                                                                \
-        }                                                                                                                    \
-        hipLaunchKernelGGL(kfn, dim3(p.M / 128), dim3(256), LDS, s, p);                                                      \
-    } while (0)
-    if (p.pre && p.np == 3) QKV_LAUNCH(true, 3);
-    else if (p.pre) QKV_LAUNCH(true, 1);
-    else if (p.np == 3) QKV_LAUNCH(false, 3);
-    else QKV_LAUNCH(false, 1);
-#undef QKV_LAUNCH
-    GL_LAUNCH_CHECK();
-    return GL_OK;
+    // (125 KB of LDS: the attribute is set at the first launch of each form, as before)
+    const dim3 grid(p.M / 128), block(256);
+    if (p.pre && p.np == 3) return launch_lds<qkv_rows_kernel<320, 40, true, 3>>(grid, block, LDS, s, p);
+    if (p.pre) return launch_lds<qkv_rows_kernel<320, 40, true, 1>>(grid, block, LDS, s, p);
+    if (p.np == 3) return launch_lds<qkv_rows_kernel<320, 40, false, 3>>(grid, block, LDS, s, p);
+    return launch_lds<qkv_rows_kernel<320, 40, false, 1>>(grid, block, LDS, s, p);
 }
 
 }  // namespace gl

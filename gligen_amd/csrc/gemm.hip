@@ -20,16 +20,16 @@
 // The activation loader optionally performs the im2col gather of a 3x3 convolution over an NHWC tensor (stride 1|2,
 // nearest-2x upsample of the source, channel concat of two sources, asymmetric padding), so convs never materialise
 // im2col or concat / upsample copies in HBM. Split-K goes through an fp32 slab workspace + a deterministic reduce kernel.
-#include "gemm.h"
+//
+// Which kernel runs a problem (family, tile, K split, resident grid, item order) is decided in gemm_plan.h / gemm_plan.hip, host code
+// without a HIP call; this file holds the kernels, execute() for a GemmPlan and the on-device tuner's timing loop.
+#include "gemm_plan.h"
 
 #include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <mutex>
-#include <string>
 #include <type_traits>
-#include <unordered_map>
 
 namespace gl {
 
@@ -491,18 +491,6 @@ __device__ __forceinline__ void epi_geglu4_t16(const Epilogue& E, int m, int nv0
 // hides behind matrix work instead of serialising with it. Tiles are 2x2 waves of TM x TN
 // v_mfma_f32_16x16x32_bf16 fragments: BN = 160 divides every UNet channel count (320 / 640 /
 // 960 / 1280 / 1920 / 2560 ...) exactly, BN = 128 serves GEGLU pairs and the VAE.
-struct WorkDesc {
-    int tiles_n;
-    int splits;
-    int kt_per_split;
-    int n_items;
-    // XCD partition of the item space. box < 0: contiguous ranges of the linear (tm, tn, z) order. Otherwise the 8 XCDs
-    // form a 2^lgm x 2^lgn x 2^lgz grid over (M tiles, N tiles, K splits), box = lgm | lgn << 4, and each owns an
-    // rm x tiles_n x rz box (tiles_n = N tiles PER BOX then), so that an activation panel is fetched by 2^lgn L2s and a
-    // weight panel by 2^lgm (the K axis duplicates nothing). rz = splits when box < 0.
-    int box, rm, rz;
-};
-
 template <int TM, int TN, int AMODE>
 __global__ void __launch_bounds__(256, 2)
 gemm_p_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Epilogue E, float* __restrict__ ws, WorkDesc wd) {
@@ -1198,7 +1186,7 @@ gemm_u_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Epilo
             const int m = mrow + i * 16;
             mo[i] = (AMODE == A_ROWS && E.mode == EPI_ROWMAJOR && E.remap_in) ? (m / E.remap_in) * E.remap_out + (m % E.remap_in) + E.remap_off : m;
         }
-        if (AMODE == A_CONV3 && E.bias2) {  // + broadcast per-sample bias (ResBlock time embedding); never combined with a residual; convs only (gemm_p_launch)
+        if (AMODE == A_CONV3 && E.bias2) {  // + broadcast per-sample bias (ResBlock time embedding); never combined with a residual; convs only (gemm_route)
             float4 b2[TM][TN];
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
@@ -1632,11 +1620,6 @@ splitk_reduce_kernel(const float* __restrict__ ws, int splits, int M, int N, Epi
 //   Per (chunk, tap):  vmcnt(0) -> barrier -> DMA of the next weight tile + ONE pass of the next chunk's halo (taps 0..6)
 //                      -> fragment reads + 40 MFMAs per wave.
 //   Split-K splits by chunks and goes through the same fp32 slabs + splitk_reduce_kernel as the kernel above.
-struct HaloDesc {
-    int tiles_n, splits, chunks_per_split, n_items;
-    int lgW, lgH;   // image width / height (powers of two)
-};
-
 // GN = true (round 6): GroupNorm-apply + SiLU as the conv's prologue (reference openaimodel.py:212-232: GroupNorm32 -> SiLU -> conv).
 // The RAW tensor is staged; every lane then normalises, in LDS, exactly the 16-byte piece its own DMA wrote (pass p of the next
 // chunk is issued with tap p, has landed behind tap p + 1's vmcnt(0) and is rewritten during tap p + 1: no extra barrier, the
@@ -2142,11 +2125,6 @@ conv_halo_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Ep
 #ifndef GL_WIDE_NST
 #define GL_WIDE_NST 2
 #endif
-struct WideDesc {
-    int tiles_n, splits, kt_per_split, n_items;
-    int xcd;   // 1: every XCD walks a contiguous range of the (tile_m, tile_n) order (see launch_wide)
-};
-
 template <int TN>
 __global__ void __launch_bounds__(512, 1)
 gemm_wide_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Epilogue E, float* __restrict__ ws, WideDesc wd) {
@@ -2477,483 +2455,109 @@ gemm_wide_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Ep
 
 
 
-static int g_gemm_variant = -1;  // 1: LDS-DMA v2 (one tile per workgroup), 2: persistent v3, 4: v5 buffer-DMA persistent (default)
-void gemm_set_variant(int v) { g_gemm_variant = v; }
-static int gemm_variant() {
-    if (g_gemm_variant < 0) {
-        const char* e = dev_env("GL_GEMM_VARIANT");
-        g_gemm_variant = e ? atoi(e) : 4;
-    }
-    return g_gemm_variant;
-}
-// GEGLU weight-row packing the current main-loop variant expects (pack_geglu_launch layout argument)
-int gemm_geglu_layout() { return gemm_variant() >= 2 ? 1 : 0; }
-bool gemm_supports_qkv() { return gemm_variant() == 4; }
-
-static int g_force_tm = 0, g_force_tn = 0, g_force_splits = 0;  // developer override (kbench sweeps)
-static int g_force_grid = 0;
-void gemm_force_cfg(int tm, int tn, int splits) { g_force_tm = tm; g_force_tn = tn; g_force_splits = splits; }
-void gemm_force_grid(int g) { g_force_grid = g; }
-void gemm_set_autotune(int on);
-static thread_local int g_last_cfg[3] = {0, 0, 0};      // per calling thread: one engine context per thread
-static thread_local int g_last_stats_nb = 0;
-int gemm_last_stats_nb() { return g_last_stats_nb; }
-static thread_local char g_last_name[96] = "gemm";
-const char* gemm_last_kernel_name() { return g_last_name; }
-void gemm_last_cfg(int* tm, int* tn, int* splits) { *tm = g_last_cfg[0]; *tn = g_last_cfg[1]; *splits = g_last_cfg[2]; }
+// ---------------------------------------------------------------------------------------------------------------------------
+// Host side: gemm_plan.h decides what runs; here a GemmPlan is executed, and the on-device tuner times the planner's candidates.
+static thread_local GemmPlan t_last = [] { GemmPlan p{}; strcpy(p.name, "gemm"); return p; }();   // per calling thread: one engine context per thread
+int gemm_last_stats_nb() { return t_last.stats_nb; }
+const char* gemm_last_kernel_name() { return t_last.name; }
+void gemm_last_cfg(int* tm, int* tn, int* splits) { *tm = t_last.tm; *tn = t_last.tn; *splits = t_last.splits; }
 
 namespace {
 
-struct Cfg {
-    int bm, bn;
-    float speed;
+// The arguments every GEMM kernel starts with, and the stream it runs on
+struct Launch {
+    const AOperand& A; const bf16* W; int M, N, K; const Epilogue& E; float* ws;
+    hipStream_t stream;
+    template <auto KFN, class... Tail> int run(dim3 grid, int block, size_t lds, const Tail&... tail) const {
+        return launch_lds<KFN>(grid, dim3(block), lds, stream, A, W, M, N, K, E, ws, tail...);
+    }
 };
-const Cfg kCfgs[4] = {{128, 128, 1.0f}, {128, 64, 0.8f}, {64, 64, 0.55f}, {128, 32, 0.45f}};
 
 template <int WM, int WN, int TM, int TN>
-int launch_cfg(const AOperand& A, const bf16* W, int M, int N, int K, const Epilogue& E, float* ws,
-               int splits, int kt_per_split, hipStream_t stream) {
-    constexpr int BM = WM * TM * 32, BN = WN * TN * 32;
-    const int tiles_m = cdiv(M, BM), tiles_n = cdiv(N, BN);
-    dim3 grid(tiles_m * tiles_n, 1, splits);
-    dim3 block(WM * WN * 64);
-    size_t lds = 2 * (BM + BN) * 128;
-    const int n_tiles = tiles_m * tiles_n;
-#define GL_LAUNCH_ONE(KFN, ...)                                                                                  \
-    do {                                                                                                         \
-        auto kfn = KFN;                                                                                          \
-        static bool attr_done = false; /* once per instantiation; never inside a stream capture */              \
-        if (!attr_done && lds > 48 * 1024) {                                                                     \
-            GL_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            attr_done = true;                                                                                    \
-        }                                                                                                        \
-        hipLaunchKernelGGL(kfn, grid, block, lds, stream, A, W, M, N, K, E, ws, kt_per_split, tiles_n, ##__VA_ARGS__); \
-    } while (0)
-    if (A.mode == A_ROWS) GL_LAUNCH_ONE((gemm_glds_kernel<WM, WN, TM, TN, A_ROWS>), n_tiles);
-    else GL_LAUNCH_ONE((gemm_glds_kernel<WM, WN, TM, TN, A_CONV3>), n_tiles);
-#undef GL_LAUNCH_ONE
-    GL_LAUNCH_CHECK();
-    return GL_OK;
+int exec_glds(const Launch& l, const GemmPlan& p) {
+    const dim3 grid(p.grid, 1, p.splits);
+    const size_t lds = 2 * (WM * TM * 32 + WN * TN * 32) * 128;
+    if (p.amode == A_ROWS) return l.run<gemm_glds_kernel<WM, WN, TM, TN, A_ROWS>>(grid, WM * WN * 64, lds, p.work.kt_per_split, p.work.tiles_n, p.grid);
+    return l.run<gemm_glds_kernel<WM, WN, TM, TN, A_CONV3>>(grid, WM * WN * 64, lds, p.work.kt_per_split, p.work.tiles_n, p.grid);
 }
-
-}  // namespace
-
-namespace {
-
 template <int TM, int TN>
-int launch_p(const AOperand& A, const bf16* W, int M, int N, int K, const Epilogue& E, float* ws, const WorkDesc& wd,
-             hipStream_t stream) {
-    const int cap = g_force_grid ? g_force_grid : 512;
-    dim3 grid(wd.n_items < cap ? wd.n_items : cap);
-    dim3 block(256);
+int exec_p(const Launch& l, const GemmPlan& p) {
     const size_t lds = 2 * (TM * 32 + TN * 32) * 128;
-#define GL_LAUNCH_P(KFN)                                                                                         \
-    do {                                                                                                         \
-        auto kfn = KFN;                                                                                          \
-        static bool attr_done = false; /* once per instantiation; never inside a stream capture */              \
-        if (!attr_done && lds > 48 * 1024) {                                                                     \
-            GL_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            attr_done = true;                                                                                    \
-        }                                                                                                        \
-        hipLaunchKernelGGL(kfn, grid, block, lds, stream, A, W, M, N, K, E, ws, wd);                             \
-    } while (0)
-    if (A.mode == A_ROWS) GL_LAUNCH_P((gemm_p_kernel<TM, TN, A_ROWS>));
-    else GL_LAUNCH_P((gemm_p_kernel<TM, TN, A_CONV3>));
-#undef GL_LAUNCH_P
-    GL_LAUNCH_CHECK();
-    return GL_OK;
+    if (p.amode == A_ROWS) return l.run<gemm_p_kernel<TM, TN, A_ROWS>>(p.grid, 256, lds, p.work);
+    return l.run<gemm_p_kernel<TM, TN, A_CONV3>>(p.grid, 256, lds, p.work);
 }
-
-template <int WMW, int TM, int TN, int NST>
-int launch_u(const AOperand& A, const bf16* W, int M, int N, int K, const Epilogue& E, float* ws, const WorkDesc& wd,
-             hipStream_t stream) {
-    constexpr int NT = WMW * 128, RPP = NT / 8, BM = WMW * TM * 16, BN = TN * 32;
-    const int cap = g_force_grid ? g_force_grid : 512;   // workgroups resident per launch: two per CU unless the tuner says otherwise
-    dim3 grid(wd.n_items < cap ? wd.n_items : cap);
-    dim3 block(NT);
-    const size_t lds = NST * (BM + BN) * 128;
-#define GL_LAUNCH_U(KFN)                                                                                         \
-    do {                                                                                                         \
-        auto kfn = KFN;                                                                                          \
-        static bool attr_done = false; /* once per instantiation; never inside a stream capture */              \
-        if (!attr_done && lds > 48 * 1024) {                                                                     \
-            GL_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            attr_done = true;                                                                                    \
-        }                                                                                                        \
-        hipLaunchKernelGGL(kfn, grid, block, lds, stream, A, W, M, N, K, E, ws, wd);                             \
-    } while (0)
-    if (E.mode == EPI_QKV_HEADS || (E.mode == EPI_QK_HEADS && E.ln_stats)) {
-        // (the 128 x 160 tile is not built for QKV: with the second MFMA form it needs more than 256 registers)
-        // q-only / q,k projections behind a folded LayerNorm run here too: these instantiations hold the statistics code
+template <int TM, int TN>
+int exec_u(const Launch& l, const GemmPlan& p) {   // 2 x 2 waves (WMW = 2) on a 2-stage ring
+    const size_t lds = 2 * (TM * 32 + TN * 32) * 128;
+    if (p.qkv) {   // (no 128 x 160 tile for the head layouts: gemm_plan_tile refuses it)
         if constexpr (TM == 4 && TN == 5) return set_error(GL_ERR_UNSUPPORTED, "gemm: no 128x160 tile for EPI_QKV_HEADS");
-        else GL_LAUNCH_U((gemm_u_kernel<WMW, TM, TN, A_ROWS, NST, true>));
-    } else if (A.mode == A_ROWS) GL_LAUNCH_U((gemm_u_kernel<WMW, TM, TN, A_ROWS, NST>));
-    else GL_LAUNCH_U((gemm_u_kernel<WMW, TM, TN, A_CONV3, NST>));
-#undef GL_LAUNCH_U
-    GL_LAUNCH_CHECK();
-    return GL_OK;
-}
-
-// Tile shape + K split for the persistent kernel: minimise a cycle model of
-//   (items per block) x (K tiles per item x cycles per K tile + fixed per-item cost) + split-K reduce pass
-// over the tile shapes {128,64} x {160,128} and a few split counts.
-// Autotuner: the first (eager, non-capturing) launch of every distinct problem times the feasible tile / split /
-// residency candidates on the device with the caller's own buffers and caches the winner; captured launches and
-// GL_GEMM_AUTOTUNE=0 use the analytic cost model below. A launch only writes E.out (and the split-K workspace),
-// and the engine never aliases E.out with an input, so re-running a launch is idempotent.
-// The halo kernel's problems: 3x3, stride 1, pad 1, power-of-two images up to 64 wide whose 256-pixel tiles are whole rows of one
-// image or whole images, plain row-major epilogue (bias, per-sample bias, residual, SiLU, fp32 slabs for split-K).
-static inline int ilog2_exact(int v) {
-    int l = 0;
-    while ((1 << l) < v) ++l;
-    return (1 << l) == v ? l : -1;
-}
-bool halo_eligible(const AOperand& A, int M, int N, int K, const Epilogue& E) {
-    if (A.mode != A_CONV3 || A.stride != 1 || A.ups || A.pad_lo != 1 || A.Ho != A.Hin || A.Wo != A.Win) return false;
-    const int lgW = ilog2_exact(A.Win), lgH = ilog2_exact(A.Hin);
-    if (lgW < 3 || lgW > 6 || lgH < 0 || M % 256) return false;
-    const int R = 256 >> lgW, HB = std::min(A.Hin, R);
-    if ((R / HB) * (HB + 2) * (A.Win + 2) > 448) return false;
-    if (A.C0 % 64 || A.C1 % 64 || (N % 160 && N % 128)) return false;   // whole 160- or 128-wide tiles only
-    if (E.mode != EPI_ROWMAJOR || E.remap_in || (E.act != ACT_NONE && E.act != ACT_SILU) || (E.bias2 && E.res)) return false;
-    if (E.bias2 && (E.rows_per_b != A.Hin * A.Win)) return false;
-    const size_t a_rows = (size_t)M;
-    return a_rows * (size_t)std::max(A.ld0, A.ld1) * 2 < 0x7fff0000ull && (size_t)N * K * 2 < 0x7fff0000ull;
-}
-
-int launch_halo(const AOperand& A, const bf16* W, int M, int N, int K, const Epilogue& E, float* ws, size_t ws_bytes, int want_splits,
-                hipStream_t stream) {
-    const int tn = N % 160 == 0 ? 5 : 4;
-    const int bn = tn * 32;
-    HaloDesc hd;
-    hd.lgW = ilog2_exact(A.Win);
-    hd.lgH = ilog2_exact(A.Hin);
-    hd.tiles_n = cdiv(N, bn);
-    const int tiles = (M / 256) * hd.tiles_n;
-    const int nch = (A.C0 + A.C1) / 64;
-    int sp = want_splits;
-    if (sp <= 0) {   // one work item per CU where the chunks allow it
-        sp = 1;
-        while (tiles * sp < 200 && nch / (sp * 2) >= 2) sp *= 2;
+        else return l.run<gemm_u_kernel<2, TM, TN, A_ROWS, 2, true>>(p.grid, 256, lds, p.work);
     }
-    sp = std::max(1, std::min(sp, nch));
-    if (!ws) sp = 1;
-    while (sp > 1 && (size_t)sp * M * N * sizeof(float) > ws_bytes) --sp;
-    hd.chunks_per_split = cdiv(nch, sp);
-    hd.splits = cdiv(nch, hd.chunks_per_split);
-    hd.n_items = tiles * hd.splits;
-    const int halo_waves = 8;
-    g_last_cfg[0] = 8; g_last_cfg[1] = tn; g_last_cfg[2] = hd.splits;
-    snprintf(g_last_name, sizeof g_last_name, "conv_halo_kernel<%d, %d%s>%s", tn, halo_waves, A.gn ? ", gn" : "", hd.splits > 1 ? " + splitk_reduce_kernel" : "");
-    dim3 grid(std::min(hd.n_items, 256)), block(halo_waves * 64);
-    const size_t lds = 2 * 7 * 64 * 128 + 2 * bn * 128 + (A.gn ? 2048 : 0);
-#define GL_LAUNCH_HALO(KFN)                                                                                      \
-    do {                                                                                                         \
-        auto kfn = KFN;                                                                                          \
-        static bool attr_done = false;                                                                           \
-        if (!attr_done) {                                                                                        \
-            GL_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            attr_done = true;                                                                                    \
-        }                                                                                                        \
-        hipLaunchKernelGGL(kfn, grid, block, lds, stream, A, W, M, N, K, E, ws, hd);                             \
-    } while (0)
-    if (A.gn) {
-        if (tn == 5) GL_LAUNCH_HALO((conv_halo_kernel<5, 8, true>));
-        else GL_LAUNCH_HALO((conv_halo_kernel<4, 8, true>));
-    } else {
-        if (tn == 5) GL_LAUNCH_HALO((conv_halo_kernel<5, 8>));
-        else GL_LAUNCH_HALO((conv_halo_kernel<4, 8>));
+    if (p.amode == A_ROWS) return l.run<gemm_u_kernel<2, TM, TN, A_ROWS, 2>>(p.grid, 256, lds, p.work);
+    return l.run<gemm_u_kernel<2, TM, TN, A_CONV3, 2>>(p.grid, 256, lds, p.work);
+}
+// (the halo and wide kernels always need more than 48 KiB of LDS: launch_lds sets their attribute as unconditionally as before)
+constexpr size_t halo_lds(int tn, bool gn) { return 2 * 7 * 64 * 128 + 2 * tn * 32 * 128 + (gn ? 2048 : 0); }
+constexpr size_t wide_lds(int tn) { return GL_WIDE_NST * (256 + tn * 32) * 128; }
+
+// Launch what the plan says on `stream`: the kernel of its instantiation, then the split-K reduce.
+int execute(const GemmPlan& p, const AOperand& A, const bf16* W, int M, int N, int K, const Epilogue& E_in, float* ws, hipStream_t stream) {
+    Epilogue E = E_in;                                                                     // what the kernels see: no statistics pointer
+    if ((p.family == GEMM_P || p.family == GEMM_U) && !p.stats_nb) E.stats_out = nullptr;  // unless this launch produces them (the staged epilogue writes whenever the pointer is set)
+    const Launch l{A, W, M, N, K, E, ws, stream};
+    int rc = set_error(GL_ERR_UNSUPPORTED, "gemm: unknown tile candidate");
+    switch (p.family * 1000 + p.gn * 100 + p.tm * 10 + p.tn) {   // (in the order the kernels have in the code object)
+        case GEMM_HALO * 1000 + 185: rc = l.run<conv_halo_kernel<5, 8, true>>(p.grid, 512, halo_lds(5, true), p.halo); break;
+        case GEMM_HALO * 1000 + 184: rc = l.run<conv_halo_kernel<4, 8, true>>(p.grid, 512, halo_lds(4, true), p.halo); break;
+        case GEMM_HALO * 1000 + 85: rc = l.run<conv_halo_kernel<5, 8>>(p.grid, 512, halo_lds(5, false), p.halo); break;
+        case GEMM_HALO * 1000 + 84: rc = l.run<conv_halo_kernel<4, 8>>(p.grid, 512, halo_lds(4, false), p.halo); break;
+        case GEMM_WIDE * 1000 + 85: rc = l.run<gemm_wide_kernel<5>>(p.grid, 512, wide_lds(5), p.wide); break;
+        case GEMM_WIDE * 1000 + 84: rc = l.run<gemm_wide_kernel<4>>(p.grid, 512, wide_lds(4), p.wide); break;
+        case GEMM_U * 1000 + 45: rc = exec_u<4, 5>(l, p); break;
+        case GEMM_U * 1000 + 44: rc = exec_u<4, 4>(l, p); break;
+        case GEMM_U * 1000 + 25: rc = exec_u<2, 5>(l, p); break;
+        case GEMM_U * 1000 + 24: rc = exec_u<2, 4>(l, p); break;
+        case GEMM_U * 1000 + 22: rc = exec_u<2, 2>(l, p); break;
+        case GEMM_P * 1000 + 45: rc = exec_p<4, 5>(l, p); break;
+        case GEMM_P * 1000 + 44: rc = exec_p<4, 4>(l, p); break;
+        case GEMM_P * 1000 + 25: rc = exec_p<2, 5>(l, p); break;
+        case GEMM_P * 1000 + 24: rc = exec_p<2, 4>(l, p); break;
+        case GEMM_GLDS * 1000 + 44: rc = exec_glds<2, 2, 2, 2>(l, p); break;
+        case GEMM_GLDS * 1000 + 42: rc = exec_glds<2, 2, 2, 1>(l, p); break;
+        case GEMM_GLDS * 1000 + 22: rc = exec_glds<2, 2, 1, 1>(l, p); break;
+        case GEMM_GLDS * 1000 + 41: rc = exec_glds<4, 1, 1, 1>(l, p); break;
     }
-#undef GL_LAUNCH_HALO
-    GL_LAUNCH_CHECK();
-    if (hd.splits > 1) {
+    GL_TRY(rc);
+    if (p.splits > 1) {
         int64_t total = (int64_t)M * (N / 4);
         int blocks = (int)fmin((double)cdiv64(total, 256), 4096.0);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, ws, hd.splits, M, N, E);
+        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, ws, p.splits, M, N, E);
         GL_LAUNCH_CHECK();
     }
     return GL_OK;
 }
 
-// The wide kernel's problems: row-major activations, whole 256 x BN tiles, plain / residual / SiLU / GEGLU row-major epilogues.
-bool wide_eligible(const AOperand& A, int M, int N, int K, const Epilogue& E) {
-    if (A.mode != A_ROWS || M % 256 || (N % 160 && N % 128)) return false;
-    if (A.C1 && A.C0 % 64) return false;
-    if (E.mode != EPI_ROWMAJOR || E.remap_in || E.bias2) return false;
-    if (E.act == ACT_GEGLU) { if (N % 128 || !E.geglu16 || E.res || E.out_f32) return false; }
-    else if (E.act != ACT_NONE && E.act != ACT_SILU) return false;
-    return (size_t)M * (size_t)std::max(A.ld0, A.ld1) * 2 < 0x7fff0000ull && (size_t)N * K * 2 < 0x7fff0000ull;
-}
-
-int launch_wide(const AOperand& A, const bf16* W, int M, int N, int K, const Epilogue& E, float* ws, size_t ws_bytes, int want_splits,
-                hipStream_t stream) {
-    const int tn = (E.act != ACT_GEGLU && N % 160 == 0) ? 5 : 4;
-    const int bn = tn * 32;
-    WideDesc wd;
-    wd.tiles_n = N / bn;
-    const int tiles = (M / 256) * wd.tiles_n;
-    const int nk = K / 64;
-    int sp = want_splits;
-    if (sp <= 0) {
-        sp = 1;
-        while (tiles * sp < 200 && nk / (sp * 2) >= 4) sp *= 2;
-    }
-    sp = std::max(1, std::min(sp, nk));
-    if (!ws || E.act == ACT_GEGLU) sp = 1;
-    while (sp > 1 && (size_t)sp * M * N * sizeof(float) > ws_bytes) --sp;
-    wd.kt_per_split = cdiv(nk, sp);
-    wd.splits = cdiv(nk, wd.kt_per_split);
-    wd.n_items = tiles * wd.splits;
-    // Item order against the 8 XCD L2s (profiles/r3/wide_ring_kbench.txt, per-problem fabric traffic in profiles/r3_final/).
-    // Linear order with tiles_n a multiple of 8 is weight-stationary by accident: XCD x only ever sees the column tiles = x mod 8,
-    // an eighth of the weight matrix stays in its L2 and the activations cross the fabric 8 times -- the cheaper side when the
-    // weights are the larger operand (32x32 / 16x16 levels: 6.5 / 26 MB of weights against 10 / 5 MB of activations; contiguous
-    // ranges measured 7-8 % slower there). At 64x64 (tiles_n = 20, 1.6 MB of weights, 21 MB of activations) linear order sends
-    // every stripe to every XCD for nothing: contiguous ranges are 4-5 % faster.
-    static const char* xcd_env = dev_env("GL_WIDE_XCD");
-    wd.xcd = xcd_env ? atoi(xcd_env) : (wd.tiles_n % 8 != 0 && wd.n_items >= 512);
-    if (wd.n_items < 256 || std::min(wd.n_items, 256) % 8) wd.xcd = 0;
-    g_last_cfg[0] = 8; g_last_cfg[1] = tn; g_last_cfg[2] = wd.splits;
-    snprintf(g_last_name, sizeof g_last_name, "gemm_wide_kernel<%d>%s", tn, wd.splits > 1 ? " + splitk_reduce_kernel" : "");
-    dim3 grid(std::min(wd.n_items, 256)), block(512);
-    const size_t lds = GL_WIDE_NST * (256 + bn) * 128;
-#define GL_LAUNCH_WIDE(KFN)                                                                                      \
-    do {                                                                                                         \
-        auto kfn = KFN;                                                                                          \
-        static bool attr_done = false;                                                                           \
-        if (!attr_done) {                                                                                        \
-            GL_HIP(hipFuncSetAttribute((const void*)kfn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-            attr_done = true;                                                                                    \
-        }                                                                                                        \
-        hipLaunchKernelGGL(kfn, grid, block, lds, stream, A, W, M, N, K, E, ws, wd);                             \
-    } while (0)
-    if (tn == 5) GL_LAUNCH_WIDE(gemm_wide_kernel<5>);
-    else GL_LAUNCH_WIDE(gemm_wide_kernel<4>);
-#undef GL_LAUNCH_WIDE
-    GL_LAUNCH_CHECK();
-    if (wd.splits > 1) {
-        int64_t total = (int64_t)M * (N / 4);
-        int blocks = (int)fmin((double)cdiv64(total, 256), 4096.0);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, ws, wd.splits, M, N, E);
-        GL_LAUNCH_CHECK();
-    }
-    return GL_OK;
-}
-
-struct TunedCfg { int c, sp, grid; };
-static std::unordered_map<std::string, TunedCfg> g_tuned;   // process-wide, guarded by g_tune_mu (ctypes drops the GIL during calls)
-static std::mutex g_tune_mu;
-static int g_autotune = -1;
-void gemm_set_autotune_impl(int on) { g_autotune = on; }
-static thread_local int t_no_split = 0;
-void gemm_set_no_split_impl(int on) { t_no_split = on; }
-
-// Does this problem go to conv_halo_kernel? (one predicate for the launcher and for gemm_gn_prologue_supported)
-// eligible 3x3 convs with M >= 256 * GL_CONV_HALO (default 8; 0 = never) go to the halo kernel: at M = 512 (the 8 x 8 level) its
-// 16 tiles x deep split lose to the 64 x 160 tiles of gemm_u_kernel
-static bool routes_to_halo(const AOperand& A, int M, int N, int K, const Epilogue& E) {
-    static const int halo = dev_env("GL_CONV_HALO") ? atoi(dev_env("GL_CONV_HALO")) : 8;
-    if (!halo || gemm_variant() != 4 || g_force_tm || N < 128 || (E.bias2 && E.res)) return false;
-    return halo_eligible(A, M, N, K, E) && M >= halo * 256;   // (halo_eligible includes the 2 GiB operand limit of the buffer loader)
-}
-int gemm_p_launch(const AOperand& A, const bf16* W, int M, int N, int K, const Epilogue& E, float* ws, size_t ws_bytes,
-                  hipStream_t stream) {
-    // candidates 0-3: 4 waves on a 2-stage ring, two (or three) workgroups per CU.
-    // Measured and dropped (twice: round 1 sweeps, round 2 on-device autotune over all 107 problems of the benchmark, 0 wins):
-    // the same tiles on a 4-stage ring (three K tiles in flight) with ONE workgroup per CU for the <= 256-item problems of the
-    // 16x16 / 8x8 UNet levels; and (round 1) an 8-wave 256-row tile on a 3-stage ring.
-    // candidate 4 (round 3): 64 x 64 tiles, 32 KB of LDS, up to four workgroups per CU -- for the M = 2048 / 512 problems of the
-    // 16x16 / 8x8 levels, whose 128 / 64-row tiles leave each CU one or two K-tile-deep latency chains (v5 kernel only)
-    constexpr int NC = 5;
-    static const int kTm[NC] = {4, 4, 2, 2, 2}, kTn[NC] = {5, 4, 5, 4, 2};
-    static const int kSp[10] = {1, 2, 3, 4, 6, 8, 12, 16, 24, 32};
-    const int nk = K / 64;
-    // v5 addresses both operands through 32-bit buffer offsets: every operand must be < 2 GiB
-    const size_t a_rows = A.mode == A_CONV3 ? (size_t)(M / (A.Ho * A.Wo)) * A.Hin * A.Win : (size_t)M;
-    const bool fits32 = a_rows * (size_t)std::max(A.ld0, A.ld1) * 2 < 0x7fff0000ull && (size_t)N * K * 2 < 0x7fff0000ull;
-    // v5's epilogue has no bias2 + residual form, and the per-sample bias only in its conv instantiations
-    const bool use_u = gemm_variant() == 4 && fits32 && !(E.bias2 && (E.res || A.mode == A_ROWS));
-    // (GL_CONV_HALO_SPLITS=n forces the halo kernel's K split)
-    static const int halo_splits = dev_env("GL_CONV_HALO_SPLITS") ? atoi(dev_env("GL_CONV_HALO_SPLITS")) : 0;
-    if (use_u && routes_to_halo(A, M, N, K, E))
-        return launch_halo(A, W, M, N, K, E, ws, ws_bytes, halo_splits, stream);
-    // The wide kernel takes the GEGLU projections (GL_GEMM_WIDE=1, default): 0.78-0.82x the time of gemm_u_kernel's 128x128 tiles at the
-    // 64x64 / 32x32 levels, even below. Everything else it is eligible for is slower there (narrow N: 256-row tiles leave CUs idle or
-    // need a K split) or within 4 % (FF-out): GL_GEMM_WIDE=2 sends all of it for A/B runs, 0 none. (profiles/r2_final/wide_kbench.txt)
-    static const int wide = dev_env("GL_GEMM_WIDE") ? atoi(dev_env("GL_GEMM_WIDE")) : 1;
-    static const int wide_splits = dev_env("GL_GEMM_WIDE_SPLITS") ? atoi(dev_env("GL_GEMM_WIDE_SPLITS")) : 0;
-    if (wide && use_u && !g_force_tm && (wide >= 2 || E.act == ACT_GEGLU) && wide_eligible(A, M, N, K, E))
-        return launch_wide(A, W, M, N, K, E, ws, ws_bytes, wide_splits, stream);
-    static const int xcd_boxes = dev_env("GL_GEMM_XCD_BOXES") ? atoi(dev_env("GL_GEMM_XCD_BOXES")) : 1;
-
-    auto feasible = [&](int c, int& sp) {
-        const int tm = kTm[c], tn = kTn[c];
-        if (c == 4 && !use_u) return false;
-        if (E.act == ACT_GEGLU && (tn & 1)) return false;
-        if (E.mode == EPI_QKV_HEADS && (sp > 1 || (2 * E.C) % (tn * 32) || (tm == 4 && tn == 5))) return false;   // an item must not straddle the k | v boundary
-        if (E.mode == EPI_QK_HEADS && E.ln_stats && (sp > 1 || (tm == 4 && tn == 5))) return false;                   // (same kernel family, no V third)
-        if (sp > 1 && (t_no_split || !ws || nk / sp < 2 || (size_t)sp * M * N * sizeof(float) > ws_bytes)) return false;
-        const int kps = cdiv(nk, sp);
-        sp = cdiv(nk, kps);
-        return true;
-    };
-    auto run_cfg = [&](int c, int sp, int grid_cap) -> int {
-        WorkDesc wd;
-        const int tm = kTm[c], tn = kTn[c];
-        wd.tiles_n = cdiv(N, tn * 32);
-        wd.kt_per_split = cdiv(nk, sp);
-        wd.splits = cdiv(nk, wd.kt_per_split);
-        wd.n_items = cdiv(M, tm * 32) * wd.tiles_n * wd.splits;
-        wd.box = -1; wd.rm = 0; wd.rz = wd.splits;
-        if (use_u && xcd_boxes) {
-            // fabric-side bytes ~ A_bytes * (#N bands) + W_bytes * (#M bands); only exact partitions (all boxes equal)
-            const int tiles_m = cdiv(M, tm * 32), tiles_n = wd.tiles_n;
-            const double a_bytes = (double)a_rows * (A.C0 + A.C1) * 2, w_bytes = (double)N * K * 2;
-            double best = 1e300;
-            for (int lgm = 3; lgm >= 0; --lgm)
-                for (int lgn = 3 - lgm; lgn >= 0; --lgn) {
-                    const int lgz = 3 - lgm - lgn;
-                    if (tiles_m % (1 << lgm) || tiles_n % (1 << lgn) || wd.splits % (1 << lgz)) continue;
-                    const double cost = a_bytes * (1 << lgn) + w_bytes * (1 << lgm);
-                    if (cost < best) {
-                        best = cost;
-                        wd.box = lgm | lgn << 4;
-                        wd.rm = tiles_m >> lgm; wd.tiles_n = tiles_n >> lgn; wd.rz = wd.splits >> lgz;
-                    }
-                }
-        }
-        g_last_cfg[0] = tm; g_last_cfg[1] = tn; g_last_cfg[2] = wd.splits;
-        // row statistics for a folded LayerNorm downstream: only the staged row-major epilogue of gemm_u_kernel produces them
-        // (one partial per row and wave column block of tn * 16 columns)
-        g_last_stats_nb = (E.stats_out && use_u && wd.splits == 1 && A.mode == A_ROWS && E.mode == EPI_ROWMAJOR && !E.out_f32 && E.act != ACT_GEGLU &&
-                           E.act != ACT_GELU && E.act != ACT_QUICK_GELU && !(E.res && E.act == ACT_SILU) /* (epilogue_staged does not take that combination) */ &&
-                           N % (tn * 16) == 0 && N / (tn * 16) <= E.stats_ld)
-                              ? N / (tn * 16) : 0;
-        if (E.ln_stats && (!use_u || A.mode != A_ROWS || wd.splits > 1 || (tm == 4 && tn == 5) || (E.mode != EPI_QKV_HEADS && E.mode != EPI_QK_HEADS)))
-            return set_error(GL_ERR_UNSUPPORTED, "gemm: the folded-LayerNorm epilogue exists for the head layouts of gemm_u_kernel and the GEGLU form of gemm_wide_kernel");
-        Epilogue Ek = E;                                   // what the kernels see: no statistics pointer unless this launch produces them
-        if (!g_last_stats_nb) Ek.stats_out = nullptr;     // (the staged epilogue writes whenever the pointer is set)
-        const Epilogue& E = Ek;
-        if (use_u && E.mode == EPI_QKV_HEADS) snprintf(g_last_name, sizeof g_last_name, "gemm_u_kernel<2, %d, %d, 0, 2, true>", tm, tn);
-        else if (use_u) snprintf(g_last_name, sizeof g_last_name, "gemm_u_kernel<2, %d, %d, %d, 2, false>", tm, tn, A.mode);
-        else snprintf(g_last_name, sizeof g_last_name, "gemm_p_kernel<%d, %d, %d>", tm, tn, A.mode);
-        if (wd.splits > 1) strncat(g_last_name, " + splitk_reduce_kernel", sizeof g_last_name - strlen(g_last_name) - 1);
-        const int saved_grid = g_force_grid;
-        if (grid_cap) g_force_grid = grid_cap;
-        int rc;
-        if (use_u) {
-            switch (c) {
-                case 0: rc = launch_u<2, 4, 5, 2>(A, W, M, N, K, E, ws, wd, stream); break;
-                case 1: rc = launch_u<2, 4, 4, 2>(A, W, M, N, K, E, ws, wd, stream); break;
-                case 2: rc = launch_u<2, 2, 5, 2>(A, W, M, N, K, E, ws, wd, stream); break;
-                case 3: rc = launch_u<2, 2, 4, 2>(A, W, M, N, K, E, ws, wd, stream); break;
-                case 4: rc = launch_u<2, 2, 2, 2>(A, W, M, N, K, E, ws, wd, stream); break;
-                default: g_force_grid = saved_grid; return set_error(GL_ERR_UNSUPPORTED, "gemm: unknown tile candidate");
-            }
-        } else {
-            switch (c) {
-                case 0: rc = launch_p<4, 5>(A, W, M, N, K, E, ws, wd, stream); break;
-                case 1: rc = launch_p<4, 4>(A, W, M, N, K, E, ws, wd, stream); break;
-                case 2: rc = launch_p<2, 5>(A, W, M, N, K, E, ws, wd, stream); break;
-                default: rc = launch_p<2, 4>(A, W, M, N, K, E, ws, wd, stream); break;
-            }
-        }
-        g_force_grid = saved_grid;
-        GL_TRY(rc);
-        if (wd.splits > 1) {
-            int64_t total = (int64_t)M * (N / 4);
-            int blocks = (int)fmin((double)cdiv64(total, 256), 4096.0);
-            hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, ws, wd.splits, M, N, E);
-            GL_LAUNCH_CHECK();
-        }
-        return GL_OK;
-    };
-
-    // ---- developer override (kbench sweeps): exactly this tile / split if it fits the problem
-    if (g_force_tm) {
-        for (int c = 0; c < NC; ++c) {
-            if (kTm[c] != g_force_tm || kTn[c] != g_force_tn) continue;
-            for (int si = 0; si < 10; ++si) {
-                int sp = kSp[si];
-                if (g_force_splits && sp != g_force_splits) continue;
-                if (!feasible(c, sp)) continue;
-                if (g_force_splits && sp != g_force_splits) continue;
-                if (!g_force_splits && si > 0) break;  // no split given: unsplit
-                return run_cfg(c, sp, 0);
-            }
-        }
-    }
-
-    // ---- autotuned choice
-    if (g_autotune < 0) {
-        const char* e = dev_env("GL_GEMM_AUTOTUNE");
-        g_autotune = e ? atoi(e) : 1;
-    }
-    char key[160];
-    snprintf(key, sizeof key, "%d,%d,%d|%d,%d,%d,%d,%d,%d,%d|%d,%d,%d,%d,%d,%d|%d%s", M, N, K, A.mode, A.C0, A.C1, A.stride, A.ups, A.Win,
-             A.Hin, E.mode, E.act, E.res != nullptr, E.bias2 != nullptr, E.out_f32, E.gate != nullptr, (int)use_u,
-             (E.mode == EPI_QK_HEADS && E.ln_stats) ? "|ln" : t_no_split ? "|ns" : "");   // (q-only projection behind a folded LayerNorm: another kernel family; "|ns": gemm_set_no_split)
-    std::unique_lock<std::mutex> tune_lock(g_tune_mu);
-    if (g_tuned.empty() && use_u && !dev_env("GL_GEMM_NO_TABLE")) {
-        // shipped choices for the problems of the benchmark configurations (generated by tools/make_tuned_table.py from an
-        // autotune log taken on MI355X with 10 timed launches per candidate): deterministic kernel selection run to run
-        static const struct { const char* key; int c, sp, grid; } kTable[] = {
-#include "gemm_tuned.inc"
-        };
-        for (const auto& e : kTable) g_tuned.emplace(e.key, TunedCfg{e.c, e.sp, e.grid});
-    }
-    auto it = g_tuned.find(key);
-    if (it != g_tuned.end()) {
-        const TunedCfg t = it->second;
-        tune_lock.unlock();
-        return run_cfg(t.c, t.sp, t.grid);
-    }
-
-    // ---- analytic model (also the capture-time / tuning-off fallback)
-    double best_t = 1e30;
-    int best_c = -1, best_sp = 1;
-    for (int c = 0; c < 4; ++c) {   // (the analytic model was fitted without the 64 x 64 candidate: the autotuner alone may pick it)
-        const int tm = kTm[c], tn = kTn[c];
-        const int bm = tm * 32, bn = tn * 32;
-        const int tiles = cdiv(M, bm) * cdiv(N, bn);
-        for (int si = 0; si < 10; ++si) {
-            int sp = kSp[si];
-            if (!feasible(c, sp)) continue;
-            const int kps = cdiv(nk, sp);
-            const int items = tiles * sp;
-            const int per_block = cdiv(items, 512);
-            // cycles per K tile of one block with two blocks per CU, fitted to kbench sweeps on MI355X
-            double t_kt = 0.15 * bm * bn + 500.0;
-            if (items <= 256) t_kt *= 0.75;
-            const double t_item = kps * t_kt + (E.act == ACT_GEGLU ? 9000.0 : 6000.0) * (bm * bn / 20480.0);
-            double tt = per_block * t_item;
-            if (sp > 1) tt += 6000.0 + (double)sp * M * N * 8.0 / 2000.0;  // fp32 slabs out and back + reduce launch
-            if (tt < best_t) { best_t = tt; best_c = c; best_sp = sp; }
-        }
-    }
-    if (best_c < 0) return set_error(GL_ERR_ARG, "gemm: no tile configuration for M=%d N=%d K=%d", M, N, K);
-
+// Autotuner: the first (eager, non-capturing) launch of every distinct problem the shipped table does not hold times the planner's
+// tile / split / residency candidates on the device with the caller's own buffers; gemm_plan caches the winner. A launch only writes
+// E.out (and the split-K workspace), and the engine never aliases E.out with an input, so re-running a launch is idempotent.
+int tune(const bf16* W, float* ws, hipStream_t stream, const GemmProblem& pb, bool use_u, const char* key, const GemmCand& model, GemmCand* win, bool* cache) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     if (stream) (void)hipStreamIsCapturing(stream, &cap);
-    if (!g_autotune || cap != hipStreamCaptureStatusNone) {
-        tune_lock.unlock();
-        return run_cfg(best_c, best_sp, 0);
-    }
-
-    // timing events live on the device that is current for this call (the context's device), for this tuning pass only;
-    // the lock is held across the pass: two threads tuning at once would time each other's launches
+    if (cap != hipStreamCaptureStatusNone) return GL_OK;   // (the model's choice, not remembered)
+    auto run = [&](const GemmCand& c, hipStream_t s) -> int {
+        GemmPlan plan{};
+        GL_TRY(gemm_plan_tile(pb, use_u, c, plan));
+        return execute(plan, pb.A, W, pb.M, pb.N, pb.K, pb.E, ws, s);
+    };
+    // timing events live on the device that is current for this call (the context's device), for this tuning pass only
     GL_HIP(hipDeviceSynchronize());     // a quiet chip: work another execution context has in flight on its own stream must not share the timed launches
-    hipEvent_t g_tune_ev[2];
-    GL_HIP(hipEventCreate(&g_tune_ev[0]));
-    GL_HIP(hipEventCreate(&g_tune_ev[1]));
-    struct EvGuard { hipEvent_t* e; ~EvGuard() { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); } } ev_guard{g_tune_ev};
-    TunedCfg win{best_c, best_sp, 0};
+    hipEvent_t ev[2];
+    GL_HIP(hipEventCreate(&ev[0]));
+    GL_HIP(hipEventCreate(&ev[1]));
+    struct EvGuard { hipEvent_t* e; ~EvGuard() { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); } } ev_guard{ev};
     float win_ms = 1e30f;
-    static const int tune_reps = dev_env("GL_GEMM_TUNE_REPS") ? std::max(1, atoi(dev_env("GL_GEMM_TUNE_REPS"))) : 3;
-    // GL_GEMM_TUNE_CORUN=1 (developer): the candidates are timed as TWO streams running the same launches side by side -- the cost of a
-    // launch while another batch shares the chip (bench.py / the CLI keep two batches in flight), not its latency on a quiet chip: a
-    // tile that leaves CUs to the neighbour is credited for it. Adds resident-grid caps below two workgroups per CU to the candidates.
-    static const bool corun = dev_env("GL_GEMM_TUNE_CORUN") && atoi(dev_env("GL_GEMM_TUNE_CORUN")) != 0;
+    // GL_GEMM_TUNE_CORUN=1 (developer, tools/README.md): the candidates are timed as TWO streams running the same launches side by side
+    const int tune_reps = gemm_knobs().tune_reps, corun = gemm_knobs().corun;
     hipStream_t s2 = nullptr;
     hipEvent_t ev_fork = nullptr, ev_join = nullptr;
     struct CoGuard { hipStream_t& s; hipEvent_t &a, &b; ~CoGuard() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); if (s) (void)hipStreamDestroy(s); } } co_guard{s2, ev_fork, ev_join};
@@ -2962,161 +2566,44 @@ int gemm_p_launch(const AOperand& A, const bf16* W, int M, int N, int K, const E
         GL_HIP(hipEventCreateWithFlags(&ev_fork, hipEventDisableTiming));
         GL_HIP(hipEventCreateWithFlags(&ev_join, hipEventDisableTiming));
     }
-    for (int c = 0; c < NC; ++c) {
-        const int tiles = cdiv(M, kTm[c] * 32) * cdiv(N, kTn[c] * 32);
-        if (c == 4 && ((size_t)M * N > ((size_t)1 << 23) || N % 64)) continue;   // small problems only (M N <= 8 M outputs: 2048 x 3840, 8192 x 640 ..)
-        int last_sp = -1;
-        for (int si = 0; si < 10; ++si) {
-            int sp = kSp[si];
-            if (!feasible(c, sp) || sp == last_sp) continue;
-            last_sp = sp;
-            if (sp > 1 && tiles * sp > 4096) continue;      // splitting an already over-subscribed grid never paid
-            for (int gi = 0; gi < (corun ? 5 : 3); ++gi) {
-                const int grid = gi == 0 ? 0 : gi == 1 ? 768 : gi == 2 ? 1024 : gi == 3 ? 256 : 128;
-                if (gi == 1 && (kTm[c] * 32 + kTn[c] * 32 > 192 || tiles * sp <= 512)) continue;  // 3 workgroups/CU need <= 48 KB LDS each
-                if (gi == 2 && (kTm[c] * 32 + kTn[c] * 32 > 128 || tiles * sp <= 768)) continue;  // 4 workgroups/CU: the 64 x 64 tile (32 KB)
-                if (gi == 3 && tiles * sp <= 256) continue;                                        // (co-run tuning) one workgroup per CU
-                if (gi == 4 && tiles * sp <= 128) continue;                                        // (co-run tuning) half the CUs
-                GL_TRY(run_cfg(c, sp, grid));  // warm-up (also sets the kernel's LDS attribute outside the timed region)
-                GL_HIP(hipEventRecord(g_tune_ev[0], stream));
-                if (corun) {
-                    GL_HIP(hipEventRecord(ev_fork, stream));
-                    GL_HIP(hipStreamWaitEvent(s2, ev_fork, 0));
-                    for (int r = 0; r < tune_reps; ++r) {
-                        GL_TRY(run_cfg(c, sp, grid));
-                        hipStream_t keep = stream;
-                        stream = s2;                       // run_cfg launches on `stream` (captured by reference)
-                        const int rc2 = run_cfg(c, sp, grid);
-                        stream = keep;
-                        GL_TRY(rc2);
-                    }
-                    GL_HIP(hipEventRecord(ev_join, s2));
-                    GL_HIP(hipStreamWaitEvent(stream, ev_join, 0));
-                } else
-                for (int r = 0; r < tune_reps; ++r) GL_TRY(run_cfg(c, sp, grid));
-                GL_HIP(hipEventRecord(g_tune_ev[1], stream));
-                GL_HIP(hipEventSynchronize(g_tune_ev[1]));
-                float ms = 0.f;
-                GL_HIP(hipEventElapsedTime(&ms, g_tune_ev[0], g_tune_ev[1]));
-                if (ms < win_ms) { win_ms = ms; win = TunedCfg{c, sp, grid}; }
+    for (const GemmCand& c : gemm_tune_candidates(pb, use_u)) {
+        GL_TRY(run(c, stream));  // warm-up (also sets the kernel's LDS attribute outside the timed region)
+        GL_HIP(hipEventRecord(ev[0], stream));
+        if (corun) {
+            GL_HIP(hipEventRecord(ev_fork, stream));
+            GL_HIP(hipStreamWaitEvent(s2, ev_fork, 0));
+            for (int r = 0; r < tune_reps; ++r) {
+                GL_TRY(run(c, stream));
+                GL_TRY(run(c, s2));
             }
-        }
+            GL_HIP(hipEventRecord(ev_join, s2));
+            GL_HIP(hipStreamWaitEvent(stream, ev_join, 0));
+        } else
+            for (int r = 0; r < tune_reps; ++r) GL_TRY(run(c, stream));
+        GL_HIP(hipEventRecord(ev[1], stream));
+        GL_HIP(hipEventSynchronize(ev[1]));
+        float ms = 0.f;
+        GL_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+        if (ms < win_ms) { win_ms = ms; *win = c; }
     }
-    g_tuned[key] = win;
-    tune_lock.unlock();
-    static const bool tune_log = dev_env("GL_GEMM_TUNE_LOG") != nullptr;
-    if (tune_log)
-        fprintf(stderr, "[gemm autotune] %s -> %dx%d / %d splits @%d (%.1f us; model said %dx%d / %d) cfg %d %d %d\n", key, kTm[win.c] * 32,
-                kTn[win.c] * 32, win.sp, win.grid ? win.grid : 512, win_ms * 1e3f / tune_reps, kTm[best_c] * 32, kTn[best_c] * 32, best_sp,
-                win.c, win.sp, win.grid);
-    return run_cfg(win.c, win.sp, win.grid);
+    *cache = true;
+    if (gemm_knobs().tune_log)
+        fprintf(stderr, "[gemm autotune] %s -> %dx%d / %d splits @%d (%.1f us; model said %dx%d / %d) cfg %d %d %d\n", key, kGemmTm[win->c] * 32,
+                kGemmTn[win->c] * 32, win->sp, win->grid ? win->grid : 512, win_ms * 1e3f / tune_reps, kGemmTm[model.c] * 32, kGemmTn[model.c] * 32, model.sp,
+                win->c, win->sp, win->grid);
+    return GL_OK;
 }
 
 }  // namespace
 
-void gemm_set_autotune(int on) { gemm_set_autotune_impl(on); }
-void gemm_set_no_split(int on) { gemm_set_no_split_impl(on); }
-
-// AOperand::gn (GroupNorm-apply + SiLU inside the conv's loader) exists in conv_halo_kernel only, for tiles that lie inside one
-// image (H W a multiple of 256: the tile's 256 pixels share one sample's coefficients)
-bool gemm_gn_prologue_supported(const AOperand& A, int M, int N, int K, const Epilogue& E) {
-    return K % 64 == 0 && routes_to_halo(A, M, N, K, E) && (A.Hin * A.Win) % 256 == 0;
-}
-
-// Can a GEMM with this epilogue consume raw rows + row statistics instead of LayerNorm'ed rows (Epilogue::ln_stats)?
-// Mirrors the routing of gemm_launch: the head-layout epilogues of gemm_u_kernel, the GEGLU epilogue of gemm_wide_kernel.
-bool gemm_ln_fold_supported(const AOperand& A, int M, int N, int K, const Epilogue& E) {
-    if (gemm_variant() != 4 || A.mode != A_ROWS || A.C1 || N < 128 || K % 64) return false;
-    if ((size_t)M * (size_t)A.ld0 * 2 >= 0x7fff0000ull || (size_t)N * K * 2 >= 0x7fff0000ull) return false;
-    static const int wide = dev_env("GL_GEMM_WIDE") ? atoi(dev_env("GL_GEMM_WIDE")) : 1;
-    if (E.act == ACT_GEGLU) return wide && E.mode == EPI_ROWMAJOR && wide_eligible(A, M, N, K, E);
-    return E.mode == EPI_QKV_HEADS || E.mode == EPI_QK_HEADS;
-}
-
 int gemm_launch(const AOperand& A, const bf16* W, int M, int N, int K, const Epilogue& E_in, float* ws,
                 size_t ws_bytes, hipStream_t stream) {
-    g_last_stats_nb = 0;
+    t_last.stats_nb = 0;
     Epilogue E = E_in;
-    if (E.rows_per_b < 1) return set_error(GL_ERR_ARG, "gemm: rows_per_b=%d", E.rows_per_b);
-    {   // divide-free m / rows_per_b for the epilogues (div_rpb)
-        const unsigned d = (unsigned)E.rows_per_b;
-        int sh = 0;
-        while ((1ull << sh) < d) ++sh;
-        E.rpb_shift = sh;
-        E.rpb_magic = (unsigned)((((1ull << sh) - d) << 32) / d + 1);
-    }
-    if (M <= 0 || N <= 0 || K <= 0) return set_error(GL_ERR_ARG, "gemm: empty problem M=%d N=%d K=%d", M, N, K);
-    if (E.ln_stats && (!E.ln_csum || !E.bias || E.ln_nb < 1 || E.ln_ld < E.ln_nb || !gemm_ln_fold_supported(A, M, N, K, E)))
-        return set_error(GL_ERR_UNSUPPORTED, "gemm: folded LayerNorm needs csum + folded bias + statistics, and an epilogue that applies them");
-    if (K % 64 != 0) return set_error(GL_ERR_ARG, "gemm: K=%d must be a multiple of 64", K);
-    if (N % 4 != 0) return set_error(GL_ERR_ARG, "gemm: N=%d must be a multiple of 4", N);
-    if (A.gn && !gemm_gn_prologue_supported(A, M, N, K, E))
-        return set_error(GL_ERR_UNSUPPORTED, "gemm: the GroupNorm prologue (AOperand::gn) exists in conv_halo_kernel only (3x3, stride 1, H W %% 256 == 0)");
-    if (A.mode == A_CONV3) {
-        if ((A.C0 + A.C1) % 64 != 0 || A.C0 % 64 != 0 || K != 9 * (A.C0 + A.C1))
-            return set_error(GL_ERR_ARG, "conv3x3: channels (%d,%d) must be multiples of 64 and K=9*Cin (K=%d)", A.C0, A.C1, K);
-    } else {
-        if (K != A.C0 + A.C1 || (A.C1 && A.C0 % 64 != 0))
-            return set_error(GL_ERR_ARG, "gemm: K=%d does not match operand channels (%d,%d)", K, A.C0, A.C1);
-    }
-    if (A.mode == A_CONV3 && (E.gate || E.remap_in))
-        return set_error(GL_ERR_UNSUPPORTED, "conv3x3: the gated residual and the row remap are row-GEMM epilogues");
-    if ((E.act == ACT_GELU || E.act == ACT_QUICK_GELU) && (E.res || E.bias2 || A.mode != A_ROWS))
-        return set_error(GL_ERR_UNSUPPORTED, "gemm: the GELU / quick-GELU epilogues have no residual / broadcast-bias form");
-    if (E.act == ACT_GEGLU && (N % 32 != 0 || E.mode != EPI_ROWMAJOR))
-        return set_error(GL_ERR_ARG, "gemm: GEGLU epilogue needs packed N %% 32 == 0 (N=%d)", N);
-    if (E.act == ACT_GEGLU && E.geglu16 != gemm_geglu_layout())
-        return set_error(GL_ERR_STATE, "gemm: GEGLU weights were packed for a different main-loop variant");
-    if (E.mode == EPI_QKV_HEADS) {
-        if (A.mode != A_ROWS || A.C1) return set_error(GL_ERR_ARG, "gemm: EPI_QKV_HEADS takes a single row-major activation operand");
-        const size_t a_bytes = (size_t)M * A.ld0 * 2;
-        if (!gemm_supports_qkv() || a_bytes >= 0x7fff0000ull || (size_t)N * K * 2 >= 0x7fff0000ull || N != 3 * E.C || (2 * E.C) % 128 || !E.vt || !E.q || !E.k ||
-            E.T % 64 || M % E.T)
-            return set_error(GL_ERR_UNSUPPORTED, "gemm: EPI_QKV_HEADS needs the v5 main loop, N = 3C with 2C %% 128 == 0, tokens per sample %% 64 == 0");
-    }
-    if (gemm_variant() >= 2 && (N >= 128 || E.act == ACT_GEGLU)) return gemm_p_launch(A, W, M, N, K, E, ws, ws_bytes, stream);
-
-    // pick the tile: padding efficiency x relative tile speed x chip fill
-    int best = 0;
-    float best_score = -1.f;
-    for (int c = 0; c < 4; ++c) {
-        if (c == 3 && N > 32) continue;
-        if (c != 3 && N <= 32) continue;
-        const Cfg& cf = kCfgs[c];
-        double tm = cdiv(M, cf.bm), tn = cdiv(N, cf.bn);
-        double pad = ((double)M * N) / (tm * cf.bm * tn * cf.bn);
-        double fill = fmin(1.0, tm * tn / 256.0);
-        float score = (float)(pad * cf.speed * (0.35 + 0.65 * fill));
-        if (score > best_score) { best_score = score; best = c; }
-    }
-    const Cfg& cf = kCfgs[best];
-    snprintf(g_last_name, sizeof g_last_name, "gemm_glds_kernel<%dx%d, %d>", cf.bm, cf.bn, A.mode);
-    const int tiles = cdiv(M, cf.bm) * cdiv(N, cf.bn);
-    const int nk = K / 64;
-    int splits = 1;
-    if (ws && !t_no_split && tiles < 256 && nk >= 8) {
-        splits = min(min(cdiv(512, tiles), nk / 4), 16);
-        while (splits > 1 && (size_t)splits * M * N * sizeof(float) > ws_bytes) --splits;
-    }
-    int kt_per_split = cdiv(nk, splits);
-    splits = cdiv(nk, kt_per_split);
-    g_last_cfg[0] = cf.bm / 32; g_last_cfg[1] = cf.bn / 32; g_last_cfg[2] = splits;
-
-    int rc;
-    switch (best) {
-        case 0: rc = launch_cfg<2, 2, 2, 2>(A, W, M, N, K, E, ws, splits, kt_per_split, stream); break;
-        case 1: rc = launch_cfg<2, 2, 2, 1>(A, W, M, N, K, E, ws, splits, kt_per_split, stream); break;
-        case 2: rc = launch_cfg<2, 2, 1, 1>(A, W, M, N, K, E, ws, splits, kt_per_split, stream); break;
-        default: rc = launch_cfg<4, 1, 1, 1>(A, W, M, N, K, E, ws, splits, kt_per_split, stream); break;
-    }
-    GL_TRY(rc);
-    if (splits > 1) {
-        int64_t total = (int64_t)M * (N / 4);
-        int blocks = (int)fmin((double)cdiv64(total, 256), 4096.0);
-        hipLaunchKernelGGL(splitk_reduce_kernel, dim3(blocks), dim3(256), 0, stream, ws, splits, M, N, E);
-        GL_LAUNCH_CHECK();
-    }
-    return GL_OK;
+    GemmPlan plan;
+    GL_TRY(gemm_plan(A, M, N, K, E, ws != nullptr, ws_bytes, plan, [&](auto&&... a) { return tune(W, ws, stream, a...); }));
+    t_last = plan;
+    return execute(plan, A, W, M, N, K, E, ws, stream);
 }
 
 int gemm_launch_t(const bf16* Wrows, int Mw, const bf16* X, int Nx, int K, const Epilogue& E, hipStream_t stream) {
