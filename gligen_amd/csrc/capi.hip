@@ -887,6 +887,16 @@ int gl_op_conv3x3(gl_ctx* ctx, const void* x0, int C0, const void* x1, int C1, i
     Arena& ar = ctx->eng->arena();
     ar.reset();
     const int Cin = C0 + C1;
+    if (stride == 1 && ups == 1 && pad_lo == 1 && !res && Engine::upconv_phase_form(Cin, Cout)) {   // the engine's Upsample: phase form
+        ConvW c;
+        c.Cin = Cin; c.Cout = Cout; c.Npad = Cout; c.b = bias;
+        bf16* w4 = ar.get<bf16>((size_t)16 * Cout * Cin);
+        const int rp = pack_upconv_phases_launch(w_oihw, w4, Cout, Cin, Cout, S(s));
+        if (rp != GL_OK) throw GlError(rp, gl::last_error());
+        c.w4 = w4;
+        ctx->eng->conv3x3(TRef{(const bf16*)x0, C0, (const bf16*)x1, C1}, B, H, W, c, 1, 1, 1, nullptr, 0, nullptr, S(s), (bf16*)y);
+        return GL_OK;
+    }
     bf16* wp = ar.get<bf16>((size_t)Cout * 9 * Cin);
     int r = pack_conv_weight_launch(w_oihw, wp, Cout, Cin, 3, 3, Cout, S(s));
     if (r != GL_OK) throw GlError(r, gl::last_error());

@@ -67,7 +67,8 @@ class Arena {
 struct NormW { const float* g = nullptr; const float* b = nullptr; int C = 0; };
 struct LinW { const bf16* w = nullptr; const float* b = nullptr; int K = 0, N = 0; };
 // Kpad: the small-channel im2col form (conv3_small / conv3x3_small): w is [Cout][Kpad], K = 9 * Cin zero-padded to a multiple of 64
-struct ConvW { const bf16* w = nullptr; const float* b = nullptr; int Cin = 0, Cout = 0, Npad = 0, Kpad = 0; };
+// w4: the four folded 2x2 filters of an upsample conv's phase form ([4][Cout][4 Cin], gemm.h A_CONV2UP); such a conv holds no nine-tap copy
+struct ConvW { const bf16* w = nullptr; const float* b = nullptr; int Cin = 0, Cout = 0, Npad = 0, Kpad = 0; const bf16* w4 = nullptr; };
 
 struct ResW {
     int Cin = 0, Cout = 0;
@@ -224,6 +225,12 @@ class Engine {
     // loader where conv_halo_kernel takes the problem (gn_prologue_), as a separate pass elsewhere
     bf16* gn_silu_conv3x3(const TRef& x, int B, int H, int W, const NormW& n, float eps, const ConvW& c, const float* bias2, int bias2_ld,
                           const bf16* res, bf16* out, hipStream_t s);
+    // conv3x3 (stride 1 | 2, optional nearest-2x upsample of the source); out: where the result goes (default: a new arena block)
+    bf16* conv3x3(const TRef& x, int B, int Hin, int Win, const ConvW& c, int stride, int ups, int pad_lo,
+                  const float* bias2, int bias2_ld, const bf16* res, hipStream_t s, bf16* out = nullptr);
+    // Does the conv behind a nearest-2x Upsample (Cin -> Cout channels, stride 1, pad 1, bias only) run as four 2x2 phase convs?
+    // GL_UPCONV_PHASES=0 (developer A/B): never, i.e. the nine-tap loader with the replication as a view
+    static bool upconv_phase_form(int Cin, int Cout);
     // Off by default: measured on MI355X (profiles/r6/gnconv_kbench.txt) the prologue costs conv_halo_kernel more (LDS port + VALU slots,
     // the two things that kernel is short of) than the apply pass it removes; GL_GN_PROLOGUE=1 (developer switch) turns it on in the
     // engine, gl_op_gn_silu_conv3x3(mode = 1) runs it for one operator
@@ -265,7 +272,8 @@ class Engine {
     std::unordered_set<std::string> keep_raw_;
     NormW norm(const std::string& prefix);
     LinW linear(const std::string& prefix, bool bias = true);
-    ConvW conv3(const std::string& prefix, int Npad = 0);
+    // up2x: the conv behind a nearest-2x Upsample; packed for the phase form where upconv_phase_form() says so
+    ConvW conv3(const std::string& prefix, int Npad = 0, bool up2x = false);
     ConvW conv3_small(const std::string& prefix, int Cout);
     LinW conv1(const std::string& prefix);
     const bf16* cast_rows(const std::vector<std::string>& weight_keys);
@@ -284,8 +292,6 @@ class Engine {
     bf16* layernorm_plain(const bf16* x, int B, int N, int C, bool pad64, hipStream_t s);   // (x - mean) * rstd, no affine
     bf16* groupnorm(const TRef& x, int B, int HW, const NormW& n, float eps, bool silu, hipStream_t s);
     bf16* layernorm(const bf16* x, int B, int N, int C, const NormW& n, bool pad64, hipStream_t s);
-    bf16* conv3x3(const TRef& x, int B, int Hin, int Win, const ConvW& c, int stride, int ups, int pad_lo,
-                  const float* bias2, int bias2_ld, const bf16* res, hipStream_t s);
     bf16* conv3x3_small(const ConvW& c, Im2colParams P, int reps, hipStream_t s);
     void gn_silu_conv3x3_nchw(const bf16* x, int C, int B, int H, int W, const NormW& n, float eps, const ConvW& c, int n_real, float* out, hipStream_t s);
     bf16* resblock(const ResW& r, const TRef& x, int B, int H, int W, const float* embout, int emb_ld, float eps, hipStream_t s);

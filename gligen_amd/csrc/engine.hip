@@ -315,16 +315,27 @@ LinW Engine::linear(const std::string& p, bool bias) {
 
 LinW Engine::conv1(const std::string& p) { return linear(p, true); }
 
-ConvW Engine::conv3(const std::string& p, int Npad) {
+bool Engine::upconv_phase_form(int Cin, int Cout) {
+    static const bool on = !(dev_env("GL_UPCONV_PHASES") && atoi(dev_env("GL_UPCONV_PHASES")) == 0);
+    return on && gemm_supports_qkv() /* (the v5 main loop) */ && Cin % 64 == 0 && Cout % 8 == 0;
+}
+
+ConvW Engine::conv3(const std::string& p, int Npad, bool up2x) {
     ConvW c;
     const RawTensor& w = raw(p + ".weight");
     if (w.shape.size() != 4 || w.shape[2] != 3 || w.shape[3] != 3) throw GlError(GL_ERR_ARG, "'" + p + ".weight' is not a 3x3 conv");
     c.Cout = (int)w.shape[0];
     c.Cin = (int)w.shape[1];
     c.Npad = Npad ? Npad : c.Cout;
-    bf16* dst = reinterpret_cast<bf16*>(persist((size_t)c.Npad * 9 * c.Cin * sizeof(bf16), false));
-    CK(pack_conv_weight_launch(w.p, dst, c.Cout, c.Cin, 3, 3, c.Npad, 0));
-    c.w = dst;
+    if (up2x && c.Npad == c.Cout && upconv_phase_form(c.Cin, c.Cout)) {
+        bf16* dst = reinterpret_cast<bf16*>(persist((size_t)16 * c.Cout * c.Cin * sizeof(bf16), false));
+        CK(pack_upconv_phases_launch(w.p, dst, c.Cout, c.Cin, c.Cout, 0));
+        c.w4 = dst;
+    } else {
+        bf16* dst = reinterpret_cast<bf16*>(persist((size_t)c.Npad * 9 * c.Cin * sizeof(bf16), false));
+        CK(pack_conv_weight_launch(w.p, dst, c.Cout, c.Cin, 3, 3, c.Npad, 0));
+        c.w = dst;
+    }
     if (c.Npad != c.Cout) {
         float* b = reinterpret_cast<float*>(persist(c.Npad * sizeof(float), true));
         HIPCK(hipMemcpy(b, F(p + ".bias"), c.Cout * sizeof(float), hipMemcpyDeviceToDevice));
@@ -505,7 +516,7 @@ void Engine::gemm(const AOperand& A, const bf16* W, int M, int N, int K, const E
     // counter rows (which carry the kernel symbol but not the problem) with their shapes
     FILE* launch_log = launch_log_file();
     if (launch_log) {
-        const double a_rows = A.mode == A_CONV3 ? (double)(M / (A.Ho * A.Wo)) * A.Hin * A.Win : (double)M;
+        const double a_rows = A.mode != A_ROWS ? (double)(M / (A.Ho * A.Wo)) * A.Hin * A.Win : (double)M;
         const double out_b = E.mode == EPI_NCHW_F32 ? 4.0 * M * E.n_real : (E.act == ACT_GEGLU ? 1.0 : 2.0) * M * (double)N * (E.out_f32 ? 2 : 1);
         const double bytes = a_rows * (A.C0 + A.C1) * 2 + (double)N * K * 2 + out_b + (E.res ? 2.0 * M * N : 0.0);
         fprintf(launch_log, "%s|%d|%d|%d|%d|%.0f\n", gemm_last_kernel_name(), M, N, K, A.mode, bytes);
@@ -604,13 +615,30 @@ bf16* Engine::layernorm_plain(const bf16* x, int B, int N, int C, bool pad64, hi
 }
 
 bf16* Engine::conv3x3(const TRef& x, int B, int Hin, int Win, const ConvW& c, int stride, int ups, int pad_lo,
-                      const float* bias2, int bias2_ld, const bf16* res, hipStream_t s) {
+                      const float* bias2, int bias2_ld, const bf16* res, hipStream_t s, bf16* out) {
     if (x.C() != c.Cin) throw GlError(GL_ERR_ARG, fmt("conv3x3: input has %d channels, weight expects %d", x.C(), c.Cin));
+    if (c.w4) {
+        // Upsample (reference openaimodel.py:54-82, VAE model.py:42-57) in phase form: four 2x2 convs on the source, 4/9 of the MACs.
+        // A batch whose source tensor is beyond the kernel's 32-bit buffer offsets goes in pieces of whole images.
+        if (stride != 1 || ups != 1 || pad_lo != 1 || bias2 || res) throw GlError(GL_ERR_ARG, "conv3x3: phase-form weights serve the plain upsample conv only");
+        const int Mi = 4 * Hin * Win;
+        if (!out) out = arena_.get<bf16>((size_t)B * Mi * c.Cout);
+        auto ok = [&](int b) { return gemm_upconv_phases_supported(a_conv2up(x, Hin, Win), b * Mi, c.Cout, 4 * c.Cin, e_rows(out, c.Cout, c.b)); };
+        int Bc = B;
+        while (Bc > 1 && !ok(Bc)) Bc = (Bc + 1) / 2;
+        if (!ok(Bc)) throw GlError(GL_ERR_UNSUPPORTED, fmt("conv3x3: no phase form for a %d x %d x %d -> %d upsample conv", Hin, Win, c.Cin, c.Cout));
+        for (int b0 = 0; b0 < B; b0 += Bc) {
+            const size_t px = (size_t)b0 * Hin * Win;
+            const TRef xb{x.p0 + px * x.C0, x.C0, x.p1 ? x.p1 + px * x.C1 : nullptr, x.C1};
+            gemm(a_conv2up(xb, Hin, Win), c.w4, std::min(Bc, B - b0) * Mi, c.Cout, 4 * c.Cin, e_rows(out + (size_t)b0 * Mi * c.Cout, c.Cout, c.b), s);
+        }
+        return out;
+    }
     const int Hup = Hin << ups, Wup = Win << ups;
     const int Ho = stride == 1 ? Hup : (pad_lo ? (Hup + 2 - 3) / 2 + 1 : (Hup + 1 - 3) / 2 + 1);
     const int Wo = stride == 1 ? Wup : (pad_lo ? (Wup + 2 - 3) / 2 + 1 : (Wup + 1 - 3) / 2 + 1);
     const int M = B * Ho * Wo;
-    bf16* out = arena_.get<bf16>((size_t)M * c.Cout);
+    if (!out) out = arena_.get<bf16>((size_t)M * c.Cout);
     Epilogue E = e_rows_res(out, c.Cout, c.b, res);
     E.bias2 = bias2; E.bias2_ld = bias2_ld; E.rows_per_b = Ho * Wo;
     gemm(a_conv3(x, Hin, Win, Ho, Wo, stride, ups, pad_lo), c.w, M, c.Cout, 9 * c.Cin, E, s);

@@ -49,6 +49,12 @@ inline AOperand a_conv3(const TRef& x, int Hin, int Win, int Ho, int Wo, int str
     A.Hin = Hin; A.Win = Win; A.Ho = Ho; A.Wo = Wo; A.stride = stride; A.ups = ups; A.pad_lo = pad_lo;
     return A;
 }
+// nearest-2x upsample + 3x3 / pad 1 conv of the NHWC channel-concat x in phase form (gemm.h A_CONV2UP): M = 4 B Hin Win
+inline AOperand a_conv2up(const TRef& x, int Hin, int Win) {
+    AOperand A = a_conv3(x, Hin, Win, 2 * Hin, 2 * Win, 1, 0, 1);
+    A.mode = A_CONV2UP;
+    return A;
+}
 // row-major [M][ldo] (bf16 unless the caller sets out_f32) + bias
 inline Epilogue e_rows(void* out, int ldo, const float* bias = nullptr) {
     Epilogue E;

@@ -209,7 +209,7 @@ void Engine::build_unet() {
                 j = 2;
             }
             if (level && i == c.num_res_blocks) {
-                unet_.updown.push_back(conv3(p + fmt(".%d.conv", j)));
+                unet_.updown.push_back(conv3(p + fmt(".%d.conv", j), 0, true));
                 b.layers.push_back(Layer{L_UP, (int)unet_.updown.size() - 1});
                 ds /= 2;
             }

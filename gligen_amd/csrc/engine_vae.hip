@@ -39,7 +39,7 @@ void Engine::build_vae() {
         }
         if (level != 0) {
             vae_.dec.levels[level].has_resample = true;
-            vae_.dec.levels[level].resample = conv3(V + fmt("decoder.up.%d.upsample.conv", level));
+            vae_.dec.levels[level].resample = conv3(V + fmt("decoder.up.%d.upsample.conv", level), 0, true);
         }
     }
     vae_.dec.norm_out = norm(V + "decoder.norm_out");

@@ -4,12 +4,19 @@
 
 namespace gl {
 
-enum { A_ROWS = 0, A_CONV3 = 1 };
+enum { A_ROWS = 0, A_CONV3 = 1, A_CONV2UP = 2 };
 
 // The activation ("rows") operand: logical matrix [M][K], bf16.
 //  A_ROWS : row m = concat(p0[m*ld0 .. +C0), p1[m*ld1 .. +C1)),  K = C0 + C1
 //  A_CONV3: implicit im2col of an NHWC tensor (channel-concat of p0,p1), 3x3 taps,
 //           k = tap*(C0+C1) + c; optional nearest-2x upsample of the source and stride 1|2.
+//  A_CONV2UP: nearest-2x upsample + 3x3 / pad 1 conv as four 2x2 convs on the SOURCE, one per output phase (py, px) = (oy & 1, ox & 1):
+//           after the replication the three row taps of output row 2y + py read two source rows (py = 0: y-1 <- w[0], y <- w[1]+w[2];
+//           py = 1: y <- w[0]+w[1], y+1 <- w[2]), columns alike, and zero padding carries over unchanged. 4/9 of the MACs.
+//           M = 4 B Hin Win (= B Ho Wo) in the order [phase p = 2 py + px][b][y][x]; every phase has its own row tiles, so a tile lies
+//           in one phase. k = (2a + b)*(C0+C1) + c for source tap (y - 1 + py + a, x - 1 + px + b); W = [4][N][K] from
+//           pack_upconv_phases_launch (misc.h). Ho = 2 Hin, Wo = 2 Win; stride, ups, pad_lo are not read. gemm_u_kernel only, plain
+//           bias epilogue to row-major bf16: ask gemm_upconv_phases_supported() first.
 struct AOperand {
     const bf16* p0;
     const bf16* p1;
@@ -61,6 +68,8 @@ struct Epilogue {
     int n_real;         // EPI_NCHW_F32: number of real output channels (<= N)
     // EPI_ROWMAJOR optional row remap: out row = (m / remap_in) * remap_out + m % remap_in + remap_off
     int remap_in, remap_out, remap_off;
+    int up_win;         // A_CONV2UP launches: the source width Win (filled by gemm_launch, which also points rpb_magic / rpb_shift at it: phase
+                        // row r = (b Hin + y) Win + x is output row (2 (r / Win) + py) 2 Win + 2 (r % Win) + px); 0 otherwise
     int geglu16;        // ACT_GEGLU: weight rows packed for the 16x16-tile kernel (pack_geglu layout 1)
     // ---- LayerNorm folded into the GEMM that consumes it (reference attention.py:333-338: x + attn(norm(x)), ff(norm(x))):
     //   LN(x) W^T + b = rstd_m (x W'^T - mean_m csum) + b',  W' = W * gamma (bf16), csum[n] = sum_k W'[n][k], b' = b + W beta
@@ -114,6 +123,7 @@ void gemm_set_no_split(int on);
 void gemm_last_cfg(int* tm, int* tn, int* splits);
 const char* gemm_last_kernel_name();  // kernel symbol (template arguments included) of the most recent gemm_launch
 bool gemm_gn_prologue_supported(const AOperand& A, int M, int N, int K, const Epilogue& E);   // may this launch take AOperand::gn?
+bool gemm_upconv_phases_supported(const AOperand& A, int M, int N, int K, const Epilogue& E);   // may this launch take A_CONV2UP?
 bool gemm_ln_fold_supported(const AOperand& A, int M, int N, int K, const Epilogue& E);   // may this launch take Epilogue::ln_stats?
 int gemm_last_stats_nb();             // column blocks per row written to Epilogue::stats_out by the most recent gemm_launch (0: none)
 void aoperand_rows(AOperand& A, const bf16* p, int K, int ld);

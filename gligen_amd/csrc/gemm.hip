@@ -19,7 +19,8 @@
 // ONE output row and groups of 4 CONSECUTIVE output columns: 8-byte bf16 stores, bias as float4, no transpose.
 // The activation loader optionally performs the im2col gather of a 3x3 convolution over an NHWC tensor (stride 1|2,
 // nearest-2x upsample of the source, channel concat of two sources, asymmetric padding), so convs never materialise
-// im2col or concat / upsample copies in HBM. Split-K goes through an fp32 slab workspace + a deterministic reduce kernel.
+// im2col or concat / upsample copies in HBM. gemm_u_kernel also runs the upsample + conv pair as four 2x2 convs on the source, one per
+// output phase (A_CONV2UP, gemm.h: 4/9 of the multiply-adds; the nine-tap upsample loader stays for the training forward). Split-K goes through an fp32 slab workspace + a deterministic reduce kernel.
 //
 // Which kernel runs a problem (family, tile, K split, resident grid, item order) is decided in gemm_plan.h / gemm_plan.hip, host code
 // without a HIP call; this file holds the kernels, execute() for a GemmPlan and the on-device tuner's timing loop.
@@ -761,6 +762,10 @@ gemm_u_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Epilo
     constexpr int WP = BN / RPP;                // weight passes
     constexpr int STAGE = (BM + BN) * 128;      // two stages: the two (to four) 4-wave workgroups of a CU hide each other's DMA latency
     constexpr unsigned SENT = 0x80000000u;      // >= num_records of every descriptor: reads as zeros
+    // A_CONV2UP (gemm.h): the four output phases are four ranges of TPP row tiles; a tile's rows are phase-local (< MP), its slab rows
+    // for split-K are phase-major (phase * MP + row) and only the final store knows the interleaved output row
+    constexpr bool UP = AMODE == A_CONV2UP;
+    constexpr int TAPW = UP ? 2 : 3;            // filter taps per row
     static_assert(WMW == 2 && NST == 2, "one geometry: 4 waves, two LDS stages (deeper rings and the 8-wave form lost every A/B, DESIGN.md section 4)");
     static_assert(BM % RPP == 0 && BN % RPP == 0, "tile/loader mismatch");
 
@@ -775,8 +780,10 @@ gemm_u_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Epilo
     const unsigned chb = (((t & 7) ^ ((r0 >> 1) & 7)) * 16);        // byte offset of this lane's (swizzled) source chunk
     const int nk = K >> 6;
     const int Cin = A.C0 + A.C1;
-    const int Hup = A.Hin << A.ups;
-    const int Wup = A.Win << A.ups;
+    const int Hup = UP ? A.Hin : A.Hin << A.ups;   // (UP walks the source itself)
+    const int Wup = UP ? A.Win : A.Win << A.ups;
+    const int MP = UP ? M >> 2 : M;             // rows a tile's row index is checked against
+    const int TPP = (MP + BM - 1) / BM;         // (UP) row tiles per phase
 
     const __amdgpu_buffer_rsrc_t ra0 = __builtin_amdgcn_make_buffer_rsrc((void*)A.p0, 0, 0x80000000u, 0x00020000);
     const __amdgpu_buffer_rsrc_t ra1 = __builtin_amdgcn_make_buffer_rsrc((void*)(A.p1 ? A.p1 : A.p0), 0, 0x80000000u, 0x00020000);
@@ -815,14 +822,14 @@ gemm_u_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Epilo
 #pragma unroll
             for (int i = 0; i < XP; ++i) va[i] = xm[i] >= 0 ? (unsigned)(xm[i] * ld) * 2u + chb : SENT;
         } else {
-            const int ky = l_tap / 3;
-            const int kx = l_tap - ky * 3;
+            const int ky = l_tap / TAPW;
+            const int kx = l_tap - ky * TAPW;
 #pragma unroll
             for (int i = 0; i < XP; ++i) {
                 const int iy = xy[i] + ky;
                 const int ix = xx[i] + kx;
                 const bool ok = iy >= 0 && iy < Hup && ix >= 0 && ix < Wup;
-                const int pix = (xm[i] + (iy >> A.ups)) * A.Win + (ix >> A.ups);
+                const int pix = UP ? (xm[i] + iy) * A.Win + ix : (xm[i] + (iy >> A.ups)) * A.Win + (ix >> A.ups);
                 va[i] = ok ? (unsigned)(pix * ld) * 2u + chb : SENT;
             }
         }
@@ -833,13 +840,23 @@ gemm_u_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Epilo
         decode(item, tm, tn, z);
         l_kt = z * wd.kt_per_split;
         l_kt_end = min(nk, l_kt + wd.kt_per_split);
+        int ph = 0;                             // (UP) output phase 2 py + px of the tile; tm becomes its row tile inside the phase
+        if constexpr (UP) { ph = tm / TPP; tm -= ph * TPP; }
 #pragma unroll
         for (int i = 0; i < XP; ++i) {
             const int m = tm * BM + r0 + i * RPP;
-            const bool ok = m < M;
+            const bool ok = m < MP;
             if constexpr (AMODE == A_ROWS) {
                 xm[i] = ok ? m : -1;
                 xy[i] = xx[i] = 0;
+            } else if constexpr (UP) {
+                // phase row m = (b Hin + y) Win + x; top-left source tap (y - 1 + py, x - 1 + px)
+                const int ox = m % A.Win;
+                const int tmp = m / A.Win;
+                const int oy = tmp % A.Hin;
+                xm[i] = tmp - oy;               // b * Hin
+                xy[i] = ok ? oy - 1 + (ph >> 1) : -(1 << 20);
+                xx[i] = ox - 1 + (ph & 1);
             } else {
                 const int ox = m % A.Wo;
                 const int tmp = m / A.Wo;
@@ -852,7 +869,7 @@ gemm_u_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Epilo
 #pragma unroll
         for (int i = 0; i < WP; ++i) {
             const int n = tn * BN + r0 + i * RPP;
-            vw[i] = (n < N) ? (unsigned)(n * K) * 2u + chb : SENT;
+            vw[i] = (n < N) ? (unsigned)((UP ? ph * N + n : n) * K) * 2u + chb : SENT;   // (UP: the phase's folded filter, W = [4][N][K])
         }
         const int k0 = l_kt << 6;
         if constexpr (AMODE == A_ROWS) {
@@ -893,7 +910,7 @@ gemm_u_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Epilo
             l_item += gridDim.x;
             more = l_item < wd.n_items;
             if (more) setup_load(l_item);
-        } else if constexpr (AMODE == A_CONV3) {
+        } else if constexpr (AMODE != A_ROWS) {
             if (l_cc == Cin) {
                 l_cc = 0;
                 ++l_tap;
@@ -1119,23 +1136,26 @@ gemm_u_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Epilo
     // Epilogue: every load (bias, time-embedding bias, residual, gate) of the wave's TM x TN fragments is issued
     // before the first store (see epi_store4).
     auto epilogue = [&](int tm, int tn, int z) {
+        int slab0 = 0;                          // (UP) first slab row of the tile's phase
+        if constexpr (UP) { const int ph = tm / TPP; tm -= ph * TPP; slab0 = ph * MP; }
         const int mrow = tm * BM + wm * TM * 16 + l15;
         const int ncol = tn * BN + wn * TN * 16 + (lane >> 4) * 4;
         if (wd.splits > 1) {
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
                 const int m = mrow + i * 16;
-                if (m >= M) continue;
+                if (m >= MP) continue;
 #pragma unroll
                 for (int j = 0; j < TN; ++j) {
                     const int n0 = ncol + j * 16;
                     if (n0 >= N) continue;
-                    *reinterpret_cast<float4*>(ws + ((size_t)z * M + m) * N + n0) =
+                    *reinterpret_cast<float4*>(ws + ((size_t)z * M + slab0 + m) * N + n0) =
                         make_float4(acc[i][j][0], acc[i][j][1], acc[i][j][2], acc[i][j][3]);
                 }
             }
             return;
         }
+        if constexpr (UP) return;               // (unsplit A_CONV2UP items always leave through epilogue_staged: gemm_upconv_phases_supported)
         if (E.act == ACT_GEGLU) {
             if constexpr (TN % 2 == 0) {
                 float4 bv[TN / 2], bg[TN / 2];
@@ -1333,6 +1353,8 @@ gemm_u_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Epilo
                 return true;
             }
         }
+        int up_py = 0, up_px = 0;                              // (UP) output phase of the tile; tm becomes its row tile inside the phase
+        if constexpr (UP) { const int ph = tm / TPP; tm -= ph * TPP; up_py = ph >> 1; up_px = ph & 1; }
         const int mrow = tm * BM + wm * TM * 16;               // first row of the wave's sub-tile
         const int ncb = tn * BN + wn * WCOLS;                  // first column
         const int rr = lane / LPR, cc = lane - rr * LPR;       // read side: row inside a read instruction, 8-column group
@@ -1353,7 +1375,11 @@ gemm_u_kernel(AOperand A, const bf16* __restrict__ W, int M, int N, int K, Epilo
         auto out_row = [&](int i, int k) {  // output row of read instruction k of fragment row i, or -1
             const int r = k * RPI + rr;
             const int m = mrow + i * 16 + r;
-            if (!(col_ok && r < 16 && m < M)) return -1;
+            if (!(col_ok && r < 16 && m < MP)) return -1;
+            if constexpr (UP) {   // phase row (b Hin + y) Win + x -> output row (b 2 Hin + 2 y + py) 2 Win + 2 x + px (div_rpb divides by Win here)
+                const int q = div_rpb(E, m);
+                return ((2 * q + up_py) * E.up_win + (m - q * E.up_win)) * 2 + up_px;
+            }
             return (AMODE == A_ROWS && E.remap_in) ? (m / E.remap_in) * E.remap_out + (m % E.remap_in) + E.remap_off : m;
         };
         // the residual is prefetched for two fragment rows at a time (register budget); the second pair's loads queue behind
@@ -1598,7 +1624,12 @@ splitk_reduce_kernel(const float* __restrict__ ws, int splits, int M, int N, Epi
 #pragma unroll
                     for (int i = 0; i < 4; ++i) v[i] = bf2f(r.e[i]) + g * v[i];
                 }
-                store_bf16x4(reinterpret_cast<bf16*>(E.out) + (size_t)m * E.ldo + n0, v);
+                int mo = m;
+                if (E.up_win) {   // A_CONV2UP: slab row = phase * (M / 4) + phase row; see epilogue_staged of gemm_u_kernel
+                    const int mp = M >> 2, ph = m / mp, r = m - ph * mp, q = div_rpb(E, r);
+                    mo = ((2 * q + (ph >> 1)) * E.up_win + (r - q * E.up_win)) * 2 + (ph & 1);
+                }
+                store_bf16x4(reinterpret_cast<bf16*>(E.out) + (size_t)mo * E.ldo + n0, v);
             } else {
                 epi_finish4(E, m, n0, v);
             }
@@ -2494,6 +2525,7 @@ int exec_u(const Launch& l, const GemmPlan& p) {   // 2 x 2 waves (WMW = 2) on a
         else return l.run<gemm_u_kernel<2, TM, TN, A_ROWS, 2, true>>(p.grid, 256, lds, p.work);
     }
     if (p.amode == A_ROWS) return l.run<gemm_u_kernel<2, TM, TN, A_ROWS, 2>>(p.grid, 256, lds, p.work);
+    if (p.amode == A_CONV2UP) return l.run<gemm_u_kernel<2, TM, TN, A_CONV2UP, 2>>(p.grid, 256, lds, p.work);
     return l.run<gemm_u_kernel<2, TM, TN, A_CONV3, 2>>(p.grid, 256, lds, p.work);
 }
 // (the halo and wide kernels always need more than 48 KiB of LDS: launch_lds sets their attribute as unconditionally as before)

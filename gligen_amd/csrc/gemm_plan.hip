@@ -44,10 +44,12 @@ bool gemm_supports_qkv() { return gemm_knobs().variant == 4; }   // the v5 famil
 // v5 addresses both operands through 32-bit buffer offsets: every operand must be < 2 GiB. The rows of the activation tensor: M for
 // row operands and for same-size stride-1 convs (M = B Ho Wo), the source pixels for strided / upsampling convs.
 static size_t a_rows(const AOperand& A, int M) {
-    return A.mode == A_CONV3 && A.Ho * A.Wo > 0 ? (size_t)(M / (A.Ho * A.Wo)) * A.Hin * A.Win : (size_t)M;
+    return A.mode != A_ROWS && A.Ho * A.Wo > 0 ? (size_t)(M / (A.Ho * A.Wo)) * A.Hin * A.Win : (size_t)M;
 }
+// row tiles of `bm` rows: A_CONV2UP tiles each of its four phases on its own
+static int row_tiles(const AOperand& A, int M, int bm) { return A.mode == A_CONV2UP ? 4 * cdiv(M / 4, bm) : cdiv(M, bm); }
 static bool fits_buffer_offsets(const AOperand& A, int M, int N, int K) {
-    return a_rows(A, M) * (size_t)std::max(A.ld0, A.ld1) * 2 < 0x7fff0000ull && (size_t)N * K * 2 < 0x7fff0000ull;
+    return a_rows(A, M) * (size_t)std::max(A.ld0, A.ld1) * 2 < 0x7fff0000ull && (size_t)N * K * 2 * (A.mode == A_CONV2UP ? 4 : 1) < 0x7fff0000ull;
 }
 
 static inline int ilog2_exact(int v) {
@@ -81,6 +83,8 @@ static bool wide_eligible(const AOperand& A, int M, int N, int K, const Epilogue
 // The kernel family a (valid) problem goes to. honour_force = false: as if no gemm_force_cfg override were set.
 static int gemm_route(const AOperand& A, int M, int N, int K, const Epilogue& E, bool honour_force = true) {
     const GemmKnobs& kn = gemm_knobs();
+    // the phase form of the upsample convs exists in gemm_u_kernel only, narrow outputs included (gemm_validate refuses every other family)
+    if (A.mode == A_CONV2UP) return kn.variant == 4 && fits_buffer_offsets(A, M, N, K) ? GEMM_U : GEMM_P;
     // gemm_glds_kernel: narrow outputs, and everything under variant 1
     if (kn.variant < 2 || (N < 128 && E.act != ACT_GEGLU)) return GEMM_GLDS;
     // v5's epilogue has no bias2 + residual form, and the per-sample bias only in its conv instantiations
@@ -103,6 +107,14 @@ bool gemm_gn_prologue_supported(const AOperand& A, int M, int N, int K, const Ep
     return K % 64 == 0 && gemm_route(A, M, N, K, E) == GEMM_HALO && (A.Hin * A.Win) % 256 == 0;
 }
 
+// A_CONV2UP: gemm_u_kernel with the staged row-major epilogue (or fp32 slabs + splitk_reduce_kernel): bias only, bf16 out
+bool gemm_upconv_phases_supported(const AOperand& A, int M, int N, int K, const Epilogue& E) {
+    if (A.mode != A_CONV2UP || M <= 0 || M != 4 * (M / (4 * A.Hin * A.Win)) * A.Hin * A.Win || A.Ho != 2 * A.Hin || A.Wo != 2 * A.Win) return false;
+    if ((A.C0 + A.C1) % 64 || A.C0 % 64 || K != 4 * (A.C0 + A.C1) || N % 8 || A.gn) return false;
+    if (E.mode != EPI_ROWMAJOR || E.act != ACT_NONE || E.out_f32 || E.bias2 || E.res || E.gate || E.remap_in || E.stats_out || E.ln_stats) return false;
+    return gemm_route(A, M, N, K, E) == GEMM_U;
+}
+
 // Can a GEMM with this epilogue consume raw rows + row statistics instead of LayerNorm'ed rows (Epilogue::ln_stats)?
 // The head-layout epilogues of gemm_u_kernel and the GEGLU epilogue of gemm_wide_kernel apply them. Looser than the launcher in two
 // cases, kept as they are: a gemm_force_cfg override is not looked at (under one the launcher leaves the wide kernel), nor is a
@@ -120,7 +132,8 @@ bool gemm_ln_fold_supported(const AOperand& A, int M, int N, int K, const Epilog
 static int gemm_validate(const AOperand& A, int M, int N, int K, Epilogue& E) {
     if (E.rows_per_b < 1) return set_error(GL_ERR_ARG, "gemm: rows_per_b=%d", E.rows_per_b);
     {   // divide-free m / rows_per_b for the epilogues (div_rpb)
-        const unsigned d = (unsigned)E.rows_per_b;
+        E.up_win = A.mode == A_CONV2UP ? A.Win : 0;
+        const unsigned d = E.up_win ? (unsigned)E.up_win : (unsigned)E.rows_per_b;   // (A_CONV2UP has no per-sample bias: its epilogue divides by Win)
         int sh = 0;
         while ((1ull << sh) < d) ++sh;
         E.rpb_shift = sh;
@@ -133,14 +146,17 @@ static int gemm_validate(const AOperand& A, int M, int N, int K, Epilogue& E) {
     if (N % 4 != 0) return set_error(GL_ERR_ARG, "gemm: N=%d must be a multiple of 4", N);
     if (A.gn && !gemm_gn_prologue_supported(A, M, N, K, E))
         return set_error(GL_ERR_UNSUPPORTED, "gemm: the GroupNorm prologue (AOperand::gn) exists in conv_halo_kernel only (3x3, stride 1, H W %% 256 == 0)");
-    if (A.mode == A_CONV3) {
+    if (A.mode == A_CONV2UP) {
+        if (!gemm_upconv_phases_supported(A, M, N, K, E))
+            return set_error(GL_ERR_UNSUPPORTED, "conv3x3: no phase form of the upsample conv for this launch (gemm_u_kernel, bias-only bf16 epilogue, K = 4 Cin, N %% 8 == 0)");
+    } else if (A.mode == A_CONV3) {
         if ((A.C0 + A.C1) % 64 != 0 || A.C0 % 64 != 0 || K != 9 * (A.C0 + A.C1))
             return set_error(GL_ERR_ARG, "conv3x3: channels (%d,%d) must be multiples of 64 and K=9*Cin (K=%d)", A.C0, A.C1, K);
     } else {
         if (K != A.C0 + A.C1 || (A.C1 && A.C0 % 64 != 0))
             return set_error(GL_ERR_ARG, "gemm: K=%d does not match operand channels (%d,%d)", K, A.C0, A.C1);
     }
-    if (A.mode == A_CONV3 && (E.gate || E.remap_in))
+    if (A.mode != A_ROWS && (E.gate || E.remap_in))
         return set_error(GL_ERR_UNSUPPORTED, "conv3x3: the gated residual and the row remap are row-GEMM epilogues");
     if ((E.act == ACT_GELU || E.act == ACT_QUICK_GELU) && (E.res || E.bias2 || A.mode != A_ROWS))
         return set_error(GL_ERR_UNSUPPORTED, "gemm: the GELU / quick-GELU epilogues have no residual / broadcast-bias form");
@@ -299,7 +315,7 @@ static bool model_choice(const GemmProblem& pb, bool use_u, GemmCand& out) {
     out = GemmCand{-1, 1, 0};
     for (int c = 0; c < 4; ++c) {   // (the analytic model was fitted without the 64 x 64 candidate: the autotuner alone may pick it)
         const int bm = kGemmTm[c] * 32, bn = kGemmTn[c] * 32;
-        const int tiles = cdiv(M, bm) * cdiv(N, bn);
+        const int tiles = row_tiles(pb.A, M, bm) * cdiv(N, bn);
         for (int si = 0; si < 10; ++si) {
             int sp = kSp[si];
             if (!feasible(pb, use_u, c, sp)) continue;
@@ -324,7 +340,7 @@ std::vector<GemmCand> gemm_tune_candidates(const GemmProblem& pb, bool use_u) {
     const bool corun = gemm_knobs().corun;
     std::vector<GemmCand> out;
     for (int c = 0; c < kGemmTiles; ++c) {
-        const int tiles = cdiv(M, kGemmTm[c] * 32) * cdiv(N, kGemmTn[c] * 32);
+        const int tiles = row_tiles(pb.A, M, kGemmTm[c] * 32) * cdiv(N, kGemmTn[c] * 32);
         if (c == 4 && ((size_t)M * N > ((size_t)1 << 23) || N % 64)) continue;   // small problems only (M N <= 8 M outputs: 2048 x 3840, 8192 x 640 ..)
         int last_sp = -1;
         for (int si = 0; si < 10; ++si) {
@@ -354,11 +370,11 @@ int gemm_plan_tile(const GemmProblem& pb, bool use_u, const GemmCand& cand, Gemm
     wd.tiles_n = cdiv(N, tn * 32);
     wd.kt_per_split = cdiv(nk, cand.sp);
     wd.splits = cdiv(nk, wd.kt_per_split);
-    wd.n_items = cdiv(M, tm * 32) * wd.tiles_n * wd.splits;
+    wd.n_items = row_tiles(A, M, tm * 32) * wd.tiles_n * wd.splits;
     wd.box = -1; wd.rm = 0; wd.rz = wd.splits;
     if (use_u && gemm_knobs().xcd_boxes) {
         // fabric-side bytes ~ A_bytes * (#N bands) + W_bytes * (#M bands); only exact partitions (all boxes equal)
-        const int tiles_m = cdiv(M, tm * 32), tiles_n = wd.tiles_n;
+        const int tiles_m = row_tiles(A, M, tm * 32), tiles_n = wd.tiles_n;
         const double a_bytes = (double)a_rows(A, M) * (A.C0 + A.C1) * 2, w_bytes = (double)N * K * 2;
         double best = 1e300;
         for (int lgm = 3; lgm >= 0; --lgm)

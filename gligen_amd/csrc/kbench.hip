@@ -440,7 +440,46 @@ int main(int argc, char** argv) {
             E.out = a2; E.ldo = Cout; E.bias = bias; E.bias2 = gam; E.bias2_ld = Cout; E.rows_per_b = Ho * Wo;
             if (Cout == 32) { E.mode = EPI_NCHW_F32; E.n_real = 4; E.bias2 = nullptr; }
             relaunch = [=] { GC(gemm_launch(A, w, M, Cout, K, E, cur_s == s ? ws : ws2, ws_bytes, cur_s)); };
-            us = time_us(relaunch, reps, s);
+            if (stride == 1 && ups == 1 && !C1 && Cout != 32 && (size_t)C0 * Cout <= (size_t)1280 * 1280) {
+                // The conv behind a nearest-2x Upsample (reference openaimodel.py:54-82; bias only, as the engine launches it), both forms
+                // from one fp32 filter: the shape's own line is the nine-tap loader with the replication as a view, the UPCONV line
+                // behind it the four 2x2 phase convs (gemm.h A_CONV2UP); outputs compared
+                static float* wf = nullptr;
+                static bf16 *w9 = nullptr, *w4 = nullptr;
+                if (!wf) {
+                    wf = dev_f32((size_t)9 * 1280 * 1280, 31, 0.02f);
+                    HC(hipMalloc(&w9, (size_t)9 * 1280 * 1280 * 2));
+                    HC(hipMalloc(&w4, (size_t)16 * 1280 * 1280 * 2));
+                    HC(hipDeviceSynchronize());
+                }
+                GC(pack_conv_weight_launch(wf, w9, Cout, C0, 3, 3, Cout, s));
+                GC(pack_upconv_phases_launch(wf, w4, Cout, C0, Cout, s));
+                E.bias2 = nullptr;
+                const bf16* w9c = w9;
+                relaunch = [=] { GC(gemm_launch(A, w9c, M, Cout, K, E, cur_s == s ? ws : ws2, ws_bytes, cur_s)); };
+                AOperand A4 = A;
+                A4.mode = A_CONV2UP; A4.ups = 0;
+                Epilogue E4 = E;
+                E4.out = a1;
+                if (gemm_upconv_phases_supported(A4, M, Cout, 4 * C0, E4)) {
+                    const bf16* w4c = w4;
+                    auto phases = [=] { GC(gemm_launch(A4, w4c, M, Cout, 4 * C0, E4, cur_s == s ? ws : ws2, ws_bytes, cur_s)); };
+                    const float us4 = time_us(phases, reps, s);
+                    int ptm, ptn, psp;
+                    gemm_last_cfg(&ptm, &ptn, &psp);
+                    us = time_us(relaunch, reps, s);
+                    float d, m;
+                    maxdiff(a2, a1, (size_t)M * Cout, s, &d, &m);
+                    const bool ok = d <= 0.02f * m + 1e-6f;
+                    if (!ok) ++n_bad;
+                    printf("UPCONV %-51s %9.1f %9.1f  phase form %dx%d/%d (nine-tap FLOP rate; %.2fx of the nine-tap %.1f us) maxdiff %g of %g %s\n", line, us4,
+                           flop / us4 * 1e-6, ptm * 32, ptn * 32, psp, us4 / us, us, d, m, ok ? "ok" : "MISMATCH");
+                } else {
+                    us = time_us(relaunch, reps, s);
+                }
+            } else {
+                us = time_us(relaunch, reps, s);
+            }
         } else if (!strcmp(kind, "gnconv")) {
             // GroupNorm32 -> SiLU -> conv3x3 (reference openaimodel.py:212-232): "gnconv B H W C0 C1 Cout count". Two forms on the same
             // buffers: GroupNorm + SiLU as its own pass (stats + apply) in front of the conv, and statistics + coefficients with the

@@ -50,6 +50,8 @@ int pad_rows_bf16_launch(const bf16* src, bf16* dst, int B, int rows, int rows_p
 int set_f32_launch(float* dst, float v, hipStream_t stream);
 // conv weight OIHW fp32 -> [O_pad][kh*kw][I] bf16 (K-major: k = tap*I + c), rows >= O zero
 int pack_conv_weight_launch(const float* src, bf16* dst, int O, int I, int KH, int KW, int O_pad, hipStream_t stream);
+// fp32 OIHW 3x3 -> the four folded 2x2 filters of the upsample conv's phase form, [4][O_pad][4 I] bf16 (gemm.h A_CONV2UP)
+int pack_upconv_phases_launch(const float* src, bf16* dst, int O, int I, int O_pad, hipStream_t stream);
 // small-Cin conv weight OIHW fp32 -> [O][Kpad] bf16 with k = tap*I + c
 // I_src (0 = I): input channels of the source weight when it has fewer than the packed layout (extra channels get zeros)
 int pack_conv_small_launch(const float* src, bf16* dst, int O, int I, int Kpad, hipStream_t stream, int I_src = 0);

@@ -205,6 +205,41 @@ int pack_conv_weight_launch(const float* src, bf16* dst, int O, int I, int KH, i
     return GL_OK;
 }
 
+// Folded filters of the phase form of nearest-2x upsample + 3x3 conv (gemm.h A_CONV2UP): fp32 OIHW 3x3 -> [4 phases p = 2 py + px][O_pad][4 I] bf16,
+// k = (2 a + b) I + c for source tap (a, b). Row tap a of phase py sums the filter rows that read the same source row after the
+// replication -- py = 0: a = 0 <- {ky 0}, a = 1 <- {ky 1, 2}; py = 1: a = 0 <- {ky 0, 1}, a = 1 <- {ky 2} -- and column tap b of px the
+// filter columns alike. The (up to four) terms are added in fp32 in the order ky ascending, kx ascending inside, starting from the first
+// term, and the sum is rounded to bf16 once.
+__global__ void pack_upconv_phases_kernel(const float* __restrict__ s, bf16* __restrict__ d, int O, int I, int O_pad) {
+    const int64_t total = (int64_t)4 * O_pad * 4 * I;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (int64_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % I);
+        const int64_t r = i / I;
+        const int tap = (int)(r & 3);
+        const int o = (int)((r >> 2) % O_pad);
+        const int p = (int)((r >> 2) / O_pad);
+        const int py = p >> 1, px = p & 1, a = tap >> 1, b = tap & 1;
+        const int ky0 = a == 0 ? 0 : py == 0 ? 1 : 2, ky1 = a == 0 ? py : 2;
+        const int kx0 = b == 0 ? 0 : px == 0 ? 1 : 2, kx1 = b == 0 ? px : 2;
+        float sum = 0.f;
+        if (o < O) {
+            const float* w = s + ((size_t)o * I + c) * 9;
+            bool first = true;
+            for (int ky = ky0; ky <= ky1; ++ky)
+                for (int kx = kx0; kx <= kx1; ++kx) {
+                    sum = first ? w[ky * 3 + kx] : sum + w[ky * 3 + kx];
+                    first = false;
+                }
+        }
+        d[i] = f2bf(sum);
+    }
+}
+int pack_upconv_phases_launch(const float* src, bf16* dst, int O, int I, int O_pad, hipStream_t stream) {
+    hipLaunchKernelGGL(pack_upconv_phases_kernel, dim3(grid_for((int64_t)16 * O_pad * I)), dim3(256), 0, stream, src, dst, O, I, O_pad);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
 // I_src <= I: the source weight has fewer input channels than the packed layout (the SD first conv restored into a
 // 4 + k channel GLIGEN first conv); the missing channels get zero weights
 __global__ void pack_conv_small_kernel(const float* __restrict__ s, bf16* __restrict__ d, int O, int I, int I_src, int Kpad) {
