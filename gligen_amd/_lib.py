@@ -1,4 +1,5 @@
-"""ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h and include/gligen_amd_maps.h).
+"""ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
+include/gligen_amd_train_maps.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -81,6 +82,11 @@ class TrainUNetIn(C.Structure):   # = gl_train_unet_in
 class TrainSpatialIn(C.Structure):   # = gl_train_spatial_in
     _fields_ = [("map", C.c_void_p)] + [(n, C.c_int) for n in ("map_channels", "map_h", "map_w")] + [("mask", C.c_void_p), ("extra", C.c_void_p)] + \
                [(n, C.c_int) for n in ("extra_in_channels", "extra_h", "extra_w", "ds_resize", "ds_mode", "ds_n_in", "ds_mid")]
+
+
+class TrainSpatialClassesIn(C.Structure):   # = gl_train_spatial_classes_in
+    _fields_ = [("map", C.c_void_p), ("map_h", C.c_int), ("map_w", C.c_int), ("mask", C.c_void_p), ("extra", C.c_void_p)] + \
+               [(n, C.c_int) for n in ("extra_h", "extra_w", "ds_resize", "ds_mode", "ds_n_in", "ds_mid")]
 
 
 class BoxCalibration(C.Structure):   # = gl_box_calibration
@@ -175,6 +181,13 @@ MAP_SYMBOLS = {
     "gl_op_grounding_downsample_classes": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _I, _P, _P, _I, _P, _P]),
 }
 
+# every symbol include/gligen_amd_train_maps.h declares (training from class maps)
+TRAIN_MAP_SYMBOLS = {
+    "gl_unet_train_step_spatial_classes": (_I, [_P, C.POINTER(UNetConfig), C.POINTER(TrainUNetIn), C.POINTER(TrainSpatialClassesIn), _I, C.POINTER(C.c_char_p),
+                                                C.POINTER(_P), C.POINTER(_P), _P, _P, _P]),
+    "gl_op_class_conv_wgrad": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
+}
+
 _lib = None
 
 
@@ -192,7 +205,7 @@ def load() -> C.CDLL:
     # torch.cuda.is_available() is True) -- seen with build() called before the first `import torch` of the process.
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -3,6 +3,7 @@
 #include "engine_impl.h"
 #include "image.h"
 #include "train.h"
+#include "../../include/gligen_amd_train_maps.h"
 
 #include <cstdlib>
 
@@ -818,24 +819,26 @@ int gl_unet_train_step(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_un
     GL_API_END
 }
 
-int gl_unet_train_step_spatial(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, const gl_train_spatial_in* sp, int n_params,
-                               const char* const* names, const float* const* params, float* const* grads, float* eps_out, float* loss, gl_stream s) {
+// gl_unet_train_step_spatial and gl_unet_train_step_spatial_classes: `spi` holds the planes or the class maps
+static int train_step_spatial(const char* what, gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, const gl::TrainSpatialIn& spi, int n_params,
+                              const char* const* names, const float* const* params, float* const* grads, float* eps_out, float* loss, gl_stream s) {
     NEED(ctx);
-    if (!cfg || !in || !sp || !names || !params || !grads || !loss || n_params <= 0) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial: null pointer");
+    if (!cfg || !in || !names || !params || !grads || !loss || n_params <= 0) return gl::set_error(GL_ERR_ARG, "%s: null pointer", what);
     if (cfg->inpaint_mode)
-        return gl::set_error(GL_ERR_UNSUPPORTED, "gl_unet_train_step_spatial: training an inpainting model (9-channel first conv) is not built");
+        return gl::set_error(GL_ERR_UNSUPPORTED, "%s: training an inpainting model (9-channel first conv) is not built", what);
     if (cfg->grounding_kind != 3 || cfg->fuser_kind != 0)
-        return gl::set_error(GL_ERR_UNSUPPORTED, "gl_unet_train_step_spatial: built for a spatial-map tokenizer (grounding_kind 3) with gatedSA fusers");
+        return gl::set_error(GL_ERR_UNSUPPORTED, "%s: built for a spatial-map tokenizer (grounding_kind 3) with gatedSA fusers", what);
     if (cfg->tok_resize < 32 || cfg->tok_resize % 32 || cfg->extra_channels < 0)
-        return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial: tok_resize must be a positive multiple of 32");
+        return gl::set_error(GL_ERR_ARG, "%s: tok_resize must be a positive multiple of 32", what);
     if (in->boxes || in->masks || in->positive_embeddings || in->text_masks || in->image_masks || in->image_embeddings)
-        return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial: the box / embedding inputs of gl_train_unet_in are NULL for a spatial-map model");
-    if (!in->x || !in->timesteps || !in->context || !in->target || !sp->map || !sp->mask || ((cfg->extra_channels > 0) != (sp->extra != nullptr)))
-        return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial: null input (grounding_extra_input is given iff extra_channels > 0)");
+        return gl::set_error(GL_ERR_ARG, "%s: the box / embedding inputs of gl_train_unet_in are NULL for a spatial-map model", what);
+    const bool has_map = spi.map || spi.map_cls, has_extra = spi.extra || spi.extra_cls;
+    if (!in->x || !in->timesteps || !in->context || !in->target || !has_map || !spi.mask || ((cfg->extra_channels > 0) != has_extra))
+        return gl::set_error(GL_ERR_ARG, "%s: null input (grounding_extra_input is given iff extra_channels > 0)", what);
     const int Ng = (cfg->tok_resize / 32) * (cfg->tok_resize / 32);
-    if (in->Ng != Ng) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial: Ng = %d, the tokenizer makes (tok_resize / 32)^2 = %d tokens", in->Ng, Ng);
+    if (in->Ng != Ng) return gl::set_error(GL_ERR_ARG, "%s: Ng = %d, the tokenizer makes (tok_resize / 32)^2 = %d tokens", what, in->Ng, Ng);
     if (cfg->gr_out_dim != cfg->context_dim)
-        return gl::set_error(GL_ERR_UNSUPPORTED, "gl_unet_train_step_spatial: grounding out dim and context_dim are expected to be equal (768 in every shipped config)");
+        return gl::set_error(GL_ERR_UNSUPPORTED, "%s: grounding out dim and context_dim are expected to be equal (768 in every shipped config)", what);
     GL_API_BEGIN
     Engine& eng = *ctx->eng;
     eng.arena().reset();
@@ -846,12 +849,49 @@ int gl_unet_train_step_spatial(gl_ctx* ctx, const gl_unet_config* cfg, const gl_
     c.extra_channels = cfg->extra_channels; c.tok_resize = cfg->tok_resize; c.tok_in_dim = cfg->tok_in_dim;
     gl::TrainUNetIn u{in->B, in->H, in->W, in->ctx_T, Ng, Ng, in->x, in->timesteps, in->context, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                       in->target, in->fuser_scale, in->checkpoint};
-    gl::TrainSpatialIn spi{sp->map, sp->map_channels, sp->map_h, sp->map_w, sp->mask, sp->extra, sp->extra_in_channels, sp->extra_h, sp->extra_w,
-                           sp->ds_resize, sp->ds_mode, sp->ds_n_in, sp->ds_mid};
     int rc = gl::unet_train_step(eng.arena(), eng.splitk_ws(), eng.splitk_ws_bytes(), c, u, n_params, names, params, grads, k_train_block_names, eps_out, loss, S(s),
                                  eng.train_events(), Engine::kTrainEvents, in->use_weight_cache ? eng.train_cache : nullptr, &spi);
     if (rc != GL_OK) throw GlError(rc, gl::last_error());
     eng.train_events_recorded = true;
+    GL_API_END
+}
+
+int gl_unet_train_step_spatial(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, const gl_train_spatial_in* sp, int n_params,
+                               const char* const* names, const float* const* params, float* const* grads, float* eps_out, float* loss, gl_stream s) {
+    if (!sp) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial: null pointer");
+    gl::TrainSpatialIn spi{sp->map, sp->map_channels, sp->map_h, sp->map_w, sp->mask, sp->extra, sp->extra_in_channels, sp->extra_h, sp->extra_w,
+                           sp->ds_resize, sp->ds_mode, sp->ds_n_in, sp->ds_mid};
+    return train_step_spatial("gl_unet_train_step_spatial", ctx, cfg, in, spi, n_params, names, params, grads, eps_out, loss, s);
+}
+
+// ---- include/gligen_amd_train_maps.h: the same iteration from u8 class maps, and its weight-gradient operator
+int gl_unet_train_step_spatial_classes(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, const gl_train_spatial_classes_in* sp,
+                                       int n_params, const char* const* names, const float* const* params, float* const* grads, float* eps_out,
+                                       float* loss, gl_stream s) {
+    if (!sp) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial_classes: null pointer");
+    if (!sp->map || !sp->extra)
+        return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial_classes: the tokenizer's map and grounding_extra_input are both u8 class maps here; one is NULL");
+    gl::TrainSpatialIn spi{nullptr, 0, sp->map_h, sp->map_w, sp->mask, nullptr, 0, sp->extra_h, sp->extra_w, sp->ds_resize, sp->ds_mode, sp->ds_n_in, sp->ds_mid};
+    spi.map_cls = sp->map;
+    spi.extra_cls = sp->extra;
+    return train_step_spatial("gl_unet_train_step_spatial_classes", ctx, cfg, in, spi, n_params, names, params, grads, eps_out, loss, s);
+}
+
+int gl_op_class_conv_wgrad(gl_ctx* ctx, int kind, const uint8_t* cls, int B, int H, int W, int n_classes, int R, const float* dy, int c_out,
+                           float* dW, float* db, gl_stream s) {
+    NEED(ctx);
+    if (!cls || !dy || (!dW && !db)) return gl::set_error(GL_ERR_ARG, "gl_op_class_conv_wgrad: null class map / dy, or neither gradient asked for");
+    GL_API_BEGIN
+    size_t n = 0;
+    GL_TRY(class_conv_wgrad_partial_floats(kind, B, H, W, n_classes, c_out, R, &n));
+    gl::Arena& ar = ctx->eng->arena();
+    const size_t mk = ar.mark();
+    float* part = ar.get<float>(n);
+    const size_t Ro = kind == kClassWgradDown ? R / 2 : R;
+    const int rc = class_conv_wgrad_launch(kind, cls, dy, {(size_t)c_out * Ro * Ro, Ro * Ro, Ro, 1}, part, dW, db, B, H, W, n_classes, c_out, R, S(s));
+    ar.release(mk);      // stream-ordered reuse, as every operator's workspace
+    if (rc != GL_OK) return rc;
+    ctx->eng->n_launches += 2;
     GL_API_END
 }
 

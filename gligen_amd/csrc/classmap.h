@@ -48,4 +48,17 @@ int class_conv_weight_relayout_launch(const float* w, float* g, int c_out, int n
 int class_conv4x4s2_launch(const uint8_t* cls, const float* g, const float* bias, float* y, int B, int H, int W, int n_classes, int c_out, int R, int silu,
                            hipStream_t stream);
 
+// Weight and bias gradient of the two convs above, from the class map: with cls' the map seen through the nearest resize to R,
+//   dW[o][c][ky][kx] = sum over (b, y, x) of [cls'(b, s y + ky - 1, s x + kx - 1) == c] dy[b][o][y][x],   db[o] = sum of dy[b][o][y][x]
+// A tap in the padding or on a class >= n_classes adds nothing. kind: kClassWgradInConv (3 x 3, stride 1, c_out = 3) or kClassWgradDown
+// (4 x 4, stride 2, c_out a multiple of 4, R even). dy: fp32, element (b, o, y, x) at the given strides (NCHW or pixel rows); dW fp32
+// [c_out][n_classes][k][k] and db [c_out], either may be null. part: class_conv_wgrad_partial_floats floats of workspace. Two launches,
+// no atomics: per-tile partials are added in tile order, so the result has the same bits every run.
+constexpr int kClassWgradInConv = 0, kClassWgradDown = 1;
+constexpr int kClassWgradMaxOut = 4096;
+struct ClassDyStrides { size_t b, c, y, x; };
+int class_conv_wgrad_partial_floats(int kind, int B, int H, int W, int n_classes, int c_out, int R, size_t* n);
+int class_conv_wgrad_launch(int kind, const uint8_t* cls, const float* dy, ClassDyStrides ds, float* part, float* dW, float* db, int B, int H, int W, int n_classes,
+                            int c_out, int R, hipStream_t stream);
+
 }  // namespace gl

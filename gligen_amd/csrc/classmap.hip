@@ -1,6 +1,7 @@
 // Semantic maps as class indices (see classmap.h): Pillow's crop + nearest resize of u8 class maps, and the two convolutions that
 // read one-hot planes -- the tokenizer's in_conv and the downsampler's first conv -- as gathers of one weight per tap, fused with
-// the nearest resize in front of them. Once per prompt: plain latency-bound kernels, a thread per output pixel.
+// the nearest resize in front of them. Once per prompt: plain latency-bound kernels, a thread per output pixel. For training, the
+// weight gradients of the same two convs as sums of dy binned by the class under each tap, in a fixed order.
 #include "classmap.h"
 
 #include <algorithm>
@@ -206,6 +207,104 @@ __global__ __launch_bounds__(256) void class_conv4x4s2_kernel(const uint8_t* __r
     }
 }
 
+// ---- weight gradients of the two convs. dW[o][c][tap] is dy binned by the class under each tap, so nothing is multiplied by a zero
+// plane: a workgroup stages one 16 x 16 tile of output pixels -- its dy values and the u16 class patch under it, 0xffff in the padding --
+// and thread (tap, class lane) holds NB classes x CO channels of bins in registers. It walks the tile's pixels in ascending order, reads
+// the class under its tap and adds dy to the bin of that class. A workgroup takes `tpb` consecutive tiles and writes one partial
+// [bins][c_out] | bias [c_out]; class_conv_wgrad_reduce_kernel adds the partials in ascending order. No atomics: the same bits every run.
+constexpr int kWgTile = 16;
+
+template <int K, int S, int CO, int NB>
+__global__ __launch_bounds__(256) void class_conv_wgrad_kernel(const uint8_t* __restrict__ cls, const float* __restrict__ dy, ClassDyStrides ds,
+                                                               float* __restrict__ part, int H, int W, int n_classes, int c_out, int R, int Ro, int tiles_side,
+                                                               int n_tiles, int tpb) {
+    constexpr int T = K * K, CL = 256 / T, TS = kWgTile, PS = S * (TS - 1) + K;
+    __shared__ uint16_t patch[PS * PS];
+    __shared__ float dyl[TS * TS * CO];
+    const int tid = threadIdx.x;
+    const int tap = tid % T, cl = tid / T, ky = tap / K, kx = tap - ky * K;
+    const int c0 = (int)blockIdx.y * (CL * NB) + cl;      // this thread's classes: c0 + j CL
+    const int o0 = (int)blockIdx.z * CO;
+    const float sy = (float)H / (float)R, sx = (float)W / (float)R;
+    float acc[NB][CO], bacc[CO];
+#pragma unroll
+    for (int o = 0; o < CO; ++o) {
+        bacc[o] = 0.f;
+#pragma unroll
+        for (int j = 0; j < NB; ++j) acc[j][o] = 0.f;
+    }
+    const int t_end = min(n_tiles, ((int)blockIdx.x + 1) * tpb);
+    for (int tile = (int)blockIdx.x * tpb; tile < t_end; ++tile) {
+        const int b = tile / (tiles_side * tiles_side), tr = tile - b * tiles_side * tiles_side;
+        const int y0 = (tr / tiles_side) * TS, x0 = (tr % tiles_side) * TS;
+        const uint8_t* __restrict__ src = cls + (size_t)b * H * W;
+        __syncthreads();      // the tile before has been read
+        for (int i = tid; i < PS * PS; i += 256) {
+            const int pr = i / PS, pc = i - pr * PS;
+            const int iy = nearest_src(S * y0 - 1 + pr, R, sy, H), ix = nearest_src(S * x0 - 1 + pc, R, sx, W);
+            patch[i] = (iy >= 0 && ix >= 0) ? (uint16_t)src[(size_t)iy * W + ix] : (uint16_t)0xffff;
+        }
+        for (int i = tid; i < TS * TS * CO; i += 256) {
+            const int o = i / (TS * TS), p = i - o * (TS * TS);
+            const int oy = y0 + p / TS, ox = x0 + p % TS;
+            dyl[p * CO + o] = (oy < Ro && ox < Ro) ? dy[(size_t)b * ds.b + (size_t)(o0 + o) * ds.c + (size_t)oy * ds.y + (size_t)ox * ds.x] : 0.f;
+        }
+        __syncthreads();
+        const int nh = min(TS, Ro - y0), nw = min(TS, Ro - x0);
+        for (int py = 0; py < nh; ++py) {
+            const uint16_t* __restrict__ prow = patch + (S * py + ky) * PS + kx;
+            const float* __restrict__ drow = dyl + py * TS * CO;
+            for (int px = 0; px < nw; ++px) {
+                const int dc = (int)prow[S * px] - c0;
+                float d[CO];
+#pragma unroll
+                for (int o = 0; o < CO; ++o) {
+                    d[o] = drow[px * CO + o];
+                    bacc[o] += d[o];
+                }
+#pragma unroll
+                for (int j = 0; j < NB; ++j) {
+                    const float m = dc == j * CL ? 1.f : 0.f;      // 1 * d + acc is acc + d exactly
+#pragma unroll
+                    for (int o = 0; o < CO; ++o) acc[j][o] = fmaf(m, d[o], acc[j][o]);
+                }
+            }
+        }
+    }
+    float* __restrict__ po = part + (size_t)blockIdx.x * ((size_t)n_classes * T + 1) * c_out;
+    if (cl < CL) {
+#pragma unroll
+        for (int j = 0; j < NB; ++j) {
+            const int c = c0 + j * CL;
+            if (c < n_classes) {
+#pragma unroll
+                for (int o = 0; o < CO; ++o) po[((size_t)c * T + tap) * c_out + o0 + o] = acc[j][o];
+            }
+        }
+    }
+    if (tid == 0 && blockIdx.y == 0) {
+#pragma unroll
+        for (int o = 0; o < CO; ++o) po[(size_t)n_classes * T * c_out + o0 + o] = bacc[o];
+    }
+}
+
+// part [n_part][E + 1][c_out] (E = n_classes * taps; row E: the bias) -> dW [c_out][E] (OIHW), db [c_out]: partials added in ascending order
+__global__ __launch_bounds__(256) void class_conv_wgrad_reduce_kernel(const float* __restrict__ part, int n_part, int E, int c_out, float* __restrict__ dW,
+                                                                      float* __restrict__ db) {
+    const int total = (E + 1) * c_out;
+    const int i = (int)blockIdx.x * 256 + (int)threadIdx.x;
+    if (i >= total) return;
+    float s = 0.f;
+#pragma unroll 8
+    for (int k = 0; k < n_part; ++k) s += part[(size_t)k * total + i];
+    const int e = i / c_out, o = i - e * c_out;
+    if (e < E) {
+        if (dW) dW[(size_t)o * E + e] = s;
+    } else if (db) {
+        db[o] = s;
+    }
+}
+
 inline int grid_for(int64_t n, int cap) {
     int64_t g = cdiv64(n, 256);
     if (g > cap) g = cap;
@@ -298,6 +397,58 @@ int class_conv4x4s2_launch(const uint8_t* cls, const float* g, const float* bias
     if (reinterpret_cast<uintptr_t>(g) & 15) return set_error(GL_ERR_ARG, "class conv4x4s2: the gather weights must be 16-byte aligned");
     hipLaunchKernelGGL(class_conv4x4s2_kernel, dim3(grid_for((int64_t)B * (c_out / 4) * (R / 2) * (R / 2), 8192)), dim3(256), 0, stream, cls, g, bias, y, B, H, W,
                        n_classes, c_out, R, silu);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
+namespace {
+
+struct WgradPlan { int Ro, tiles_side, n_tiles, tpb, n_part, T; };
+
+int class_conv_wgrad_plan(int kind, const void* cls, int B, int H, int W, int n_classes, int c_out, int R, WgradPlan* p) {
+    const char* what = kind == kClassWgradDown ? "class conv4x4s2 wgrad" : "class in_conv wgrad";
+    if (kind != kClassWgradInConv && kind != kClassWgradDown) return set_error(GL_ERR_ARG, "class conv wgrad: kind %d; 0 (in_conv) or 1 (down) is built", kind);
+    GL_TRY(check_map(what, cls, B, H, W, n_classes, R));
+    if (kind == kClassWgradInConv && c_out != 3) return set_error(GL_ERR_UNSUPPORTED, "%s: %d output channels; in_conv has exactly 3", what, c_out);
+    if (kind == kClassWgradDown && (c_out < 4 || c_out % 4 || c_out > kClassWgradMaxOut))
+        return set_error(GL_ERR_UNSUPPORTED, "%s: %d output channels; a thread holds 4, so a multiple of 4 up to %d is needed", what, c_out, kClassWgradMaxOut);
+    if (kind == kClassWgradDown && (R & 1)) return set_error(GL_ERR_ARG, "%s: odd input size %d", what, R);
+    p->Ro = kind == kClassWgradDown ? R / 2 : R;
+    p->T = kind == kClassWgradDown ? 16 : 9;
+    p->tiles_side = cdiv(p->Ro, kWgTile);
+    const int64_t n_tiles = (int64_t)B * p->tiles_side * p->tiles_side;
+    if (n_tiles > (1 << 30)) return set_error(GL_ERR_UNSUPPORTED, "%s: %lld tiles of %d x %d output pixels; at most 2^30 are indexed", what, (long long)n_tiles, kWgTile, kWgTile);
+    p->n_tiles = (int)n_tiles;
+    p->tpb = cdiv(p->n_tiles, 512);      // a function of the shape alone: the summation order is fixed
+    p->n_part = cdiv(p->n_tiles, p->tpb);
+    return GL_OK;
+}
+
+}  // namespace
+
+int class_conv_wgrad_partial_floats(int kind, int B, int H, int W, int n_classes, int c_out, int R, size_t* n) {
+    WgradPlan p;
+    if (!n) return set_error(GL_ERR_ARG, "class conv wgrad: null size");
+    GL_TRY(class_conv_wgrad_plan(kind, n, B, H, W, n_classes, c_out, R, &p));
+    *n = (size_t)p.n_part * ((size_t)n_classes * p.T + 1) * c_out;
+    return GL_OK;
+}
+
+int class_conv_wgrad_launch(int kind, const uint8_t* cls, const float* dy, ClassDyStrides ds, float* part, float* dW, float* db, int B, int H, int W, int n_classes,
+                            int c_out, int R, hipStream_t stream) {
+    WgradPlan p;
+    GL_TRY(class_conv_wgrad_plan(kind, cls, B, H, W, n_classes, c_out, R, &p));
+    if (!dy || !part || (!dW && !db)) return set_error(GL_ERR_ARG, "class conv wgrad: null dy / partials, or neither gradient asked for");
+    if (kind == kClassWgradInConv) {      // 28 class lanes x 6 classes per workgroup, the 3 output channels
+        hipLaunchKernelGGL((class_conv_wgrad_kernel<3, 1, 3, 6>), dim3(p.n_part, cdiv(n_classes, 28 * 6), 1), dim3(256), 0, stream, cls, dy, ds, part, H, W, n_classes, c_out, R, p.Ro,
+                           p.tiles_side, p.n_tiles, p.tpb);
+    } else {                              // 16 class lanes x 6 classes per workgroup, 4 output channels
+        hipLaunchKernelGGL((class_conv_wgrad_kernel<4, 2, 4, 6>), dim3(p.n_part, cdiv(n_classes, 16 * 6), c_out / 4), dim3(256), 0, stream, cls, dy, ds, part, H, W,
+                           n_classes, c_out, R, p.Ro, p.tiles_side, p.n_tiles, p.tpb);
+    }
+    GL_LAUNCH_CHECK();
+    const int E = n_classes * p.T;
+    hipLaunchKernelGGL(class_conv_wgrad_reduce_kernel, dim3(cdiv((E + 1) * c_out, 256)), dim3(256), 0, stream, (const float*)part, p.n_part, E, c_out, dW, db);
     GL_LAUNCH_CHECK();
     return GL_OK;
 }

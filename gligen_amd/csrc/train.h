@@ -72,6 +72,10 @@ struct TrainSpatialIn {
     const float* extra;                 // [B][Ce][He][We]; null iff extra_channels == 0
     int Ce, He, We;
     int ds_resize, ds_mode, ds_n_in, ds_mid;   // resize, 0 bicubic / 1 nearest, channels read, channels of the first conv (0: no layers)
+    // A semantic-map model's inputs as u8 class maps (classmap.h) instead of one-hot planes: both set and map / extra null, or both
+    // null. The class counts are tok_in_dim and ds_n_in; Ct and Ce are not read.
+    const uint8_t* map_cls = nullptr;   // [B][Ht][Wt]
+    const uint8_t* extra_cls = nullptr; // [B][He][We]
 };
 struct TrainUNetIn {
     int B, H, W, ctx_T, Ng;             // Ng: grounding tokens per sample = Ng_boxes (text) or 2 * Ng_boxes (text+image)

@@ -19,6 +19,7 @@
 #include <tuple>
 #include <unordered_set>
 
+#include "classmap.h"
 #include "engine.h"
 
 #include <cstdarg>
@@ -1840,6 +1841,17 @@ void conv_wgrad(const Ctx& c, const float* x, int B, int Cin, int H, int W, Stri
     c.ar.release(mk);
 }
 
+// the same two gradients from the u8 class map that stands for the one-hot planes x (classmap.h): dy binned by the class under each tap
+void class_wgrad(const Ctx& c, int kind, const uint8_t* cls, const float* dy, ClassDyStrides ds, int B, int H, int W, int n_classes, int Cout, int R, float* dW,
+                 float* db) {
+    if (!dW && !db) return;
+    const size_t mk = c.ar.mark();
+    size_t n = 0;
+    c.ck(class_conv_wgrad_partial_floats(kind, B, H, W, n_classes, Cout, R, &n));
+    c.ck(class_conv_wgrad_launch(kind, cls, dy, ds, c.f32(n), dW, db, B, H, W, n_classes, Cout, R, c.s));
+    c.ar.release(mk);
+}
+
 const int kCnxDims[4] = {96, 192, 384, 768};       // ConvNeXt-tiny (convnext.py:203-207)
 const char* const kPN = "position_net.";
 const char* const kBB = "position_net.convnext_tiny_backbone.";
@@ -1863,11 +1875,19 @@ SpatialSaved spatial_forward(const Ctx& c, const Names& nm, const TrainUNetCfg& 
     t.R = R;
     t.Cuse = cfg.tok_in_dim ? cfg.tok_in_dim : 3;
     if (R < 32 || R % 32) throw GlError(GL_ERR_ARG, "unet_train_step: tok_resize must be a positive multiple of 32");
-    if (!sp.map || !sp.mask || sp.Ct < t.Cuse) throw GlError(GL_ERR_ARG, fmt("unet_train_step: the tokenizer reads %d map channels", t.Cuse));
-    t.img = c.f32((size_t)B * t.Cuse * R * R);
-    c.ck(resize_f32_launch(sp.map, t.img, B, sp.Ct, t.Cuse, sp.Ht, sp.Wt, R, 1, s));      // F.interpolate(x, resize_input): nearest
-    t.img3 = t.img;
-    if (cfg.tok_in_dim) {
+    if (sp.map_cls) {     // the class map: the nearest resize and in_conv are one gather (classmap.h), the resized planes never exist
+        if (!cfg.tok_in_dim)
+            throw GlError(GL_ERR_UNSUPPORTED, "unet_train_step: a class map was given to a tokenizer without in_dim (canny, hed, depth, normal read an image, not classes)");
+        if (!sp.mask) throw GlError(GL_ERR_ARG, "unet_train_step: null mask");
+        t.img3 = c.f32((size_t)B * 3 * R * R);
+        c.ck(class_inconv_launch(sp.map_cls, nm.w(PN + "in_conv.weight"), nm.w(PN + "in_conv.bias"), t.img3, B, sp.Ht, sp.Wt, cfg.tok_in_dim, R, s));
+    } else {
+        if (!sp.map || !sp.mask || sp.Ct < t.Cuse) throw GlError(GL_ERR_ARG, fmt("unet_train_step: the tokenizer reads %d map channels", t.Cuse));
+        t.img = c.f32((size_t)B * t.Cuse * R * R);
+        c.ck(resize_f32_launch(sp.map, t.img, B, sp.Ct, t.Cuse, sp.Ht, sp.Wt, R, 1, s));      // F.interpolate(x, resize_input): nearest
+        t.img3 = t.img;
+    }
+    if (cfg.tok_in_dim && !sp.map_cls) {
         t.img3 = c.f32((size_t)B * 3 * R * R);
         c.ck(conv3x3_f32_launch(t.img, nm.w(PN + "in_conv.weight"), nm.w(PN + "in_conv.bias"), t.img3, B, t.Cuse, 3, R, R, s));
     }
@@ -1997,7 +2017,10 @@ void spatial_backward(const Ctx& c, const Names& nm, const TrainUNetCfg& cfg, co
         float* g3 = c.f32(n);
         const Strides r = pixel_rows(3, R, R);
         hipLaunchKernelGGL(unpatchify_kernel, Ctx::g1(n), dim3(256), 0, s, (const float*)gcol, 64, 3, R, R, 4, r.b, r.c, r.y, r.x, n, g3);
-        conv_wgrad(c, t.img, B, t.Cuse, R, R, nchw(t.Cuse, R, R), 3, 1, 1, R, R, g3, 3, nm.g(PN + "in_conv.weight"), nm.g(PN + "in_conv.bias"));
+        if (sp.map_cls)
+            class_wgrad(c, kClassWgradInConv, sp.map_cls, g3, {r.b, r.c, r.y, r.x}, B, sp.Ht, sp.Wt, t.Cuse, 3, R, nm.g(PN + "in_conv.weight"), nm.g(PN + "in_conv.bias"));
+        else
+            conv_wgrad(c, t.img, B, t.Cuse, R, R, nchw(t.Cuse, R, R), 3, 1, 1, R, R, g3, 3, nm.g(PN + "in_conv.weight"), nm.g(PN + "in_conv.bias"));
     }
 }
 
@@ -2006,17 +2029,30 @@ struct DsSaved { float *r = nullptr, *a1 = nullptr, *s1 = nullptr, *out = nullpt
 DsSaved downsampler_forward(const Ctx& c, const Names& nm, const TrainSpatialIn& sp, int B, int Ce, int H0, int W0) {
     DsSaved d;
     const int Rd = sp.ds_resize, ni = sp.ds_n_in, mid = sp.ds_mid;
-    if (!sp.extra || ni < 1 || sp.Ce < ni || Rd < 4) throw GlError(GL_ERR_ARG, "unet_train_step: grounding_extra_input / downsampler constants");
+    if (sp.extra_cls) {
+        if (sp.ds_mode != 1) throw GlError(GL_ERR_UNSUPPORTED, "unet_train_step: a class map was given to a downsampler that is not nearest mode (a bicubic resize mixes classes)");
+        if (!mid) throw GlError(GL_ERR_UNSUPPORTED, "unet_train_step: a class map was given to a downsampler without layers (its output would be the planes themselves)");
+    }
+    if ((!sp.extra && !sp.extra_cls) || ni < 1 || (!sp.extra_cls && sp.Ce < ni) || Rd < 4)
+        throw GlError(GL_ERR_ARG, "unet_train_step: grounding_extra_input / downsampler constants");
     if (mid ? (Rd != 4 * H0 || Rd != 4 * W0) : (Rd != H0 || Rd != W0 || ni != Ce))
         throw GlError(GL_ERR_ARG, fmt("unet_train_step: the downsampler (resize %d) does not match the %d x %d latent", Rd, H0, W0));
-    d.r = c.f32((size_t)B * ni * Rd * Rd);
-    c.ck(resize_f32_launch(sp.extra, d.r, B, sp.Ce, ni, sp.He, sp.We, Rd, sp.ds_mode == 1 ? 1 : 0, c.s));
+    if (!sp.extra_cls) {
+        d.r = c.f32((size_t)B * ni * Rd * Rd);
+        c.ck(resize_f32_launch(sp.extra, d.r, B, sp.Ce, ni, sp.He, sp.We, Rd, sp.ds_mode == 1 ? 1 : 0, c.s));
+    }
     d.out = d.r;
     if (mid) {
         const int Rh = Rd / 2;
         const size_t nh = (size_t)B * mid * Rh * Rh;
         d.a1 = c.f32(nh);           // the first conv's pre-activation: the SiLU backward reads it
-        c.ck(conv4x4s2_f32_launch(d.r, nm.w("downsample_net.layers.0.weight"), nm.w("downsample_net.layers.0.bias"), d.a1, B, ni, mid, Rd, Rd, 0, c.s));
+        if (sp.extra_cls) {     // the gather form of these trainable weights is rebuilt every step: arena memory, never the frozen-weight cache
+            float* gw = c.f32((size_t)ni * 16 * mid);
+            c.ck(class_conv_weight_relayout_launch(nm.w("downsample_net.layers.0.weight"), gw, mid, ni, c.s));
+            c.ck(class_conv4x4s2_launch(sp.extra_cls, gw, nm.w("downsample_net.layers.0.bias"), d.a1, B, sp.He, sp.We, ni, mid, Rd, 0, c.s));
+        } else {
+            c.ck(conv4x4s2_f32_launch(d.r, nm.w("downsample_net.layers.0.weight"), nm.w("downsample_net.layers.0.bias"), d.a1, B, ni, mid, Rd, Rd, 0, c.s));
+        }
         d.s1 = c.f32(nh);
         hipLaunchKernelGGL(silu_kernel, Ctx::g1(nh), dim3(256), 0, c.s, (const float*)d.a1, nh, d.s1);
         d.out = c.f32((size_t)B * Ce * H0 * W0);
@@ -2043,6 +2079,10 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
                               (ds_model && (!strncmp(names[i], "downsample_net.", 15) || !strcmp(names[i], "input_blocks.0.0.weight")))))
                 throw GlError(GL_ERR_ARG, fmt("unet_train_step: a gradient was asked for '%s', which the reference keeps frozen", names[i]));
         if (cfg.grounding_kind == 3 && !spatial) throw GlError(GL_ERR_ARG, "unet_train_step: a spatial-map model needs its TrainSpatialIn");
+        if (spatial && (spatial->map_cls || spatial->extra_cls) &&
+            (!spatial->map_cls || !spatial->extra_cls || spatial->map || spatial->extra || !cfg.extra_channels))
+            throw GlError(GL_ERR_ARG, "unet_train_step: a mixture of class maps and planes: the tokenizer's map and grounding_extra_input are both u8 class maps "
+                                      "or both fp32 planes");
         Ctx c{ar, ws, ws_bytes, s};
         std::unordered_set<const void*> frozen;
         if (cache) {
@@ -2358,9 +2398,15 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
                                    nh, gs1);
                 float* ga1 = c.f32(nh);
                 hipLaunchKernelGGL(silu_bwd_kernel, Ctx::g1(nh), dim3(256), 0, s, (const float*)gs1, (const float*)dsv.a1, nh, ga1);
-                const float* ga1r = im2col(c, ga1, B, mid, Rh, Rh, nchw(mid, Rh, Rh), 1, 1, 0, Rh, Rh, mid);     // NCHW -> pixel rows
-                conv_wgrad(c, dsv.r, B, ni, Rd, Rd, nchw(ni, Rd, Rd), 4, 2, 1, Rh, Rh, ga1r, mid, nm.g("downsample_net.layers.0.weight"),
-                           nm.g("downsample_net.layers.0.bias"));
+                if (spatial->extra_cls) {
+                    const Strides r = nchw(mid, Rh, Rh);
+                    class_wgrad(c, kClassWgradDown, spatial->extra_cls, ga1, {r.b, r.c, r.y, r.x}, B, spatial->He, spatial->We, ni, mid, Rd,
+                                nm.g("downsample_net.layers.0.weight"), nm.g("downsample_net.layers.0.bias"));
+                } else {
+                    const float* ga1r = im2col(c, ga1, B, mid, Rh, Rh, nchw(mid, Rh, Rh), 1, 1, 0, Rh, Rh, mid);     // NCHW -> pixel rows
+                    conv_wgrad(c, dsv.r, B, ni, Rd, Rd, nchw(ni, Rd, Rd), 4, 2, 1, Rh, Rh, ga1r, mid, nm.g("downsample_net.layers.0.weight"),
+                               nm.g("downsample_net.layers.0.bias"));
+                }
             }
         }
         // ---- position_net backward (Linear, SiLU, Linear, SiLU, Linear per branch; the learnable null embeddings: the position one is

@@ -423,6 +423,25 @@ class Engine:
                                                           int(w1.shape[0]), _ptr(w2), _ptr(b2), int(w2.shape[0]), _ptr(out), _stream(self.device)))
         return out
 
+    def op_class_conv_wgrad(self, cls: torch.Tensor, dy: torch.Tensor, n_classes: int, R: int, kind: str):
+        """Weight and bias gradient of a conv over F.interpolate(one_hot(cls), R, mode="nearest"), from the class map u8 [B, 1, H, W]
+        itself (gl_op_class_conv_wgrad). kind "in_conv": Conv2d(n_classes, 3, 3, 1, 1), dy [B, 3, R, R]; "down": Conv2d(n_classes,
+        c_out, 4, 2, 1), dy [B, c_out, R/2, R/2]. Returns (dW [c_out, n_classes, k, k], db [c_out]); the same bits on every call."""
+        if kind not in ("in_conv", "down"):
+            raise ValueError(f"op_class_conv_wgrad: kind {kind!r}; 'in_conv' or 'down' is built")
+        cls = self._class_map(cls, "op_class_conv_wgrad")
+        B, H, W = cls.shape
+        dy = _f32(dy, self.device)
+        Ro, k = (int(R) // 2, 4) if kind == "down" else (int(R), 3)
+        if dy.dim() != 4 or dy.shape[0] != B or (int(R) > 0 and tuple(dy.shape[2:]) != (Ro, Ro)):
+            raise ValueError(f"op_class_conv_wgrad: dy is {tuple(dy.shape)}; [{B}, c_out, {Ro}, {Ro}] is read")
+        c_out = int(dy.shape[1])
+        dW = torch.empty((c_out, max(int(n_classes), 0), k, k), device=self.device, dtype=torch.float32)
+        db = torch.empty((c_out,), device=self.device, dtype=torch.float32)
+        check(self.lib.gl_op_class_conv_wgrad(self._ctx, 1 if kind == "down" else 0, _ptr(cls), int(B), int(H), int(W), int(n_classes), int(R), _ptr(dy), c_out,
+                                              _ptr(dW), _ptr(db), _stream(self.device)))
+        return dW, db
+
     def set_fuser_scale(self, scale: float) -> None:
         check(self.lib.gl_unet_set_fuser_scale(self._ctx, C.c_float(float(scale)), _stream(self.device)))
 
@@ -686,6 +705,9 @@ class Engine:
         positive_embeddings (or, for the text+image tokenizer, text_embeddings, image_embeddings, text_masks, image_masks), target [B, 4, H, W] (the noise).
         A spatial-map model (cfg["grounding_tokenizer"] one of the five *_grounding_net targets; gl_unet_train_step_spatial) takes the map
         under the reference's key (canny_edge, hed_edge, depth, normal, sem), mask [B] and grounding_extra_input instead of the boxes.
+        The sem model also trains from class maps: `sem` and `grounding_extra_input` both torch.uint8 [B, 1, H, W] or [B, H, W]
+        (gl_unet_train_step_spatial_classes) give the loss, eps and gradients of their one-hot planes bit for bit, except in_conv's and
+        downsample_net.layers.0's gradients, which are summed in another order; one u8 and one float input is a ValueError.
         Returns (loss, eps [B, 4, H, W], grads) with grads over the reference's
         trainable set (train.trainable_names: trainer.py:189-245) or the `trainable` names given; `grads`: buffers to
         write into instead of fresh ones (every entry is overwritten); `checkpoint`: keep only block inputs / outputs and recompute each block's
@@ -729,6 +751,25 @@ class Engine:
         garr = (C.c_void_p * n)(*[(grads[k].data_ptr() if k in grads else None) for k in names])
         eps = torch.empty((B, H * W, c.out_channels), device=dev, dtype=torch.float32)
         loss = torch.zeros(1, device=dev, dtype=torch.float32)
+        if sp and (batch[sp["map_key"]].dtype == torch.uint8 or (sp["ds"] and batch["grounding_extra_input"].dtype == torch.uint8)):
+            # the semantic-map model from u8 class maps (gl_unet_train_step_spatial_classes): both inputs are class maps
+            if not sp["ds"]:
+                raise ValueError("unet_train_step: a class map trains a model with a grounding downsampler; this config has none")
+            cm = self._class_map(batch[sp["map_key"]], "unet_train_step")
+            ce = self._class_map(batch["grounding_extra_input"], "unet_train_step")
+            if cm.shape[0] != B or ce.shape[0] != B:
+                raise ValueError(f"unet_train_step: the class maps hold {cm.shape[0]} and {ce.shape[0]} samples, x holds {B}")
+            keep = dict(x=rows(x), t=_f32(batch["timesteps"], dev), ctx=_f32(batch["context"], dev), target=rows(target), mask=_f32(batch["mask"].reshape(-1), dev))
+            if keep["mask"].shape[0] != B:
+                raise ValueError("unet_train_step: one mask value per sample")
+            ds = sp["ds"]
+            u = _lib.TrainUNetIn(int(B), int(H), int(W), int(keep["ctx"].shape[1]), (sp["tok_resize"] // 32) ** 2, keep["x"].data_ptr(), keep["t"].data_ptr(),
+                                 keep["ctx"].data_ptr(), None, None, None, keep["target"].data_ptr(), float(fuser_scale), None, None, None,
+                                 int(bool(checkpoint)), int(bool(use_weight_cache)))
+            s = _lib.TrainSpatialClassesIn(cm.data_ptr(), int(cm.shape[1]), int(cm.shape[2]), keep["mask"].data_ptr(), ce.data_ptr(), int(ce.shape[1]), int(ce.shape[2]),
+                                           ds["resize"], ds["mode"], ds["n_in"], ds["mid"])
+            check(self.lib.gl_unet_train_step_spatial_classes(self._ctx, C.byref(c), C.byref(u), C.byref(s), n, narr, parr, garr, _ptr(eps), _ptr(loss), _stream(dev)))
+            return loss, eps.reshape(B, H, W, c.out_channels).permute(0, 3, 1, 2).contiguous(), grads
         if sp:      # batch: the map under the reference's key, mask, grounding_extra_input (gl_unet_train_step_spatial)
             keep = dict(x=rows(x), t=_f32(batch["timesteps"], dev), ctx=_f32(batch["context"], dev), target=rows(target),
                         map=_f32(batch[sp["map_key"]], dev), mask=_f32(batch["mask"].reshape(-1), dev))

@@ -46,8 +46,11 @@ def warmup_schedule(base_lr: float, warmup_steps: int, total_iters: Optional[int
 
 
 def null_grounding(batch: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
-    """GroundingNetInput.get_null_input (grounding_input/*_tokinzer_input.py:30-45): every grounding tensor zeroed."""
-    return {k: (torch.zeros_like(v) if k in GROUNDING_KEYS else v) for k, v in batch.items()}
+    """GroundingNetInput.get_null_input (grounding_input/*_tokinzer_input.py:30-45): every grounding tensor zeroed. A semantic map given
+    as a torch.uint8 class map becomes 255 everywhere instead, the "no class" of grounding_input/_base.py: zeros would read as class 0
+    in every pixel. grounding_extra_input is kept in either format."""
+    null = lambda v: torch.full_like(v, 255) if v.dtype == torch.uint8 else torch.zeros_like(v)
+    return {k: (null(v) if k in GROUNDING_KEYS else v) for k, v in batch.items()}
 
 
 def has_grounding_downsampler(state_dict: Mapping[str, torch.Tensor], cfg: Optional[Mapping] = None) -> bool:
@@ -93,7 +96,8 @@ def gradient_milestones(names):
 class TrainStep:
     """lr: a float, or a callable step -> rate (warmup_schedule: the reference's warm-up schedulers). drop_prob: the probability with
     which an iteration trains on the null grounding input (UNetModel.forward, openaimodel.py:428: 0.1 while training; 0 here by
-    default so that a step is a pure function of its batch) -- drawn from `rng` (random.Random; seed it identically on every rank
+    default so that a step is a pure function of its batch; null_grounding: zeros, or 255 = "no class" for a u8 class map, so class-map
+    batches of the sem model drop the same way) -- drawn from `rng` (random.Random; seed it identically on every rank
     or not at all, as the reference does). With torch.distributed initialised, rank 0's trainable parameters are broadcast once at
     construction, as DistributedDataParallel does (trainer.py:321-322): replicas that start from different state_dicts would
     otherwise drift apart silently.

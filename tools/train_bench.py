@@ -1,8 +1,9 @@
 """Wall time of one training iteration (gl_unet_train_step: forward + loss + backward) of the correctness path, per configuration:
 small UNet at a 16 x 16 latent, the shipped topology at 16 x 16 and at the real 64 x 64 latent. Synthetic inputs, seeded weights.
 --spatial MODALITY: the shipped topology with that spatial-map tokenizer (ConvNeXt-tiny, resize 256: 64 tokens) and grounding
-downsampler instead (gl_unet_train_step_spatial), B = 4, 64 x 64 latent, checkpoint=True.
-   PYTHONPATH=. python tools/train_bench.py [--full64] [--spatial {canny,depth,normal,hed,sem}]"""
+downsampler instead (gl_unet_train_step_spatial), B = 4, 64 x 64 latent, checkpoint=True. --class-maps (with --spatial sem): the same
+iteration fed from the u8 class maps of those planes (gl_unet_train_step_spatial_classes).
+   PYTHONPATH=. python tools/train_bench.py [--full64] [--spatial {canny,depth,normal,hed,sem} [--class-maps]]"""
 import json
 import sys
 import time
@@ -40,8 +41,9 @@ def run(name, cfg, B, hw, reps, eng, checkpoint=False, cache=False):
         eng.train_weight_cache(False)
 
 
-def run_spatial(modality, B, hw, reps, checkpoint=True):
-    """The shipped topology (syn.UNET_CFG) with a spatial-map tokenizer and its downsampler (configs/cc3m_canny.yaml etc.)."""
+def run_spatial(modality, B, hw, reps, checkpoint=True, class_maps=False):
+    """The shipped topology (syn.UNET_CFG) with a spatial-map tokenizer and its downsampler (configs/cc3m_canny.yaml etc.).
+    class_maps: sem's one-hot planes replaced by their u8 class map, argmax over the planes."""
     from ldm.modules.diffusionmodules.openaimodel import UNetModel
     from gligen_amd.engine import SPATIAL_MAP_KEYS
     from gligen_amd.train import trainable_names
@@ -57,6 +59,10 @@ def run_spatial(modality, B, hw, reps, checkpoint=True):
     eng = Engine(0, arena_gb=160.0)
     sd = {k: v.float().to(eng.device).contiguous() for k, v in syn.seeded_state_dict(shapes, 1234).items()}
     img = syn.make_spatial_map(modality, B, 256, seed=3)
+    if class_maps:
+        if modality != "sem":
+            raise SystemExit("--class-maps: only the sem model reads class maps")
+        img = img.argmax(1, keepdim=True).to(torch.uint8)
     batch = {SPATIAL_MAP_KEYS[modality]: img, "mask": torch.ones(B, 1), "grounding_extra_input": img, "x": syn.make_latent(B, 4, hw, hw, seed=6),
              "timesteps": torch.tensor([981, 441, 300, 77][:B]).float(), "context": syn.make_context(B, seed=6), "target": syn.make_latent(B, 4, hw, hw, seed=7)}
     grads = {k: torch.zeros_like(sd[k]) for k in trainable_names(sd, cfg)}
@@ -67,7 +73,8 @@ def run_spatial(modality, B, hw, reps, checkpoint=True):
         loss, _, _ = eng.unet_train_step(cfg, sd, batch, grads=grads, checkpoint=checkpoint)
     torch.cuda.synchronize()
     dt = (time.time() - t0) / reps
-    print(json.dumps(dict(config=f"shipped topology, {modality} tokenizer + downsampler", B=B, latent=hw, tok_resize=256, checkpoint=bool(checkpoint),
+    print(json.dumps(dict(config=f"shipped topology, {modality} tokenizer + downsampler", inputs="u8 class maps" if class_maps else "fp32 planes", B=B, latent=hw,
+                          tok_resize=256, checkpoint=bool(checkpoint),
                           s_per_iteration=round(dt, 4), loss=float(loss), arena_high_water_gb=round(eng.arena_high_water() / 2 ** 30, 2),
                           trainable_values=sum(int(g.numel()) for g in grads.values()))), flush=True)
 
@@ -77,9 +84,9 @@ if __name__ == "__main__":
         modality = sys.argv[sys.argv.index("--spatial") + 1]
         if "--full64" in sys.argv:
             run("shipped topology", syn.UNET_CFG, 4, 64, 1, Engine(0, arena_gb=1.0), checkpoint=True)     # the text model's line, same box
-            run_spatial(modality, 4, 64, 1)
+            run_spatial(modality, 4, 64, 1, class_maps="--class-maps" in sys.argv)
         else:
-            run_spatial(modality, 1, 16, 2)
+            run_spatial(modality, 1, 16, 2, class_maps="--class-maps" in sys.argv)
         sys.exit(0)
     eng = Engine(0, arena_gb=160.0)
     if "--b4only" in sys.argv:          # the profiled line (tools/gpu_run.sh train with TRAIN_PROF=1): the bench line's train_step shape
