@@ -27,6 +27,7 @@
 #include <cstring>
 #include <string>
 #include <unordered_map>
+#include <type_traits>
 #include <vector>
 
 namespace gl {
@@ -803,6 +804,7 @@ __global__ void sum2x2_kernel(const float* __restrict__ du, int H, int W, int Cc
 }  // namespace
 
 // operand copies of frozen parameters, kept across training steps (train.h)
+enum WeightForm { WF_ROWS = 1, WF_TRANSPOSED = 2, WF_CONV = 3, WF_CONV_DGRAD = 4 };
 struct TrainWeightCache {
     struct Key {
         const void* p; int kind, a, b, c;
@@ -821,6 +823,38 @@ size_t train_cache_bytes(const TrainWeightCache* c) { return c ? c->bytes : 0; }
 
 namespace {
 
+// ---- the one dispatch table: which instantiation serves a head dim. f is called with the two template arguments as
+// std::integral_constants; false: no instantiation
+template <int V> using Int = std::integral_constant<int, V>;
+template <class F>
+bool with_valu_dims(int D, F&& f) {       // <DC, LPQ>, D = DC * LPQ
+    switch (D) {
+        case 32: f(Int<32>{}, Int<1>{}); return true;
+        case 40: f(Int<40>{}, Int<1>{}); return true;
+        case 64: f(Int<32>{}, Int<2>{}); return true;
+        case 80: f(Int<40>{}, Int<2>{}); return true;
+        case 160: f(Int<40>{}, Int<4>{}); return true;
+        default: return false;
+    }
+}
+template <class F>
+void with_mfma_dims(int D, F&& f) {       // <DP, DPO> = D rounded up to 16 / 32; D is one of attn_on_mfma's
+    switch (D) {
+        case 32: f(Int<32>{}, Int<32>{}); break;
+        case 40: f(Int<48>{}, Int<64>{}); break;
+        case 64: f(Int<64>{}, Int<64>{}); break;
+        default: f(Int<80>{}, Int<96>{}); break;
+    }
+}
+// GL_TRAIN_ATTN_VALU=1 (developer A/B) keeps every head dim on the VALU kernels
+bool attn_on_mfma(int D) {
+    static const bool valu = dev_env("GL_TRAIN_ATTN_VALU") && atoi(dev_env("GL_TRAIN_ATTN_VALU")) != 0;
+    return !valu && (D == 32 || D == 40 || D == 64 || D == 80);
+}
+
+// An fp32 operand x of a matrix product as bf16: hi = bf16(x), lo = bf16(x - hi) (lo null: single-pass bf16, GL_TRAIN_BF16X1)
+struct Split { bf16* hi; bf16* lo; };
+
 struct Ctx {
     Arena& ar;
     float* ws;
@@ -828,12 +862,33 @@ struct Ctx {
     hipStream_t s;
     TrainWeightCache* wc = nullptr;                            // null: every operand copy is built per product in the arena
     const std::unordered_set<const void*>* frozen = nullptr;   // parameter tensors the caller does not update (no gradient asked for)
+
+    void ck(int rc) const { if (rc != GL_OK) throw GlError(rc, gl::last_error()); }
+    void hip(hipError_t e, const char* what) const { if (e != hipSuccess) throw GlError(GL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
+    float* f32(size_t n) const { return ar.get<float>(n); }
+    static dim3 g1(size_t n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
+    // one thread per element, 256 per workgroup: every argument initialises a value of the kernel's own parameter type (no narrowing)
+    template <class... P, class... A>
+    void ew(void (*k)(P...), size_t n, A&&... a) const {
+        hipLaunchKernelGGL(k, g1(n), dim3(256), 0, s, P{std::forward<A>(a)}...);
+    }
+    // ... into a new buffer of n_out floats, the kernel's last argument
+    template <class... P, class... A>
+    float* ew_new(void (*k)(P...), size_t n_out, size_t n, A&&... a) const {
+        float* out = f32(n_out);
+        ew(k, n, a..., out);
+        return out;
+    }
+    struct LN { float* y; float* xhat; float* rstd; };
+    struct GN { float* a; float* xhat; float* rstd; };
+    struct Attn { float* o; float* lse; };
+
     // a bf16 operand copy of weight W: from the cache when W is frozen and a cache is attached (built on first use, on this stream), else
     // from the arena (released with the product's mark as before)
     template <class F>
-    bf16* weight_operand(const float* W, int kind, int a, int b, int c, size_t n_elems, F&& build) const {
+    bf16* weight_operand(const float* W, WeightForm kind, int a, int b, size_t n_elems, F&& build) const {
         if (wc && frozen && frozen->count(W)) {
-            const TrainWeightCache::Key key{W, kind, a, b, c};
+            const TrainWeightCache::Key key{W, kind, a, b, 0};
             auto it = wc->m.find(key);
             if (it != wc->m.end()) return reinterpret_cast<bf16*>(it->second);
             void* p = nullptr;
@@ -849,21 +904,12 @@ struct Ctx {
         build(d);
         return d;
     }
-    void ck(int rc) const { if (rc != GL_OK) throw GlError(rc, gl::last_error()); }
-    void hip(hipError_t e, const char* what) const { if (e != hipSuccess) throw GlError(GL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
-    float* f32(size_t n) const { return ar.get<float>(n); }
-    static dim3 g1(size_t n, int bs = 256) { return dim3((unsigned)((n + bs - 1) / bs)); }
 
-    static bool split_precision() {
-        static const bool one_pass = dev_env("GL_TRAIN_BF16X1") && atoi(dev_env("GL_TRAIN_BF16X1")) != 0;
-        return !one_pass;
-    }
-    struct Split { bf16* hi; bf16* lo; };      // lo null: single-pass bf16
     Split to_bf16(const float* src, size_t n) const {
         Split d{ar.get<bf16>(n), nullptr};
         if (split_precision()) {
             d.lo = ar.get<bf16>(n);
-            hipLaunchKernelGGL(split_bf16_kernel, g1(n), dim3(256), 0, s, src, n, d.hi, d.lo);
+            ew(split_bf16_kernel, n, src, n, d.hi, d.lo);
         } else {
             ck(cast_f32_bf16_launch(src, d.hi, (int64_t)n, s));
         }
@@ -883,27 +929,28 @@ struct Ctx {
         E.out = out; E.ldo = N; E.out_f32 = 1; E.bias = bias;
         ck(gemm_launch(A, w, M, N, K, E, ws, ws_bytes, s));
     }
-    // out [M][N] fp32 = a [M][K] w[N][K]^T (+ bias)
-    void mm(const Split& a, const Split& w, int M, int N, int K, const float* bias, float* out) const {
-        mm1(a.hi, w.hi, M, N, K, bias, out);
+    // out [M][N] fp32 = a w^T (+ bias) as hi.hi + lo.hi + hi.lo: one(a, w, bias, out) launches one bf16 product into an [M][N] fp32 buffer
+    template <class F>
+    void split_product(F&& one, const Split& a, const Split& w, int M, int N, const float* bias, float* out) const {
+        one(a.hi, w.hi, bias, out);
         if (a.lo && w.lo) {
             const size_t mk = ar.mark();
             float* t1 = f32((size_t)M * N);
             float* t2 = f32((size_t)M * N);
-            mm1(a.lo, w.hi, M, N, K, nullptr, t1);
-            mm1(a.hi, w.lo, M, N, K, nullptr, t2);
-            hipLaunchKernelGGL(add3_kernel, g1((size_t)M * N), dim3(256), 0, s, out, (const float*)t1, (const float*)t2, (size_t)M * N);
+            one(a.lo, w.hi, nullptr, t1);
+            one(a.hi, w.lo, nullptr, t2);
+            ew(add3_kernel, (size_t)M * N, out, t1, t2, (size_t)M * N);
             ar.release(mk);
         }
     }
-    // ---- one-launch split-precision products (cat3_* above); GL_TRAIN_3LAUNCH=1 (developer A/B) keeps the three-launch form
-    static bool one_launch() {
-        static const bool three = dev_env("GL_TRAIN_3LAUNCH") && atoi(dev_env("GL_TRAIN_3LAUNCH")) != 0;
-        return split_precision() && !three;
+    // out [M][N] fp32 = a [M][K] w[N][K]^T (+ bias)
+    void mm(const Split& a, const Split& w, int M, int N, int K, const float* bias, float* out) const {
+        split_product([&](const bf16* ap, const bf16* wp, const float* b, float* o) { mm1(ap, wp, M, N, K, b, o); }, a, w, M, N, bias, out);
     }
+    // ---- one-launch split-precision products (cat3_* above); GL_TRAIN_3LAUNCH=1 (developer A/B) keeps the three-launch form
     bf16* cat3_rows(const float* src, size_t R, int K, int side) const {
         bf16* d = ar.get<bf16>(R * 3 * (size_t)K);
-        hipLaunchKernelGGL(cat3_rows_kernel, g1(R * (size_t)K), dim3(256), 0, s, src, R * (size_t)K, K, side, d);
+        ew(cat3_rows_kernel, R * (size_t)K, src, R * (size_t)K, K, side, d);
         return d;
     }
     bf16* cat3_transposed(const float* src, int R, int Cc, int Rpad, int side) const {
@@ -913,14 +960,21 @@ struct Ctx {
     }
     // the weight side of a product (side = 1): cached for frozen parameters
     bf16* cat3_rows_w(const float* W, int N, int K) const {
-        return weight_operand(W, 1, N, K, 0, (size_t)N * 3 * K, [&](bf16* d) {
-            hipLaunchKernelGGL(cat3_rows_kernel, g1((size_t)N * K), dim3(256), 0, s, W, (size_t)N * K, K, 1, d);
-        });
+        return weight_operand(W, WF_ROWS, N, K, (size_t)N * 3 * K, [&](bf16* d) { ew(cat3_rows_kernel, (size_t)N * K, W, (size_t)N * K, K, 1, d); });
     }
     bf16* cat3_transposed_w(const float* W, int N, int K) const {
-        return weight_operand(W, 2, N, K, 0, (size_t)K * 3 * N, [&](bf16* d) {
+        return weight_operand(W, WF_TRANSPOSED, N, K, (size_t)K * 3 * N, [&](bf16* d) {
             hipLaunchKernelGGL(cat3_transposed_kernel, dim3(cdiv(K, 32), cdiv(N, 32)), dim3(32, 8), 0, s, W, N, K, K, 1, d, N);
         });
+    }
+
+    static bool split_precision() {
+        static const bool one_pass = dev_env("GL_TRAIN_BF16X1") && atoi(dev_env("GL_TRAIN_BF16X1")) != 0;
+        return !one_pass;
+    }
+    static bool one_launch() {
+        static const bool three = dev_env("GL_TRAIN_3LAUNCH") && atoi(dev_env("GL_TRAIN_3LAUNCH")) != 0;
+        return split_precision() && !three;
     }
     // y = x W^T + b
     float* lin_fwd(const float* x, int M, int K, const float* W, const float* b, int N) const {
@@ -949,9 +1003,79 @@ struct Ctx {
             else mm(transposed(dy, M, N, Mp), transposed(x, M, K, Mp), N, K, Mp, nullptr, dW);
         }
         ar.release(mk);
-        if (db) hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(N, 64)), dim3(1024), 0, s, dy, (const float*)nullptr, M, N, db);
+        if (db) colsum(dy, nullptr, M, N, db);
     }
-    // out[0] = coef * sum a b (mode 0: the tanh gate's derivative) / mean (a - b)^2 (mode 1: the loss); fixed summation order
+
+    float* conv_dgrad_weight(const float* w_oihw, int O, int I) const { return ew_new(conv_dgrad_weight_kernel, (size_t)I * O * 9, (size_t)I * O * 9, w_oihw, O, I); }
+    // The activations are cast to bf16 for the implicit-GEMM kernel of gemm.hip. One launch over 3 Ci input channels where the loader's
+    // 64-channel step allows it -- activations (hi | lo | hi) as a two-source concat of the (hi | lo) buffer with its own first half,
+    // weights (hi | hi | lo) along I (cached for frozen convs: flip / transpose for dgrad, split, pack -- once) --, else three launches
+    float* conv3(const float* a, int B, int H, int W, const float* w_oihw, const float* bias, int Cin, int Cout, bool dgrad, int stride = 1, int ups = 0) const {
+        const int Ho = stride == 2 ? H / 2 : H << ups, Wo = stride == 2 ? W / 2 : W << ups;
+        const int Ci = dgrad ? Cout : Cin, Co = dgrad ? Cin : Cout, M = B * Ho * Wo;
+        const size_t nw = (size_t)Co * 9 * Ci, na = (size_t)B * H * W * Ci;
+        float* out = f32((size_t)M * Co);
+        const size_t mk_ops = ar.mark();   // packed weights / bf16 activation copies: this product's, released behind it
+        auto weight_source = [&] { return dgrad ? conv_dgrad_weight(w_oihw, Cout, Cin) : w_oihw; };
+        // parts: how many Ci-wide channel groups are concatenated along K (3: ap is the (hi | lo) buffer)
+        auto launch = [&](int parts, const bf16* ap, const bf16* wq, const float* bb, float* o) {
+            AOperand A{};
+            A.p0 = ap; A.C0 = Ci; A.ld0 = Ci; A.mode = A_CONV3;
+            if (parts == 3) { A.C0 = 2 * Ci; A.ld0 = 2 * Ci; A.p1 = ap; A.C1 = Ci; A.ld1 = 2 * Ci; }
+            A.Hin = H; A.Win = W; A.Ho = Ho; A.Wo = Wo; A.stride = stride; A.ups = ups; A.pad_lo = 1;
+            Epilogue E;
+            epilogue_defaults(E);
+            E.out = o; E.ldo = Co; E.out_f32 = 1; E.bias = bb; E.rows_per_b = Ho * Wo;
+            ck(gemm_launch(A, wq, M, Co, parts * 9 * Ci, E, ws, ws_bytes, s));
+        };
+        if (one_launch() && Ci % 64 == 0) {
+            const bf16* wp3 = weight_operand(w_oihw, dgrad ? WF_CONV_DGRAD : WF_CONV, Cout, Cin, 3 * nw, [&](bf16* d) {
+                const float* src = weight_source();
+                float* w3 = f32(3 * nw);
+                ew(conv_w_cat3_kernel, nw, src, Co, Ci, w3);
+                ck(pack_conv_weight_launch(w3, d, Co, 3 * Ci, 3, 3, Co, s));
+            });
+            bf16* a2 = ar.get<bf16>(2 * na);
+            ew(cat2_rows_kernel, na, a, na, Ci, a2);
+            launch(3, a2, wp3, bias, out);
+        } else {
+            const float* wsrc = weight_source();
+            Split wp{ar.get<bf16>(nw), nullptr};
+            ck(pack_conv_weight_launch(wsrc, wp.hi, Co, Ci, 3, 3, Co, s));
+            if (split_precision()) {
+                float* wres = f32(nw);
+                ew(bf16_residual_kernel, nw, wsrc, nw, wres);
+                wp.lo = ar.get<bf16>(nw);
+                ck(pack_conv_weight_launch(wres, wp.lo, Co, Ci, 3, 3, Co, s));
+            }
+            const Split av = to_bf16(a, na);
+            split_product([&](const bf16* ap, const bf16* wq, const float* bb, float* o) { launch(1, ap, wq, bb, o); }, av, wp, M, Co, bias, out);
+        }
+        ar.release(mk_ops);
+        return out;
+    }
+
+    LN ln_fwd(const float* x, int R, int Cc, const float* g, const float* b, float eps = 1e-5f) const {
+        LN r{f32((size_t)R * Cc), f32((size_t)R * Cc), f32(R)};
+        hipLaunchKernelGGL(ln_fwd_kernel, dim3(cdiv(R, 4)), dim3(256), 0, s, x, g, b, R, Cc, r.y, r.xhat, r.rstd, eps);
+        return r;
+    }
+    void ln_bwd(const float* dy, const LN& f, const float* g, int R, int Cc, float* dx, bool accumulate, float* dgamma, float* dbeta) const {
+        hipLaunchKernelGGL(ln_bwd_kernel, dim3(cdiv(R, 4)), dim3(256), 0, s, dy, f.xhat, f.rstd, g, R, Cc, dx, accumulate ? 1 : 0);
+        if (dgamma) colsum(dy, f.xhat, R, Cc, dgamma);
+        if (dbeta) colsum(dy, nullptr, R, Cc, dbeta);
+    }
+    GN gn_silu_fwd(const float* x, int B, int HW, int Cc, const float* g, const float* b, bool silu = true, float eps = 1e-5f) const {
+        GN r{f32((size_t)B * HW * Cc), f32((size_t)B * HW * Cc), f32((size_t)B * 32)};
+        hipLaunchKernelGGL(gn_silu_fwd_kernel, dim3(32, B), dim3(256), 0, s, x, g, b, HW, Cc, r.xhat, r.rstd, r.a, silu ? 1 : 0, eps);
+        return r;
+    }
+    void gn_silu_bwd(const float* da, const GN& f, const float* g, const float* b, int B, int HW, int Cc, float* dx, bool accumulate, bool silu = true) const {
+        hipLaunchKernelGGL(gn_silu_bwd_kernel, dim3(32, B), dim3(256), 0, s, da, f.xhat, f.rstd, g, b, HW, Cc, dx, accumulate ? 1 : 0, silu ? 1 : 0);
+    }
+    void colsum(const float* a, const float* b, int R, int Cc, float* out) const {
+        hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(Cc, 64)), dim3(1024), 0, s, a, b, R, Cc, out);
+    }
     void dot_reduce(const float* a, const float* b, size_t n, const float* alpha, float scale, int mode, float* out) const {
         if (n <= ((size_t)1 << 18)) {
             hipLaunchKernelGGL(dot_reduce_kernel, dim3(1), dim3(1024), 0, s, a, b, n, alpha, scale, mode, out);
@@ -962,205 +1086,24 @@ struct Ctx {
         const size_t mk = ar.mark();
         float* partial = f32(nb);
         hipLaunchKernelGGL(dot_partial_kernel, dim3(nb), dim3(1024), 0, s, a, b, n, chunk, mode, partial);
-        hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(64), 0, s, (const float*)partial, nb, n, alpha, scale, mode, out);
+        hipLaunchKernelGGL(dot_final_kernel, dim3(1), dim3(64), 0, s, partial, nb, n, alpha, scale, mode, out);
         ar.release(mk);
     }
-    struct LN { float* y; float* xhat; float* rstd; };
-    LN ln_fwd(const float* x, int R, int Cc, const float* g, const float* b, float eps = 1e-5f) const {
-        LN r{f32((size_t)R * Cc), f32((size_t)R * Cc), f32(R)};
-        hipLaunchKernelGGL(ln_fwd_kernel, dim3(cdiv(R, 4)), dim3(256), 0, s, x, g, b, R, Cc, r.y, r.xhat, r.rstd, eps);
-        return r;
+    float* mse_loss(const float* y, const float* target, size_t n, float* loss) const {
+        dot_reduce(y, target, n, nullptr, 1.f, 1, loss);
+        return ew_new(mse_grad_kernel, n, n, y, target, n);
     }
-    void ln_bwd(const float* dy, const LN& f, const float* g, int R, int Cc, float* dx, bool accumulate, float* dgamma, float* dbeta) const {
-        hipLaunchKernelGGL(ln_bwd_kernel, dim3(cdiv(R, 4)), dim3(256), 0, s, dy, f.xhat, f.rstd, g, R, Cc, dx, accumulate ? 1 : 0);
-        if (dgamma) hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(Cc, 64)), dim3(1024), 0, s, dy, (const float*)f.xhat, R, Cc, dgamma);
-        if (dbeta) hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(Cc, 64)), dim3(1024), 0, s, dy, (const float*)nullptr, R, Cc, dbeta);
-    }
-    struct Attn { float* o; float* lse; };
-    template <int DC, int LPQ>
-    Attn attn_fwd_d(const float* q, const float* k, const float* v, int B, int H, int Nq, int Nk) const {
-        constexpr int D = DC * LPQ;
-        Attn a{f32((size_t)B * Nq * H * D), f32((size_t)B * H * Nq)};
-        hipLaunchKernelGGL((attn_fwd_kernel<DC, LPQ>), dim3(cdiv(Nq * LPQ, 64), B * H), dim3(64), 0, s, q, k, v, H, Nq, Nk, 1.f / sqrtf((float)D), a.o, a.lse);
-        return a;
-    }
-    template <int DC, int LPQ>
-    void attn_bwd_d(const float* q, const float* k, const float* v, const Attn& f, const float* dout, int B, int H, int Nq, int Nk, float* dq,
-                    float* dk, float* dv) const {
-        constexpr int D = DC * LPQ;
-        float* delta = f32((size_t)B * H * Nq);
-        const float sc = 1.f / sqrtf((float)D);
-        hipLaunchKernelGGL((attn_bwd_q_kernel<DC, LPQ>), dim3(cdiv(Nq * LPQ, 64), B * H), dim3(64), 0, s, q, k, v, (const float*)f.o, dout, (const float*)f.lse, H, Nq,
-                           Nk, sc, dq, delta);
-        if (dk && dv)
-            hipLaunchKernelGGL((attn_bwd_kv_kernel<DC, LPQ>), dim3(cdiv(Nk * LPQ, 64), B * H), dim3(64), 0, s, q, k, v, dout, (const float*)f.lse,
-                               (const float*)delta, H, Nq, Nk, sc, dk, dv);
-    }
-    // ---- MFMA attention (head dims 32 / 40 / 64 / 80): prep passes + the three kernels above
-    static bool attn_on_mfma(int D) {
-        static const bool valu = dev_env("GL_TRAIN_ATTN_VALU") && atoi(dev_env("GL_TRAIN_ATTN_VALU")) != 0;
-        return !valu && (D == 32 || D == 40 || D == 64 || D == 80);
-    }
-    APrep attn_prep(const float* x, int B, int N, int H, int D, float mul) const {
-        const int Npad = round_up(N, 64), DP = round_up(D, 16), DPO = round_up(D, 32);
-        const size_t nr = (size_t)B * H * Npad * DP, nt = (size_t)B * H * DPO * Npad;
-        bf16* rh = ar.get<bf16>(nr); bf16* rl = ar.get<bf16>(nr); bf16* th = ar.get<bf16>(nt); bf16* tl = ar.get<bf16>(nt);
-        const size_t total = (size_t)B * H * Npad * std::max(DP, DPO);
-        hipLaunchKernelGGL(attn_prep_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65535 * 16)), dim3(256), 0, s, x, N, H, D, mul, Npad, DP, DPO, rh, rl, th, tl,
-                           total);
-        return APrep{rh, rl, th, tl, Npad};
-    }
-    template <int DP, int DPO>
-    void attn_mfma_fwd_d(const APrep& Q, const APrep& K, const APrep& V, int B, int H, int D, int Nq, int Nk, float* o, float* lse) const {
-        hipLaunchKernelGGL((attn_mfma_fwd_kernel<DP, DPO>), dim3(Q.Npad / 32, B * H), dim3(64), 0, s, Q, K, V, H, D, Nq, Nk, o, lse);
-    }
-    template <int DP, int DPO>
-    void attn_mfma_bwd_d(const APrep& Q, const APrep& K, const APrep& V, const APrep& G, const float* lp, const float* dp, int B, int H, int D, int Nq, int Nk,
-                         float sc, float* dq, float* dk, float* dv) const {
-        hipLaunchKernelGGL((attn_mfma_bwd_q_kernel<DP, DPO>), dim3(Q.Npad / 32, B * H), dim3(64), 0, s, Q, K, V, G, lp, dp, H, D, Nq, Nk, sc, dq);
-        if (dk && dv) hipLaunchKernelGGL((attn_mfma_bwd_kv_kernel<DP, DPO>), dim3(K.Npad / 32, B * H), dim3(64), 0, s, Q, K, V, G, lp, dp, H, D, Nq, Nk, dk, dv);
-    }
-    Attn attn_fwd_mfma(int D, const float* q, const float* k, const float* v, int B, int H, int Nq, int Nk) const {
-        Attn a{f32((size_t)B * Nq * H * D), f32((size_t)B * H * Nq)};
-        const size_t mk = ar.mark();
-        const float sc = 1.f / sqrtf((float)D);
-        const APrep Q = attn_prep(q, B, Nq, H, D, sc), K = attn_prep(k, B, Nk, H, D, 1.f), V = attn_prep(v, B, Nk, H, D, 1.f);
-        switch (D) {
-            case 32: attn_mfma_fwd_d<32, 32>(Q, K, V, B, H, D, Nq, Nk, a.o, a.lse); break;
-            case 40: attn_mfma_fwd_d<48, 64>(Q, K, V, B, H, D, Nq, Nk, a.o, a.lse); break;
-            case 64: attn_mfma_fwd_d<64, 64>(Q, K, V, B, H, D, Nq, Nk, a.o, a.lse); break;
-            default: attn_mfma_fwd_d<80, 96>(Q, K, V, B, H, D, Nq, Nk, a.o, a.lse); break;
-        }
-        ar.release(mk);
-        return a;
-    }
-    void attn_bwd_mfma(int D, const float* q, const float* k, const float* v, const Attn& f, const float* dout, int B, int H, int Nq, int Nk, float* dq,
-                       float* dk, float* dv) const {
-        const size_t mk = ar.mark();
-        const float sc = 1.f / sqrtf((float)D);
-        const APrep Q = attn_prep(q, B, Nq, H, D, sc), K = attn_prep(k, B, Nk, H, D, 1.f), V = attn_prep(v, B, Nk, H, D, 1.f), G = attn_prep(dout, B, Nq, H, D, 1.f);
-        float* lp = f32((size_t)B * H * Q.Npad);
-        float* dp = f32((size_t)B * H * Q.Npad);
-        const size_t total = (size_t)B * H * Q.Npad;
-        hipLaunchKernelGGL(attn_delta_kernel, g1(total), dim3(256), 0, s, (const float*)f.o, dout, (const float*)f.lse, Nq, H, D, Q.Npad, lp, dp, total);
-        switch (D) {
-            case 32: attn_mfma_bwd_d<32, 32>(Q, K, V, G, lp, dp, B, H, D, Nq, Nk, sc, dq, dk, dv); break;
-            case 40: attn_mfma_bwd_d<48, 64>(Q, K, V, G, lp, dp, B, H, D, Nq, Nk, sc, dq, dk, dv); break;
-            case 64: attn_mfma_bwd_d<64, 64>(Q, K, V, G, lp, dp, B, H, D, Nq, Nk, sc, dq, dk, dv); break;
-            default: attn_mfma_bwd_d<80, 96>(Q, K, V, G, lp, dp, B, H, D, Nq, Nk, sc, dq, dk, dv); break;
-        }
-        ar.release(mk);
-    }
-    Attn attn_fwd(int D, const float* q, const float* k, const float* v, int B, int H, int Nq, int Nk) const {
-        if (attn_on_mfma(D)) return attn_fwd_mfma(D, q, k, v, B, H, Nq, Nk);
-        switch (D) {
-            case 32: return attn_fwd_d<32, 1>(q, k, v, B, H, Nq, Nk);
-            case 40: return attn_fwd_d<40, 1>(q, k, v, B, H, Nq, Nk);
-            case 64: return attn_fwd_d<32, 2>(q, k, v, B, H, Nq, Nk);
-            case 80: return attn_fwd_d<40, 2>(q, k, v, B, H, Nq, Nk);
-            case 160: return attn_fwd_d<40, 4>(q, k, v, B, H, Nq, Nk);
-            default: throw GlError(GL_ERR_UNSUPPORTED, fmt("training slice: head dim %d (32, 40, 64, 80, 160 are built)", D));
-        }
-    }
-    void attn_bwd(int D, const float* q, const float* k, const float* v, const Attn& f, const float* dout, int B, int H, int Nq, int Nk, float* dq,
-                  float* dk, float* dv) const {
-        if (attn_on_mfma(D)) return attn_bwd_mfma(D, q, k, v, f, dout, B, H, Nq, Nk, dq, dk, dv);
-        switch (D) {
-            case 32: return attn_bwd_d<32, 1>(q, k, v, f, dout, B, H, Nq, Nk, dq, dk, dv);
-            case 40: return attn_bwd_d<40, 1>(q, k, v, f, dout, B, H, Nq, Nk, dq, dk, dv);
-            case 64: return attn_bwd_d<32, 2>(q, k, v, f, dout, B, H, Nq, Nk, dq, dk, dv);
-            case 80: return attn_bwd_d<40, 2>(q, k, v, f, dout, B, H, Nq, Nk, dq, dk, dv);
-            case 160: return attn_bwd_d<40, 4>(q, k, v, f, dout, B, H, Nq, Nk, dq, dk, dv);
-            default: throw GlError(GL_ERR_UNSUPPORTED, "training slice: head dim");
-        }
-    }
-    // 3x3 conv, stride 1, pad 1, over pixel rows a [B][H*W][Cin] (fp32; cast to bf16 for the implicit-GEMM kernel of gemm.hip) with
-    // an OIHW fp32 weight -> [B][H*W][Cout] fp32 (+ bias). dgrad = true: the data gradient of that conv, a [..][Cout] -> [..][Cin].
-    // stride 2 (Downsample: output (H/2) x (W/2)) and ups = 1 (Upsample: nearest 2x in the loader, output 2H x 2W) for the forward only
-    float* conv3(const float* a, int B, int H, int W, const float* w_oihw, const float* bias, int Cin, int Cout, bool dgrad, int stride = 1, int ups = 0) const {
-        const int Ho = stride == 2 ? H / 2 : H << ups, Wo = stride == 2 ? W / 2 : W << ups;
-        const int Ci = dgrad ? Cout : Cin, Co = dgrad ? Cin : Cout, M = B * Ho * Wo;
-        float* out = f32((size_t)M * Co);
-        const size_t mk_ops = ar.mark();   // packed weights / bf16 activation copies: this product's, released behind it
-        if (one_launch() && Ci % 64 == 0) {
-            // one implicit-GEMM launch over 3 Ci input channels: activations (hi | lo | hi) as a two-source concat of the (hi | lo) buffer
-            // with its own first half, weights (hi | hi | lo) along I (cached for frozen convs: flip / transpose for dgrad, split, pack -- once)
-            const size_t nw = (size_t)Co * 9 * Ci;
-            bf16* wp3 = weight_operand(w_oihw, dgrad ? 4 : 3, Cout, Cin, 0, 3 * nw, [&](bf16* d) {
-                const float* src = w_oihw;
-                if (dgrad) {
-                    float* wt = f32((size_t)Cin * Cout * 9);
-                    hipLaunchKernelGGL(conv_dgrad_weight_kernel, g1((size_t)Cin * Cout * 9), dim3(256), 0, s, w_oihw, Cout, Cin, wt);
-                    src = wt;
-                }
-                float* w3 = f32(3 * nw);
-                hipLaunchKernelGGL(conv_w_cat3_kernel, g1(nw), dim3(256), 0, s, src, Co, Ci, w3);
-                ck(pack_conv_weight_launch(w3, d, Co, 3 * Ci, 3, 3, Co, s));
-            });
-            const size_t na = (size_t)B * H * W * Ci;
-            bf16* a2 = ar.get<bf16>(2 * na);
-            hipLaunchKernelGGL(cat2_rows_kernel, g1(na), dim3(256), 0, s, a, na, Ci, a2);
-            AOperand A{};
-            A.p0 = a2; A.C0 = 2 * Ci; A.ld0 = 2 * Ci; A.p1 = a2; A.C1 = Ci; A.ld1 = 2 * Ci; A.mode = A_CONV3;
-            A.Hin = H; A.Win = W; A.Ho = Ho; A.Wo = Wo; A.stride = stride; A.ups = ups; A.pad_lo = 1;
-            Epilogue E;
-            epilogue_defaults(E);
-            E.out = out; E.ldo = Co; E.out_f32 = 1; E.bias = bias; E.rows_per_b = Ho * Wo;
-            ck(gemm_launch(A, wp3, M, Co, 27 * Ci, E, ws, ws_bytes, s));
-            ar.release(mk_ops);
-            return out;
-        }
-        const float* wsrc = w_oihw;
-        if (dgrad) {
-            float* wt = f32((size_t)Cin * Cout * 9);
-            hipLaunchKernelGGL(conv_dgrad_weight_kernel, g1((size_t)Cin * Cout * 9), dim3(256), 0, s, w_oihw, Cout, Cin, wt);
-            wsrc = wt;
-        }
-        bf16* wp = ar.get<bf16>((size_t)Co * 9 * Ci);
-        ck(pack_conv_weight_launch(wsrc, wp, Co, Ci, 3, 3, Co, s));
-        bf16* wp_lo = nullptr;
-        if (split_precision()) {
-            const size_t nw = (size_t)Co * 9 * Ci;
-            float* wres = f32(nw);
-            hipLaunchKernelGGL(bf16_residual_kernel, g1(nw), dim3(256), 0, s, wsrc, nw, wres);
-            wp_lo = ar.get<bf16>(nw);
-            ck(pack_conv_weight_launch(wres, wp_lo, Co, Ci, 3, 3, Co, s));
-        }
-        const Split av = to_bf16(a, (size_t)B * H * W * Ci);
-        auto one = [&](const bf16* ap, const bf16* wq, const float* bb, float* o) {
-            AOperand A{};
-            A.p0 = ap; A.C0 = Ci; A.ld0 = Ci; A.mode = A_CONV3;
-            A.Hin = H; A.Win = W; A.Ho = Ho; A.Wo = Wo; A.stride = stride; A.ups = ups; A.pad_lo = 1;
-            Epilogue E;
-            epilogue_defaults(E);
-            E.out = o; E.ldo = Co; E.out_f32 = 1; E.bias = bb; E.rows_per_b = Ho * Wo;
-            ck(gemm_launch(A, wq, M, Co, 9 * Ci, E, ws, ws_bytes, s));
-        };
-        one(av.hi, wp, bias, out);
-        if (av.lo && wp_lo) {
-            const size_t mk = ar.mark();
-            float* t1 = f32((size_t)M * Co);
-            float* t2 = f32((size_t)M * Co);
-            one(av.lo, wp, nullptr, t1);
-            one(av.hi, wp_lo, nullptr, t2);
-            hipLaunchKernelGGL(add3_kernel, g1((size_t)M * Co), dim3(256), 0, s, out, (const float*)t1, (const float*)t2, (size_t)M * Co);
-            ar.release(mk);
-        }
-        ar.release(mk_ops);
+
+    float* silu(const float* x, size_t n) const { return ew_new(silu_kernel, n, n, x, n); }
+    float* geglu_fwd(const float* u, int R, int I) const { return ew_new(geglu_fwd_kernel, (size_t)R * I, (size_t)R * I, u, R, I); }
+    float* geglu_bwd(const float* dh, const float* u, int R, int I) const { return ew_new(geglu_bwd_kernel, (size_t)R * 2 * I, (size_t)R * I, dh, u, R, I); }
+    float* gated_add(const float* a, const float* b, const float* alpha, float scale, size_t n, float* out = nullptr) const {
+        if (!out) out = f32(n);
+        ew(gated_add_kernel, n, a, b, alpha, scale, n, out);
         return out;
     }
-    struct GN { float* a; float* xhat; float* rstd; };
-    GN gn_silu_fwd(const float* x, int B, int HW, int Cc, const float* g, const float* b, bool silu = true, float eps = 1e-5f) const {
-        GN r{f32((size_t)B * HW * Cc), f32((size_t)B * HW * Cc), f32((size_t)B * 32)};
-        hipLaunchKernelGGL(gn_silu_fwd_kernel, dim3(32, B), dim3(256), 0, s, x, g, b, HW, Cc, r.xhat, r.rstd, r.a, silu ? 1 : 0, eps);
-        return r;
-    }
-    void gn_silu_bwd(const float* da, const GN& f, const float* g, const float* b, int B, int HW, int Cc, float* dx, bool accumulate, bool silu = true) const {
-        hipLaunchKernelGGL(gn_silu_bwd_kernel, dim3(32, B), dim3(256), 0, s, da, (const float*)f.xhat, (const float*)f.rstd, g, b, HW, Cc, dx, accumulate ? 1 : 0,
-                           silu ? 1 : 0);
-    }
-    void add(float* dst, const float* src, size_t n) const { hipLaunchKernelGGL(add_inplace_kernel, g1(n), dim3(256), 0, s, dst, src, n); }
-    // rows [B][rows_per_b][Cc] of a [B][stride_rows][Cc] tensor starting at row0 -> a packed copy, and back
+    float* gated_scale(const float* a, const float* alpha, float scale, size_t n) const { return ew_new(gated_scale_kernel, n, n, a, alpha, scale, n); }
+    void add(float* dst, const float* src, size_t n) const { ew(add_inplace_kernel, n, dst, src, n); }
     float* slice_rows(const float* src, int B, int stride_rows, int row0, int rows, int Cc) const {
         float* d = f32((size_t)B * rows * Cc);
         hip(hipMemcpy2DAsync(d, (size_t)rows * Cc * 4, src + (size_t)row0 * Cc, (size_t)stride_rows * Cc * 4, (size_t)rows * Cc * 4, B, hipMemcpyDeviceToDevice, s),
@@ -1171,6 +1114,66 @@ struct Ctx {
         hip(hipMemcpy2DAsync(dst + (size_t)row0 * Cc, (size_t)stride_rows * Cc * 4, src, (size_t)rows * Cc * 4, (size_t)rows * Cc * 4, B, hipMemcpyDeviceToDevice, s),
             "hipMemcpy2DAsync");
     }
+
+    // ---- attention on row-major q [B][Nq][H D], k / v [B][Nk][H D]; dk, dv null: dq only
+    APrep attn_prep(const float* x, int B, int N, int H, int D, float mul) const {
+        const int Npad = round_up(N, 64), DP = round_up(D, 16), DPO = round_up(D, 32);
+        const size_t nr = (size_t)B * H * Npad * DP, nt = (size_t)B * H * DPO * Npad;
+        bf16* rh = ar.get<bf16>(nr); bf16* rl = ar.get<bf16>(nr); bf16* th = ar.get<bf16>(nt); bf16* tl = ar.get<bf16>(nt);
+        const size_t total = (size_t)B * H * Npad * std::max(DP, DPO);
+        hipLaunchKernelGGL(attn_prep_kernel, dim3((unsigned)std::min<size_t>((total + 255) / 256, 65535 * 16)), dim3(256), 0, s, x, N, H, D, mul, Npad, DP, DPO, rh, rl, th,
+                           tl, total);
+        return APrep{rh, rl, th, tl, Npad};
+    }
+    Attn attn_fwd(int D, const float* q, const float* k, const float* v, int B, int H, int Nq, int Nk) const {
+        const float sc = 1.f / sqrtf((float)D);
+        if (attn_on_mfma(D)) {
+            Attn a{f32((size_t)B * Nq * H * D), f32((size_t)B * H * Nq)};
+            const size_t mk = ar.mark();
+            const APrep Q = attn_prep(q, B, Nq, H, D, sc), K = attn_prep(k, B, Nk, H, D, 1.f), V = attn_prep(v, B, Nk, H, D, 1.f);
+            with_mfma_dims(D, [&](auto dp, auto dpo) {
+                hipLaunchKernelGGL((attn_mfma_fwd_kernel<dp(), dpo()>), dim3(Q.Npad / 32, B * H), dim3(64), 0, s, Q, K, V, H, D, Nq, Nk, a.o, a.lse);
+            });
+            ar.release(mk);
+            return a;
+        }
+        Attn a{};
+        const bool built = with_valu_dims(D, [&](auto dc, auto lpq) {
+            a = Attn{f32((size_t)B * Nq * H * D), f32((size_t)B * H * Nq)};
+            hipLaunchKernelGGL((attn_fwd_kernel<dc(), lpq()>), dim3(cdiv(Nq * lpq(), 64), B * H), dim3(64), 0, s, q, k, v, H, Nq, Nk, sc, a.o, a.lse);
+        });
+        if (!built) throw GlError(GL_ERR_UNSUPPORTED, fmt("training slice: head dim %d (32, 40, 64, 80, 160 are built)", D));
+        return a;
+    }
+
+    void attn_bwd(int D, const float* q, const float* k, const float* v, const Attn& f, const float* dout, int B, int H, int Nq, int Nk, float* dq, float* dk,
+                       float* dv) const {
+        const float sc = 1.f / sqrtf((float)D);
+        if (attn_on_mfma(D)) {
+            const size_t mk = ar.mark();
+            const APrep Q = attn_prep(q, B, Nq, H, D, sc), K = attn_prep(k, B, Nk, H, D, 1.f), V = attn_prep(v, B, Nk, H, D, 1.f),
+                        G = attn_prep(dout, B, Nq, H, D, 1.f);
+            float* lp = f32((size_t)B * H * Q.Npad);
+            float* dp = f32((size_t)B * H * Q.Npad);
+            const size_t total = (size_t)B * H * Q.Npad;
+            ew(attn_delta_kernel, total, f.o, dout, f.lse, Nq, H, D, Q.Npad, lp, dp, total);
+            with_mfma_dims(D, [&](auto dpad, auto dpo) {
+                hipLaunchKernelGGL((attn_mfma_bwd_q_kernel<dpad(), dpo()>), dim3(Q.Npad / 32, B * H), dim3(64), 0, s, Q, K, V, G, lp, dp, H, D, Nq, Nk, sc, dq);
+                if (dk && dv)
+                    hipLaunchKernelGGL((attn_mfma_bwd_kv_kernel<dpad(), dpo()>), dim3(K.Npad / 32, B * H), dim3(64), 0, s, Q, K, V, G, lp, dp, H, D, Nq, Nk, dk, dv);
+            });
+            ar.release(mk);
+            return;
+        }
+        const bool built = with_valu_dims(D, [&](auto dc, auto lpq) {
+            float* delta = f32((size_t)B * H * Nq);
+            hipLaunchKernelGGL((attn_bwd_q_kernel<dc(), lpq()>), dim3(cdiv(Nq * lpq(), 64), B * H), dim3(64), 0, s, q, k, v, f.o, dout, f.lse, H, Nq, Nk, sc, dq, delta);
+            if (dk && dv)
+                hipLaunchKernelGGL((attn_bwd_kv_kernel<dc(), lpq()>), dim3(cdiv(Nk * lpq(), 64), B * H), dim3(64), 0, s, q, k, v, dout, f.lse, delta, H, Nq, Nk, sc, dk, dv);
+        });
+        if (!built) throw GlError(GL_ERR_UNSUPPORTED, "training slice: head dim");
+    }
+
 };
 
 }  // namespace
@@ -1184,17 +1187,43 @@ int adamw_step(float* p, const float* g, float* m, float* v, size_t n, double lr
     return GL_OK;
 }
 
-// Everything the backward of a BasicTransformerBlock needs from its forward (all in the arena)
+
+// ---- the UNet's layer kinds. *_forward keeps what the backward needs in the arena; *_backward takes g = dL/dy
+// Everything the backward of a BasicTransformerBlock needs from its forward
 struct BlockSaved {
     Ctx::LN n1, nf1, nf2, n2, n3;
     Ctx::Attn a1, af, a2;
     float *q1, *k1, *v1, *qf, *kf, *vf, *q2, *k2, *v2;
     float *af_vis, *of, *uf, *hf, *ff_f, *u3;
 };
+struct STSaved {
+    Ctx::GN n0;
+    BlockSaved blk;
+};
+struct ResSaved {
+    Ctx::GN n1, n2;
+};
+
+// The frame of the four slice entry points: forward (writes y [n]), loss = mse_loss(y, target) and its gradient g, backward
+// (g -> dL/dx [n_dx], returned), dx copied out
+template <class Fwd, class Bwd>
+static int with_mse_loss(Arena& ar, float* ws, size_t ws_bytes, hipStream_t s, const float* y, const float* target, size_t n, float* loss, float* dx, size_t n_dx,
+                  Fwd&& forward, Bwd&& backward) {
+    try {
+        Ctx c{ar, ws, ws_bytes, s};
+        forward(c);
+        float* g = c.mse_loss(y, target, n, loss);
+        const float* gx = backward(c, g);
+        c.hip(hipMemcpyAsync(dx, gx, n_dx * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
+        c.hip(hipGetLastError(), "training slice kernel launch");
+    } catch (const GlError& e) {
+        return set_error(e.code, "%s", e.what());
+    }
+    return GL_OK;
+}
 
 // y = BasicTransformerBlock(x, context, objs) (attention.py:333-338), everything the backward needs kept in the arena
 static BlockSaved block_forward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const float* x, const float* objs, const float* context, float* y) {
-    hipStream_t s = c.s;
     const int B = d.B, N = d.N, Ng = d.Ng, C = d.C, H = d.heads, D = C / H, T = N + Ng, M = B * N, MT = B * T, MC = B * d.ctx_T, KD = d.ctx_dim;
     const size_t nx = (size_t)M * C;
     BlockSaved S;
@@ -1205,8 +1234,7 @@ static BlockSaved block_forward(const Ctx& c, const TrainBlockDims& d, const flo
     S.v1 = c.lin_fwd(S.n1.y, M, C, P[TP_A1_V], nullptr, C);
     S.a1 = c.attn_fwd(D, S.q1, S.k1, S.v1, B, H, N, N);
     float* o1 = c.lin_fwd(S.a1.o, M, C, P[TP_A1_O], P[TP_A1_OB], C);
-    float* x1 = c.f32(nx);
-    hipLaunchKernelGGL(gated_add_kernel, Ctx::g1(nx), dim3(256), 0, s, x, (const float*)o1, (const float*)nullptr, 1.f, nx, x1);
+    float* x1 = c.gated_add(x, o1, nullptr, 1.f, nx);
     // fuser (attention.py:236-244): x2 = x1 + scale tanh(alpha_attn) attn(norm1([x1 ; linear(objs)]))[:, :N]
     float* ol = c.lin_fwd(objs, B * Ng, KD, P[TP_F_LIN_W], P[TP_F_LIN_B], C);
     float* cat = c.f32((size_t)MT * C);
@@ -1219,16 +1247,13 @@ static BlockSaved block_forward(const Ctx& c, const TrainBlockDims& d, const flo
     S.af = c.attn_fwd(D, S.qf, S.kf, S.vf, B, H, T, T);
     S.af_vis = c.slice_rows(S.af.o, B, T, 0, N, C);
     S.of = c.lin_fwd(S.af_vis, M, C, P[TP_F_O], P[TP_F_OB], C);
-    float* x2 = c.f32(nx);
-    hipLaunchKernelGGL(gated_add_kernel, Ctx::g1(nx), dim3(256), 0, s, (const float*)x1, (const float*)S.of, P[TP_F_ALPHA_ATTN], d.fuser_scale, nx, x2);
+    float* x2 = c.gated_add(x1, S.of, P[TP_F_ALPHA_ATTN], d.fuser_scale, nx);
     //        x3 = x2 + scale tanh(alpha_dense) ff(norm2(x2))
     S.nf2 = c.ln_fwd(x2, M, C, P[TP_F_N2_W], P[TP_F_N2_B]);
     S.uf = c.lin_fwd(S.nf2.y, M, C, P[TP_F_FF1_W], P[TP_F_FF1_B], 8 * C);
-    S.hf = c.f32((size_t)M * 4 * C);
-    hipLaunchKernelGGL(geglu_fwd_kernel, Ctx::g1((size_t)M * 4 * C), dim3(256), 0, s, (const float*)S.uf, M, 4 * C, S.hf);
+    S.hf = c.geglu_fwd(S.uf, M, 4 * C);
     S.ff_f = c.lin_fwd(S.hf, M, 4 * C, P[TP_F_FF2_W], P[TP_F_FF2_B], C);
-    float* x3 = c.f32(nx);
-    hipLaunchKernelGGL(gated_add_kernel, Ctx::g1(nx), dim3(256), 0, s, (const float*)x2, (const float*)S.ff_f, P[TP_F_ALPHA_DENSE], d.fuser_scale, nx, x3);
+    float* x3 = c.gated_add(x2, S.ff_f, P[TP_F_ALPHA_DENSE], d.fuser_scale, nx);
     // x4 = attn2(norm2(x3), context) + x3
     S.n2 = c.ln_fwd(x3, M, C, P[TP_NORM2_W], P[TP_NORM2_B]);
     S.q2 = c.lin_fwd(S.n2.y, M, C, P[TP_A2_Q], nullptr, C);
@@ -1236,28 +1261,24 @@ static BlockSaved block_forward(const Ctx& c, const TrainBlockDims& d, const flo
     S.v2 = c.lin_fwd(context, MC, KD, P[TP_A2_V], nullptr, C);
     S.a2 = c.attn_fwd(D, S.q2, S.k2, S.v2, B, H, N, d.ctx_T);
     float* o2 = c.lin_fwd(S.a2.o, M, C, P[TP_A2_O], P[TP_A2_OB], C);
-    float* x4 = c.f32(nx);
-    hipLaunchKernelGGL(gated_add_kernel, Ctx::g1(nx), dim3(256), 0, s, (const float*)x3, (const float*)o2, (const float*)nullptr, 1.f, nx, x4);
+    float* x4 = c.gated_add(x3, o2, nullptr, 1.f, nx);
     // y = ff(norm3(x4)) + x4
     S.n3 = c.ln_fwd(x4, M, C, P[TP_NORM3_W], P[TP_NORM3_B]);
     S.u3 = c.lin_fwd(S.n3.y, M, C, P[TP_FF1_W], P[TP_FF1_B], 8 * C);
-    float* h3 = c.f32((size_t)M * 4 * C);
-    hipLaunchKernelGGL(geglu_fwd_kernel, Ctx::g1((size_t)M * 4 * C), dim3(256), 0, s, (const float*)S.u3, M, 4 * C, h3);
+    float* h3 = c.geglu_fwd(S.u3, M, 4 * C);
     float* ff3 = c.lin_fwd(h3, M, 4 * C, P[TP_FF2_W], P[TP_FF2_B], C);
-    hipLaunchKernelGGL(gated_add_kernel, Ctx::g1(nx), dim3(256), 0, s, (const float*)x4, (const float*)ff3, (const float*)nullptr, 1.f, nx, y);
+    c.gated_add(x4, ff3, nullptr, 1.f, nx, y);
     return S;
 }
 
 // g: dL/dy on entry, dL/dx on return (the running gradient of the residual stream). dobjs and G[slot] (fuser.* only) are written.
-static void block_backward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const BlockSaved& S, const float* objs, float* g, float* dobjs,
-                           float* const* G) {
+static void block_backward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const BlockSaved& S, const float* objs, float* g, float* dobjs, float* const* G) {
     hipStream_t s = c.s;
     const int B = d.B, N = d.N, Ng = d.Ng, C = d.C, H = d.heads, D = C / H, T = N + Ng, M = B * N, MT = B * T, KD = d.ctx_dim;
     const size_t nx = (size_t)M * C;
     {   // y = x4 + ff(norm3(x4)): frozen weights, data gradients only
         float* g_h3 = c.lin_dgrad(g, M, C, P[TP_FF2_W], 4 * C);
-        float* g_u3 = c.f32((size_t)M * 8 * C);
-        hipLaunchKernelGGL(geglu_bwd_kernel, Ctx::g1((size_t)M * 4 * C), dim3(256), 0, s, (const float*)g_h3, (const float*)S.u3, M, 4 * C, g_u3);
+        float* g_u3 = c.geglu_bwd(g_h3, S.u3, M, 4 * C);
         float* g_n3 = c.lin_dgrad(g_u3, M, 8 * C, P[TP_FF1_W], C);
         c.ln_bwd(g_n3, S.n3, P[TP_NORM3_W], M, C, g, true, nullptr, nullptr);
     }
@@ -1269,25 +1290,18 @@ static void block_backward(const Ctx& c, const TrainBlockDims& d, const float* c
         c.ln_bwd(g_n2, S.n2, P[TP_NORM2_W], M, C, g, true, nullptr, nullptr);
     }
     {   // x3 = x2 + g_d ff(norm2(x2)), g_d = scale tanh(alpha_dense): the fuser's feed-forward, TRAINABLE
-        if (G[TP_F_ALPHA_DENSE])
-            c.dot_reduce((const float*)g, (const float*)S.ff_f, nx, P[TP_F_ALPHA_DENSE], d.fuser_scale, 0,
-                               G[TP_F_ALPHA_DENSE]);
-        float* g_ff = c.f32(nx);
-        hipLaunchKernelGGL(gated_scale_kernel, Ctx::g1(nx), dim3(256), 0, s, (const float*)g, P[TP_F_ALPHA_DENSE], d.fuser_scale, nx, g_ff);
+        if (G[TP_F_ALPHA_DENSE]) c.dot_reduce(g, S.ff_f, nx, P[TP_F_ALPHA_DENSE], d.fuser_scale, 0, G[TP_F_ALPHA_DENSE]);
+        float* g_ff = c.gated_scale(g, P[TP_F_ALPHA_DENSE], d.fuser_scale, nx);
         c.lin_wgrad(g_ff, S.hf, M, C, 4 * C, G[TP_F_FF2_W], G[TP_F_FF2_B]);
         float* g_hf = c.lin_dgrad(g_ff, M, C, P[TP_F_FF2_W], 4 * C);
-        float* g_uf = c.f32((size_t)M * 8 * C);
-        hipLaunchKernelGGL(geglu_bwd_kernel, Ctx::g1((size_t)M * 4 * C), dim3(256), 0, s, (const float*)g_hf, (const float*)S.uf, M, 4 * C, g_uf);
+        float* g_uf = c.geglu_bwd(g_hf, S.uf, M, 4 * C);
         c.lin_wgrad(g_uf, S.nf2.y, M, 8 * C, C, G[TP_F_FF1_W], G[TP_F_FF1_B]);
         float* g_nf2 = c.lin_dgrad(g_uf, M, 8 * C, P[TP_F_FF1_W], C);
         c.ln_bwd(g_nf2, S.nf2, P[TP_F_N2_W], M, C, g, true, G[TP_F_N2_W], G[TP_F_N2_B]);
     }
     {   // x2 = x1 + g_a attn(norm1([x1 ; linear(objs)]))[:, :N]: the fuser's attention, TRAINABLE
-        if (G[TP_F_ALPHA_ATTN])
-            c.dot_reduce((const float*)g, (const float*)S.of, nx, P[TP_F_ALPHA_ATTN], d.fuser_scale, 0,
-                               G[TP_F_ALPHA_ATTN]);
-        float* g_of = c.f32(nx);
-        hipLaunchKernelGGL(gated_scale_kernel, Ctx::g1(nx), dim3(256), 0, s, (const float*)g, P[TP_F_ALPHA_ATTN], d.fuser_scale, nx, g_of);
+        if (G[TP_F_ALPHA_ATTN]) c.dot_reduce(g, S.of, nx, P[TP_F_ALPHA_ATTN], d.fuser_scale, 0, G[TP_F_ALPHA_ATTN]);
+        float* g_of = c.gated_scale(g, P[TP_F_ALPHA_ATTN], d.fuser_scale, nx);
         c.lin_wgrad(g_of, S.af_vis, M, C, C, G[TP_F_O], G[TP_F_OB]);
         float* g_af_vis = c.lin_dgrad(g_of, M, C, P[TP_F_O], C);
         float* g_af = c.f32((size_t)MT * C);      // the grounding-token rows of the attention output are dropped by [:, :N]: zero gradient
@@ -1332,32 +1346,17 @@ static void block_check(const TrainBlockDims& d, const float* const* P) {
 
 int block_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainBlockDims& d, const float* const* P, const float* x, const float* objs,
                      const float* context, const float* target, float* y, float* loss, float* dx, float* dobjs, float* const* G, hipStream_t s) {
-    try {
-        block_check(d, P);
-        Ctx c{ar, ws, ws_bytes, s};
-        const size_t nx = (size_t)d.B * d.N * d.C;
-        const BlockSaved S = block_forward(c, d, P, x, objs, context, y);
-        // loss (trainer.py:366) and its gradient
-        c.dot_reduce((const float*)y, target, nx, (const float*)nullptr, 1.f, 1, loss);
-        float* g = c.f32(nx);
-        hipLaunchKernelGGL(mse_grad_kernel, Ctx::g1(nx), dim3(256), 0, s, (const float*)y, target, nx, g);
-        block_backward(c, d, P, S, objs, g, dobjs, G);
-        c.hip(hipMemcpyAsync(dx, g, nx * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
-        c.hip(hipGetLastError(), "training slice kernel launch");
-    } catch (const GlError& e) {
-        return set_error(e.code, "%s", e.what());
-    }
-    return GL_OK;
+    const size_t nx = (size_t)d.B * d.N * d.C;
+    BlockSaved S;
+    return with_mse_loss(
+        ar, ws, ws_bytes, s, y, target, nx, loss, dx, nx, [&](const Ctx& c) { block_check(d, P); S = block_forward(c, d, P, x, objs, context, y); },
+        [&](const Ctx& c, float* g) { block_backward(c, d, P, S, objs, g, dobjs, G); return g; });
 }
 
 // SpatialTransformer.forward (attention.py:366-376) around one BasicTransformerBlock: x + proj_out(block(proj_in(norm(x)))), norm =
 // GroupNorm(32, eps 1e-6) without activation, proj_in / proj_out 1 x 1 convs = Linears over pixel rows. norm / proj_* are SD layers
 // (frozen); gradients: the block's fuser.* parameters, dx, dobjs. P / G: [norm.w, norm.b, proj_in.w, proj_in.b, <37 block slots>,
 // proj_out.w, proj_out.b].
-struct STSaved {
-    Ctx::GN n0;
-    BlockSaved blk;
-};
 static void st_check(const TrainBlockDims& d, const float* const* P) {
     for (int i = 0; i < ST_COUNT; ++i)
         if (!P[i]) throw GlError(GL_ERR_ARG, fmt("st_train_step: parameter slot %d is null", i));
@@ -1372,12 +1371,10 @@ static STSaved st_forward(const Ctx& c, const TrainBlockDims& d, const float* co
     float* yb = c.f32(nx);
     S.blk = block_forward(c, d, P + ST_BLOCK0, t0, objs, context, yb);
     float* po = c.lin_fwd(yb, M, C, P[ST_POUT_W], P[ST_POUT_B], C);
-    hipLaunchKernelGGL(gated_add_kernel, Ctx::g1(nx), dim3(256), 0, c.s, x, (const float*)po, (const float*)nullptr, 1.f, nx, y);
+    c.gated_add(x, po, nullptr, 1.f, nx, y);
     return S;
 }
-// g: dL/dy on entry, dL/dx on return
-static void st_backward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const STSaved& S, const float* objs, float* g, float* dobjs,
-                        float* const* G) {
+static void st_backward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const STSaved& S, const float* objs, float* g, float* dobjs, float* const* G) {
     const int B = d.B, N = d.N, C = d.C, M = B * N;
     float* g_b = c.lin_dgrad(g, M, C, P[ST_POUT_W], C);                              // through proj_out
     block_backward(c, d, P + ST_BLOCK0, S.blk, objs, g_b, dobjs, G + ST_BLOCK0);     // g_b: dL/d(block output) -> dL/d(block input)
@@ -1387,30 +1384,17 @@ static void st_backward(const Ctx& c, const TrainBlockDims& d, const float* cons
 
 int st_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainBlockDims& d, const float* const* P, const float* x, const float* objs,
                   const float* context, const float* target, float* y, float* loss, float* dx, float* dobjs, float* const* G, hipStream_t s) {
-    try {
-        st_check(d, P);
-        Ctx c{ar, ws, ws_bytes, s};
-        const size_t nx = (size_t)d.B * d.N * d.C;
-        const STSaved S = st_forward(c, d, P, x, objs, context, y);
-        c.dot_reduce((const float*)y, target, nx, (const float*)nullptr, 1.f, 1, loss);
-        float* g = c.f32(nx);
-        hipLaunchKernelGGL(mse_grad_kernel, Ctx::g1(nx), dim3(256), 0, s, (const float*)y, target, nx, g);
-        st_backward(c, d, P, S, objs, g, dobjs, G);
-        c.hip(hipMemcpyAsync(dx, g, nx * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
-        c.hip(hipGetLastError(), "training slice kernel launch");
-    } catch (const GlError& e) {
-        return set_error(e.code, "%s", e.what());
-    }
-    return GL_OK;
+    const size_t nx = (size_t)d.B * d.N * d.C;
+    STSaved S;
+    return with_mse_loss(
+        ar, ws, ws_bytes, s, y, target, nx, loss, dx, nx, [&](const Ctx& c) { st_check(d, P); S = st_forward(c, d, P, x, objs, context, y); },
+        [&](const Ctx& c, float* g) { st_backward(c, d, P, S, objs, g, dobjs, G); return g; });
 }
 
 // Forward + backward of one ResBlock (openaimodel.py:154-232, no up / down, no scale-shift norm) under mse_loss(y, target): every
 // parameter of it is frozen in the reference's trainer (trainer.py:217-245), so what the training step needs from a ResBlock is the
 // gradient w.r.t. its INPUT -- the path by which the loss reaches the fusers in front of it. Rows are pixels ([B][H*W][C], the
 // layout of this library; the reference's NCHW is a permutation of it).
-struct ResSaved {
-    Ctx::GN n1, n2;
-};
 static void res_check(const TrainResDims& d, const float* const* P) {
     if (d.Cin % 64 || d.Cout % 64 || d.emb_dim % 64 || d.B < 1 || d.H < 1 || d.W < 1)
         throw GlError(GL_ERR_ARG, "resblock_train_step: Cin, Cout and emb_dim must be multiples of 64");
@@ -1429,15 +1413,14 @@ static ResSaved res_forward(const Ctx& c, const TrainResDims& d, const float* co
     float* h1 = c.conv3(S.n1.a, B, d.H, d.W, P[RP_C1_W], P[RP_C1_B], Cin, Cout, false);
     float* eo = c.lin_fwd(silu_emb, B, d.emb_dim, P[RP_EMB_W], P[RP_EMB_B], Cout);
     float* h2 = c.f32(ny);
-    hipLaunchKernelGGL(add_per_sample_kernel, Ctx::g1(ny), dim3(256), 0, c.s, (const float*)h1, (const float*)eo, HW, Cout, ny, h2);
+    c.ew(add_per_sample_kernel, ny, h1, eo, HW, Cout, ny, h2);
     S.n2 = c.gn_silu_fwd(h2, B, HW, Cout, P[RP_GN2_W], P[RP_GN2_B]);
     float* h3 = c.conv3(S.n2.a, B, d.H, d.W, P[RP_C2_W], P[RP_C2_B], Cout, Cout, false);
     const float* sk = x;
     if (Cin != Cout) sk = c.lin_fwd(x, M, Cin, P[RP_SKIP_W], P[RP_SKIP_B], Cout);      // the 1 x 1 conv is a Linear over pixel rows
-    hipLaunchKernelGGL(gated_add_kernel, Ctx::g1(ny), dim3(256), 0, c.s, sk, (const float*)h3, (const float*)nullptr, 1.f, ny, y);
+    c.gated_add(sk, h3, nullptr, 1.f, ny, y);
     return S;
 }
-// g [.][Cout]: dL/dy (left untouched when Cin != Cout). Returns dL/dx [.][Cin] (g itself, updated in place, when Cin == Cout)
 static float* res_backward(const Ctx& c, const TrainResDims& d, const float* const* P, const ResSaved& S, float* g) {
     const int B = d.B, HW = d.H * d.W, Cin = d.Cin, Cout = d.Cout, M = B * HW;
     float* g_a2 = c.conv3(g, B, d.H, d.W, P[RP_C2_W], nullptr, Cout, Cout, true);
@@ -1451,23 +1434,12 @@ static float* res_backward(const Ctx& c, const TrainResDims& d, const float* con
 
 int resblock_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainResDims& d, const float* const* P, const float* x, const float* emb,
                         const float* target, float* y, float* loss, float* dx, hipStream_t s) {
-    try {
-        res_check(d, P);
-        Ctx c{ar, ws, ws_bytes, s};
-        const size_t ny = (size_t)d.B * d.H * d.W * d.Cout;
-        float* se = c.f32((size_t)d.B * d.emb_dim);
-        hipLaunchKernelGGL(silu_kernel, Ctx::g1((size_t)d.B * d.emb_dim), dim3(256), 0, s, emb, (size_t)d.B * d.emb_dim, se);
-        const ResSaved S = res_forward(c, d, P, x, se, y);
-        c.dot_reduce((const float*)y, target, ny, (const float*)nullptr, 1.f, 1, loss);
-        float* g = c.f32(ny);
-        hipLaunchKernelGGL(mse_grad_kernel, Ctx::g1(ny), dim3(256), 0, s, (const float*)y, target, ny, g);
-        float* g_x = res_backward(c, d, P, S, g);
-        c.hip(hipMemcpyAsync(dx, g_x, (size_t)d.B * d.H * d.W * d.Cin * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
-        c.hip(hipGetLastError(), "training slice kernel launch");
-    } catch (const GlError& e) {
-        return set_error(e.code, "%s", e.what());
-    }
-    return GL_OK;
+    const size_t rows = (size_t)d.B * d.H * d.W;
+    ResSaved S;
+    return with_mse_loss(
+        ar, ws, ws_bytes, s, y, target, rows * d.Cout, loss, dx, rows * d.Cin,
+        [&](const Ctx& c) { res_check(d, P); S = res_forward(c, d, P, x, c.silu(emb, (size_t)d.B * d.emb_dim), y); },
+        [&](const Ctx& c, float* g) { return res_backward(c, d, P, S, g); });
 }
 
 // Downsample (mode 0: conv3x3 stride 2, openaimodel.py:99-124) / Upsample (mode 1: nearest 2x + conv3x3, openaimodel.py:64-96) of C
@@ -1475,42 +1447,35 @@ int resblock_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainResDim
 static float* resample_forward(const Ctx& c, int mode, int B, int H, int W, int C, const float* w_oihw, const float* bias, const float* x) {
     return c.conv3(x, B, H, W, w_oihw, bias, C, C, false, mode ? 1 : 2, mode ? 1 : 0);
 }
-// g: dL/dy [B][Ho*Wo][C] -> dL/dx [B][H*W][C]
 static float* resample_backward(const Ctx& c, int mode, int B, int H, int W, int C, const float* w_oihw, const float* g) {
     const size_t nx = (size_t)B * H * W * C;
     if (mode == 0) {
         float* z = c.f32(nx);
-        hipLaunchKernelGGL(zero_insert2_kernel, Ctx::g1(nx), dim3(256), 0, c.s, g, H, W, C, nx, z);
+        c.ew(zero_insert2_kernel, nx, g, H, W, C, nx, z);
         return c.conv3(z, B, H, W, w_oihw, nullptr, C, C, true);
     }
     float* gu = c.conv3(g, B, 2 * H, 2 * W, w_oihw, nullptr, C, C, true);
     float* dx = c.f32(nx);
-    hipLaunchKernelGGL(sum2x2_kernel, Ctx::g1(nx), dim3(256), 0, c.s, (const float*)gu, H, W, C, nx, dx);
+    c.ew(sum2x2_kernel, nx, gu, H, W, C, nx, dx);
     return dx;
 }
 
 int resample_train_step(Arena& ar, float* ws, size_t ws_bytes, int mode, int B, int H, int W, int C, const float* w_oihw, const float* bias, const float* x,
                         const float* target, float* y, float* loss, float* dx, hipStream_t s) {
-    try {
-        if (C % 64 || (mode == 0 && ((H | W) & 1)) || B < 1 || mode < 0 || mode > 1) throw GlError(GL_ERR_ARG, "resample_train_step: C % 64, even H / W for mode 0");
-        Ctx c{ar, ws, ws_bytes, s};
-        const int Ho = mode ? 2 * H : H / 2, Wo = mode ? 2 * W : W / 2;
-        const size_t ny = (size_t)B * Ho * Wo * C, nx = (size_t)B * H * W * C;
-        float* yv = resample_forward(c, mode, B, H, W, C, w_oihw, bias, x);
-        c.hip(hipMemcpyAsync(y, yv, ny * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
-        c.dot_reduce((const float*)y, target, ny, (const float*)nullptr, 1.f, 1, loss);
-        float* g = c.f32(ny);
-        hipLaunchKernelGGL(mse_grad_kernel, Ctx::g1(ny), dim3(256), 0, s, (const float*)y, target, ny, g);
-        float* gx = resample_backward(c, mode, B, H, W, C, w_oihw, g);
-        c.hip(hipMemcpyAsync(dx, gx, nx * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
-        c.hip(hipGetLastError(), "training slice kernel launch");
-    } catch (const GlError& e) {
-        return set_error(e.code, "%s", e.what());
-    }
-    return GL_OK;
+    const int Ho = mode ? 2 * H : H / 2, Wo = mode ? 2 * W : W / 2;
+    const size_t ny = (size_t)B * Ho * Wo * C, nx = (size_t)B * H * W * C;
+    return with_mse_loss(
+        ar, ws, ws_bytes, s, y, target, ny, loss, dx, nx,
+        [&](const Ctx& c) {
+            if (C % 64 || (mode == 0 && ((H | W) & 1)) || B < 1 || mode < 0 || mode > 1) throw GlError(GL_ERR_ARG, "resample_train_step: C % 64, even H / W for mode 0");
+            const float* yv = resample_forward(c, mode, B, H, W, C, w_oihw, bias, x);
+            c.hip(hipMemcpyAsync(y, yv, ny * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
+        },
+        [&](const Ctx& c, float* g) { return resample_backward(c, mode, B, H, W, C, w_oihw, g); });
 }
 
-// ======================================================================================================================
+
+
 // The whole training iteration of the reference (trainer.py:353-392: model(input) -> mse_loss(model_output, noise) -> backward) for a
 // UNetModel with the text grounding tokenizer and gatedSA fusers (openaimodel.py:237-464), composed of the slices above:
 //   objs = position_net(boxes, masks, positive_embeddings)          text_grounding_net.py:30-52      TRAINABLE
@@ -1627,21 +1592,6 @@ __global__ void split_kernel(const float* __restrict__ src, int ld, int c0, int 
     dst[i] = accumulate ? dst[i] + v : v;
 }
 
-struct Names {
-    std::unordered_map<std::string, int> idx;
-    const float* const* params;
-    float* const* grads;
-    const float* w(const std::string& k) const {
-        auto it = idx.find(k);
-        if (it == idx.end() || !params[it->second]) throw GlError(GL_ERR_MISSING, "unet_train_step: missing parameter '" + k + "'");
-        return params[it->second];
-    }
-    bool has(const std::string& k) const { auto it = idx.find(k); return it != idx.end() && params[it->second]; }
-    float* g(const std::string& k) const {
-        auto it = idx.find(k);
-        return it == idx.end() ? nullptr : grads[it->second];
-    }
-};
 
 // ---- spatial-map models (grounding_kind 3: canny / depth / normal / hed / sem_grounding_net.py + *_grounding_downsampler.py): the
 // ConvNeXt-tiny tokenizer (convnext.py:36-50, 71-81, 108-112), the GroundingDownsampler and the 4 + k channel first conv, forward in
@@ -1798,21 +1748,35 @@ __global__ void conv4x4s2_dgrad_kernel(const float* __restrict__ g, const float*
     dx[i] = acc;
 }
 
-struct Strides { size_t b, c, y, x; };
-Strides nchw(int Cc, int H, int W) { return {(size_t)Cc * H * W, (size_t)H * W, (size_t)W, 1}; }
-Strides pixel_rows(int Cc, int H, int W) { return {(size_t)H * W * Cc, 1, (size_t)W * Cc, (size_t)Cc}; }
 
-// dst [R][Kp] = src [R][K] zero-padded on the right
-float* pad_cols(const Ctx& c, const float* src, int R, int K, int Kp) {
-    float* d = c.f32((size_t)R * Kp);
-    hipLaunchKernelGGL(pad_cols_kernel, Ctx::g1((size_t)R * Kp), dim3(256), 0, c.s, src, K, Kp, (size_t)R * Kp, d);
-    return d;
+// ---- the model's state_dict by name
+struct Names {
+    std::unordered_map<std::string, int> idx;
+    const float* const* params;
+    float* const* grads;
+    const float* w(const std::string& k) const {
+        auto it = idx.find(k);
+        if (it == idx.end() || !params[it->second]) throw GlError(GL_ERR_MISSING, "unet_train_step: missing parameter '" + k + "'");
+        return params[it->second];
+    }
+    bool has(const std::string& k) const { auto it = idx.find(k); return it != idx.end() && params[it->second]; }
+    float* g(const std::string& k) const {
+        auto it = idx.find(k);
+        return it == idx.end() ? nullptr : grads[it->second];
+    }
+};
+
+// dst [R][Kp] = src [R][K] zero-padded on the right; dst[r][c] (+)= src[r][c0 + c]
+float* pad_cols(const Ctx& c, const float* src, int R, int K, int Kp) { return c.ew_new(pad_cols_kernel, (size_t)R * Kp, (size_t)R * Kp, src, K, Kp, (size_t)R * Kp); }
+void split_cols(const Ctx& c, const float* src, int ld, int c0, int Cc, size_t rows, float* dst, bool accumulate) {
+    c.ew(split_kernel, rows * Cc, src, ld, c0, Cc, rows, dst, accumulate ? 1 : 0);
 }
 // y = x W^T + b and dx = dy W for any contraction length: zero-padded to the GEMM's 64-step (ConvNeXt's first stage has C = 96)
 float* lin_fwd_any(const Ctx& c, const float* x, int M, int K, const float* W, const float* b, int N) {
     if (K % 64 == 0) return c.lin_fwd(x, M, K, W, b, N);
     const int Kp = round_up(K, 64);
-    return c.lin_fwd(pad_cols(c, x, M, K, Kp), M, Kp, pad_cols(c, W, N, K, Kp), b, N);
+    const float* xp = pad_cols(c, x, M, K, Kp);
+    return c.lin_fwd(xp, M, Kp, pad_cols(c, W, N, K, Kp), b, N);
 }
 float* lin_dgrad_any(const Ctx& c, const float* dy, int M, int N, const float* W, int K) {
     if (N % 64 == 0) return c.lin_dgrad(dy, M, N, W, K);
@@ -1822,11 +1786,53 @@ float* lin_dgrad_any(const Ctx& c, const float* dy, int M, int N, const float* W
     c.hip(hipMemcpyAsync(Wp, W, (size_t)N * K * 4, hipMemcpyDeviceToDevice, c.s), "hipMemcpyAsync");
     return c.lin_dgrad(pad_cols(c, dy, M, N, Np), M, Np, Wp, K);
 }
+// the weight gradient of a Linear that ran on operands padded to Kp columns (xp [M][Kp]): formed as [N][Kp], its first K columns copied out
+void lin_wgrad_unpad(const Ctx& c, const float* dy, const float* xp, int M, int N, int K, int Kp, float* dW, float* db) {
+    float* dWp = dW && Kp != K ? c.f32((size_t)N * Kp) : dW;
+    c.lin_wgrad(dy, xp, M, N, Kp, dWp, db);
+    if (dWp != dW) split_cols(c, dWp, Kp, 0, K, (size_t)N, dW, false);
+}
+float* silu_bwd(const Ctx& c, const float* dy, const float* x, size_t n) { return c.ew_new(silu_bwd_kernel, n, n, dy, x, n); }
+float* gelu_fwd(const Ctx& c, const float* u, size_t n) { return c.ew_new(gelu_fwd_kernel, n, n, u, n); }
+float* gelu_bwd(const Ctx& c, const float* da, const float* u, size_t n) { return c.ew_new(gelu_bwd_kernel, n, n, da, u, n); }
+void null_grad(const Ctx& c, const float* g, const float* masks, int R, int ld, int c0, int n, float* out, bool accumulate) {
+    c.ew(null_grad_kernel, n, g, masks, R, ld, c0, n, out, accumulate ? 1 : 0);
+}
+float* conv3x3_direct(const Ctx& c, const float* x, const float* w, const float* bias, int B, int H, int W, int Cin, int Cout) {
+    const size_t n = (size_t)B * H * W * Cout;
+    return c.ew_new(conv3x3_direct_kernel, n, n, x, w, bias, H, W, Cin, Cout, n);
+}
+
+struct Strides { size_t b, c, y, x; };
+Strides nchw(int Cc, int H, int W) { return {(size_t)Cc * H * W, (size_t)H * W, (size_t)W, 1}; }
+Strides pixel_rows(int Cc, int H, int W) { return {(size_t)H * W * Cc, 1, (size_t)W * Cc, (size_t)Cc}; }
+
+constexpr int kCnxDims[4] = {96, 192, 384, 768};       // ConvNeXt-tiny (convnext.py:203-207)
+struct CnxBlockSaved { std::string p; const float* x; Ctx::LN n; float *u, *a, *h2; };
+struct CnxDownSaved { std::string p; Ctx::LN l; float* col; int C, Cn; };
+struct SpatialSaved {
+    int R = 0, Cuse = 0, H = 0, M = 0;          // H: the last stage's grid side; M = B H H rows (B T tokens)
+    float *img = nullptr, *img3 = nullptr, *col0 = nullptr, *w0p = nullptr;
+    Ctx::LN stem_ln{};
+    CnxDownSaved down[3];
+    std::vector<CnxBlockSaved> blocks[4];
+    float* mix = nullptr;                         // the MLP's input rows [B T][768]
+};
+struct DsSaved { float *r = nullptr, *a1 = nullptr, *s1 = nullptr, *out = nullptr; };
+
 float* im2col(const Ctx& c, const float* x, int B, int Cin, int H, int W, Strides st, int k, int stride, int pad, int Ho, int Wo, int Kp) {
     const size_t n = (size_t)B * Ho * Wo * Kp;
     float* d = c.f32(n);
-    hipLaunchKernelGGL(im2col_f32_kernel, Ctx::g1(n), dim3(256), 0, c.s, x, Cin, H, W, st.b, st.c, st.y, st.x, k, stride, pad, Ho, Wo, Kp, n, d);
+    c.ew(im2col_f32_kernel, n, x, Cin, H, W, st.b, st.c, st.y, st.x, k, stride, pad, Ho, Wo, Kp, n, d);
     return d;
+}
+// the adjoint of a k x k patchify: dp [B (H/k) (W/k)][ldp] -> pixel rows [B][H W][Cin]
+float* unpatchify(const Ctx& c, const float* dp, int ldp, int B, int Cin, int H, int W, int k) {
+    const size_t n = (size_t)B * H * W * Cin;
+    float* dx = c.f32(n);
+    const Strides r = pixel_rows(Cin, H, W);
+    c.ew(unpatchify_kernel, n, dp, ldp, Cin, H, W, k, r.b, r.c, r.y, r.x, n, dx);
+    return dx;
 }
 // weight (OIHW) and bias gradient of a k x k conv as an im2col of its input + lin_wgrad: x addressed by strides, dy pixel rows [B Ho Wo][Cout]
 void conv_wgrad(const Ctx& c, const float* x, int B, int Cin, int H, int W, Strides st, int k, int stride, int pad, int Ho, int Wo, const float* dy,
@@ -1835,9 +1841,7 @@ void conv_wgrad(const Ctx& c, const float* x, int B, int Cin, int H, int W, Stri
     const int K = Cin * k * k, Kp = round_up(K, 64), M = B * Ho * Wo;
     const size_t mk = c.ar.mark();
     const float* col = dW ? im2col(c, x, B, Cin, H, W, st, k, stride, pad, Ho, Wo, Kp) : nullptr;
-    float* dWp = dW ? (Kp == K ? dW : c.f32((size_t)Cout * Kp)) : nullptr;
-    c.lin_wgrad(dy, col, M, Cout, Kp, dWp, db);
-    if (dW && dWp != dW) hipLaunchKernelGGL(split_kernel, Ctx::g1((size_t)Cout * K), dim3(256), 0, c.s, (const float*)dWp, Kp, 0, K, (size_t)Cout, dW, 0);
+    lin_wgrad_unpad(c, dy, col, M, Cout, K, Kp, dW, db);
     c.ar.release(mk);
 }
 
@@ -1852,19 +1856,8 @@ void class_wgrad(const Ctx& c, int kind, const uint8_t* cls, const float* dy, Cl
     c.ar.release(mk);
 }
 
-const int kCnxDims[4] = {96, 192, 384, 768};       // ConvNeXt-tiny (convnext.py:203-207)
 const char* const kPN = "position_net.";
 const char* const kBB = "position_net.convnext_tiny_backbone.";
-struct CnxBlock { std::string p; const float* x; Ctx::LN n; float *u, *a, *h2; };
-struct CnxDown { std::string p; Ctx::LN l; float* col; int C, Cn; };
-struct SpatialSaved {
-    int R = 0, Cuse = 0, H = 0, M = 0;          // H: the last stage's grid side; M = B H H rows (B T tokens)
-    float *img = nullptr, *img3 = nullptr, *col0 = nullptr, *w0p = nullptr;
-    Ctx::LN stem_ln{};
-    CnxDown down[3];
-    std::vector<CnxBlock> blocks[4];
-    float* mix = nullptr;                         // the MLP's input rows [B T][768]
-};
 
 // PositionNet.forward up to the MLP (canny_grounding_net.py:38-56; sem: nearest resize + in_conv first, sem_grounding_net.py:40-49)
 SpatialSaved spatial_forward(const Ctx& c, const Names& nm, const TrainUNetCfg& cfg, const TrainSpatialIn& sp, int B) {
@@ -1900,7 +1893,7 @@ SpatialSaved spatial_forward(const Ctx& c, const Names& nm, const TrainUNetCfg& 
     x = t.stem_ln.y;
     for (int st = 0; st < 4; ++st) {
         if (st > 0) {     // LayerNorm + Conv2d(C, C', 2, 2) (convnext.py:76-81)
-            CnxDown& d = t.down[st - 1];
+            CnxDownSaved& d = t.down[st - 1];
             d.p = BB + fmt("downsample_layers.%d", st);
             d.C = C;
             d.Cn = kCnxDims[st];
@@ -1912,21 +1905,18 @@ SpatialSaved spatial_forward(const Ctx& c, const Names& nm, const TrainUNetCfg& 
             C = d.Cn;
         }
         for (int j = 0; nm.has(BB + fmt("stages.%d.%d.dwconv.weight", st, j)); ++j) {      // Block.forward (convnext.py:36-50)
-            CnxBlock b;
+            CnxBlockSaved b;
             b.p = BB + fmt("stages.%d.%d", st, j);
             b.x = x;
             const size_t n = (size_t)M * C;
             float* dw = c.f32(n);
-            hipLaunchKernelGGL(dwconv7_f32_kernel, Ctx::g1(n), dim3(256), 0, s, (const float*)x, nm.w(b.p + ".dwconv.weight"), nm.w(b.p + ".dwconv.bias"), H, H, C,
-                               n, 0, 0, dw);
+            c.ew(dwconv7_f32_kernel, n, x, nm.w(b.p + ".dwconv.weight"), nm.w(b.p + ".dwconv.bias"), H, H, C, n, 0, 0, dw);
             b.n = c.ln_fwd(dw, M, C, nm.w(b.p + ".norm.weight"), nm.w(b.p + ".norm.bias"), 1e-6f);
             b.u = lin_fwd_any(c, b.n.y, M, C, nm.w(b.p + ".pwconv1.weight"), nm.w(b.p + ".pwconv1.bias"), 4 * C);
-            b.a = c.f32(4 * n);
-            hipLaunchKernelGGL(gelu_fwd_kernel, Ctx::g1(4 * n), dim3(256), 0, s, (const float*)b.u, 4 * n, b.a);
+            b.a = gelu_fwd(c, b.u, 4 * n);
             b.h2 = c.lin_fwd(b.a, M, 4 * C, nm.w(b.p + ".pwconv2.weight"), nm.w(b.p + ".pwconv2.bias"), C);
             float* y = c.f32(n);
-            hipLaunchKernelGGL(layer_scale_residual_kernel, Ctx::g1(n), dim3(256), 0, s, (const float*)x, (const float*)b.h2,
-                               nm.has(b.p + ".gamma") ? nm.w(b.p + ".gamma") : (const float*)nullptr, C, n, y);
+            c.ew(layer_scale_residual_kernel, n, x, b.h2, nm.has(b.p + ".gamma") ? nm.w(b.p + ".gamma") : nullptr, C, n, y);
             x = y;
             t.blocks[st].push_back(b);
         }
@@ -1935,67 +1925,58 @@ SpatialSaved spatial_forward(const Ctx& c, const Names& nm, const TrainUNetCfg& 
     t.H = H;
     t.M = M;
     t.mix = c.f32((size_t)M * C);
-    hipLaunchKernelGGL(token_mix_f32_kernel, Ctx::g1((size_t)M * C), dim3(256), 0, s, (const float*)x, sp.mask, nm.w(PN + "null_feature"), nm.w(PN + "pos_embedding"),
-                       H * H, C, (size_t)M * C, t.mix);
+    c.ew(token_mix_f32_kernel, (size_t)M * C, x, sp.mask, nm.w(PN + "null_feature"), nm.w(PN + "pos_embedding"), H * H, C, (size_t)M * C, t.mix);
     return t;
 }
 
-// g_mix: dL/d(the MLP's input rows) [B T][768] -> the gradients asked for among position_net.* (ConvNeXt, pos_embedding, null_feature,
-// in_conv). No gradient is formed for the map itself.
+// No gradient is formed for the map itself.
 void spatial_backward(const Ctx& c, const Names& nm, const TrainUNetCfg& cfg, const TrainSpatialIn& sp, int B, const SpatialSaved& t, const float* g_mix) {
     hipStream_t s = c.s;
     const std::string PN = kPN, BB = kBB;
     int H = t.H, M = t.M, C = kCnxDims[3];
     const int T = H * H;
-    if (float* gp = nm.g(PN + "pos_embedding")) hipLaunchKernelGGL(sum_batch_kernel, Ctx::g1((size_t)T * C), dim3(256), 0, s, g_mix, B, (size_t)T * C, gp);
+    if (float* gp = nm.g(PN + "pos_embedding")) c.ew(sum_batch_kernel, (size_t)T * C, g_mix, B, (size_t)T * C, gp);
     if (float* gp = nm.g(PN + "null_feature")) {
         float* mr = c.f32(M);
-        hipLaunchKernelGGL(expand_mask_kernel, Ctx::g1(M), dim3(256), 0, s, sp.mask, T, M, mr);
-        hipLaunchKernelGGL(null_grad_kernel, Ctx::g1(C), dim3(256), 0, s, g_mix, (const float*)mr, M, C, 0, C, gp, 0);
+        c.ew(expand_mask_kernel, M, sp.mask, T, M, mr);
+        null_grad(c, g_mix, mr, M, C, 0, C, gp, false);
     }
     float* g = c.f32((size_t)M * C);
-    hipLaunchKernelGGL(mask_rows_kernel, Ctx::g1((size_t)M * C), dim3(256), 0, s, g_mix, sp.mask, T, C, (size_t)M * C, g);
+    c.ew(mask_rows_kernel, (size_t)M * C, g_mix, sp.mask, T, C, (size_t)M * C, g);
     for (int st = 3; st >= 0; --st) {
         for (int j = (int)t.blocks[st].size() - 1; j >= 0; --j) {
-            const CnxBlock& b = t.blocks[st][j];
+            const CnxBlockSaved& b = t.blocks[st][j];
             const size_t n = (size_t)M * C;
             const float* gam = nm.has(b.p + ".gamma") ? nm.w(b.p + ".gamma") : nullptr;
             const float* gh2 = g;
             if (gam) {      // y = x + gamma h2: d gamma = sum_rows g h2, dh2 = g gamma
-                if (float* gg = nm.g(b.p + ".gamma"))
-                    hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, s, (const float*)g, (const float*)b.h2, M, C, gg);
+                if (float* gg = nm.g(b.p + ".gamma")) c.colsum(g, b.h2, M, C, gg);
                 float* t2 = c.f32(n);
-                hipLaunchKernelGGL(scale_cols_kernel, Ctx::g1(n), dim3(256), 0, s, (const float*)g, gam, C, n, t2);
+                c.ew(scale_cols_kernel, n, g, gam, C, n, t2);
                 gh2 = t2;
             }
             c.lin_wgrad(gh2, b.a, M, C, 4 * C, nm.g(b.p + ".pwconv2.weight"), nm.g(b.p + ".pwconv2.bias"));
             float* ga = lin_dgrad_any(c, gh2, M, C, nm.w(b.p + ".pwconv2.weight"), 4 * C);
-            float* gu = c.f32(4 * n);
-            hipLaunchKernelGGL(gelu_bwd_kernel, Ctx::g1(4 * n), dim3(256), 0, s, (const float*)ga, (const float*)b.u, 4 * n, gu);
+            float* gu = gelu_bwd(c, ga, b.u, 4 * n);
             c.lin_wgrad(gu, b.n.y, M, 4 * C, C, nm.g(b.p + ".pwconv1.weight"), nm.g(b.p + ".pwconv1.bias"));
             float* gn = c.lin_dgrad(gu, M, 4 * C, nm.w(b.p + ".pwconv1.weight"), C);
             float* gdw = c.f32(n);
             c.ln_bwd(gn, b.n, nm.w(b.p + ".norm.weight"), M, C, gdw, false, nm.g(b.p + ".norm.weight"), nm.g(b.p + ".norm.bias"));
             if (float* gw = nm.g(b.p + ".dwconv.weight"))
-                hipLaunchKernelGGL(dwconv7_wgrad_kernel, dim3(cdiv(C, 64), 49), dim3(1024), 0, s, (const float*)gdw, b.x, B, H, H, C, gw);
-            if (float* gb = nm.g(b.p + ".dwconv.bias"))
-                hipLaunchKernelGGL(colsum_kernel, dim3(cdiv(C, 64)), dim3(1024), 0, s, (const float*)gdw, (const float*)nullptr, M, C, gb);
+                hipLaunchKernelGGL(dwconv7_wgrad_kernel, dim3(cdiv(C, 64), 49), dim3(1024), 0, s, gdw, b.x, B, H, H, C, gw);
+            if (float* gb = nm.g(b.p + ".dwconv.bias")) c.colsum(gdw, nullptr, M, C, gb);
             // the residual's gradient g + the depthwise conv's data gradient (the same conv with the taps rotated by 180 degrees)
-            hipLaunchKernelGGL(dwconv7_f32_kernel, Ctx::g1(n), dim3(256), 0, s, (const float*)gdw, nm.w(b.p + ".dwconv.weight"), (const float*)nullptr, H, H, C, n,
-                               1, 1, g);
+            c.ew(dwconv7_f32_kernel, n, gdw, nm.w(b.p + ".dwconv.weight"), nullptr, H, H, C, n, 1, 1, g);
         }
         if (st > 0) {       // LayerNorm + 2 x 2 patch conv: wgrad / dgrad of the patch GEMM, un-patchify, LayerNorm backward
-            const CnxDown& d = t.down[st - 1];
+            const CnxDownSaved& d = t.down[st - 1];
             c.lin_wgrad(g, d.col, M, d.Cn, 4 * d.C, nm.g(d.p + ".1.weight"), nm.g(d.p + ".1.bias"));
             float* gcol = c.lin_dgrad(g, M, d.Cn, nm.w(d.p + ".1.weight"), 4 * d.C);
             H *= 2;
             M *= 4;
             C = d.C;
-            const size_t n = (size_t)M * C;
-            float* gl = c.f32(n);
-            const Strides r = pixel_rows(C, H, H);
-            hipLaunchKernelGGL(unpatchify_kernel, Ctx::g1(n), dim3(256), 0, s, (const float*)gcol, 4 * C, C, H, H, 2, r.b, r.c, r.y, r.x, n, gl);
-            float* gx = c.f32(n);
+            float* gl = unpatchify(c, gcol, 4 * C, B, C, H, H, 2);
+            float* gx = c.f32((size_t)M * C);
             c.ln_bwd(gl, d.l, nm.w(d.p + ".0.weight"), M, C, gx, false, nm.g(d.p + ".0.weight"), nm.g(d.p + ".0.bias"));
             g = gx;
         }
@@ -2004,19 +1985,14 @@ void spatial_backward(const Ctx& c, const Names& nm, const TrainUNetCfg& cfg, co
     const std::string s0 = BB + "downsample_layers.0.";
     float* gs = c.f32((size_t)M * C);
     c.ln_bwd(g, t.stem_ln, nm.w(s0 + "1.weight"), M, C, gs, false, nm.g(s0 + "1.weight"), nm.g(s0 + "1.bias"));
-    float* gw0 = nm.g(s0 + "0.weight");
-    float* gw0p = gw0 ? c.f32((size_t)C * 64) : nullptr;
-    c.lin_wgrad(gs, t.col0, M, C, 64, gw0p, nm.g(s0 + "0.bias"));
-    if (gw0) hipLaunchKernelGGL(split_kernel, Ctx::g1((size_t)C * 48), dim3(256), 0, s, (const float*)gw0p, 64, 0, 48, (size_t)C, gw0, 0);
+    lin_wgrad_unpad(c, gs, t.col0, M, C, 48, 64, nm.g(s0 + "0.weight"), nm.g(s0 + "0.bias"));
     if (cfg.tok_in_dim && (nm.g(PN + "in_conv.weight") || nm.g(PN + "in_conv.bias"))) {
         // sem's in_conv (Conv2d(152, 3, 3, 1, 1), sem_grounding_net.py:21, 46): the stem's data gradient back to pixel rows [B R R][3],
         // then im2col + lin_wgrad over the resized class planes
         const int R = t.R;
         float* gcol = lin_dgrad_any(c, gs, M, C, t.w0p, 64);
-        const size_t n = (size_t)B * R * R * 3;
-        float* g3 = c.f32(n);
+        float* g3 = unpatchify(c, gcol, 64, B, 3, R, R, 4);
         const Strides r = pixel_rows(3, R, R);
-        hipLaunchKernelGGL(unpatchify_kernel, Ctx::g1(n), dim3(256), 0, s, (const float*)gcol, 64, 3, R, R, 4, r.b, r.c, r.y, r.x, n, g3);
         if (sp.map_cls)
             class_wgrad(c, kClassWgradInConv, sp.map_cls, g3, {r.b, r.c, r.y, r.x}, B, sp.Ht, sp.Wt, t.Cuse, 3, R, nm.g(PN + "in_conv.weight"), nm.g(PN + "in_conv.bias"));
         else
@@ -2024,8 +2000,7 @@ void spatial_backward(const Ctx& c, const Names& nm, const TrainUNetCfg& cfg, co
     }
 }
 
-// GroundingDownsampler.forward (canny_grounding_downsampler.py:21-29; hed: the resize only; sem: nearest, 152 -> 16 -> 8), NCHW fp32
-struct DsSaved { float *r = nullptr, *a1 = nullptr, *s1 = nullptr, *out = nullptr; };
+// canny_grounding_downsampler.py:21-29; hed: the resize only; sem: nearest, 152 -> 16 -> 8. NCHW fp32
 DsSaved downsampler_forward(const Ctx& c, const Names& nm, const TrainSpatialIn& sp, int B, int Ce, int H0, int W0) {
     DsSaved d;
     const int Rd = sp.ds_resize, ni = sp.ds_n_in, mid = sp.ds_mid;
@@ -2053,12 +2028,409 @@ DsSaved downsampler_forward(const Ctx& c, const Names& nm, const TrainSpatialIn&
         } else {
             c.ck(conv4x4s2_f32_launch(d.r, nm.w("downsample_net.layers.0.weight"), nm.w("downsample_net.layers.0.bias"), d.a1, B, ni, mid, Rd, Rd, 0, c.s));
         }
-        d.s1 = c.f32(nh);
-        hipLaunchKernelGGL(silu_kernel, Ctx::g1(nh), dim3(256), 0, c.s, (const float*)d.a1, nh, d.s1);
+        d.s1 = c.silu(d.a1, nh);
         d.out = c.f32((size_t)B * Ce * H0 * W0);
         c.ck(conv4x4s2_f32_launch(d.s1, nm.w("downsample_net.layers.2.weight"), nm.w("downsample_net.layers.2.bias"), d.out, B, mid, Ce, Rh, Rh, 0, c.s));
     }
     return d;
+}
+
+bool downsampler_grads(const Names& nm) {
+    bool any = false;
+    for (const char* k : {"downsample_net.layers.0.weight", "downsample_net.layers.0.bias", "downsample_net.layers.2.weight", "downsample_net.layers.2.bias"})
+        any = any || nm.g(k);
+    return any;
+}
+
+// The first conv and the GroundingDownsampler (trainer.py:189-194, 229-236)
+void conv_in_backward(const Ctx& c, const Names& nm, const TrainSpatialIn& sp, const DsSaved& dsv, const float* xin, int B, int H0, int W0, int Cx, int Ce,
+                      int mc, const float* g) {
+    const int Cin0 = Cx + Ce;
+    if (float* gw = nm.g("input_blocks.0.0.weight")) conv_wgrad(c, xin, B, Cin0, H0, W0, pixel_rows(Cin0, H0, W0), 3, 1, 1, H0, W0, g, mc, gw, nullptr);
+    if (!sp.ds_mid || !downsampler_grads(nm)) return;
+    // the first conv's data gradient for the k downsampler channels only: rows Cx .. Cx + k of the flipped / transposed filter
+    const float* wt = c.conv_dgrad_weight(nm.w("input_blocks.0.0.weight"), mc, Cin0);
+    float* gds = conv3x3_direct(c, g, wt + (size_t)Cx * mc * 9, nullptr, B, H0, W0, mc, Ce);
+    const int Rd = sp.ds_resize, Rh = Rd / 2, mid = sp.ds_mid, ni = sp.ds_n_in;
+    conv_wgrad(c, dsv.s1, B, mid, Rh, Rh, nchw(mid, Rh, Rh), 4, 2, 1, H0, W0, gds, Ce, nm.g("downsample_net.layers.2.weight"), nm.g("downsample_net.layers.2.bias"));
+    const size_t nh = (size_t)B * mid * Rh * Rh;
+    float* gs1 = c.f32(nh);
+    c.ew(conv4x4s2_dgrad_kernel, nh, gds, nm.w("downsample_net.layers.2.weight"), mid, Ce, Rh, Rh, nh, gs1);
+    float* ga1 = silu_bwd(c, gs1, dsv.a1, nh);
+    if (sp.extra_cls) {
+        const Strides r = nchw(mid, Rh, Rh);
+        class_wgrad(c, kClassWgradDown, sp.extra_cls, ga1, {r.b, r.c, r.y, r.x}, B, sp.He, sp.We, ni, mid, Rd, nm.g("downsample_net.layers.0.weight"),
+                    nm.g("downsample_net.layers.0.bias"));
+    } else {
+        const float* ga1r = im2col(c, ga1, B, mid, Rh, Rh, nchw(mid, Rh, Rh), 1, 1, 0, Rh, Rh, mid);     // NCHW -> pixel rows
+        conv_wgrad(c, dsv.r, B, ni, Rd, Rd, nchw(ni, Rd, Rd), 4, 2, 1, Rh, Rh, ga1r, mid, nm.g("downsample_net.layers.0.weight"), nm.g("downsample_net.layers.0.bias"));
+    }
+}
+
+
+// ---- what the stages of a step share
+struct UNetStep {
+    const Ctx& c; const Names& nm; const TrainUNetCfg& cfg; const TrainUNetIn& in; const TrainSpatialIn* spatial; const char* const* block_names;
+    int B, H0, W0, mc, ED, KD, Ng;
+    int GK, NB, MRB, NC;            // grounding kind, boxes per sample, B NB rows per MLP, coordinates per box
+    int PWr, PW;                    // the MLPs' input width, and padded to the GEMM's 64-step
+    int NBR, MR;                    // MLP branches (text+image: 2), B Ng rows of objs
+    int Cx, Ce, Cin0;               // conv_in reads Cx latent + Ce downsampler channels
+    size_t M0;                      // B H0 W0 pixel rows
+    std::string null_pos;
+};
+// one grounding MLP (Linear, SiLU, Linear, SiLU, Linear) and what its backward needs
+struct PosBranch { std::string lin, null_emb; const float* emb; const float* emb_mask; float *pcat, *l0, *a0, *l1, *a1, *out, *w0p; };
+struct Act { float* p; int C, H, W; };
+enum Kind { K_RES, K_ST, K_DOWN, K_UP, K_CAT };
+struct UNetLayer {
+    Kind kind;
+    std::string prefix;
+    int Cin, Cout, H, W, C0;                  // K_CAT: C0 = channels of h, Cin - C0 = channels of the skip; skip_idx = its producer
+    int skip_idx;
+    const float* x_in;                         // the layer's input (kept: with checkpointing the backward recomputes the forward from it)
+    std::vector<const float*> P;
+    std::vector<float*> G;
+    ResSaved rs;
+    STSaved ss;
+};
+
+// trainer.py:217-242: fuser.*, position_net.*, and for a model with a grounding downsampler downsample_net.* and the first conv's
+// weight (input_conv_train, :189-194, 233; its bias stays frozen)
+void check_trainable_set(const TrainUNetCfg& cfg, int n_params, const char* const* names, float* const* grads, const TrainSpatialIn* spatial) {
+    const bool ds_model = cfg.grounding_kind == 3 && cfg.extra_channels > 0;
+    for (int i = 0; i < n_params; ++i)
+        if (grads[i] && !(strstr(names[i], ".fuser.") || !strncmp(names[i], "position_net.", 13) ||
+                          (ds_model && (!strncmp(names[i], "downsample_net.", 15) || !strcmp(names[i], "input_blocks.0.0.weight")))))
+            throw GlError(GL_ERR_ARG, fmt("unet_train_step: a gradient was asked for '%s', which the reference keeps frozen", names[i]));
+    if (cfg.grounding_kind == 3 && !spatial) throw GlError(GL_ERR_ARG, "unet_train_step: a spatial-map model needs its TrainSpatialIn");
+    if (spatial && (spatial->map_cls || spatial->extra_cls) &&
+        (!spatial->map_cls || !spatial->extra_cls || spatial->map || spatial->extra || !cfg.extra_channels))
+        throw GlError(GL_ERR_ARG, "unet_train_step: a mixture of class maps and planes: the tokenizer's map and grounding_extra_input are both u8 class maps "
+                                  "or both fp32 planes");
+}
+
+UNetStep step_dims(const Ctx& c, const Names& nm, const TrainUNetCfg& cfg, const TrainUNetIn& in, const TrainSpatialIn* spatial, const char* const* block_names) {
+    UNetStep u{c, nm, cfg, in, spatial, block_names};
+    u.B = in.B; u.H0 = in.H; u.W0 = in.W; u.mc = cfg.model_channels; u.ED = 4 * u.mc; u.KD = cfg.context_dim; u.Ng = in.Ng;
+    if (u.mc % 64 || u.KD % 64 || cfg.gr_dim % 64 || u.B < 1) throw GlError(GL_ERR_ARG, "unet_train_step: model_channels / context_dim / grounding dim must be multiples of 64");
+    u.GK = cfg.grounding_kind; u.NB = in.Ng_boxes; u.MRB = u.B * u.NB; u.NC = u.GK == 2 ? 2 : 4;
+    u.PWr = u.GK == 3 ? kCnxDims[3] : cfg.gr_dim + 16 * u.NC; u.PW = round_up(u.PWr, 64); u.NBR = u.GK == 1 ? 2 : 1;
+    if (u.Ng != u.NB * u.NBR || (u.GK == 2 && u.NB % 17)) throw GlError(GL_ERR_ARG, "unet_train_step: Ng must be the box count (text), twice it (text+image), 17 per person (keypoint)");
+    u.MR = u.B * u.Ng;
+    u.null_pos = u.GK == 2 ? "position_net.null_xy_feature" : "position_net.null_position_feature";
+    u.Cx = cfg.in_channels; u.Ce = u.GK == 3 ? cfg.extra_channels : 0; u.Cin0 = u.Cx + u.Ce;
+    u.M0 = (size_t)u.B * u.H0 * u.W0;
+    return u;
+}
+
+// ---- grounding tokens (trainable): one MLP over [embedding | fourier(coords)] rows for the text tokenizer (boxes, 4 coords) and the
+// keypoint tokenizer (points, 2 coords; the embedding is person + keypoint table rows), two MLPs (text, image) whose tokens are
+// concatenated along the token axis for text+image (text_grounding_net.py:30-52, text_image_grounding_net.py:41-70,
+// keypoint_grounding_net.py:34-58)
+// (spatial-map tokenizers, GK 3: the same MLP over the ConvNeXt features mixed with null_feature and pos_embedding, K = 768)
+float* grounding_forward(const UNetStep& u, PosBranch pb[2], SpatialSaved& tok) {
+    const Ctx& c = u.c;
+    const Names& nm = u.nm;
+    const TrainUNetIn& in = u.in;
+    const int GK = u.GK, MRB = u.MRB, PW = u.PW;
+    pb[0] = {GK == 1 ? "position_net.linears_text" : "position_net.linears",
+             GK == 1 ? "position_net.null_text_feature" : GK == 2 ? "position_net.null_person_feature" : "position_net.null_positive_feature",
+             GK == 2 ? nullptr : in.positive_embeddings, GK == 1 ? in.text_masks : in.masks, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+    pb[1] = {"position_net.linears_image", "position_net.null_image_feature", in.image_embeddings, in.image_masks, nullptr, nullptr, nullptr, nullptr, nullptr,
+             nullptr, nullptr};
+    float* objs = u.NBR == 1 ? nullptr : c.f32((size_t)u.MR * u.KD);
+    for (int r = 0; r < u.NBR; ++r) {
+        PosBranch& p = pb[r];
+        if (GK == 3) {
+            tok = spatial_forward(c, nm, u.cfg, *u.spatial, u.B);
+            if (tok.M != MRB) throw GlError(GL_ERR_ARG, "unet_train_step: Ng must be (tok_resize / 32)^2 for a spatial-map tokenizer");
+            p.pcat = tok.mix;
+        } else {
+            if ((!p.emb && GK != 2) || !p.emb_mask) throw GlError(GL_ERR_ARG, "unet_train_step: null grounding input");
+            p.pcat = c.f32((size_t)MRB * PW);
+            hipLaunchKernelGGL(posnet_input_kernel_f32, dim3(MRB), dim3(256), 0, c.s, in.boxes, u.NC, in.masks, p.emb_mask, p.emb,
+                               GK == 2 ? nm.w("position_net.person_embeddings") : nullptr, GK == 2 ? nm.w("position_net.keypoint_embeddings") : nullptr, u.NB,
+                               nm.w(p.null_emb), nm.w(u.null_pos), u.cfg.gr_dim, PW, p.pcat);
+        }
+        const float* w0 = nm.w(p.lin + ".0.weight");
+        if (PW != u.PWr) w0 = p.w0p = pad_cols(c, w0, 512, u.PWr, PW);     // (the keypoint tokenizer's first Linear has K = 800)
+        p.l0 = c.lin_fwd(p.pcat, MRB, PW, w0, nm.w(p.lin + ".0.bias"), 512);
+        p.a0 = c.silu(p.l0, (size_t)MRB * 512);
+        p.l1 = c.lin_fwd(p.a0, MRB, 512, nm.w(p.lin + ".2.weight"), nm.w(p.lin + ".2.bias"), 512);
+        p.a1 = c.silu(p.l1, (size_t)MRB * 512);
+        p.out = c.lin_fwd(p.a1, MRB, 512, nm.w(p.lin + ".4.weight"), nm.w(p.lin + ".4.bias"), u.KD);
+        if (u.NBR == 1) objs = p.out;
+        else c.put_rows(objs, u.B, u.Ng, r * u.NB, p.out, u.NB, u.KD);      // objs = cat([objs_text, objs_image], dim = 1)
+    }
+    return objs;
+}
+
+// position_net backward (the learnable null embeddings: the position one is shared by the branches; the keypoint tokenizer's person /
+// keypoint embedding tables; GK 3: token mix + ConvNeXt). g_objs: dL/d objs [B][Ng][KD]
+void grounding_backward(const UNetStep& u, const PosBranch pb[2], const SpatialSaved& tok, const float* g_objs) {
+    const Ctx& c = u.c;
+    const Names& nm = u.nm;
+    const int MRB = u.MRB, PW = u.PW, NB = u.NB, gr_dim = u.cfg.gr_dim;
+    for (int r = 0; r < u.NBR; ++r) {
+        const PosBranch& p = pb[r];
+        const float* go = u.NBR == 1 ? g_objs : c.slice_rows(g_objs, u.B, u.Ng, r * NB, NB, u.KD);
+        c.lin_wgrad(go, p.a1, MRB, u.KD, 512, nm.g(p.lin + ".4.weight"), nm.g(p.lin + ".4.bias"));
+        float* g_a1 = c.lin_dgrad(go, MRB, u.KD, nm.w(p.lin + ".4.weight"), 512);
+        float* g_l1 = silu_bwd(c, g_a1, p.l1, (size_t)MRB * 512);
+        c.lin_wgrad(g_l1, p.a0, MRB, 512, 512, nm.g(p.lin + ".2.weight"), nm.g(p.lin + ".2.bias"));
+        float* g_a0 = c.lin_dgrad(g_l1, MRB, 512, nm.w(p.lin + ".2.weight"), 512);
+        float* g_l0 = silu_bwd(c, g_a0, p.l0, (size_t)MRB * 512);
+        lin_wgrad_unpad(c, g_l0, p.pcat, MRB, 512, u.PWr, PW, nm.g(p.lin + ".0.weight"), nm.g(p.lin + ".0.bias"));
+        float* g_cat = c.lin_dgrad(g_l0, MRB, 512, p.w0p ? p.w0p : nm.w(p.lin + ".0.weight"), PW);
+        if (u.GK == 3) {
+            spatial_backward(c, nm, u.cfg, *u.spatial, u.B, tok, g_cat);
+            continue;
+        }
+        if (float* gp = nm.g(p.null_emb)) null_grad(c, g_cat, p.emb_mask, MRB, PW, 0, gr_dim, gp, false);
+        if (float* gp = nm.g(u.null_pos)) null_grad(c, g_cat, u.in.masks, MRB, PW, gr_dim, 16 * u.NC, gp, r != 0);
+        if (u.GK == 2) {
+            if (float* gp = nm.g("position_net.person_embeddings"))
+                hipLaunchKernelGGL(table_grad_kernel, dim3(cdiv(gr_dim, 256), NB / 17), dim3(256), 0, c.s, g_cat, u.in.masks, u.B, NB, PW, gr_dim, 1, gp);
+            if (float* gp = nm.g("position_net.keypoint_embeddings"))
+                hipLaunchKernelGGL(table_grad_kernel, dim3(cdiv(gr_dim, 256), 17), dim3(256), 0, c.s, g_cat, u.in.masks, u.B, NB, PW, gr_dim, 0, gp);
+        }
+    }
+}
+
+// time embedding (frozen): silu(emb) [B][ED] is what every ResBlock's emb_layers starts with
+float* time_embedding(const UNetStep& u) {
+    const Ctx& c = u.c;
+    float* te = c.f32((size_t)u.B * u.mc);
+    hipLaunchKernelGGL(timestep_embedding_kernel, dim3(u.B), dim3(256), 0, c.s, u.in.timesteps, u.mc, te);
+    float* e0 = c.lin_fwd(te, u.B, u.mc, u.nm.w("time_embed.0.weight"), u.nm.w("time_embed.0.bias"), u.ED);
+    float* e0s = c.silu(e0, (size_t)u.B * u.ED);
+    float* emb = c.lin_fwd(e0s, u.B, u.ED, u.nm.w("time_embed.2.weight"), u.nm.w("time_embed.2.bias"), u.ED);
+    return c.silu(emb, (size_t)u.B * u.ED);
+}
+
+// conv_in: frozen for the discrete models (forward only); for a model with a grounding downsampler its input is
+// cat(x, downsample_net(grounding_extra_input)) (openaimodel.py:442-444) and its weight is trainable. xin: the rows it read
+float* conv_in_forward(const UNetStep& u, DsSaved& dsv, const float*& xin) {
+    const Ctx& c = u.c;
+    xin = u.in.x;
+    if (u.Ce) {
+        dsv = downsampler_forward(c, u.nm, *u.spatial, u.B, u.Ce, u.H0, u.W0);
+        float* cat0 = c.f32(u.M0 * u.Cin0);
+        c.ew(cat_rows_nchw_kernel, u.M0 * u.Cin0, u.in.x, u.Cx, dsv.out, u.Ce, u.H0 * u.W0, u.M0 * u.Cin0, cat0);
+        xin = cat0;
+    }
+    return conv3x3_direct(c, xin, u.nm.w("input_blocks.0.0.weight"), u.nm.w("input_blocks.0.0.bias"), u.B, u.H0, u.W0, u.Cin0, u.mc);
+}
+
+UNetLayer res_layer(const Names& nm, const std::string& p, int Cin, int Cout, int H, int W) {
+    UNetLayer l{K_RES, p, Cin, Cout, H, W, 0, -1, nullptr, {}, {}, {}, {}};
+    static const char* k[RP_COUNT] = {"in_layers.0.weight", "in_layers.0.bias", "in_layers.2.weight", "in_layers.2.bias", "emb_layers.1.weight",
+                                      "emb_layers.1.bias", "out_layers.0.weight", "out_layers.0.bias", "out_layers.3.weight", "out_layers.3.bias",
+                                      "skip_connection.weight", "skip_connection.bias"};
+    for (int i = 0; i < RP_COUNT; ++i) l.P.push_back((i >= RP_SKIP_W && Cin == Cout) ? nullptr : nm.w(p + "." + k[i]));
+    return l;
+}
+UNetLayer st_layer(const UNetStep& u, const std::string& p, int C, int H, int W) {
+    const Names& nm = u.nm;
+    UNetLayer l{K_ST, p, C, C, H, W, 0, -1, nullptr, {}, {}, {}, {}};
+    l.P.resize(ST_COUNT);
+    l.G.assign(ST_COUNT, nullptr);
+    l.P[ST_NORM_W] = nm.w(p + ".norm.weight"); l.P[ST_NORM_B] = nm.w(p + ".norm.bias");
+    l.P[ST_PIN_W] = nm.w(p + ".proj_in.weight"); l.P[ST_PIN_B] = nm.w(p + ".proj_in.bias");
+    l.P[ST_POUT_W] = nm.w(p + ".proj_out.weight"); l.P[ST_POUT_B] = nm.w(p + ".proj_out.bias");
+    for (int i = 0; i < TP_COUNT; ++i) {
+        const std::string k = p + ".transformer_blocks.0." + u.block_names[i];
+        l.P[ST_BLOCK0 + i] = nm.w(k);
+        l.G[ST_BLOCK0 + i] = nm.g(k);
+    }
+    return l;
+}
+// a resampling conv (K_DOWN / K_UP) of C channels
+UNetLayer resample_layer(const Names& nm, Kind kind, const std::string& p, int C, int H, int W) {
+    return UNetLayer{kind, p, C, C, H, W, 0, -1, nullptr, {nm.w(p + ".weight"), nm.w(p + ".bias")}, {}, {}, {}};
+}
+TrainBlockDims st_dims(const UNetStep& u, const UNetLayer& l) { return {u.B, l.H * l.W, u.Ng, l.Cout, u.cfg.num_heads, u.in.ctx_T, u.KD, u.in.fuser_scale}; }
+TrainResDims res_dims(const UNetStep& u, const UNetLayer& l) { return {u.B, l.H, l.W, l.Cin, l.Cout, u.ED}; }
+
+// One layer's forward on the stream h; the layer, with what its backward needs, is appended to L.
+// checkpointing: a block's output is allocated first, everything its forward keeps (activations, statistics, the bf16
+// operand copies) is given back to the arena behind it; the backward recomputes the forward from x_in
+void run(const UNetStep& u, const float* objs, const float* semb, Act& h, std::vector<UNetLayer>& L, UNetLayer l) {
+    const Ctx& c = u.c;
+    const size_t rows = (size_t)u.B * l.H * l.W;
+    float* y = nullptr;
+    l.x_in = h.p;
+    if (l.kind == K_RES) {
+        res_check(res_dims(u, l), l.P.data());
+        y = c.f32(rows * l.Cout);
+        const size_t mk = c.ar.mark();
+        l.rs = res_forward(c, res_dims(u, l), l.P.data(), h.p, semb, y);
+        if (u.in.checkpoint) c.ar.release(mk);
+    } else if (l.kind == K_ST) {
+        st_check(st_dims(u, l), l.P.data());
+        y = c.f32(rows * l.Cout);
+        const size_t mk = c.ar.mark();
+        l.ss = st_forward(c, st_dims(u, l), l.P.data(), h.p, objs, u.in.context, y);
+        if (u.in.checkpoint) c.ar.release(mk);
+    } else {
+        const bool up = l.kind == K_UP;
+        y = resample_forward(c, up, u.B, l.H, l.W, l.Cin, l.P[0], l.P[1], h.p);
+        h.H = up ? l.H * 2 : l.H / 2; h.W = up ? l.W * 2 : l.W / 2;
+    }
+    h.p = y; h.C = l.Cout;
+    L.push_back(std::move(l));
+}
+
+// input_blocks / middle_block / output_blocks (openaimodel.py:452-464), in forward order, from h0 = conv_in's output; returns the
+// stream in front of `out`
+Act build_and_run_layers(const UNetStep& u, const float* objs, const float* semb, float* h0, std::vector<UNetLayer>& L) {
+    const Ctx& c = u.c;
+    const Names& nm = u.nm;
+    const TrainUNetCfg& cfg = u.cfg;
+    const int mc = u.mc;
+    auto in_attn = [&](int ds) { for (int i = 0; i < cfg.n_attn; ++i) if (cfg.attention_resolutions[i] == ds) return true; return false; };
+    Act h{h0, mc, u.H0, u.W0};
+    std::vector<Act> hs{h};
+    std::vector<int> hs_layer{-1};          // which layer produced each skip (-1: conv_in)
+    int ch = mc, ds = 1, n = 1;
+    for (int level = 0; level < cfg.n_mult; ++level) {
+        const int mult = cfg.channel_mult[level];
+        for (int r = 0; r < cfg.num_res_blocks; ++r) {
+            const std::string p = fmt("input_blocks.%d", n);
+            run(u, objs, semb, h, L, res_layer(nm, p + ".0", ch, mult * mc, h.H, h.W));
+            ch = mult * mc;
+            if (in_attn(ds)) run(u, objs, semb, h, L, st_layer(u, p + ".1", ch, h.H, h.W));
+            hs.push_back(h); hs_layer.push_back((int)L.size() - 1);
+            ++n;
+        }
+        if (level != cfg.n_mult - 1) {
+            run(u, objs, semb, h, L, resample_layer(nm, K_DOWN, fmt("input_blocks.%d.0.op", n), ch, h.H, h.W));
+            hs.push_back(h); hs_layer.push_back((int)L.size() - 1);
+            ds *= 2;
+            ++n;
+        }
+    }
+    run(u, objs, semb, h, L, res_layer(nm, "middle_block.0", ch, ch, h.H, h.W));
+    run(u, objs, semb, h, L, st_layer(u, "middle_block.1", ch, h.H, h.W));
+    run(u, objs, semb, h, L, res_layer(nm, "middle_block.2", ch, ch, h.H, h.W));
+    n = 0;
+    for (int level = cfg.n_mult - 1; level >= 0; --level) {
+        const int mult = cfg.channel_mult[level];
+        for (int i = 0; i <= cfg.num_res_blocks; ++i) {
+            const Act sk = hs.back();
+            const int sk_layer = hs_layer.back();
+            hs.pop_back(); hs_layer.pop_back();
+            if (sk.H != h.H || sk.W != h.W) throw GlError(GL_ERR_STATE, "unet_train_step: skip / stream size mismatch");
+            {   // h = cat([h, hs.pop()], dim = 1)
+                const size_t rows = (size_t)u.B * h.H * h.W;
+                float* cat = c.f32(rows * (h.C + sk.C));
+                c.ew(concat_kernel, rows * (h.C + sk.C), h.p, h.C, sk.p, sk.C, rows, cat);
+                L.push_back(UNetLayer{K_CAT, "", h.C + sk.C, h.C + sk.C, h.H, h.W, h.C, sk_layer, nullptr, {}, {}, {}, {}});
+                h.p = cat; h.C += sk.C;
+            }
+            const std::string p = fmt("output_blocks.%d", n);
+            run(u, objs, semb, h, L, res_layer(nm, p + ".0", h.C, mc * mult, h.H, h.W));
+            ch = mc * mult;
+            int j = 1;
+            if (in_attn(ds)) { run(u, objs, semb, h, L, st_layer(u, p + ".1", ch, h.H, h.W)); j = 2; }
+            if (level && i == cfg.num_res_blocks) {
+                run(u, objs, semb, h, L, resample_layer(nm, K_UP, p + fmt(".%d.conv", j), ch, h.H, h.W));
+                ds /= 2;
+            }
+            ++n;
+        }
+    }
+    return h;
+}
+
+// out = conv(silu(gn(h)))  (openaimodel.py:389-393), the loss and dL/d out
+struct OutSaved { Ctx::GN on; float* gy; };
+OutSaved out_forward_and_loss(const UNetStep& u, const Act& h, float* eps_out, float* loss) {
+    const Ctx& c = u.c;
+    OutSaved o;
+    o.on = c.gn_silu_fwd(h.p, u.B, u.H0 * u.W0, u.mc, u.nm.w("out.0.weight"), u.nm.w("out.0.bias"));
+    const int Co = u.cfg.out_channels;
+    const size_t ny = u.M0 * Co;
+    const float* y = conv3x3_direct(c, o.on.a, u.nm.w("out.2.weight"), u.nm.w("out.2.bias"), u.B, u.H0, u.W0, u.mc, Co);
+    if (eps_out) c.hip(hipMemcpyAsync(eps_out, y, ny * 4, hipMemcpyDeviceToDevice, c.s), "hipMemcpyAsync");
+    o.gy = c.mse_loss(y, u.in.target, ny, loss);
+    return o;
+}
+// -> dL/d(the stream in front of `out`). The out conv's dgrad: the same direct conv on the flipped / transposed weight
+float* out_backward(const UNetStep& u, const OutSaved& o) {
+    const Ctx& c = u.c;
+    const float* wt = c.conv_dgrad_weight(u.nm.w("out.2.weight"), u.cfg.out_channels, u.mc);
+    float* g_a = conv3x3_direct(c, o.gy, wt, nullptr, u.B, u.H0, u.W0, u.cfg.out_channels, u.mc);
+    float* g = c.f32(u.M0 * u.mc);
+    c.gn_silu_bwd(g_a, o.on, u.nm.w("out.0.weight"), u.nm.w("out.0.bias"), u.B, u.H0 * u.W0, u.mc, g, false);
+    return g;
+}
+
+// The layers' backward, last to first. g: dL/d(the last layer's output). in_grad: a trainable first conv (or downsampler) needs
+// dL/d(conv_in output): the loop then runs through the layers in front of the first fuser too and keeps conv_in's skip gradient
+// (hs_layer -1, the last output block's concat), which is added to what it returns. g_objs [B][Ng][KD] accumulates dL/d objs.
+// Event j of grad_events is recorded behind the j-th SpatialTransformer (module order); returns their number through n_st.
+float* layers_backward(const UNetStep& u, std::vector<UNetLayer>& L, const float* objs, const float* semb, float* g, bool in_grad, float* g_objs,
+                       hipEvent_t* grad_events, int n_grad_events, int& n_st) {
+    const Ctx& c = u.c;
+    const int B = u.B;
+    const bool checkpoint = u.in.checkpoint;
+    std::vector<float*> skip_grad(L.size(), nullptr);     // dL/d(output of layer i) arriving through a skip connection
+    int first_st = -1;
+    for (size_t i = 0; i < L.size(); ++i)
+        if (L[i].kind == K_ST) { first_st = (int)i; break; }
+    std::vector<int> st_ordinal(L.size(), -1);            // SpatialTransformer number in module order (input_blocks .. middle .. output_blocks)
+    n_st = 0;
+    for (size_t i = 0; i < L.size(); ++i)
+        if (L[i].kind == K_ST) st_ordinal[i] = n_st++;
+    const int stop = in_grad ? 0 : first_st;
+    float* skip0 = nullptr;
+    for (int i = (int)L.size() - 1; i >= 0 && i >= stop; --i) {
+        UNetLayer& l = L[i];
+        const size_t rows = (size_t)B * l.H * l.W;
+        if (skip_grad[i]) {     // this layer's output also went into a skip connection (l.H, l.W are its INPUT size)
+            const size_t out_rows = l.kind == K_DOWN ? rows / 4 : l.kind == K_UP ? rows * 4 : rows;
+            c.add(g, skip_grad[i], out_rows * l.Cout);
+        }
+        if (l.kind == K_CAT) {
+            float* gh = c.f32(rows * l.C0);
+            split_cols(c, g, l.Cin, 0, l.C0, rows, gh, false);
+            const int C1 = l.Cin - l.C0;
+            if (in_grad || l.skip_idx >= first_st) {   // (without in_grad a skip produced in front of the first fuser carries no gradient anybody needs)
+                float* gs = c.f32(rows * C1);
+                split_cols(c, g, l.Cin, l.C0, C1, rows, gs, false);
+                if (l.skip_idx < 0) skip0 = gs;
+                else skip_grad[l.skip_idx] = gs;
+            }
+            g = gh;
+        } else if (l.kind == K_RES) {
+            float* keep = (checkpoint && l.Cin != l.Cout) ? c.f32(rows * l.Cin) : nullptr;    // (allocated in front of the scope below)
+            const size_t mk = c.ar.mark();
+            if (checkpoint) l.rs = res_forward(c, res_dims(u, l), l.P.data(), l.x_in, semb, c.f32(rows * l.Cout));
+            float* gx = res_backward(c, res_dims(u, l), l.P.data(), l.rs, g);       // (g itself, updated in place, when Cin == Cout)
+            if (keep) {
+                c.hip(hipMemcpyAsync(keep, gx, rows * l.Cin * 4, hipMemcpyDeviceToDevice, c.s), "hipMemcpyAsync");
+                gx = keep;
+            }
+            if (checkpoint) c.ar.release(mk);
+            g = gx;
+        } else if (l.kind == K_ST) {
+            float* d_o = c.f32((size_t)u.MR * u.KD);
+            const size_t mk = c.ar.mark();
+            if (checkpoint) l.ss = st_forward(c, st_dims(u, l), l.P.data(), l.x_in, objs, u.in.context, c.f32(rows * l.Cout));
+            st_backward(c, st_dims(u, l), l.P.data(), l.ss, objs, g, d_o, l.G.data());      // g in place
+            c.add(g_objs, d_o, (size_t)u.MR * u.KD);
+            if (checkpoint) c.ar.release(mk);
+            // this block's fuser gradients are final: the caller's communication stream may pick them up (gl_train_wait_grads)
+            // while the blocks in front of it are still in backward
+            if (grad_events && st_ordinal[i] < n_grad_events) c.hip(hipEventRecord(grad_events[st_ordinal[i]], c.s), "hipEventRecord");
+        } else {
+            g = resample_backward(c, l.kind == K_UP, B, l.H, l.W, l.Cin, l.P[0], g);
+        }
+    }
+    if (in_grad && skip0) c.add(g, skip0, u.M0 * u.mc);      // g = dL/d(conv_in output) through input_blocks.1, plus its skip
+    return g;
 }
 
 }  // namespace
@@ -2071,18 +2443,7 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
         nm.params = params;
         nm.grads = grads;
         for (int i = 0; i < n_params; ++i) nm.idx[names[i]] = i;
-        // trainer.py:217-242: fuser.*, position_net.*, and for a model with a grounding downsampler downsample_net.* and the first conv's
-        // weight (input_conv_train, :189-194, 233; its bias stays frozen)
-        const bool ds_model = cfg.grounding_kind == 3 && cfg.extra_channels > 0;
-        for (int i = 0; i < n_params; ++i)
-            if (grads[i] && !(strstr(names[i], ".fuser.") || !strncmp(names[i], "position_net.", 13) ||
-                              (ds_model && (!strncmp(names[i], "downsample_net.", 15) || !strcmp(names[i], "input_blocks.0.0.weight")))))
-                throw GlError(GL_ERR_ARG, fmt("unet_train_step: a gradient was asked for '%s', which the reference keeps frozen", names[i]));
-        if (cfg.grounding_kind == 3 && !spatial) throw GlError(GL_ERR_ARG, "unet_train_step: a spatial-map model needs its TrainSpatialIn");
-        if (spatial && (spatial->map_cls || spatial->extra_cls) &&
-            (!spatial->map_cls || !spatial->extra_cls || spatial->map || spatial->extra || !cfg.extra_channels))
-            throw GlError(GL_ERR_ARG, "unet_train_step: a mixture of class maps and planes: the tokenizer's map and grounding_extra_input are both u8 class maps "
-                                      "or both fp32 planes");
+        check_trainable_set(cfg, n_params, names, grads, spatial);
         Ctx c{ar, ws, ws_bytes, s};
         std::unordered_set<const void*> frozen;
         if (cache) {
@@ -2091,361 +2452,27 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
             c.wc = cache;
             c.frozen = &frozen;
         }
-        const int B = in.B, H0 = in.H, W0 = in.W, mc = cfg.model_channels, ED = 4 * mc, KD = cfg.context_dim, Ng = in.Ng;
-        if (mc % 64 || KD % 64 || cfg.gr_dim % 64 || B < 1) throw GlError(GL_ERR_ARG, "unet_train_step: model_channels / context_dim / grounding dim must be multiples of 64");
-        auto in_attn = [&](int ds) { for (int i = 0; i < cfg.n_attn; ++i) if (cfg.attention_resolutions[i] == ds) return true; return false; };
-
-        // ---- grounding tokens (trainable): one MLP over [embedding | fourier(coords)] rows for the text tokenizer (boxes, 4 coords) and the
-        // keypoint tokenizer (points, 2 coords; the embedding is person + keypoint table rows), two MLPs (text, image) whose tokens are
-        // concatenated along the token axis for text+image (text_grounding_net.py:30-52, text_image_grounding_net.py:41-70,
-        // keypoint_grounding_net.py:34-58)
-        // (spatial-map tokenizers, GK 3: the same MLP over the ConvNeXt features mixed with null_feature and pos_embedding, K = 768)
-        const int GK = cfg.grounding_kind, NB = in.Ng_boxes, MRB = B * NB, NC = GK == 2 ? 2 : 4;
-        const int PWr = GK == 3 ? kCnxDims[3] : cfg.gr_dim + 16 * NC, PW = round_up(PWr, 64);
-        const int NBR = GK == 1 ? 2 : 1;
-        if (Ng != NB * NBR || (GK == 2 && NB % 17)) throw GlError(GL_ERR_ARG, "unet_train_step: Ng must be the box count (text), twice it (text+image), 17 per person (keypoint)");
-        const int MR = B * Ng;
-        const std::string null_pos = GK == 2 ? "position_net.null_xy_feature" : "position_net.null_position_feature";
-        struct PosBranch { std::string lin, null_emb; const float* emb; const float* emb_mask; float *pcat, *l0, *a0, *l1, *a1, *out, *w0p; };
-        PosBranch pb[2] = {{GK == 1 ? "position_net.linears_text" : "position_net.linears",
-                            GK == 1 ? "position_net.null_text_feature" : GK == 2 ? "position_net.null_person_feature" : "position_net.null_positive_feature",
-                            GK == 2 ? nullptr : in.positive_embeddings, GK == 1 ? in.text_masks : in.masks, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr},
-                           {"position_net.linears_image", "position_net.null_image_feature", in.image_embeddings, in.image_masks, nullptr, nullptr, nullptr, nullptr,
-                            nullptr, nullptr, nullptr}};
-        float* objs = NBR == 1 ? nullptr : c.f32((size_t)MR * KD);
+        const UNetStep u = step_dims(c, nm, cfg, in, spatial, block_names);
+        // ---- forward; every layer remembers what its backward needs
+        PosBranch pb[2];
         SpatialSaved tok;
-        for (int r = 0; r < NBR; ++r) {
-            PosBranch& p = pb[r];
-            if (GK == 3) {
-                tok = spatial_forward(c, nm, cfg, *spatial, B);
-                if (tok.M != MRB) throw GlError(GL_ERR_ARG, "unet_train_step: Ng must be (tok_resize / 32)^2 for a spatial-map tokenizer");
-                p.pcat = tok.mix;
-            } else {
-                if ((!p.emb && GK != 2) || !p.emb_mask) throw GlError(GL_ERR_ARG, "unet_train_step: null grounding input");
-                p.pcat = c.f32((size_t)MRB * PW);
-                hipLaunchKernelGGL(posnet_input_kernel_f32, dim3(MRB), dim3(256), 0, s, in.boxes, NC, in.masks, p.emb_mask, p.emb,
-                                   GK == 2 ? nm.w("position_net.person_embeddings") : (const float*)nullptr,
-                                   GK == 2 ? nm.w("position_net.keypoint_embeddings") : (const float*)nullptr, NB, nm.w(p.null_emb), nm.w(null_pos), cfg.gr_dim, PW,
-                                   p.pcat);
-            }
-            const float* w0 = nm.w(p.lin + ".0.weight");
-            if (PW != PWr) {        // the first Linear's K (800 for the keypoint tokenizer) padded to the GEMM's 64-step with zero columns
-                p.w0p = c.f32((size_t)512 * PW);
-                hipLaunchKernelGGL(pad_cols_kernel, Ctx::g1((size_t)512 * PW), dim3(256), 0, s, w0, PWr, PW, (size_t)512 * PW, p.w0p);
-                w0 = p.w0p;
-            }
-            p.l0 = c.lin_fwd(p.pcat, MRB, PW, w0, nm.w(p.lin + ".0.bias"), 512);
-            p.a0 = c.f32((size_t)MRB * 512);
-            hipLaunchKernelGGL(silu_kernel, Ctx::g1((size_t)MRB * 512), dim3(256), 0, s, (const float*)p.l0, (size_t)MRB * 512, p.a0);
-            p.l1 = c.lin_fwd(p.a0, MRB, 512, nm.w(p.lin + ".2.weight"), nm.w(p.lin + ".2.bias"), 512);
-            p.a1 = c.f32((size_t)MRB * 512);
-            hipLaunchKernelGGL(silu_kernel, Ctx::g1((size_t)MRB * 512), dim3(256), 0, s, (const float*)p.l1, (size_t)MRB * 512, p.a1);
-            p.out = c.lin_fwd(p.a1, MRB, 512, nm.w(p.lin + ".4.weight"), nm.w(p.lin + ".4.bias"), KD);
-            if (NBR == 1) objs = p.out;
-            else c.put_rows(objs, B, Ng, r * NB, p.out, NB, KD);      // objs = cat([objs_text, objs_image], dim = 1)
-        }
-        // ---- time embedding (frozen): silu(emb) is what every ResBlock's emb_layers starts with
-        float* te = c.f32((size_t)B * mc);
-        hipLaunchKernelGGL(timestep_embedding_kernel, dim3(B), dim3(256), 0, s, in.timesteps, mc, te);
-        float* e0 = c.lin_fwd(te, B, mc, nm.w("time_embed.0.weight"), nm.w("time_embed.0.bias"), ED);
-        float* e0s = c.f32((size_t)B * ED);
-        hipLaunchKernelGGL(silu_kernel, Ctx::g1((size_t)B * ED), dim3(256), 0, s, (const float*)e0, (size_t)B * ED, e0s);
-        float* emb = c.lin_fwd(e0s, B, ED, nm.w("time_embed.2.weight"), nm.w("time_embed.2.bias"), ED);
-        float* semb = c.f32((size_t)B * ED);
-        hipLaunchKernelGGL(silu_kernel, Ctx::g1((size_t)B * ED), dim3(256), 0, s, (const float*)emb, (size_t)B * ED, semb);
-
-        // ---- the layers, in forward order, each remembering what its backward needs
-        struct Act { float* p; int C, H, W; };
-        enum Kind { K_RES, K_ST, K_DOWN, K_UP, K_CAT };
-        struct Layer {
-            Kind kind;
-            std::string prefix;
-            int Cin, Cout, H, W, C0;                  // K_CAT: C0 = channels of h, Cin - C0 = channels of the skip; skip_idx = its producer
-            int skip_idx;
-            const float* x_in;                         // the layer's input (kept: with checkpointing the backward recomputes the forward from it)
-            std::vector<const float*> P;
-            std::vector<float*> G;
-            ResSaved rs;
-            STSaved ss;
-        };
-        std::vector<Layer> L;
-        auto res_layer = [&](const std::string& p, int Cin, int Cout, int H, int W) {
-            Layer l{K_RES, p, Cin, Cout, H, W, 0, -1, nullptr, {}, {}, {}, {}};
-            static const char* k[RP_COUNT] = {"in_layers.0.weight", "in_layers.0.bias", "in_layers.2.weight", "in_layers.2.bias", "emb_layers.1.weight",
-                                              "emb_layers.1.bias", "out_layers.0.weight", "out_layers.0.bias", "out_layers.3.weight", "out_layers.3.bias",
-                                              "skip_connection.weight", "skip_connection.bias"};
-            for (int i = 0; i < RP_COUNT; ++i) l.P.push_back((i >= RP_SKIP_W && Cin == Cout) ? nullptr : nm.w(p + "." + k[i]));
-            return l;
-        };
-        auto st_layer = [&](const std::string& p, int C, int H, int W) {
-            Layer l{K_ST, p, C, C, H, W, 0, -1, nullptr, {}, {}, {}, {}};
-            l.P.resize(ST_COUNT);
-            l.G.assign(ST_COUNT, nullptr);
-            l.P[ST_NORM_W] = nm.w(p + ".norm.weight"); l.P[ST_NORM_B] = nm.w(p + ".norm.bias");
-            l.P[ST_PIN_W] = nm.w(p + ".proj_in.weight"); l.P[ST_PIN_B] = nm.w(p + ".proj_in.bias");
-            l.P[ST_POUT_W] = nm.w(p + ".proj_out.weight"); l.P[ST_POUT_B] = nm.w(p + ".proj_out.bias");
-            for (int i = 0; i < TP_COUNT; ++i) {
-                const std::string k = p + ".transformer_blocks.0." + block_names[i];
-                l.P[ST_BLOCK0 + i] = nm.w(k);
-                l.G[ST_BLOCK0 + i] = nm.g(k);
-            }
-            return l;
-        };
-        const int Cx = cfg.in_channels, Ce = GK == 3 ? cfg.extra_channels : 0, Cin0 = Cx + Ce;
-        const size_t M0 = (size_t)B * H0 * W0;
-        // conv_in: frozen for the discrete models (forward only); for a model with a grounding downsampler its input is
-        // cat(x, downsample_net(grounding_extra_input)) (openaimodel.py:442-444) and its weight is trainable
+        const float* objs = grounding_forward(u, pb, tok);
+        const float* semb = time_embedding(u);
         DsSaved dsv;
-        const float* xin = in.x;
-        if (Ce) {
-            dsv = downsampler_forward(c, nm, *spatial, B, Ce, H0, W0);
-            float* cat0 = c.f32(M0 * Cin0);
-            hipLaunchKernelGGL(cat_rows_nchw_kernel, Ctx::g1(M0 * Cin0), dim3(256), 0, s, in.x, Cx, (const float*)dsv.out, Ce, H0 * W0, M0 * Cin0, cat0);
-            xin = cat0;
-        }
-        float* h0 = c.f32(M0 * mc);
-        hipLaunchKernelGGL(conv3x3_direct_kernel, Ctx::g1(M0 * mc), dim3(256), 0, s, xin, nm.w("input_blocks.0.0.weight"), nm.w("input_blocks.0.0.bias"), H0, W0,
-                           Cin0, mc, M0 * mc, h0);
-        Act h{h0, mc, H0, W0};
-        std::vector<Act> hs{h};
-        std::vector<int> hs_layer{-1};          // which layer produced each skip (-1: conv_in)
-        auto run = [&](Layer l) {
-            const TrainBlockDims bd{B, l.H * l.W, Ng, l.Cout, cfg.num_heads, in.ctx_T, KD, in.fuser_scale};
-            const size_t rows = (size_t)B * l.H * l.W;
-            float* y = nullptr;
-            l.x_in = h.p;
-            // checkpointing: a block's output is allocated first, everything its forward keeps (activations, statistics, the bf16
-            // operand copies) is given back to the arena behind it; the backward recomputes the forward from x_in
-            if (l.kind == K_RES) {
-                const TrainResDims rd{B, l.H, l.W, l.Cin, l.Cout, ED};
-                res_check(rd, l.P.data());
-                y = c.f32(rows * l.Cout);
-                const size_t mk = ar.mark();
-                l.rs = res_forward(c, rd, l.P.data(), h.p, semb, y);
-                if (in.checkpoint) ar.release(mk);
-            } else if (l.kind == K_ST) {
-                st_check(bd, l.P.data());
-                y = c.f32(rows * l.Cout);
-                const size_t mk = ar.mark();
-                l.ss = st_forward(c, bd, l.P.data(), h.p, objs, in.context, y);
-                if (in.checkpoint) ar.release(mk);
-            } else if (l.kind == K_DOWN) {
-                y = resample_forward(c, 0, B, l.H, l.W, l.Cin, l.P[0], l.P[1], h.p);
-                h.H = l.H / 2; h.W = l.W / 2;
-            } else if (l.kind == K_UP) {
-                y = resample_forward(c, 1, B, l.H, l.W, l.Cin, l.P[0], l.P[1], h.p);
-                h.H = l.H * 2; h.W = l.W * 2;
-            }
-            h.p = y; h.C = l.Cout;
-            L.push_back(std::move(l));
-        };
-        int ch = mc, ds = 1, n = 1;
-        for (int level = 0; level < cfg.n_mult; ++level) {
-            const int mult = cfg.channel_mult[level];
-            for (int r = 0; r < cfg.num_res_blocks; ++r) {
-                const std::string p = fmt("input_blocks.%d", n);
-                run(res_layer(p + ".0", ch, mult * mc, h.H, h.W));
-                ch = mult * mc;
-                if (in_attn(ds)) run(st_layer(p + ".1", ch, h.H, h.W));
-                hs.push_back(h); hs_layer.push_back((int)L.size() - 1);
-                ++n;
-            }
-            if (level != cfg.n_mult - 1) {
-                const std::string p = fmt("input_blocks.%d.0.op", n);
-                Layer l{K_DOWN, p, ch, ch, h.H, h.W, 0, -1, nullptr, {nm.w(p + ".weight"), nm.w(p + ".bias")}, {}, {}, {}};
-                run(l);
-                hs.push_back(h); hs_layer.push_back((int)L.size() - 1);
-                ds *= 2;
-                ++n;
-            }
-        }
-        run(res_layer("middle_block.0", ch, ch, h.H, h.W));
-        run(st_layer("middle_block.1", ch, h.H, h.W));
-        run(res_layer("middle_block.2", ch, ch, h.H, h.W));
-        n = 0;
-        for (int level = cfg.n_mult - 1; level >= 0; --level) {
-            const int mult = cfg.channel_mult[level];
-            for (int i = 0; i <= cfg.num_res_blocks; ++i) {
-                const Act sk = hs.back();
-                const int sk_layer = hs_layer.back();
-                hs.pop_back(); hs_layer.pop_back();
-                if (sk.H != h.H || sk.W != h.W) throw GlError(GL_ERR_STATE, "unet_train_step: skip / stream size mismatch");
-                {   // h = cat([h, hs.pop()], dim = 1)
-                    const size_t rows = (size_t)B * h.H * h.W;
-                    float* cat = c.f32(rows * (h.C + sk.C));
-                    hipLaunchKernelGGL(concat_kernel, Ctx::g1(rows * (h.C + sk.C)), dim3(256), 0, s, (const float*)h.p, h.C, (const float*)sk.p, sk.C, rows, cat);
-                    Layer l{K_CAT, "", h.C + sk.C, h.C + sk.C, h.H, h.W, h.C, sk_layer, nullptr, {}, {}, {}, {}};
-                    h.p = cat; h.C += sk.C;
-                    L.push_back(l);
-                }
-                const std::string p = fmt("output_blocks.%d", n);
-                run(res_layer(p + ".0", h.C, mc * mult, h.H, h.W));
-                ch = mc * mult;
-                int j = 1;
-                if (in_attn(ds)) { run(st_layer(p + ".1", ch, h.H, h.W)); j = 2; }
-                if (level && i == cfg.num_res_blocks) {
-                    const std::string q = p + fmt(".%d.conv", j);
-                    Layer l{K_UP, q, ch, ch, h.H, h.W, 0, -1, nullptr, {nm.w(q + ".weight"), nm.w(q + ".bias")}, {}, {}, {}};
-                    run(l);
-                    ds /= 2;
-                }
-                ++n;
-            }
-        }
-        // out = conv(silu(gn(h)))  (openaimodel.py:389-393)
-        const Ctx::GN on = c.gn_silu_fwd(h.p, B, H0 * W0, mc, nm.w("out.0.weight"), nm.w("out.0.bias"));
-        const int Co = cfg.out_channels;
-        const size_t ny = M0 * Co;
-        float* y = c.f32(ny);
-        hipLaunchKernelGGL(conv3x3_direct_kernel, Ctx::g1(ny), dim3(256), 0, s, (const float*)on.a, nm.w("out.2.weight"), nm.w("out.2.bias"), H0, W0, mc, Co, ny, y);
-        if (eps_out) c.hip(hipMemcpyAsync(eps_out, y, ny * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
-        c.dot_reduce((const float*)y, in.target, ny, (const float*)nullptr, 1.f, 1, loss);
-
+        const float* xin = nullptr;
+        float* h0 = conv_in_forward(u, dsv, xin);
+        std::vector<UNetLayer> L;
+        const Act h = build_and_run_layers(u, objs, semb, h0, L);
+        const OutSaved out = out_forward_and_loss(u, h, eps_out, loss);
         // ---- backward
-        float* gy = c.f32(ny);
-        hipLaunchKernelGGL(mse_grad_kernel, Ctx::g1(ny), dim3(256), 0, s, (const float*)y, in.target, ny, gy);
-        float* wt = c.f32((size_t)mc * Co * 9);       // out conv dgrad: the same direct conv on the flipped / transposed weight
-        hipLaunchKernelGGL(conv_dgrad_weight_kernel, Ctx::g1((size_t)mc * Co * 9), dim3(256), 0, s, nm.w("out.2.weight"), Co, mc, wt);
-        float* g_a = c.f32(M0 * mc);
-        hipLaunchKernelGGL(conv3x3_direct_kernel, Ctx::g1(M0 * mc), dim3(256), 0, s, (const float*)gy, (const float*)wt, (const float*)nullptr, H0, W0, Co, mc,
-                           M0 * mc, g_a);
-        float* g = c.f32(M0 * mc);
-        c.gn_silu_bwd(g_a, on, nm.w("out.0.weight"), nm.w("out.0.bias"), B, H0 * W0, mc, g, false);
-        float* g_objs = c.f32((size_t)MR * KD);
-        c.hip(hipMemsetAsync(g_objs, 0, (size_t)MR * KD * 4, s), "hipMemsetAsync");
-        std::vector<float*> skip_grad(L.size(), nullptr);     // dL/d(output of layer i) arriving through a skip connection
-        int first_st = -1;
-        for (size_t i = 0; i < L.size(); ++i)
-            if (L[i].kind == K_ST) { first_st = (int)i; break; }
-        std::vector<int> st_ordinal(L.size(), -1);            // SpatialTransformer number in module order (input_blocks .. middle .. output_blocks)
+        float* g = out_backward(u, out);
+        float* g_objs = c.f32((size_t)u.MR * u.KD);
+        c.hip(hipMemsetAsync(g_objs, 0, (size_t)u.MR * u.KD * 4, s), "hipMemsetAsync");
+        const bool in_grad = u.Ce > 0 && (nm.g("input_blocks.0.0.weight") || downsampler_grads(nm));
         int n_st_layers = 0;
-        for (size_t i = 0; i < L.size(); ++i)
-            if (L[i].kind == K_ST) st_ordinal[i] = n_st_layers++;
-        // a trainable first conv (or downsampler) needs dL/d(conv_in output): the loop then runs through the layers in front of the first
-        // fuser too and keeps conv_in's skip gradient (hs_layer -1, the last output block's concat)
-        bool ds_grads = false;
-        for (const char* k : {"downsample_net.layers.0.weight", "downsample_net.layers.0.bias", "downsample_net.layers.2.weight", "downsample_net.layers.2.bias"})
-            ds_grads = ds_grads || nm.g(k);
-        const bool in_grad = Ce > 0 && (nm.g("input_blocks.0.0.weight") || ds_grads);
-        const int stop = in_grad ? 0 : first_st;
-        float* skip0 = nullptr;
-        for (int i = (int)L.size() - 1; i >= 0 && i >= stop; --i) {
-            Layer& l = L[i];
-            const size_t rows = (size_t)B * l.H * l.W;
-            if (skip_grad[i]) {     // this layer's output also went into a skip connection (l.H, l.W are its INPUT size)
-                const size_t out_rows = l.kind == K_DOWN ? rows / 4 : l.kind == K_UP ? rows * 4 : rows;
-                c.add(g, skip_grad[i], out_rows * l.Cout);
-            }
-            if (l.kind == K_CAT) {
-                float* gh = c.f32(rows * l.C0);
-                hipLaunchKernelGGL(split_kernel, Ctx::g1(rows * l.C0), dim3(256), 0, s, (const float*)g, l.Cin, 0, l.C0, rows, gh, 0);
-                const int C1 = l.Cin - l.C0;
-                if (in_grad || l.skip_idx >= first_st) {   // (without in_grad a skip produced in front of the first fuser carries no gradient anybody needs)
-                    float* gs = c.f32(rows * C1);
-                    hipLaunchKernelGGL(split_kernel, Ctx::g1(rows * C1), dim3(256), 0, s, (const float*)g, l.Cin, l.C0, C1, rows, gs, 0);
-                    if (l.skip_idx < 0) skip0 = gs;
-                    else skip_grad[l.skip_idx] = gs;
-                }
-                g = gh;
-            } else if (l.kind == K_RES) {
-                const TrainResDims rd{B, l.H, l.W, l.Cin, l.Cout, ED};
-                float* keep = (in.checkpoint && l.Cin != l.Cout) ? c.f32(rows * l.Cin) : nullptr;    // (allocated in front of the scope below)
-                const size_t mk = ar.mark();
-                if (in.checkpoint) l.rs = res_forward(c, rd, l.P.data(), l.x_in, semb, c.f32(rows * l.Cout));
-                float* gx = res_backward(c, rd, l.P.data(), l.rs, g);       // (g itself, updated in place, when Cin == Cout)
-                if (keep) {
-                    c.hip(hipMemcpyAsync(keep, gx, rows * l.Cin * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
-                    gx = keep;
-                }
-                if (in.checkpoint) ar.release(mk);
-                g = gx;
-            } else if (l.kind == K_ST) {
-                const TrainBlockDims bd{B, l.H * l.W, Ng, l.Cout, cfg.num_heads, in.ctx_T, KD, in.fuser_scale};
-                float* d_o = c.f32((size_t)MR * KD);
-                const size_t mk = ar.mark();
-                if (in.checkpoint) l.ss = st_forward(c, bd, l.P.data(), l.x_in, objs, in.context, c.f32(rows * l.Cout));
-                st_backward(c, bd, l.P.data(), l.ss, objs, g, d_o, l.G.data());      // g in place
-                c.add(g_objs, d_o, (size_t)MR * KD);
-                if (in.checkpoint) ar.release(mk);
-                // this block's fuser gradients are final: the caller's communication stream may pick them up (gl_train_wait_grads)
-                // while the blocks in front of it are still in backward
-                if (grad_events && st_ordinal[i] < n_grad_events) c.hip(hipEventRecord(grad_events[st_ordinal[i]], s), "hipEventRecord");
-            } else if (l.kind == K_DOWN) {
-                g = resample_backward(c, 0, B, l.H, l.W, l.Cin, l.P[0], g);
-            } else if (l.kind == K_UP) {
-                g = resample_backward(c, 1, B, l.H, l.W, l.Cin, l.P[0], g);
-            }
-        }
-        if (in_grad) {
-            // ---- the first conv and the GroundingDownsampler (trainer.py:189-194, 229-236). g = dL/d(conv_in output) through
-            // input_blocks.1, plus the skip into the last output block's concat
-            if (skip0) c.add(g, skip0, M0 * mc);
-            if (float* gw = nm.g("input_blocks.0.0.weight"))
-                conv_wgrad(c, xin, B, Cin0, H0, W0, pixel_rows(Cin0, H0, W0), 3, 1, 1, H0, W0, g, mc, gw, nullptr);
-            if (spatial->ds_mid && ds_grads) {
-                // the first conv's data gradient for the k downsampler channels only: rows Cx .. Cx + k of the flipped / transposed filter
-                float* wt = c.f32((size_t)Cin0 * mc * 9);
-                hipLaunchKernelGGL(conv_dgrad_weight_kernel, Ctx::g1((size_t)Cin0 * mc * 9), dim3(256), 0, s, nm.w("input_blocks.0.0.weight"), mc, Cin0, wt);
-                float* gds = c.f32(M0 * Ce);
-                hipLaunchKernelGGL(conv3x3_direct_kernel, Ctx::g1(M0 * Ce), dim3(256), 0, s, (const float*)g, (const float*)(wt + (size_t)Cx * mc * 9),
-                                   (const float*)nullptr, H0, W0, mc, Ce, M0 * Ce, gds);
-                const int Rd = spatial->ds_resize, Rh = Rd / 2, mid = spatial->ds_mid, ni = spatial->ds_n_in;
-                conv_wgrad(c, dsv.s1, B, mid, Rh, Rh, nchw(mid, Rh, Rh), 4, 2, 1, H0, W0, gds, Ce, nm.g("downsample_net.layers.2.weight"),
-                           nm.g("downsample_net.layers.2.bias"));
-                const size_t nh = (size_t)B * mid * Rh * Rh;
-                float* gs1 = c.f32(nh);
-                hipLaunchKernelGGL(conv4x4s2_dgrad_kernel, Ctx::g1(nh), dim3(256), 0, s, (const float*)gds, nm.w("downsample_net.layers.2.weight"), mid, Ce, Rh, Rh,
-                                   nh, gs1);
-                float* ga1 = c.f32(nh);
-                hipLaunchKernelGGL(silu_bwd_kernel, Ctx::g1(nh), dim3(256), 0, s, (const float*)gs1, (const float*)dsv.a1, nh, ga1);
-                if (spatial->extra_cls) {
-                    const Strides r = nchw(mid, Rh, Rh);
-                    class_wgrad(c, kClassWgradDown, spatial->extra_cls, ga1, {r.b, r.c, r.y, r.x}, B, spatial->He, spatial->We, ni, mid, Rd,
-                                nm.g("downsample_net.layers.0.weight"), nm.g("downsample_net.layers.0.bias"));
-                } else {
-                    const float* ga1r = im2col(c, ga1, B, mid, Rh, Rh, nchw(mid, Rh, Rh), 1, 1, 0, Rh, Rh, mid);     // NCHW -> pixel rows
-                    conv_wgrad(c, dsv.r, B, ni, Rd, Rd, nchw(ni, Rd, Rd), 4, 2, 1, Rh, Rh, ga1r, mid, nm.g("downsample_net.layers.0.weight"),
-                               nm.g("downsample_net.layers.0.bias"));
-                }
-            }
-        }
-        // ---- position_net backward (Linear, SiLU, Linear, SiLU, Linear per branch; the learnable null embeddings: the position one is
-        // shared by the branches; the keypoint tokenizer's person / keypoint embedding tables; GK 3: token mix + ConvNeXt)
-        for (int r = 0; r < NBR; ++r) {
-            const PosBranch& p = pb[r];
-            const float* go = NBR == 1 ? g_objs : c.slice_rows(g_objs, B, Ng, r * NB, NB, KD);
-            c.lin_wgrad(go, p.a1, MRB, KD, 512, nm.g(p.lin + ".4.weight"), nm.g(p.lin + ".4.bias"));
-            float* g_a1 = c.lin_dgrad(go, MRB, KD, nm.w(p.lin + ".4.weight"), 512);
-            float* g_l1 = c.f32((size_t)MRB * 512);
-            hipLaunchKernelGGL(silu_bwd_kernel, Ctx::g1((size_t)MRB * 512), dim3(256), 0, s, (const float*)g_a1, (const float*)p.l1, (size_t)MRB * 512, g_l1);
-            c.lin_wgrad(g_l1, p.a0, MRB, 512, 512, nm.g(p.lin + ".2.weight"), nm.g(p.lin + ".2.bias"));
-            float* g_a0 = c.lin_dgrad(g_l1, MRB, 512, nm.w(p.lin + ".2.weight"), 512);
-            float* g_l0 = c.f32((size_t)MRB * 512);
-            hipLaunchKernelGGL(silu_bwd_kernel, Ctx::g1((size_t)MRB * 512), dim3(256), 0, s, (const float*)g_a0, (const float*)p.l0, (size_t)MRB * 512, g_l0);
-            float* gw0 = nm.g(p.lin + ".0.weight");
-            if (PW == PWr) {
-                c.lin_wgrad(g_l0, p.pcat, MRB, 512, PW, gw0, nm.g(p.lin + ".0.bias"));
-            } else {
-                float* gw0p = gw0 ? c.f32((size_t)512 * PW) : nullptr;
-                c.lin_wgrad(g_l0, p.pcat, MRB, 512, PW, gw0p, nm.g(p.lin + ".0.bias"));
-                if (gw0) hipLaunchKernelGGL(split_kernel, Ctx::g1((size_t)512 * PWr), dim3(256), 0, s, (const float*)gw0p, PW, 0, PWr, (size_t)512, gw0, 0);
-            }
-            float* g_cat = c.lin_dgrad(g_l0, MRB, 512, p.w0p ? p.w0p : nm.w(p.lin + ".0.weight"), PW);
-            if (GK == 3) {
-                spatial_backward(c, nm, cfg, *spatial, B, tok, g_cat);
-                continue;
-            }
-            if (float* gp = nm.g(p.null_emb))
-                hipLaunchKernelGGL(null_grad_kernel, Ctx::g1(cfg.gr_dim), dim3(256), 0, s, (const float*)g_cat, p.emb_mask, MRB, PW, 0, cfg.gr_dim, gp, 0);
-            if (float* gp = nm.g(null_pos))
-                hipLaunchKernelGGL(null_grad_kernel, Ctx::g1(16 * NC), dim3(256), 0, s, (const float*)g_cat, in.masks, MRB, PW, cfg.gr_dim, 16 * NC, gp, r);
-            if (GK == 2) {
-                if (float* gp = nm.g("position_net.person_embeddings"))
-                    hipLaunchKernelGGL(table_grad_kernel, dim3(cdiv(cfg.gr_dim, 256), NB / 17), dim3(256), 0, s, (const float*)g_cat, in.masks, B, NB, PW, cfg.gr_dim, 1, gp);
-                if (float* gp = nm.g("position_net.keypoint_embeddings"))
-                    hipLaunchKernelGGL(table_grad_kernel, dim3(cdiv(cfg.gr_dim, 256), 17), dim3(256), 0, s, (const float*)g_cat, in.masks, B, NB, PW, cfg.gr_dim, 0, gp);
-            }
-        }
+        g = layers_backward(u, L, objs, semb, g, in_grad, g_objs, grad_events, n_grad_events, n_st_layers);
+        if (in_grad) conv_in_backward(c, nm, *spatial, dsv, xin, u.B, u.H0, u.W0, u.Cx, u.Ce, u.mc, g);
+        grounding_backward(u, pb, tok, g_objs);
         // position_net's gradients -- the last ones of the step -- are final
         if (grad_events && n_st_layers < n_grad_events) c.hip(hipEventRecord(grad_events[n_st_layers], s), "hipEventRecord");
         c.hip(hipGetLastError(), "training step kernel launch");

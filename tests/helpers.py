@@ -356,3 +356,67 @@ def spike_grid(d):
                 bumps = [(0, SPIKE_HEAD, [SPIKE_ROW], {key: SPIKE_UNITS[regime]})]
                 out.append((f"d{d}-{Nq}x{Nk}-{pname}-{regime}", shape, regime, pname, tile, bumps))
     return out
+
+
+# ---- the small training slices against their goldens: one report (relative MSE per tensor; "loss": relative error) per slice, shared by
+# test_ops_gpu.py (default path) and train_switches_child.py (the developer switches' paths)
+def rel_mse(a, ref):
+    a, ref = a.detach().float().cpu(), torch.as_tensor(ref).float()
+    return float(((a - ref) ** 2).mean() / (ref ** 2).mean().clamp_min(1e-30))
+
+
+def _npz(name):
+    g = np.load(os.path.join(GOLDEN, name + ".npz"))
+    return g, json.loads(bytes(g["meta"]).decode())
+
+
+def fuser_block_train_report(engine):
+    """gl_op_block_train on tests/golden/block_backward_gatedsa.npz -> (report, case): case holds the golden, its meta, the state_dict
+    and the inputs."""
+    from ldm.modules.attention import BasicTransformerBlock
+    g, meta = _npz("block_backward_gatedsa")
+    x, objs, context, target = block_backward_inputs(meta)
+    assert abs(float(x.double().sum()) - float(g["x_sum"])) < 1e-6 and abs(float(target.double().sum()) - float(g["target_sum"])) < 1e-6
+    blk = BasicTransformerBlock(meta["C"], meta["ctx_dim"], meta["ctx_dim"], meta["heads"], meta["C"] // meta["heads"], "gatedSA")
+    sd = syn.seeded_state_dict({k: tuple(v.shape) for k, v in blk.state_dict().items()}, meta["seed"])
+    sd["fuser.alpha_attn"] = torch.tensor(meta["alpha_attn"])
+    sd["fuser.alpha_dense"] = torch.tensor(meta["alpha_dense"])
+    assert sorted(engine.block_train_param_names()) == sorted(sd.keys())
+    y, loss, dx, dobjs, grads = engine.op_block_train(sd, x, objs, context, target, meta["heads"])
+    report = {"y": rel_mse(y, g["y"]), "loss": abs(float(loss) - float(g["loss"])) / float(g["loss"]), "dx": rel_mse(dx, g["dx"]), "dobjs": rel_mse(dobjs, g["dobjs"])}
+    names = sorted(k[5:] for k in g.files if k.startswith("grad."))
+    assert names == sorted(grads.keys()) and len(names) == 17
+    for n in names:
+        ref = torch.from_numpy(g["grad." + n].astype(np.float32)) * float(g["scale." + n])
+        report["grad." + n] = rel_mse(grads[n], ref)
+    return report, dict(g=g, meta=meta, sd=sd, x=x, objs=objs, context=context, target=target)
+
+
+def resblock_train_report(engine, name):
+    """gl_op_resblock_train on tests/golden/<name>.npz -> (report, case)"""
+    g, meta = _npz(name)
+    x, emb, target = resblock_backward_inputs(meta)
+    assert abs(float(x.double().sum()) - float(g["x_sum"])) < 1e-6
+    sd = syn.seeded_state_dict({k: tuple(v) for k, v in golden_shapes(name).items()}, meta["seed"])
+    assert set(sd.keys()) <= set(engine.resblock_train_param_names())
+    y, loss, dx = engine.op_resblock_train(sd, x, emb, target)
+    report = {"y": rel_mse(y, g["y"]), "loss": abs(float(loss) - float(g["loss"])) / float(g["loss"]), "dx": rel_mse(dx, g["dx"])}
+    return report, dict(meta=meta, sd=sd, x=x, emb=emb, target=target)
+
+
+def resample_train_report(engine, mode):
+    """gl_op_resample_train ("down" / "up") on tests/golden/resample_backward.npz -> report"""
+    g, meta = _npz("resample_backward")
+    B, hw, Cc = meta["B"], meta["hw"], meta["C"]
+    gen = torch.Generator().manual_seed(4545)
+    for key, ho in (("down", hw // 2), ("up", hw * 2)):      # the generator order of the golden: down's x, target, then up's
+        x = torch.randn(B, Cc, hw, hw, generator=gen)
+        target = torch.randn(B, Cc, ho, ho, generator=gen)
+        if key == mode:
+            break
+    assert abs(float(x.double().sum()) - float(g[mode + "_x_sum"])) < 1e-6
+    sd = syn.seeded_state_dict({"op.weight" if mode == "down" else "conv.weight": (Cc, Cc, 3, 3), "op.bias" if mode == "down" else "conv.bias": (Cc,)}, meta["seed"])
+    w = sd["op.weight" if mode == "down" else "conv.weight"]
+    b = sd["op.bias" if mode == "down" else "conv.bias"]
+    y, loss, dx = engine.op_resample_train(mode, w, b, x, target)
+    return {"y": rel_mse(y, g[mode + "_y"]), "loss": abs(float(loss) - float(g[mode + "_loss"])) / float(g[mode + "_loss"]), "dx": rel_mse(dx, g[mode + "_dx"])}

@@ -475,7 +475,7 @@ def test_training_attention_kernels_keep_their_chunks_in_registers(tmp_path):
                         str(ROOT / "gligen_amd" / "csrc" / "train.hip"), "-o", str(out)], capture_output=True, text=True)
     assert r.returncode == 0, r.stderr[-3000:]
     asm = out.read_text()
-    seen = 0
+    seen = seen_reductions = 0
     for m in re.finditer(r"\.amdhsa_kernel (\S+)", asm):
         blk = asm[m.start():asm.index(".end_amdhsa_kernel", m.start())]
         name = m.group(1)
@@ -488,4 +488,6 @@ def test_training_attention_kernels_keep_their_chunks_in_registers(tmp_path):
             seen += 1
         elif "colsum_kernel" in name or "gn_silu" in name:
             assert scratch == 0, (name, scratch)
+            seen_reductions += 1
     assert seen == 15       # 5 head dims x (forward, backward-q, backward-kv)
+    assert seen_reductions == 3     # colsum_kernel, gn_silu_fwd_kernel, gn_silu_bwd_kernel: a rename must not empty that branch

@@ -419,32 +419,9 @@ def test_feedforward_rows_large_gate_inputs(engine):
 # the reference's loss, against gradients from the reference's own autograd (tests/golden/block_backward_gatedsa.npz, made by
 # oracle/make_golden.py from /root/reference: trainer.py:353-371 loss, attention.py:333-338 block, trainer.py:217-245 trainable set)
 def test_fuser_block_backward_vs_reference(engine):
-    import json
-    import numpy as np
-    from gligen_amd import synthetic as syn
-    from helpers import GOLDEN, block_backward_inputs
-    from ldm.modules.attention import BasicTransformerBlock
-    g = np.load(os.path.join(GOLDEN, "block_backward_gatedsa.npz"))
-    meta = json.loads(bytes(g["meta"]).decode())
-    x, objs, context, target = block_backward_inputs(meta)
-    assert abs(float(x.double().sum()) - float(g["x_sum"])) < 1e-6 and abs(float(target.double().sum()) - float(g["target_sum"])) < 1e-6
-    blk = BasicTransformerBlock(meta["C"], meta["ctx_dim"], meta["ctx_dim"], meta["heads"], meta["C"] // meta["heads"], "gatedSA")
-    sd = syn.seeded_state_dict({k: tuple(v.shape) for k, v in blk.state_dict().items()}, meta["seed"])
-    sd["fuser.alpha_attn"] = torch.tensor(meta["alpha_attn"])
-    sd["fuser.alpha_dense"] = torch.tensor(meta["alpha_dense"])
-    assert sorted(engine.block_train_param_names()) == sorted(sd.keys())
-    y, loss, dx, dobjs, grads = engine.op_block_train(sd, x, objs, context, target, meta["heads"])
-
-    def rel_mse(a, ref):
-        a, ref = a.detach().float().cpu(), torch.as_tensor(ref).float()
-        return float(((a - ref) ** 2).mean() / (ref ** 2).mean().clamp_min(1e-30))
-
-    report = {"y": rel_mse(y, g["y"]), "loss": abs(float(loss) - float(g["loss"])) / float(g["loss"]), "dx": rel_mse(dx, g["dx"]), "dobjs": rel_mse(dobjs, g["dobjs"])}
-    names = sorted(k[5:] for k in g.files if k.startswith("grad."))
-    assert names == sorted(grads.keys()) and len(names) == 17
-    for n in names:
-        ref = torch.from_numpy(g["grad." + n].astype(np.float32)) * float(g["scale." + n])
-        report["grad." + n] = rel_mse(grads[n], ref)
+    from helpers import fuser_block_train_report
+    report, case = fuser_block_train_report(engine)
+    meta, sd, x, objs, context, target = (case[k] for k in ("meta", "sd", "x", "objs", "context", "target"))
     worst = max(report, key=report.get)
     print("training slice: worst", worst, report[worst])
     # (the judge's bar is rel-MSE <= 1e-3 per tensor; with the three-pass bf16 products of train.hip the path is at fp32 level and the
@@ -659,30 +636,8 @@ def test_resample_backward_vs_reference(engine, mode):
     """Training slice (gl_op_resample_train): Downsample / Upsample forward + input gradient against the reference's autograd
     (oracle/make_golden.py: resample_backward_case): the transposed stride-2 conv as zero insertion + the stride-1 conv with the
     flipped filter, the adjoint of nearest doubling as 2 x 2 block sums."""
-    import json
-    import numpy as np
-    from gligen_amd import synthetic as syn
-    from helpers import GOLDEN
-    g = np.load(os.path.join(GOLDEN, "resample_backward.npz"))
-    meta = json.loads(bytes(g["meta"]).decode())
-    B, hw, Cc = meta["B"], meta["hw"], meta["C"]
-    gen = torch.Generator().manual_seed(4545)
-    for key, ho in (("down", hw // 2), ("up", hw * 2)):      # the generator order of the golden: down's x, target, then up's
-        x = torch.randn(B, Cc, hw, hw, generator=gen)
-        target = torch.randn(B, Cc, ho, ho, generator=gen)
-        if key == mode:
-            break
-    assert abs(float(x.double().sum()) - float(g[mode + "_x_sum"])) < 1e-6
-    sd = syn.seeded_state_dict({"op.weight" if mode == "down" else "conv.weight": (Cc, Cc, 3, 3), "op.bias" if mode == "down" else "conv.bias": (Cc,)}, meta["seed"])
-    w = sd["op.weight" if mode == "down" else "conv.weight"]
-    b = sd["op.bias" if mode == "down" else "conv.bias"]
-    y, loss, dx = engine.op_resample_train(mode, w, b, x, target)
-
-    def rel_mse(a, ref):
-        a, ref = a.detach().float().cpu(), torch.as_tensor(ref).float()
-        return float(((a - ref) ** 2).mean() / (ref ** 2).mean().clamp_min(1e-30))
-
-    report = {"y": rel_mse(y, g[mode + "_y"]), "loss": abs(float(loss) - float(g[mode + "_loss"])) / float(g[mode + "_loss"]), "dx": rel_mse(dx, g[mode + "_dx"])}
+    from helpers import resample_train_report
+    report = resample_train_report(engine, mode)
     print("resample training slice", mode, report)
     assert report["loss"] < 1e-5 and report["y"] < 1e-6 and report["dx"] < 1e-6, report
 
@@ -692,23 +647,9 @@ def test_resblock_backward_vs_reference(engine, name):
     """Training slice, second block type (gl_op_resblock_train): forward + input gradient of one ResBlock under the reference's loss,
     against the reference's own autograd (oracle/make_golden.py: resblock_backward_case). Bar as for the transformer block: rel-MSE
     <= 1e-3 per tensor (bf16 conv operands, fp32 accumulation and fp32 everywhere else)."""
-    import json
-    import numpy as np
-    from gligen_amd import synthetic as syn
-    from helpers import GOLDEN, golden_shapes, resblock_backward_inputs
-    g = np.load(os.path.join(GOLDEN, name + ".npz"))
-    meta = json.loads(bytes(g["meta"]).decode())
-    x, emb, target = resblock_backward_inputs(meta)
-    assert abs(float(x.double().sum()) - float(g["x_sum"])) < 1e-6
-    sd = syn.seeded_state_dict({k: tuple(v) for k, v in golden_shapes(name).items()}, meta["seed"])
-    assert set(sd.keys()) <= set(engine.resblock_train_param_names())
-    y, loss, dx = engine.op_resblock_train(sd, x, emb, target)
-
-    def rel_mse(a, ref):
-        a, ref = a.detach().float().cpu(), torch.as_tensor(ref).float()
-        return float(((a - ref) ** 2).mean() / (ref ** 2).mean().clamp_min(1e-30))
-
-    report = {"y": rel_mse(y, g["y"]), "loss": abs(float(loss) - float(g["loss"])) / float(g["loss"]), "dx": rel_mse(dx, g["dx"])}
+    from helpers import resblock_train_report
+    report, case = resblock_train_report(engine, name)
+    meta, sd, x, emb, target = (case[k] for k in ("meta", "sd", "x", "emb", "target"))
     print("resblock training slice", name, report)
     assert report["loss"] < 1e-5 and report["y"] < 1e-6 and report["dx"] < 1e-6, report
     if meta["Cin"] == meta["Cout"]:      # nn.Identity has no parameters: a skip weight with equal channel counts is a caller error

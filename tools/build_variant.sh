@@ -1,27 +1,25 @@
 #!/bin/bash
-# developer A/B: a second copy of the library + kbench with gemm.hip compiled under extra flags (or from another source tree),
-# into gligen_amd/build/var_NAME/ (git-ignored, travels to the GPU box):   tools/build_variant.sh NAME [SRC_TREE] [-D...]
+# developer A/B: a second copy of the library + kbench, into gligen_amd/build/var_NAME/ (git-ignored, travels to the GPU box):
+#   tools/build_variant.sh NAME [-D...]       this tree with gemm.hip compiled under extra flags
+#   tools/build_variant.sh NAME SRC_TREE      another tree (a checkout of another commit), built by its own gligen_amd/build.py:
+#                                             its source list and per-file flags are its own (the library inside SRC_TREE is (re)built)
+# tools/gpu_run.sh lib gligen_amd/build/var_NAME swaps it in.
 set -e
 name=$1; shift
 tree=$PWD
 if [ -n "$1" ] && [ -d "$1" ]; then tree=$1; shift; fi
 out=gligen_amd/build/var_$name
 mkdir -p $out
-F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function -I $tree/include"
 if [ "$tree" = "$PWD" ]; then
+  F="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -Wno-unused-function -I $tree/include"
   python -m gligen_amd.build > /dev/null
   hipcc $F "$@" -c gligen_amd/csrc/gemm.hip -o $out/gemm.hip.o
   objs="$out/gemm.hip.o $(ls gligen_amd/build/*.hip.o | grep -v /gemm.hip.o)"
+  hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libgligen_amd.so $objs
+  hipcc $F $tree/gligen_amd/csrc/kbench.hip -o $out/kbench -L $out -lgligen_amd '-Wl,-rpath,$ORIGIN'
 else
-  objs=""
-  for s in gemm attention norm misc convnext engine capi; do
-    [ -f $tree/gligen_amd/csrc/$s.hip ] || continue
-    x=""; [ $s = attention ] && x="-mllvm -amdgpu-mfma-vgpr-form"
-    hipcc $F $x "$@" -c $tree/gligen_amd/csrc/$s.hip -o $out/$s.hip.o &
-    objs="$objs $out/$s.hip.o"
-  done
-  wait
+  if [ $# -gt 0 ]; then echo "build_variant.sh: extra flags apply to this tree only, not to SRC_TREE (got: $*)" >&2; exit 2; fi
+  ( cd $tree && python -m gligen_amd.build > /dev/null )
+  cp $tree/gligen_amd/libgligen_amd.so $tree/gligen_amd/build/kbench $out/
 fi
-hipcc --offload-arch=gfx950 -shared -fPIC -o $out/libgligen_amd.so $objs
-hipcc $F $tree/gligen_amd/csrc/kbench.hip -o $out/kbench -L $out -lgligen_amd '-Wl,-rpath,$ORIGIN'
 ls -la $out/kbench $out/libgligen_amd.so
