@@ -1,5 +1,5 @@
 """ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
-include/gligen_amd_train_maps.h).
+include/gligen_amd_train_maps.h and include/gligen_amd_train_inputs.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -87,6 +87,12 @@ class TrainSpatialIn(C.Structure):   # = gl_train_spatial_in
 class TrainSpatialClassesIn(C.Structure):   # = gl_train_spatial_classes_in
     _fields_ = [("map", C.c_void_p), ("map_h", C.c_int), ("map_w", C.c_int), ("mask", C.c_void_p), ("extra", C.c_void_p)] + \
                [(n, C.c_int) for n in ("extra_h", "extra_w", "ds_resize", "ds_mode", "ds_n_in", "ds_mid")]
+
+
+class TrainStepInputsArgs(C.Structure):   # = gl_train_step_inputs_args
+    _fields_ = [("struct_size", C.c_uint)] + [(n, C.c_int) for n in ("B", "C", "H", "W", "n_t", "n_boxes", "inpaint")] + \
+               [(n, C.c_void_p) for n in ("z", "noise", "timesteps", "sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod", "boxes", "mask",
+                                          "x_rows", "target_rows", "t_float")]
 
 
 class BoxCalibration(C.Structure):   # = gl_box_calibration
@@ -188,6 +194,11 @@ TRAIN_MAP_SYMBOLS = {
     "gl_op_class_conv_wgrad": (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _P]),
 }
 
+# every symbol include/gligen_amd_train_inputs.h declares (the input stage of a training iteration)
+TRAIN_INPUT_SYMBOLS = {
+    "gl_train_step_inputs": (_I, [_P, C.POINTER(TrainStepInputsArgs), _P]),
+}
+
 _lib = None
 
 
@@ -205,7 +216,7 @@ def load() -> C.CDLL:
     # torch.cuda.is_available() is True) -- seen with build() called before the first `import torch` of the process.
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

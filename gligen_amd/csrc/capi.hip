@@ -4,6 +4,7 @@
 #include "image.h"
 #include "train.h"
 #include "../../include/gligen_amd_train_maps.h"
+#include "../../include/gligen_amd_train_inputs.h"
 
 #include <cstdlib>
 
@@ -795,8 +796,9 @@ int gl_unet_train_step(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_un
                        const float* const* params, float* const* grads, float* eps_out, float* loss, gl_stream s) {
     NEED(ctx);
     if (!cfg || !in || !names || !params || !grads || !loss || n_params <= 0) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step: null pointer");
-    if (cfg->grounding_kind < 0 || cfg->grounding_kind > 2 || cfg->fuser_kind != 0 || cfg->inpaint_mode || cfg->extra_channels)
-        return gl::set_error(GL_ERR_UNSUPPORTED, "gl_unet_train_step: the training step is built for the text, text+image and keypoint tokenizers with gatedSA fusers (no inpainting / downsampler channels)");
+    if (cfg->grounding_kind < 0 || cfg->grounding_kind > 2 || cfg->fuser_kind != 0 || cfg->extra_channels)
+        return gl::set_error(GL_ERR_UNSUPPORTED, "gl_unet_train_step: the training step is built for the text, text+image and keypoint tokenizers with gatedSA fusers, "
+                                                 "with or without inpaint_mode (no downsampler channels: inpaint_mode with extra_channels is undefined in the reference)");
     if (cfg->grounding_kind == 1 && (!in->text_masks || !in->image_masks || !in->image_embeddings))
         return gl::set_error(GL_ERR_ARG, "gl_unet_train_step: the text+image tokenizer needs text_masks, image_masks and image_embeddings");
     if (!in->x || !in->timesteps || !in->context || !in->boxes || !in->masks || (!in->positive_embeddings && cfg->grounding_kind != 2) || !in->target)
@@ -810,6 +812,7 @@ int gl_unet_train_step(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_un
     c.in_channels = cfg->in_channels; c.out_channels = cfg->out_channels; c.model_channels = cfg->model_channels; c.num_res_blocks = cfg->num_res_blocks;
     c.num_heads = cfg->num_heads; c.context_dim = cfg->context_dim; c.gr_dim = cfg->gr_in_dim; c.grounding_kind = cfg->grounding_kind; c.n_mult = cfg->n_mult; c.n_attn = cfg->n_attn;
     for (int i = 0; i < 8; ++i) { c.channel_mult[i] = cfg->channel_mult[i]; c.attention_resolutions[i] = cfg->attention_resolutions[i]; }
+    c.inpaint_mode = cfg->inpaint_mode ? 1 : 0;       // in->x then holds 2 * in_channels + 1 channels per pixel row
     gl::TrainUNetIn u{in->B, in->H, in->W, in->ctx_T, cfg->grounding_kind == 1 ? 2 * in->Ng : in->Ng, in->Ng, in->x, in->timesteps, in->context, in->boxes,
                       in->masks, in->positive_embeddings, in->text_masks, in->image_masks, in->image_embeddings, in->target, in->fuser_scale, in->checkpoint};
     int rc = gl::unet_train_step(eng.arena(), eng.splitk_ws(), eng.splitk_ws_bytes(), c, u, n_params, names, params, grads, k_train_block_names, eps_out, loss, S(s),
@@ -825,7 +828,8 @@ static int train_step_spatial(const char* what, gl_ctx* ctx, const gl_unet_confi
     NEED(ctx);
     if (!cfg || !in || !names || !params || !grads || !loss || n_params <= 0) return gl::set_error(GL_ERR_ARG, "%s: null pointer", what);
     if (cfg->inpaint_mode)
-        return gl::set_error(GL_ERR_UNSUPPORTED, "%s: training an inpainting model (9-channel first conv) is not built", what);
+        return gl::set_error(GL_ERR_UNSUPPORTED, "%s: inpaint_mode with a spatial-map tokenizer is undefined in the reference (openaimodel.py:445-446); "
+                                                 "gl_unet_train_step trains the inpainting models", what);
     if (cfg->grounding_kind != 3 || cfg->fuser_kind != 0)
         return gl::set_error(GL_ERR_UNSUPPORTED, "%s: built for a spatial-map tokenizer (grounding_kind 3) with gatedSA fusers", what);
     if (cfg->tok_resize < 32 || cfg->tok_resize % 32 || cfg->extra_channels < 0)
@@ -875,6 +879,21 @@ int gl_unet_train_step_spatial_classes(gl_ctx* ctx, const gl_unet_config* cfg, c
     spi.map_cls = sp->map;
     spi.extra_cls = sp->extra;
     return train_step_spatial("gl_unet_train_step_spatial_classes", ctx, cfg, in, spi, n_params, names, params, grads, eps_out, loss, s);
+}
+
+// ---- include/gligen_amd_train_inputs.h: the input stage of a training iteration, one launch
+int gl_train_step_inputs(gl_ctx* ctx, const gl_train_step_inputs_args* args, gl_stream s) {
+    NEED(ctx);
+    if (!args) return gl::set_error(GL_ERR_ARG, "gl_train_step_inputs: null args");
+    if (args->struct_size != sizeof(gl_train_step_inputs_args))
+        return gl::set_error(GL_ERR_ARG, "gl_train_step_inputs: args->struct_size is %u, this library's gl_train_step_inputs_args has %zu bytes (set it to "
+                                         "sizeof(gl_train_step_inputs_args))", args->struct_size, sizeof(gl_train_step_inputs_args));
+    GL_API_BEGIN
+    gl::TrainStepInputs a{args->B, args->C, args->H, args->W, args->n_t, args->n_boxes, args->inpaint ? 1 : 0, args->z, args->noise, args->timesteps,
+                          args->sqrt_alphas_cumprod, args->sqrt_one_minus_alphas_cumprod, args->boxes, args->mask, args->x_rows, args->target_rows, args->t_float};
+    GL_TRY(gl::train_step_inputs_launch(a, S(s)));
+    ++ctx->eng->n_launches;
+    GL_API_END
 }
 
 int gl_op_class_conv_wgrad(gl_ctx* ctx, int kind, const uint8_t* cls, int B, int H, int W, int n_classes, int R, const float* dy, int c_out,

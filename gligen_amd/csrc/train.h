@@ -62,6 +62,7 @@ struct TrainUNetCfg {
     int n_mult, channel_mult[8], n_attn, attention_resolutions[8];
     int extra_channels;                 // grounding_kind 3: GroundingDownsampler output channels in front of the first conv (0: none)
     int tok_resize, tok_in_dim;         // grounding_kind 3: PositionNet resize_input; channels of a semantic map (sem: in_conv first), else 0
+    int inpaint_mode;                   // grounding_kind 0 / 1 / 2: the first conv reads 2 * in_channels + 1 channels (openaimodel.py:299-302, 445-447)
 };
 // The spatial-map inputs of a training step (grounding_kind 3): the tokenizer's map and mask, grounding_extra_input and the
 // GroundingDownsampler's constants (canny / depth / normal / sem / hed_grounding_downsampler.py)
@@ -80,7 +81,8 @@ struct TrainSpatialIn {
 struct TrainUNetIn {
     int B, H, W, ctx_T, Ng;             // Ng: grounding tokens per sample = Ng_boxes (text) or 2 * Ng_boxes (text+image)
     int Ng_boxes;
-    const float* x;                     // [B][H*W][in_channels] pixel rows: the noised latent
+    const float* x;                     // [B][H*W][in_channels] pixel rows: the noised latent; inpaint_mode: [B][H*W][2 * in_channels + 1], the
+                                        // noised latent, z * mask, mask (inpainting_extra_input, trainer.py:343-344), concatenated by the caller
     const float* timesteps;             // [B]
     const float* context;               // [B][ctx_T][context_dim]
     const float* boxes;                 // [B][Ng_boxes][4]
@@ -109,7 +111,20 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
 // fuser gradients -- the backward runs from the last block to the first, so high j come early --, event [number of SpatialTransformers]
 // when position_net's, downsample_net's and the first conv's (the last gradients of the step) are written.
 // spatial: required for grounding_kind 3; the trainable set then also admits downsample_net.* and, with extra_channels > 0,
-// input_blocks.0.0.weight (trainer.py:189-194, 233)
+// input_blocks.0.0.weight (trainer.py:189-194, 233). An inpainting model (inpaint_mode, grounding_kind 0 / 1 / 2) admits that weight too.
+
+// The step's input stage in one launch (include/gligen_amd_train_inputs.h, train_inputs.hip): q_sample, the box mask, z * mask and the
+// concatenation as the pixel rows TrainUNetIn.x / .target point at. Device pointers; boxes xor mask when inpaint, neither otherwise.
+struct TrainStepInputs {
+    int B, C, H, W, n_t, n_boxes, inpaint;
+    const float *z, *noise;             // [B][C][H][W]
+    const int64_t* timesteps;           // [B]
+    const float *sqrt_ac, *sqrt_1mac;   // [n_t]
+    const float* boxes;                 // [B][n_boxes][4]
+    const float* mask;                  // [B][H*W]
+    float *x_rows, *target_rows, *t_float;
+};
+int train_step_inputs_launch(const TrainStepInputs& a, hipStream_t s);
 
 // One AdamW update of a flat fp32 parameter range, in place (torch.optim.AdamW semantics: trainer.py:245, :384 opt.step()); step = 1, 2, ...
 int adamw_step(float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps, double wd, int step, hipStream_t s);

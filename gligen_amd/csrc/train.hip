@@ -2043,11 +2043,14 @@ bool downsampler_grads(const Names& nm) {
 }
 
 // The first conv and the GroundingDownsampler (trainer.py:189-194, 229-236)
-void conv_in_backward(const Ctx& c, const Names& nm, const TrainSpatialIn& sp, const DsSaved& dsv, const float* xin, int B, int H0, int W0, int Cx, int Ce,
-                      int mc, const float* g) {
-    const int Cin0 = Cx + Ce;
+// (an inpainting model: Ci = Cx + 1 channels of inpainting_extra_input behind the latent's, no downsampler, `spatial` null -- only
+// the weight gradient applies: nothing trainable sits in front of the first conv)
+void conv_in_backward(const Ctx& c, const Names& nm, const TrainSpatialIn* spatial, const DsSaved& dsv, const float* xin, int B, int H0, int W0, int Cx,
+                      int Ce, int Ci, int mc, const float* g) {
+    const int Cin0 = Cx + Ce + Ci;
     if (float* gw = nm.g("input_blocks.0.0.weight")) conv_wgrad(c, xin, B, Cin0, H0, W0, pixel_rows(Cin0, H0, W0), 3, 1, 1, H0, W0, g, mc, gw, nullptr);
-    if (!sp.ds_mid || !downsampler_grads(nm)) return;
+    if (!spatial || !spatial->ds_mid || !downsampler_grads(nm)) return;
+    const TrainSpatialIn& sp = *spatial;
     // the first conv's data gradient for the k downsampler channels only: rows Cx .. Cx + k of the flipped / transposed filter
     const float* wt = c.conv_dgrad_weight(nm.w("input_blocks.0.0.weight"), mc, Cin0);
     float* gds = conv3x3_direct(c, g, wt + (size_t)Cx * mc * 9, nullptr, B, H0, W0, mc, Ce);
@@ -2075,7 +2078,7 @@ struct UNetStep {
     int GK, NB, MRB, NC;            // grounding kind, boxes per sample, B NB rows per MLP, coordinates per box
     int PWr, PW;                    // the MLPs' input width, and padded to the GEMM's 64-step
     int NBR, MR;                    // MLP branches (text+image: 2), B Ng rows of objs
-    int Cx, Ce, Cin0;               // conv_in reads Cx latent + Ce downsampler channels
+    int Cx, Ce, Ci, Cin0;           // conv_in reads Cx latent + Ce downsampler channels, or + Ci = Cx + 1 inpainting channels
     size_t M0;                      // B H0 W0 pixel rows
     std::string null_pos;
 };
@@ -2096,12 +2099,16 @@ struct UNetLayer {
 };
 
 // trainer.py:217-242: fuser.*, position_net.*, and for a model with a grounding downsampler downsample_net.* and the first conv's
-// weight (input_conv_train, :189-194, 233; its bias stays frozen)
+// weight (input_conv_train, :189-194, 233; its bias stays frozen); an inpainting model's first conv has 5 more input channels and is
+// trained the same way (:191-192)
 void check_trainable_set(const TrainUNetCfg& cfg, int n_params, const char* const* names, float* const* grads, const TrainSpatialIn* spatial) {
+    if (cfg.inpaint_mode && (cfg.grounding_kind == 3 || cfg.extra_channels))
+        throw GlError(GL_ERR_UNSUPPORTED, "unet_train_step: inpaint_mode with a spatial-map tokenizer / downsampler channels is undefined in the reference (openaimodel.py:445-446)");
     const bool ds_model = cfg.grounding_kind == 3 && cfg.extra_channels > 0;
+    const bool conv_in_train = ds_model || cfg.inpaint_mode;
     for (int i = 0; i < n_params; ++i)
-        if (grads[i] && !(strstr(names[i], ".fuser.") || !strncmp(names[i], "position_net.", 13) ||
-                          (ds_model && (!strncmp(names[i], "downsample_net.", 15) || !strcmp(names[i], "input_blocks.0.0.weight")))))
+        if (grads[i] && !(strstr(names[i], ".fuser.") || !strncmp(names[i], "position_net.", 13) || (ds_model && !strncmp(names[i], "downsample_net.", 15)) ||
+                          (conv_in_train && !strcmp(names[i], "input_blocks.0.0.weight"))))
             throw GlError(GL_ERR_ARG, fmt("unet_train_step: a gradient was asked for '%s', which the reference keeps frozen", names[i]));
     if (cfg.grounding_kind == 3 && !spatial) throw GlError(GL_ERR_ARG, "unet_train_step: a spatial-map model needs its TrainSpatialIn");
     if (spatial && (spatial->map_cls || spatial->extra_cls) &&
@@ -2119,7 +2126,7 @@ UNetStep step_dims(const Ctx& c, const Names& nm, const TrainUNetCfg& cfg, const
     if (u.Ng != u.NB * u.NBR || (u.GK == 2 && u.NB % 17)) throw GlError(GL_ERR_ARG, "unet_train_step: Ng must be the box count (text), twice it (text+image), 17 per person (keypoint)");
     u.MR = u.B * u.Ng;
     u.null_pos = u.GK == 2 ? "position_net.null_xy_feature" : "position_net.null_position_feature";
-    u.Cx = cfg.in_channels; u.Ce = u.GK == 3 ? cfg.extra_channels : 0; u.Cin0 = u.Cx + u.Ce;
+    u.Cx = cfg.in_channels; u.Ce = u.GK == 3 ? cfg.extra_channels : 0; u.Ci = cfg.inpaint_mode ? u.Cx + 1 : 0; u.Cin0 = u.Cx + u.Ce + u.Ci;
     u.M0 = (size_t)u.B * u.H0 * u.W0;
     return u;
 }
@@ -2210,7 +2217,9 @@ float* time_embedding(const UNetStep& u) {
 }
 
 // conv_in: frozen for the discrete models (forward only); for a model with a grounding downsampler its input is
-// cat(x, downsample_net(grounding_extra_input)) (openaimodel.py:442-444) and its weight is trainable. xin: the rows it read
+// cat(x, downsample_net(grounding_extra_input)) (openaimodel.py:442-444) and its weight is trainable; for an inpainting model in.x
+// already holds cat(x, inpainting_extra_input) (:445-447), Cin0 = 2 Cx + 1 channels per row, and the weight is trainable too -- the
+// direct conv reads the fp32 weight itself, so no operand copy of it can end up in the frozen-weight cache. xin: the rows it read
 float* conv_in_forward(const UNetStep& u, DsSaved& dsv, const float*& xin) {
     const Ctx& c = u.c;
     xin = u.in.x;
@@ -2468,10 +2477,10 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
         float* g = out_backward(u, out);
         float* g_objs = c.f32((size_t)u.MR * u.KD);
         c.hip(hipMemsetAsync(g_objs, 0, (size_t)u.MR * u.KD * 4, s), "hipMemsetAsync");
-        const bool in_grad = u.Ce > 0 && (nm.g("input_blocks.0.0.weight") || downsampler_grads(nm));
+        const bool in_grad = (u.Ce > 0 && (nm.g("input_blocks.0.0.weight") || downsampler_grads(nm))) || (u.Ci > 0 && nm.g("input_blocks.0.0.weight"));
         int n_st_layers = 0;
         g = layers_backward(u, L, objs, semb, g, in_grad, g_objs, grad_events, n_grad_events, n_st_layers);
-        if (in_grad) conv_in_backward(c, nm, *spatial, dsv, xin, u.B, u.H0, u.W0, u.Cx, u.Ce, u.mc, g);
+        if (in_grad) conv_in_backward(c, nm, spatial, dsv, xin, u.B, u.H0, u.W0, u.Cx, u.Ce, u.Ci, u.mc, g);
         grounding_backward(u, pb, tok, g_objs);
         // position_net's gradients -- the last ones of the step -- are final
         if (grad_events && n_st_layers < n_grad_events) c.hip(hipEventRecord(grad_events[n_st_layers], s), "hipEventRecord");

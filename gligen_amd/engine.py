@@ -708,6 +708,11 @@ class Engine:
         The sem model also trains from class maps: `sem` and `grounding_extra_input` both torch.uint8 [B, 1, H, W] or [B, H, W]
         (gl_unet_train_step_spatial_classes) give the loss, eps and gradients of their one-hot planes bit for bit, except in_conv's and
         downsample_net.layers.0's gradients, which are summed in another order; one u8 and one float input is a ValueError.
+        An inpainting model (cfg["inpaint_mode"], discrete tokenizers; trainer.py:339-344) also takes inpainting_extra_input
+        [B, 5, H, W] = cat(z * mask, mask), concatenated to x in front of the 9-channel first conv (openaimodel.py:445-447), and the
+        gradient of input_blocks.0.0.weight is returned with the others. Instead of x / target (and inpainting_extra_input) any model
+        takes x_rows [B, H, W, channels of the first conv] and target_rows [B, H, W, 4], the pixel rows train_step_inputs writes: the
+        same bits, without the two permute copies.
         Returns (loss, eps [B, 4, H, W], grads) with grads over the reference's
         trainable set (train.trainable_names: trainer.py:189-245) or the `trainable` names given; `grads`: buffers to
         write into instead of fresh ones (every entry is overwritten); `checkpoint`: keep only block inputs / outputs and recompute each block's
@@ -729,6 +734,8 @@ class Engine:
         c.grounding_kind, c.fuser_kind = (3 if sp else 1 if ti else 2 if kp else 0), 0
         c.max_persons = int(batch["points"].shape[1]) // 17 if kp else 0
         c.gr_in_dim = c.gr_out_dim = 768
+        inpaint = bool(cfg.get("inpaint_mode"))
+        c.inpaint_mode = int(inpaint)
         if sp:
             c.extra_channels = sp["ds"]["out"] if sp["ds"] else 0
             c.tok_resize, c.tok_in_dim = sp["tok_resize"], sp["tok_in_dim"]
@@ -742,9 +749,23 @@ class Engine:
         else:       # caller-owned gradient buffers (gligen_amd.dist.GradBuckets.views: the backward writes straight into the flat buckets)
             for k, gt in grads.items():
                 assert gt.is_cuda and gt.dtype == torch.float32 and gt.is_contiguous() and tuple(gt.shape) == tuple(state_dict[k].shape), k
-        x, target = batch["x"], batch["target"]
-        B, Cx, H, W = x.shape
-        rows = lambda t: _f32(t, dev).permute(0, 2, 3, 1).reshape(B, H * W, t.shape[1]).contiguous()
+        if "x_rows" in batch:       # pixel rows as train_step_inputs writes them: used in place
+            x_rows, target_rows = _f32(batch["x_rows"], dev), _f32(batch["target_rows"], dev)
+            cin = c.in_channels * 2 + 1 if inpaint else c.in_channels
+            if x_rows.dim() != 4 or target_rows.dim() != 4 or x_rows.shape[:3] != target_rows.shape[:3] or x_rows.shape[3] != cin \
+                    or target_rows.shape[3] != c.out_channels:
+                raise ValueError(f"unet_train_step: x_rows is [B, H, W, {cin}] and target_rows [B, H, W, {c.out_channels}] for this model; got "
+                                 f"{tuple(x_rows.shape)} and {tuple(target_rows.shape)}")
+            B, H, W = (int(v) for v in x_rows.shape[:3])
+        else:
+            x, target = batch["x"], batch["target"]
+            B, Cx, H, W = x.shape
+            rows = lambda t: _f32(t, dev).permute(0, 2, 3, 1).reshape(B, H * W, t.shape[1]).contiguous()
+            if inpaint:             # the first conv reads cat(x, inpainting_extra_input) (openaimodel.py:445-447)
+                if batch.get("inpainting_extra_input") is None:
+                    raise ValueError("unet_train_step: an inpainting model's batch carries inpainting_extra_input [B, 5, H, W] (or x_rows)")
+                x = torch.cat([_f32(x, dev), _f32(batch["inpainting_extra_input"], dev)], dim=1)
+            x_rows, target_rows = rows(x), rows(target)
         n = len(names)
         narr = (C.c_char_p * n)(*[k.encode() for k in names])
         parr = (C.c_void_p * n)(*[p.data_ptr() for p in params])
@@ -759,7 +780,7 @@ class Engine:
             ce = self._class_map(batch["grounding_extra_input"], "unet_train_step")
             if cm.shape[0] != B or ce.shape[0] != B:
                 raise ValueError(f"unet_train_step: the class maps hold {cm.shape[0]} and {ce.shape[0]} samples, x holds {B}")
-            keep = dict(x=rows(x), t=_f32(batch["timesteps"], dev), ctx=_f32(batch["context"], dev), target=rows(target), mask=_f32(batch["mask"].reshape(-1), dev))
+            keep = dict(x=x_rows, t=_f32(batch["timesteps"], dev), ctx=_f32(batch["context"], dev), target=target_rows, mask=_f32(batch["mask"].reshape(-1), dev))
             if keep["mask"].shape[0] != B:
                 raise ValueError("unet_train_step: one mask value per sample")
             ds = sp["ds"]
@@ -771,7 +792,7 @@ class Engine:
             check(self.lib.gl_unet_train_step_spatial_classes(self._ctx, C.byref(c), C.byref(u), C.byref(s), n, narr, parr, garr, _ptr(eps), _ptr(loss), _stream(dev)))
             return loss, eps.reshape(B, H, W, c.out_channels).permute(0, 3, 1, 2).contiguous(), grads
         if sp:      # batch: the map under the reference's key, mask, grounding_extra_input (gl_unet_train_step_spatial)
-            keep = dict(x=rows(x), t=_f32(batch["timesteps"], dev), ctx=_f32(batch["context"], dev), target=rows(target),
+            keep = dict(x=x_rows, t=_f32(batch["timesteps"], dev), ctx=_f32(batch["context"], dev), target=target_rows,
                         map=_f32(batch[sp["map_key"]], dev), mask=_f32(batch["mask"].reshape(-1), dev))
             if keep["mask"].shape[0] != B:
                 raise ValueError("unet_train_step: one mask value per sample")
@@ -786,8 +807,8 @@ class Engine:
                                     ds["resize"] if ds else 0, ds["mode"] if ds else 0, ds["n_in"] if ds else 0, ds["mid"] if ds else 0)
             check(self.lib.gl_unet_train_step_spatial(self._ctx, C.byref(c), C.byref(u), C.byref(s), n, narr, parr, garr, _ptr(eps), _ptr(loss), _stream(dev)))
             return loss, eps.reshape(B, H, W, c.out_channels).permute(0, 3, 1, 2).contiguous(), grads
-        keep = dict(x=rows(x), t=_f32(batch["timesteps"], dev), ctx=_f32(batch["context"], dev), boxes=_f32(batch["points" if kp else "boxes"], dev),
-                    masks=_f32(batch["masks"], dev), pe=None if kp else _f32(batch["text_embeddings" if ti else "positive_embeddings"], dev), target=rows(target))
+        keep = dict(x=x_rows, t=_f32(batch["timesteps"], dev), ctx=_f32(batch["context"], dev), boxes=_f32(batch["points" if kp else "boxes"], dev),
+                    masks=_f32(batch["masks"], dev), pe=None if kp else _f32(batch["text_embeddings" if ti else "positive_embeddings"], dev), target=target_rows)
         if ti:
             keep.update(tm=_f32(batch["text_masks"], dev), im=_f32(batch["image_masks"], dev), ie=_f32(batch["image_embeddings"], dev))
         u = _lib.TrainUNetIn(int(B), int(H), int(W), int(keep["ctx"].shape[1]), int(keep["boxes"].shape[1]), keep["x"].data_ptr(), keep["t"].data_ptr(),
@@ -796,6 +817,55 @@ class Engine:
                              keep["ie"].data_ptr() if ti else None, int(bool(checkpoint)), int(bool(use_weight_cache)))
         check(self.lib.gl_unet_train_step(self._ctx, C.byref(c), C.byref(u), n, narr, parr, garr, _ptr(eps), _ptr(loss), _stream(dev)))
         return loss, eps.reshape(B, H, W, c.out_channels).permute(0, 3, 1, 2).contiguous(), grads
+
+    def train_step_inputs(self, z: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor, schedule, *, boxes: Optional[torch.Tensor] = None,
+                          mask: Optional[torch.Tensor] = None, inpaint: bool = False) -> Dict[str, torch.Tensor]:
+        """What the reference's trainer computes between the VAE and the model (trainer.py:329-364), in one launch
+        (gl_train_step_inputs), as the pixel rows unet_train_step takes: x_noisy = a[t] z + s[t] noise (q_sample, ldm.py:19-22, the bits
+        torch gives on the CPU) and, with inpaint, z * mask and the mask behind it (trainer.py:342-344). z, noise [B, C, H, W];
+        timesteps [B] integers; schedule: the diffusion's buffers, a mapping with sqrt_alphas_cumprod and sqrt_one_minus_alphas_cumprod
+        (or that pair), best kept on this device. inpaint takes exactly one of boxes [B, Nb, 4] -- (x0, y0, x1, y1) fractions in
+        [0, 1], the mask of draw_masks_from_boxes(boxes, H) without its random branches (H == W); anything else is a ValueError -- and
+        mask [B, 1, H, W] / [B, H, W] / [B, H*W], e.g. the reference's random stroke masks, which are drawn on the host.
+        Returns dict(x_rows [B, H, W, 2C + 1 or C], target_rows [B, H, W, C] = the noise, timesteps [B] float)."""
+        dev = self.device
+        if z.dim() != 4 or tuple(noise.shape) != tuple(z.shape) or timesteps.numel() != z.shape[0]:
+            raise ValueError("train_step_inputs: z and noise are [B, C, H, W] of one shape, timesteps [B]")
+        B, Cz, H, W = (int(v) for v in z.shape)
+        if not inpaint and (boxes is not None or mask is not None):
+            raise ValueError("train_step_inputs: boxes / mask are the inpainting model's inputs (inpaint=True)")
+        if inpaint and (boxes is None) == (mask is None):
+            raise ValueError("train_step_inputs: an inpainting step takes boxes or mask, exactly one of them")
+        if boxes is not None:
+            if boxes.dim() != 3 or boxes.shape[0] != B or boxes.shape[2] != 4 or boxes.shape[1] < 1:
+                raise ValueError("train_step_inputs: boxes are [B, Nb, 4]")
+            if H != W:
+                raise ValueError(f"train_step_inputs: the mask drawn from boxes is square (inpaint_mask_func.py:22); the latent is {H} x {W}")
+            if not bool(((boxes >= 0) & (boxes <= 1)).all()):
+                raise ValueError("train_step_inputs: box coordinates are fractions in [0, 1]")
+            boxes = _f32(boxes, dev)
+        if mask is not None:
+            if mask.numel() != B * H * W:
+                raise ValueError(f"train_step_inputs: the mask holds {mask.numel()} values, B H W = {B * H * W}")
+            mask = _f32(mask, dev).reshape(B, H * W)
+        if isinstance(schedule, Mapping):
+            sa, s1 = schedule["sqrt_alphas_cumprod"], schedule["sqrt_one_minus_alphas_cumprod"]
+        else:
+            sa, s1 = schedule
+        sa, s1 = _f32(torch.as_tensor(sa), dev).reshape(-1), _f32(torch.as_tensor(s1), dev).reshape(-1)
+        if sa.numel() != s1.numel() or sa.numel() < 1:
+            raise ValueError("train_step_inputs: the two schedule tables have one length")
+        zd, nd = _f32(z, dev), _f32(noise, dev)
+        t = timesteps.reshape(-1).to(device=dev, dtype=torch.int64).contiguous()
+        x_rows = torch.empty((B, H, W, 2 * Cz + 1 if inpaint else Cz), device=dev, dtype=torch.float32)
+        target_rows = torch.empty((B, H, W, Cz), device=dev, dtype=torch.float32)
+        t_float = torch.empty(B, device=dev, dtype=torch.float32)
+        a = _lib.TrainStepInputsArgs(C.sizeof(_lib.TrainStepInputsArgs), B, Cz, H, W, int(sa.numel()), int(boxes.shape[1]) if boxes is not None else 0,
+                                     int(bool(inpaint)), zd.data_ptr(), nd.data_ptr(), t.data_ptr(), sa.data_ptr(), s1.data_ptr(),
+                                     boxes.data_ptr() if boxes is not None else None, mask.data_ptr() if mask is not None else None,
+                                     x_rows.data_ptr(), target_rows.data_ptr(), t_float.data_ptr())
+        check(self.lib.gl_train_step_inputs(self._ctx, C.byref(a), _stream(dev)))
+        return dict(x_rows=x_rows, target_rows=target_rows, timesteps=t_float)
 
     def train_wait_grads(self, index: int, stream=None) -> None:
         """Make `stream` (a torch.cuda.Stream; None: the current one) wait until the gradients of the index-th SpatialTransformer of the

@@ -10,7 +10,9 @@ fp32 buffers (gligen_amd.dist.GradBuckets), so the backward writes the gradients
 reduce-scatter + all-gather pair per bucket goes over RCCL, and AdamW is one launch per bucket over the flat range.
 The step is built for the three discrete grounding tokenizers and the five spatial-map ones with gatedSA fusers; the batch dict carries
 boxes + masks + positive_embeddings (text), + text_embeddings / image_embeddings / text_masks / image_masks (text+image), points + masks
-(keypoint), or the map under the reference's key (canny_edge, hed_edge, depth, normal, sem) + mask + grounding_extra_input."""
+(keypoint), or the map under the reference's key (canny_edge, hed_edge, depth, normal, sem) + mask + grounding_extra_input.
+An inpainting model (cfg["inpaint_mode"], discrete tokenizers; trainer.py:189-194, 339-344) trains its 9-channel first conv's weight
+as well; its batch carries inpainting_extra_input [B, 5, H, W] next to x, or x_rows / target_rows from Engine.train_step_inputs."""
 from __future__ import annotations
 
 import math
@@ -65,10 +67,25 @@ def has_grounding_downsampler(state_dict: Mapping[str, torch.Tensor], cfg: Optio
 
 def trainable_names(state_dict: Mapping[str, torch.Tensor], cfg: Optional[Mapping] = None):
     """trainer.py:217-245: 'transformer_blocks' + 'fuser' in the name, 'position_net', 'downsample_net', and the first conv's weight
-    when additional channels come from a grounding downsampler (trainer.py:189-194, 233: input_conv_train; the bias stays frozen)."""
-    conv_train = has_grounding_downsampler(state_dict, cfg)
+    when additional channels come from a grounding downsampler or the config says inpaint_mode (trainer.py:189-194, 233:
+    input_conv_train; the bias stays frozen). Without a config an inpainting model cannot be told from a state_dict whose first conv
+    merely has nine input channels, and its first conv stays out of the set."""
+    conv_train = has_grounding_downsampler(state_dict, cfg) or bool(cfg is not None and cfg.get("inpaint_mode"))
     return [k for k in state_dict if ".fuser." in k or k.startswith("position_net.") or k.startswith("downsample_net.")
             or (conv_train and k == "input_blocks.0.0.weight")]
+
+
+def add_input_channels(state_dict: Mapping[str, torch.Tensor], n: int) -> Dict[str, torch.Tensor]:
+    """A copy of `state_dict` whose first conv reads `n` more input channels, the new filter taps zero: what the reference does to an
+    SD / GLIGEN checkpoint before it loads it into a model with a wider first conv (trainer.py:189-193; n = 5 for inpaint_mode: the
+    masked latent's four channels and the mask). The existing channels keep their bits; the tensors of the input are not written."""
+    if n < 0:
+        raise ValueError("add_input_channels: n must be >= 0")
+    out = dict(state_dict)
+    w = state_dict["input_blocks.0.0.weight"]
+    pad = torch.zeros((w.shape[0], int(n)) + tuple(w.shape[2:]), dtype=w.dtype, device=w.device)
+    out["input_blocks.0.0.weight"] = torch.cat([w, pad], dim=1)
+    return out
 
 
 def _block_order(prefix: str):
@@ -111,7 +128,12 @@ class TrainStep:
 
     Arena: the engine's context must hold one block's recompute working set plus the saved block inputs -- 24 GB covers the shipped
     topology at batch 4 x 64 x 64 with checkpoint=True (bench.py / tools/train_bench.py create Engine(arena_gb=24)); the library
-    raises 'arena exhausted' (GL_ERR_RUNTIME) rather than spilling when it does not."""
+    raises 'arena exhausted' (GL_ERR_RUNTIME) rather than spilling when it does not.
+
+    An inpainting model (cfg["inpaint_mode"]): step(batch) takes the reference's keys -- x (the noised latent) and
+    inpainting_extra_input = cat(z * mask, mask) [B, 5, H, W] -- or x_rows [B, H, W, 9] / target_rows [B, H, W, 4] as
+    Engine.train_step_inputs writes them (no permute copies; any model takes its rows that way); the first conv's weight is part of
+    the trainable set and of the last bucket. The guidance drop leaves all three alone."""
 
     def __init__(self, engine, cfg: Mapping, state_dict: Mapping[str, torch.Tensor], lr: Union[float, Callable[[int], float]] = 5e-5,
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, bucket_mb: float = 128.0, world: Optional[int] = None,

@@ -374,14 +374,21 @@ int gl_op_resample_train(gl_ctx* ctx, int mode, int B, int H, int W, int C, cons
 
 /* ---- one whole training iteration (reference trainer.py:353-392: model(input), mse_loss(model_output, noise), loss.backward()) for a
  * UNetModel with the text, the text+image or the keypoint grounding tokenizer and gatedSA fusers (openaimodel.py:237-464; gl_unet_config with
- * grounding_kind 0 / 1 / 2, fuser_kind 0, no inpainting / extra channels). The model's parameters come as its state_dict: n_params names (the reference's
+ * grounding_kind 0 / 1 / 2, fuser_kind 0, no extra channels; inpaint_mode allowed, below). The model's parameters come as its state_dict: n_params names (the reference's
  * keys, e.g. "input_blocks.1.1.transformer_blocks.0.fuser.linear.weight") with fp32 device pointers; grads[i] is a buffer shaped
  * like parameter i for every trainable parameter wanted -- the reference's trainable set is every "*.fuser.*" key and "position_net.*"
  * (trainer.py:217-245); any other non-NULL entry is rejected -- and NULL elsewhere. Tensors fp32 on the device, x / target / eps_out
- * as pixel rows [B][H*W][channels] (eps_out optional). loss[1] = mse_loss(eps, target). */
+ * as pixel rows [B][H*W][channels] (eps_out optional). loss[1] = mse_loss(eps, target).
+ * An inpainting model (cfg->inpaint_mode = 1; trainer.py:189-194, 339-344): in->x holds 2 * in_channels + 1 channels per pixel row in the
+ * order of the reference's concatenation (openaimodel.py:447, trainer.py:343-344) -- the noised latent, z * mask, the mask --, which the
+ * first conv reads as they stand, and the trainable set also admits "input_blocks.0.0.weight" (input_conv_train, trainer.py:233; its
+ * bias stays frozen; on a model without inpaint_mode that entry is rejected like any frozen tensor). Its gradient is final at the
+ * gl_train_wait_grads milestone [number of SpatialTransformers], with position_net's. inpaint_mode together with extra_channels or a
+ * spatial-map tokenizer is refused: the reference leaves it undefined (openaimodel.py:445-446). gl_train_step_inputs in
+ * gligen_amd_train_inputs.h writes such rows, and target's, in one launch. */
 typedef struct gl_train_unet_in {
     int B, H, W, ctx_T, Ng;
-    const float* x;                     /* [B][H*W][in_channels]: the noised latent */
+    const float* x;                     /* [B][H*W][in_channels]: the noised latent; inpaint_mode: [B][H*W][2 * in_channels + 1] (above) */
     const float* timesteps;             /* [B], as float */
     const float* context;               /* [B][ctx_T][context_dim] */
     const float* boxes;                 /* [B][Ng][4]; keypoint tokenizer (grounding_kind 2, keypoint_grounding_net.py:34): points [B][Ng][2], Ng = 17 per person */

@@ -3,7 +3,11 @@ small UNet at a 16 x 16 latent, the shipped topology at 16 x 16 and at the real 
 --spatial MODALITY: the shipped topology with that spatial-map tokenizer (ConvNeXt-tiny, resize 256: 64 tokens) and grounding
 downsampler instead (gl_unet_train_step_spatial), B = 4, 64 x 64 latent, checkpoint=True. --class-maps (with --spatial sem): the same
 iteration fed from the u8 class maps of those planes (gl_unet_train_step_spatial_classes).
-   PYTHONPATH=. python tools/train_bench.py [--full64] [--spatial {canny,depth,normal,hed,sem} [--class-maps]]"""
+--inpaint: the shipped topology with inpaint_mode (9-channel first conv, its weight trained), B = 4, 64 x 64 latent with --full64
+(else B = 1, 16 x 16), checkpoint=True, the step inputs made by Engine.train_step_inputs inside the timed region; next to the text
+model's line, and the time of one train_step_inputs launch next to the torch sequence it replaces (q_sample, mask, concat, two
+permutes), medians of 20.
+   PYTHONPATH=. python tools/train_bench.py [--full64] [--spatial {canny,depth,normal,hed,sem} [--class-maps] | --inpaint]"""
 import json
 import sys
 import time
@@ -79,7 +83,77 @@ def run_spatial(modality, B, hw, reps, checkpoint=True, class_maps=False):
                           trainable_values=sum(int(g.numel()) for g in grads.values()))), flush=True)
 
 
+def run_inpaint(B, hw, reps, checkpoint=True):
+    """The shipped topology (syn.UNET_CFG) with inpaint_mode: z, noise, timesteps and boxes on the device, train_step_inputs and
+    unet_train_step per iteration."""
+    from gligen_amd.train import trainable_names
+    from ldm.models.diffusion.ldm import LatentDiffusion
+    from ldm.modules.diffusionmodules.openaimodel import UNetModel
+    cfg = dict(syn.UNET_CFG, grounding_tokenizer=syn.GROUNDING_TOKENIZERS["text"], inpaint_mode=True)
+    m = UNetModel(**cfg)
+    shapes = {k: tuple(v.shape) for k, v in m.state_dict().items()}
+    del m
+    eng = Engine(0, arena_gb=160.0)
+    dev = eng.device
+    sd = {k: v.float().to(dev).contiguous() for k, v in syn.seeded_state_dict(shapes, 1234).items()}
+    diff = LatentDiffusion(linear_start=0.00085, linear_end=0.012, timesteps=1000)
+    sched = {k: getattr(diff, k).float().to(dev).contiguous() for k in ("sqrt_alphas_cumprod", "sqrt_one_minus_alphas_cumprod")}
+    b = syn.make_batch("text", B, n_valid=3, seed=5)
+    z, noise = syn.make_latent(B, 4, hw, hw, seed=6).to(dev), syn.make_latent(B, 4, hw, hw, seed=7).to(dev)
+    t = torch.tensor([981, 441, 300, 77][:B], device=dev)
+    boxes = b["boxes"].to(dev)
+    rest = dict(context=syn.make_context(B, seed=6).to(dev), boxes=boxes, masks=b["masks"].to(dev), positive_embeddings=b["text_embeddings"].to(dev))
+    grads = {k: torch.zeros_like(sd[k]) for k in trainable_names(sd, cfg)}
+    step = lambda: eng.unet_train_step(cfg, sd, dict(rest, **eng.train_step_inputs(z, noise, t, sched, boxes=boxes, inpaint=True)), grads=grads, checkpoint=checkpoint)
+    step()                                               # warm-up (GEMM tile selection)
+    torch.cuda.synchronize()
+    t0 = time.time()
+    for _ in range(reps):
+        loss, _, _ = step()
+    torch.cuda.synchronize()
+    dt = (time.time() - t0) / reps
+    print(json.dumps(dict(config="shipped topology, inpaint_mode (9-channel first conv)", B=B, latent=hw, checkpoint=bool(checkpoint),
+                          s_per_iteration=round(dt, 4), loss=float(loss), arena_high_water_gb=round(eng.arena_high_water() / 2 ** 30, 2),
+                          trainable_values=sum(int(g.numel()) for g in grads.values()))), flush=True)
+
+    # the input stage alone: one launch against the torch sequence of trainer.py:342-344, 356 plus the two permute copies of the NCHW form
+    def torch_inputs():
+        a = sched["sqrt_alphas_cumprod"][t].reshape(-1, 1, 1, 1)
+        s1 = sched["sqrt_one_minus_alphas_cumprod"][t].reshape(-1, 1, 1, 1)
+        x_noisy = a * z + s1 * noise
+        q = (boxes * hw).to(torch.int64)
+        ar = torch.arange(hw, device=dev)
+        inx = (ar[None, None, :] >= q[:, :, 0, None]) & (ar[None, None, :] < q[:, :, 2, None])
+        iny = (ar[None, None, :] >= q[:, :, 1, None]) & (ar[None, None, :] < q[:, :, 3, None])
+        mask = 1.0 - (iny[:, :, :, None] & inx[:, :, None, :]).any(dim=1, keepdim=True).float()
+        x9 = torch.cat([x_noisy, z * mask, mask], dim=1)
+        return x9.permute(0, 2, 3, 1).contiguous(), noise.permute(0, 2, 3, 1).contiguous()
+
+    ref_rows, ref_target = torch_inputs()
+    out = eng.train_step_inputs(z, noise, t, sched, boxes=boxes, inpaint=True)
+    same = bool(torch.equal(out["target_rows"], ref_target) and torch.equal(out["x_rows"][..., 4:], ref_rows[..., 4:]))     # (torch on the GPU may contract a z + s n)
+
+    def median_ms(fn, n=20):
+        ts = []
+        for _ in range(n):
+            torch.cuda.synchronize()
+            t1 = time.perf_counter()
+            fn()
+            torch.cuda.synchronize()
+            ts.append((time.perf_counter() - t1) * 1e3)
+        return sorted(ts)[n // 2]
+
+    print(json.dumps(dict(config="step inputs", B=B, latent=hw, train_step_inputs_ms=round(median_ms(lambda: eng.train_step_inputs(z, noise, t, sched, boxes=boxes, inpaint=True)), 4),
+                          torch_sequence_ms=round(median_ms(torch_inputs), 4), mask_and_target_equal=same, timing="host wall time around one synchronised call, median of 20")), flush=True)
+    eng.close()
+
+
 if __name__ == "__main__":
+    if "--inpaint" in sys.argv:
+        full = "--full64" in sys.argv
+        run("shipped topology", syn.UNET_CFG, 4 if full else 1, 64 if full else 16, 1 if full else 2, Engine(0, arena_gb=1.0), checkpoint=True)     # the text model's line, same box
+        run_inpaint(4 if full else 1, 64 if full else 16, 1 if full else 2)
+        sys.exit(0)
     if "--spatial" in sys.argv:
         modality = sys.argv[sys.argv.index("--spatial") + 1]
         if "--full64" in sys.argv:
