@@ -1,5 +1,5 @@
 """ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
-include/gligen_amd_train_maps.h and include/gligen_amd_train_inputs.h).
+include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h and include/gligen_amd_train_fusers.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -199,6 +199,25 @@ TRAIN_INPUT_SYMBOLS = {
     "gl_train_step_inputs": (_I, [_P, C.POINTER(TrainStepInputsArgs), _P]),
 }
 
+# every symbol include/gligen_amd_train_fusers.h declares (the block slice by fuser kind, the fp32 grid resize and its adjoint)
+TRAIN_FUSER_SYMBOLS = {
+    "gl_op_block_train_fuser": (_I, [_P, _I, _P, C.POINTER(_P), _P, _P, _P, _P, _P, _P, _P, _P, C.POINTER(_P), _P]),
+    "gl_op_grid_resize": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "gl_op_grid_resize_backward": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+}
+
+# gl_unet_config.fuser_kind / the fuser_kind of gl_op_block_train_fuser, by the reference's fuser_type
+FUSER_KINDS = {"gatedSA": 0, "gatedSA2": 1, "gatedCA": 2}
+
+
+def fuser_kind(fuser_type) -> int:
+    """UNetModel's fuser_type (None: the default gatedSA) as the library's fuser_kind."""
+    try:
+        return FUSER_KINDS[fuser_type or "gatedSA"]
+    except KeyError:
+        raise ValueError(f"fuser_type {fuser_type!r}: one of {sorted(FUSER_KINDS)}") from None
+
+
 _lib = None
 
 
@@ -216,7 +235,7 @@ def load() -> C.CDLL:
     # torch.cuda.is_available() is True) -- seen with build() called before the first `import torch` of the process.
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -3,8 +3,10 @@
 #include "engine_impl.h"
 #include "image.h"
 #include "train.h"
+#include "train_fusers.h"
 #include "../../include/gligen_amd_train_maps.h"
 #include "../../include/gligen_amd_train_inputs.h"
+#include "../../include/gligen_amd_train_fusers.h"
 
 #include <cstdlib>
 
@@ -725,6 +727,44 @@ int gl_op_block_train(gl_ctx* ctx, const gl_train_block_dims* dims, const float*
     GL_API_END
 }
 
+// ---- include/gligen_amd_train_fusers.h: the block slice by fuser kind, and the grid resize the gatedSA2 fuser is built on
+int gl_op_block_train_fuser(gl_ctx* ctx, int fuser_kind, const gl_train_block_dims* dims, const float* const* params, const float* x, const float* objs,
+                            const float* context, const float* target, float* y, float* loss, float* dx, float* dobjs, float* const* grads, gl_stream s) {
+    NEED(ctx);
+    if (!dims || !params || !x || !objs || !context || !target || !y || !loss || !dx || !dobjs || !grads)
+        return gl::set_error(GL_ERR_ARG, "gl_op_block_train_fuser: null pointer");
+    if (fuser_kind < 0 || fuser_kind > 2) return gl::set_error(GL_ERR_ARG, "gl_op_block_train_fuser: fuser_kind %d (0 gatedSA, 1 gatedSA2, 2 gatedCA)", fuser_kind);
+    for (int i = 0; i < GL_TRAIN_BLOCK_PARAMS; ++i) {
+        if (fuser_kind == 2 && (i == gl::TP_F_LIN_W || i == gl::TP_F_LIN_B) && (params[i] || grads[i]))
+            return gl::set_error(GL_ERR_ARG, "gl_op_block_train_fuser: a gatedCA fuser has no '%s' (the slot is NULL in params and grads)", k_train_block_names[i]);
+        if (grads[i] && !(i >= gl::TP_F_LIN_W && i <= gl::TP_F_ALPHA_DENSE))
+            return gl::set_error(GL_ERR_ARG, "gl_op_block_train_fuser: a gradient was asked for '%s', which the reference keeps frozen", k_train_block_names[i]);
+    }
+    GL_API_BEGIN
+    Engine& eng = *ctx->eng;
+    eng.arena().reset();
+    gl::TrainBlockDims d{dims->B, dims->N, dims->Ng, dims->C, dims->heads, dims->ctx_T, dims->ctx_dim, dims->fuser_scale, fuser_kind};
+    int rc = gl::block_train_step(eng.arena(), eng.splitk_ws(), eng.splitk_ws_bytes(), d, params, x, objs, context, target, y, loss, dx, dobjs, grads, S(s));
+    if (rc != GL_OK) throw GlError(rc, gl::last_error());
+    GL_API_END
+}
+
+int gl_op_grid_resize(gl_ctx* ctx, const float* src, int B, int sg, int sv, int C, float* dst, gl_stream s) {
+    NEED(ctx);
+    GL_API_BEGIN
+    GL_TRY(gl::grid_resize_fwd_launch(src, B, sg, sv, C, dst, S(s)));
+    ++ctx->eng->n_launches;
+    GL_API_END
+}
+
+int gl_op_grid_resize_backward(gl_ctx* ctx, const float* g, int B, int sg, int sv, int C, float* dsrc, gl_stream s) {
+    NEED(ctx);
+    GL_API_BEGIN
+    GL_TRY(gl::grid_resize_bwd_launch(g, B, sg, sv, C, dsrc, S(s)));
+    ++ctx->eng->n_launches;
+    GL_API_END
+}
+
 static_assert(GL_TRAIN_ST_PARAMS == gl::ST_COUNT, "parameter table out of step with train.h");
 const char* const* gl_train_st_param_names(void) {
     static std::string store[GL_TRAIN_ST_PARAMS];
@@ -796,9 +836,10 @@ int gl_unet_train_step(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_un
                        const float* const* params, float* const* grads, float* eps_out, float* loss, gl_stream s) {
     NEED(ctx);
     if (!cfg || !in || !names || !params || !grads || !loss || n_params <= 0) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step: null pointer");
-    if (cfg->grounding_kind < 0 || cfg->grounding_kind > 2 || cfg->fuser_kind != 0 || cfg->extra_channels)
-        return gl::set_error(GL_ERR_UNSUPPORTED, "gl_unet_train_step: the training step is built for the text, text+image and keypoint tokenizers with gatedSA fusers, "
-                                                 "with or without inpaint_mode (no downsampler channels: inpaint_mode with extra_channels is undefined in the reference)");
+    if (cfg->grounding_kind < 0 || cfg->grounding_kind > 2 || cfg->fuser_kind < 0 || cfg->fuser_kind > 2 || cfg->extra_channels)
+        return gl::set_error(GL_ERR_UNSUPPORTED, "gl_unet_train_step: the training step is built for the text, text+image and keypoint tokenizers with gatedSA, gatedSA2 "
+                                                 "or gatedCA fusers (fuser_kind 0 / 1 / 2), with or without inpaint_mode (no downsampler channels: inpaint_mode with "
+                                                 "extra_channels is undefined in the reference)");
     if (cfg->grounding_kind == 1 && (!in->text_masks || !in->image_masks || !in->image_embeddings))
         return gl::set_error(GL_ERR_ARG, "gl_unet_train_step: the text+image tokenizer needs text_masks, image_masks and image_embeddings");
     if (!in->x || !in->timesteps || !in->context || !in->boxes || !in->masks || (!in->positive_embeddings && cfg->grounding_kind != 2) || !in->target)
@@ -810,7 +851,7 @@ int gl_unet_train_step(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_un
     eng.arena().reset();
     gl::TrainUNetCfg c{};
     c.in_channels = cfg->in_channels; c.out_channels = cfg->out_channels; c.model_channels = cfg->model_channels; c.num_res_blocks = cfg->num_res_blocks;
-    c.num_heads = cfg->num_heads; c.context_dim = cfg->context_dim; c.gr_dim = cfg->gr_in_dim; c.grounding_kind = cfg->grounding_kind; c.n_mult = cfg->n_mult; c.n_attn = cfg->n_attn;
+    c.num_heads = cfg->num_heads; c.context_dim = cfg->context_dim; c.gr_dim = cfg->gr_in_dim; c.grounding_kind = cfg->grounding_kind; c.fuser_kind = cfg->fuser_kind; c.n_mult = cfg->n_mult; c.n_attn = cfg->n_attn;
     for (int i = 0; i < 8; ++i) { c.channel_mult[i] = cfg->channel_mult[i]; c.attention_resolutions[i] = cfg->attention_resolutions[i]; }
     c.inpaint_mode = cfg->inpaint_mode ? 1 : 0;       // in->x then holds 2 * in_channels + 1 channels per pixel row
     gl::TrainUNetIn u{in->B, in->H, in->W, in->ctx_T, cfg->grounding_kind == 1 ? 2 * in->Ng : in->Ng, in->Ng, in->x, in->timesteps, in->context, in->boxes,
@@ -830,8 +871,8 @@ static int train_step_spatial(const char* what, gl_ctx* ctx, const gl_unet_confi
     if (cfg->inpaint_mode)
         return gl::set_error(GL_ERR_UNSUPPORTED, "%s: inpaint_mode with a spatial-map tokenizer is undefined in the reference (openaimodel.py:445-446); "
                                                  "gl_unet_train_step trains the inpainting models", what);
-    if (cfg->grounding_kind != 3 || cfg->fuser_kind != 0)
-        return gl::set_error(GL_ERR_UNSUPPORTED, "%s: built for a spatial-map tokenizer (grounding_kind 3) with gatedSA fusers", what);
+    if (cfg->grounding_kind != 3 || cfg->fuser_kind < 0 || cfg->fuser_kind > 2)
+        return gl::set_error(GL_ERR_UNSUPPORTED, "%s: built for a spatial-map tokenizer (grounding_kind 3) with gatedSA, gatedSA2 or gatedCA fusers (fuser_kind 0 / 1 / 2)", what);
     if (cfg->tok_resize < 32 || cfg->tok_resize % 32 || cfg->extra_channels < 0)
         return gl::set_error(GL_ERR_ARG, "%s: tok_resize must be a positive multiple of 32", what);
     if (in->boxes || in->masks || in->positive_embeddings || in->text_masks || in->image_masks || in->image_embeddings)
@@ -848,7 +889,7 @@ static int train_step_spatial(const char* what, gl_ctx* ctx, const gl_unet_confi
     eng.arena().reset();
     gl::TrainUNetCfg c{};
     c.in_channels = cfg->in_channels; c.out_channels = cfg->out_channels; c.model_channels = cfg->model_channels; c.num_res_blocks = cfg->num_res_blocks;
-    c.num_heads = cfg->num_heads; c.context_dim = cfg->context_dim; c.gr_dim = 768; c.grounding_kind = 3; c.n_mult = cfg->n_mult; c.n_attn = cfg->n_attn;
+    c.num_heads = cfg->num_heads; c.context_dim = cfg->context_dim; c.gr_dim = 768; c.grounding_kind = 3; c.fuser_kind = cfg->fuser_kind; c.n_mult = cfg->n_mult; c.n_attn = cfg->n_attn;
     for (int i = 0; i < 8; ++i) { c.channel_mult[i] = cfg->channel_mult[i]; c.attention_resolutions[i] = cfg->attention_resolutions[i]; }
     c.extra_channels = cfg->extra_channels; c.tok_resize = cfg->tok_resize; c.tok_in_dim = cfg->tok_in_dim;
     gl::TrainUNetIn u{in->B, in->H, in->W, in->ctx_T, Ng, Ng, in->x, in->timesteps, in->context, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,

@@ -86,6 +86,28 @@ struct PlmsParams {
 };
 int plms_update_launch(const PlmsParams& p, hipStream_t stream);
 
+// The four cubic-convolution weights (A = -0.75, torch's bicubic) of the taps floor(src) - 1 .. floor(src) + 2, t = src - floor(src):
+// fuser_resize_kernel / resize_f32_kernel (misc.hip); the training path's fp32 grid resize (train_fusers.hip) takes the factored form below
+__device__ __forceinline__ void cubic_taps(float t, float w[4]) {
+    const float A = -0.75f;
+    const float a = t + 1.f, b = 1.f - t, c = 2.f - t;
+    w[0] = ((A * a - 5.f * A) * a + 8.f * A) * a - 4.f * A;
+    w[1] = ((A + 2.f) * t - (A + 3.f)) * t * t + 1.f;
+    w[2] = ((A + 2.f) * b - (A + 3.f)) * b * b + 1.f;
+    w[3] = ((A * c - 5.f * A) * c + 8.f * A) * c - 4.f * A;
+}
+// The same four weights in factored form, from t and u = 1 - t (the caller has both as exact integer ratios: train_fusers.hip):
+// A t u^2, u (1 + t - 1.25 t^2), t (1 + u - 1.25 u^2), A u t^2. The Horner form above cancels where a weight is small (w[0] at t = 0.1 is
+// 3.06 - 3 with roundings at 3: 5e-6 relative), which the bf16 kernels never see; here every weight keeps a few ulp RELATIVE error,
+// what the fp32 training path's adjoint is held to (a source token may be reached by small weights only). Equal to cubic_taps in
+// exact arithmetic; the inference kernels keep cubic_taps and their bits.
+__device__ __forceinline__ void cubic_taps_factored(float t, float u, float w[4]) {
+    const float A = -0.75f;
+    w[0] = A * t * u * u;
+    w[1] = u * (1.f + t - 1.25f * t * t);
+    w[2] = t * (1.f + u - 1.25f * u * u);
+    w[3] = A * u * t * t;
+}
 // img = (sqrt_ac x0 + sqrt_1mac noise) * mask + (1 - mask) * img   (reference plms.py:96-100)
 int fuser_resize_launch(const bf16* tok, const bf16* x, const float* gate, bf16* y, int B, int row_stride, int grid_off, int sg, int sv,
                         int C, hipStream_t stream);

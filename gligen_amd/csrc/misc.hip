@@ -401,14 +401,7 @@ int inpaint_blend_launch(float* img, const float* x0, const float* noise, const 
 // grid of grounding tokens, resized to the sv x sv visual grid by torch's bicubic (F.interpolate mode='bicubic',
 // align_corners=False: src = (dst + 0.5) * sg / sv - 0.5, cubic convolution with A = -0.75, taps clamped to the grid),
 // then y = x + gate * residual.  tok: [B][row_stride][C] with the grid at rows [grid_off, grid_off + sg*sg);  x, y: [B][sv*sv][C].
-__device__ __forceinline__ void cubic_taps(float t, float w[4]) {
-    const float A = -0.75f;
-    const float a = t + 1.f, b = 1.f - t, c = 2.f - t;
-    w[0] = ((A * a - 5.f * A) * a + 8.f * A) * a - 4.f * A;
-    w[1] = ((A + 2.f) * t - (A + 3.f)) * t * t + 1.f;
-    w[2] = ((A + 2.f) * b - (A + 3.f)) * b * b + 1.f;
-    w[3] = ((A * c - 5.f * A) * c + 8.f * A) * c - 4.f * A;
-}
+// (cubic_taps: misc.h, next to the factored form the training path's fp32 grid resize uses, train_fusers.hip)
 __global__ void fuser_resize_kernel(const bf16* __restrict__ tok, const bf16* __restrict__ x, const float* __restrict__ gate,
                                     bf16* __restrict__ y, int B, int row_stride, int grid_off, int sg, int sv, int C) {
     const int C2 = C >> 1;

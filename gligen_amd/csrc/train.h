@@ -1,5 +1,5 @@
-// Training slice (second half): forward + backward of ONE BasicTransformerBlock with a gatedSA fuser
-// (reference ldm/modules/attention.py:333-338, 236-244) under the reference's loss, with the gradients the reference's trainer
+// Training slice (second half): forward + backward of ONE BasicTransformerBlock with a gatedSA, gatedSA2 or
+// gatedCA fuser (reference ldm/modules/attention.py:333-338, 236-244, 272-297, 207-212) under the reference's loss, with the gradients the reference's trainer
 // asks for (trainer.py:217-245: the fuser.* parameters; the block input and the grounding tokens so that the step chains into
 // position_net and the blocks in front). See train.hip.
 #pragma once
@@ -10,9 +10,13 @@ namespace gl {
 struct TrainBlockDims {
     int B, N, Ng, C, heads, ctx_T, ctx_dim;
     float fuser_scale;      // GatedSelfAttentionDense.scale (attention.py:232)
+    int fuser_kind = 0;     // 0 gatedSA, 1 gatedSA2 (N and Ng squares: the residual is the Ng tokens' attention output resized to the
+                            // visual grid, train_fusers.h), 2 gatedCA (no fuser.linear: TP_F_LIN_W / _B null in params and grads; to_k /
+                            // to_v are [C][ctx_dim] and read objs)
 };
 
-// Parameter slots: the reference state_dict of BasicTransformerBlock(fuser_type="gatedSA"), fp32 device pointers
+// Parameter slots: the reference state_dict of BasicTransformerBlock(fuser_type="gatedSA" / "gatedSA2"; "gatedCA" has no
+// fuser.linear.*), fp32 device pointers
 enum {
     TP_NORM1_W = 0, TP_NORM1_B, TP_A1_Q, TP_A1_K, TP_A1_V, TP_A1_O, TP_A1_OB,
     TP_F_LIN_W, TP_F_LIN_B, TP_F_N1_W, TP_F_N1_B, TP_F_Q, TP_F_K, TP_F_V, TP_F_O, TP_F_OB,
@@ -54,7 +58,7 @@ int resblock_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainResDim
 int resample_train_step(Arena& ar, float* ws, size_t ws_bytes, int mode, int B, int H, int W, int C, const float* w_oihw, const float* bias, const float* x,
                         const float* target, float* y, float* loss, float* dx, hipStream_t s);
 
-// ---- the whole training iteration for a UNetModel with the text grounding tokenizer and gatedSA fusers (openaimodel.py:237-464)
+// ---- the whole training iteration for a UNetModel (openaimodel.py:237-464): every grounding tokenizer, every fuser type
 struct TrainUNetCfg {
     int in_channels, out_channels, model_channels, num_res_blocks, num_heads, context_dim, gr_dim;
     int grounding_kind;                 // 0 text, 1 text+image (two MLPs, tokens concatenated), 2 keypoint (points in `boxes`, 17 tokens per person),
@@ -62,6 +66,7 @@ struct TrainUNetCfg {
     int n_mult, channel_mult[8], n_attn, attention_resolutions[8];
     int extra_channels;                 // grounding_kind 3: GroundingDownsampler output channels in front of the first conv (0: none)
     int tok_resize, tok_in_dim;         // grounding_kind 3: PositionNet resize_input; channels of a semantic map (sem: in_conv first), else 0
+    int fuser_kind;                     // TrainBlockDims::fuser_kind of every block; 1 (gatedSA2) needs H == W and a square Ng
     int inpaint_mode;                   // grounding_kind 0 / 1 / 2: the first conv reads 2 * in_channels + 1 channels (openaimodel.py:299-302, 445-447)
 };
 // The spatial-map inputs of a training step (grounding_kind 3): the tokenizer's map and mask, grounding_extra_input and the

@@ -1,4 +1,4 @@
-// Training slice for gfx950: forward + backward of one BasicTransformerBlock with a gatedSA fuser under the reference's loss.
+// Training slice for gfx950: forward + backward of one BasicTransformerBlock with a gatedSA / gatedSA2 / gatedCA fuser under the reference's loss.
 //
 // Reference: ldm/modules/attention.py:333-338 (BasicTransformerBlock._forward), :236-244 (GatedSelfAttentionDense.forward),
 // :127-186 (CrossAttention / SelfAttention), :37-64 (GEGLU / FeedForward); trainer.py:353-371 (run_one_step: mse_loss(model_output,
@@ -14,6 +14,7 @@
 // This is the first slice of the training path (DESIGN.md section 9 has the rest of the plan): op-level, held to gradients of the
 // reference's own autograd (tests/golden/block_backward_gatedsa.npz), not yet tuned.
 #include "train.h"
+#include "train_fusers.h"
 
 #include <map>
 #include <tuple>
@@ -1188,13 +1189,20 @@ int adamw_step(float* p, const float* g, float* m, float* v, size_t n, double lr
 }
 
 
+// the side of a square grid of n tokens, 0 when n is not a square
+static int isqrt_exact(int n) {
+    int r = (int)lround(sqrt((double)n));
+    return r * r == n ? r : 0;
+}
+
 // ---- the UNet's layer kinds. *_forward keeps what the backward needs in the arena; *_backward takes g = dL/dy
 // Everything the backward of a BasicTransformerBlock needs from its forward
 struct BlockSaved {
     Ctx::LN n1, nf1, nf2, n2, n3;
     Ctx::Attn a1, af, a2;
     float *q1, *k1, *v1, *qf, *kf, *vf, *q2, *k2, *v2;
-    float *af_vis, *of, *uf, *hf, *ff_f, *u3;
+    float *af_vis, *of, *uf, *hf, *ff_f, *u3;     // af_vis: the rows fuser.attn.to_out read; of: what alpha_attn gates
+    float* nf1_tail = nullptr;                    // gatedSA2: norm1's output at the grounding tokens, the rows to_q read
 };
 struct STSaved {
     Ctx::GN n0;
@@ -1235,18 +1243,44 @@ static BlockSaved block_forward(const Ctx& c, const TrainBlockDims& d, const flo
     S.a1 = c.attn_fwd(D, S.q1, S.k1, S.v1, B, H, N, N);
     float* o1 = c.lin_fwd(S.a1.o, M, C, P[TP_A1_O], P[TP_A1_OB], C);
     float* x1 = c.gated_add(x, o1, nullptr, 1.f, nx);
-    // fuser (attention.py:236-244): x2 = x1 + scale tanh(alpha_attn) attn(norm1([x1 ; linear(objs)]))[:, :N]
-    float* ol = c.lin_fwd(objs, B * Ng, KD, P[TP_F_LIN_W], P[TP_F_LIN_B], C);
-    float* cat = c.f32((size_t)MT * C);
-    c.put_rows(cat, B, T, 0, x1, N, C);
-    c.put_rows(cat, B, T, N, ol, Ng, C);
-    S.nf1 = c.ln_fwd(cat, MT, C, P[TP_F_N1_W], P[TP_F_N1_B]);
-    S.qf = c.lin_fwd(S.nf1.y, MT, C, P[TP_F_Q], nullptr, C);
-    S.kf = c.lin_fwd(S.nf1.y, MT, C, P[TP_F_K], nullptr, C);
-    S.vf = c.lin_fwd(S.nf1.y, MT, C, P[TP_F_V], nullptr, C);
-    S.af = c.attn_fwd(D, S.qf, S.kf, S.vf, B, H, T, T);
-    S.af_vis = c.slice_rows(S.af.o, B, T, 0, N, C);
-    S.of = c.lin_fwd(S.af_vis, M, C, P[TP_F_O], P[TP_F_OB], C);
+    if (d.fuser_kind == 2) {
+        // fuser (gatedCA, attention.py:207-212): x2 = x1 + scale tanh(alpha_attn) attn(norm1(x1), objs, objs): no fuser.linear, to_k / to_v read objs
+        S.nf1 = c.ln_fwd(x1, M, C, P[TP_F_N1_W], P[TP_F_N1_B]);
+        S.qf = c.lin_fwd(S.nf1.y, M, C, P[TP_F_Q], nullptr, C);
+        S.kf = c.lin_fwd(objs, B * Ng, KD, P[TP_F_K], nullptr, C);
+        S.vf = c.lin_fwd(objs, B * Ng, KD, P[TP_F_V], nullptr, C);
+        S.af = c.attn_fwd(D, S.qf, S.kf, S.vf, B, H, N, Ng);
+        S.af_vis = S.af.o;
+        S.of = c.lin_fwd(S.af_vis, M, C, P[TP_F_O], P[TP_F_OB], C);
+    } else {
+        // fuser (gatedSA, attention.py:236-244): x2 = x1 + scale tanh(alpha_attn) attn(norm1([x1 ; linear(objs)]))[:, :N]
+        float* ol = c.lin_fwd(objs, B * Ng, KD, P[TP_F_LIN_W], P[TP_F_LIN_B], C);
+        float* cat = c.f32((size_t)MT * C);
+        c.put_rows(cat, B, T, 0, x1, N, C);
+        c.put_rows(cat, B, T, N, ol, Ng, C);
+        S.nf1 = c.ln_fwd(cat, MT, C, P[TP_F_N1_W], P[TP_F_N1_B]);
+        if (d.fuser_kind == 0) {
+            S.qf = c.lin_fwd(S.nf1.y, MT, C, P[TP_F_Q], nullptr, C);
+            S.kf = c.lin_fwd(S.nf1.y, MT, C, P[TP_F_K], nullptr, C);
+            S.vf = c.lin_fwd(S.nf1.y, MT, C, P[TP_F_V], nullptr, C);
+            S.af = c.attn_fwd(D, S.qf, S.kf, S.vf, B, H, T, T);
+            S.af_vis = c.slice_rows(S.af.o, B, T, 0, N, C);
+            S.of = c.lin_fwd(S.af_vis, M, C, P[TP_F_O], P[TP_F_OB], C);
+        } else {
+            // gatedSA2 (attention.py:272-297): [:, N:] keeps the grounding tokens' outputs only, so only those Ng rows are queries; their
+            // projected outputs, an sg x sg grid, are resized to the sv x sv visual grid (bicubic) and that is the gated residual
+            const int sg = isqrt_exact(Ng), sv = isqrt_exact(N);
+            S.nf1_tail = c.slice_rows(S.nf1.y, B, T, N, Ng, C);
+            S.qf = c.lin_fwd(S.nf1_tail, B * Ng, C, P[TP_F_Q], nullptr, C);
+            S.kf = c.lin_fwd(S.nf1.y, MT, C, P[TP_F_K], nullptr, C);
+            S.vf = c.lin_fwd(S.nf1.y, MT, C, P[TP_F_V], nullptr, C);
+            S.af = c.attn_fwd(D, S.qf, S.kf, S.vf, B, H, Ng, T);
+            S.af_vis = S.af.o;
+            float* og = c.lin_fwd(S.af_vis, B * Ng, C, P[TP_F_O], P[TP_F_OB], C);
+            S.of = c.f32(nx);
+            c.ck(grid_resize_fwd_launch(og, B, sg, sv, C, S.of, c.s));
+        }
+    }
     float* x2 = c.gated_add(x1, S.of, P[TP_F_ALPHA_ATTN], d.fuser_scale, nx);
     //        x3 = x2 + scale tanh(alpha_dense) ff(norm2(x2))
     S.nf2 = c.ln_fwd(x2, M, C, P[TP_F_N2_W], P[TP_F_N2_B]);
@@ -1299,24 +1333,63 @@ static void block_backward(const Ctx& c, const TrainBlockDims& d, const float* c
         float* g_nf2 = c.lin_dgrad(g_uf, M, 8 * C, P[TP_F_FF1_W], C);
         c.ln_bwd(g_nf2, S.nf2, P[TP_F_N2_W], M, C, g, true, G[TP_F_N2_W], G[TP_F_N2_B]);
     }
-    {   // x2 = x1 + g_a attn(norm1([x1 ; linear(objs)]))[:, :N]: the fuser's attention, TRAINABLE
+    if (d.fuser_kind == 2) {   // x2 = x1 + g_a attn(norm1(x1), objs, objs): the gatedCA fuser's attention, TRAINABLE; keys and values from the raw tokens
         if (G[TP_F_ALPHA_ATTN]) c.dot_reduce(g, S.of, nx, P[TP_F_ALPHA_ATTN], d.fuser_scale, 0, G[TP_F_ALPHA_ATTN]);
         float* g_of = c.gated_scale(g, P[TP_F_ALPHA_ATTN], d.fuser_scale, nx);
         c.lin_wgrad(g_of, S.af_vis, M, C, C, G[TP_F_O], G[TP_F_OB]);
-        float* g_af_vis = c.lin_dgrad(g_of, M, C, P[TP_F_O], C);
-        float* g_af = c.f32((size_t)MT * C);      // the grounding-token rows of the attention output are dropped by [:, :N]: zero gradient
-        c.hip(hipMemsetAsync(g_af, 0, (size_t)MT * C * 4, s), "hipMemsetAsync");
-        c.put_rows(g_af, B, T, 0, g_af_vis, N, C);
-        float* g_qf = c.f32((size_t)MT * C);
-        float* g_kf = c.f32((size_t)MT * C);
-        float* g_vf = c.f32((size_t)MT * C);
-        c.attn_bwd(D, S.qf, S.kf, S.vf, S.af, g_af, B, H, T, T, g_qf, g_kf, g_vf);
-        c.lin_wgrad(g_qf, S.nf1.y, MT, C, C, G[TP_F_Q], nullptr);
-        c.lin_wgrad(g_kf, S.nf1.y, MT, C, C, G[TP_F_K], nullptr);
-        c.lin_wgrad(g_vf, S.nf1.y, MT, C, C, G[TP_F_V], nullptr);
-        float* g_nf1 = c.lin_dgrad(g_qf, MT, C, P[TP_F_Q], C);
-        c.add(g_nf1, c.lin_dgrad(g_kf, MT, C, P[TP_F_K], C), (size_t)MT * C);
-        c.add(g_nf1, c.lin_dgrad(g_vf, MT, C, P[TP_F_V], C), (size_t)MT * C);
+        float* g_af = c.lin_dgrad(g_of, M, C, P[TP_F_O], C);
+        float* g_qf = c.f32(nx);
+        float* g_kf = c.f32((size_t)B * Ng * C);
+        float* g_vf = c.f32((size_t)B * Ng * C);
+        c.attn_bwd(D, S.qf, S.kf, S.vf, S.af, g_af, B, H, N, Ng, g_qf, g_kf, g_vf);
+        c.lin_wgrad(g_qf, S.nf1.y, M, C, C, G[TP_F_Q], nullptr);
+        c.lin_wgrad(g_kf, objs, B * Ng, C, KD, G[TP_F_K], nullptr);
+        c.lin_wgrad(g_vf, objs, B * Ng, C, KD, G[TP_F_V], nullptr);
+        float* g_objs = c.lin_dgrad(g_kf, B * Ng, C, P[TP_F_K], KD);
+        c.add(g_objs, c.lin_dgrad(g_vf, B * Ng, C, P[TP_F_V], KD), (size_t)B * Ng * KD);
+        c.hip(hipMemcpyAsync(dobjs, g_objs, (size_t)B * Ng * KD * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
+        float* g_nf1 = c.lin_dgrad(g_qf, M, C, P[TP_F_Q], C);
+        c.ln_bwd(g_nf1, S.nf1, P[TP_F_N1_W], M, C, g, true, G[TP_F_N1_W], G[TP_F_N1_B]);
+    } else {   // x2 = x1 + g_a attn(norm1([x1 ; linear(objs)]))[:, :N] (gatedSA2: resize(...[:, N:])): the fuser's attention, TRAINABLE
+        if (G[TP_F_ALPHA_ATTN]) c.dot_reduce(g, S.of, nx, P[TP_F_ALPHA_ATTN], d.fuser_scale, 0, G[TP_F_ALPHA_ATTN]);
+        float* g_of = c.gated_scale(g, P[TP_F_ALPHA_ATTN], d.fuser_scale, nx);
+        float* g_nf1 = nullptr;     // dL/d norm1([x1 ; linear(objs)]) [MT][C]
+        if (d.fuser_kind == 0) {
+            c.lin_wgrad(g_of, S.af_vis, M, C, C, G[TP_F_O], G[TP_F_OB]);
+            float* g_af_vis = c.lin_dgrad(g_of, M, C, P[TP_F_O], C);
+            float* g_af = c.f32((size_t)MT * C);      // the grounding-token rows of the attention output are dropped by [:, :N]: zero gradient
+            c.hip(hipMemsetAsync(g_af, 0, (size_t)MT * C * 4, s), "hipMemsetAsync");
+            c.put_rows(g_af, B, T, 0, g_af_vis, N, C);
+            float* g_qf = c.f32((size_t)MT * C);
+            float* g_kf = c.f32((size_t)MT * C);
+            float* g_vf = c.f32((size_t)MT * C);
+            c.attn_bwd(D, S.qf, S.kf, S.vf, S.af, g_af, B, H, T, T, g_qf, g_kf, g_vf);
+            c.lin_wgrad(g_qf, S.nf1.y, MT, C, C, G[TP_F_Q], nullptr);
+            c.lin_wgrad(g_kf, S.nf1.y, MT, C, C, G[TP_F_K], nullptr);
+            c.lin_wgrad(g_vf, S.nf1.y, MT, C, C, G[TP_F_V], nullptr);
+            g_nf1 = c.lin_dgrad(g_qf, MT, C, P[TP_F_Q], C);
+            c.add(g_nf1, c.lin_dgrad(g_kf, MT, C, P[TP_F_K], C), (size_t)MT * C);
+            c.add(g_nf1, c.lin_dgrad(g_vf, MT, C, P[TP_F_V], C), (size_t)MT * C);
+        } else {
+            // the visual rows of the attention output are dropped by [:, N:]: only the Ng grounding rows are queries and carry gradient
+            const int sg = isqrt_exact(Ng), sv = isqrt_exact(N), MG = B * Ng;
+            float* g_og = c.f32((size_t)MG * C);
+            c.ck(grid_resize_bwd_launch(g_of, B, sg, sv, C, g_og, s));
+            c.lin_wgrad(g_og, S.af_vis, MG, C, C, G[TP_F_O], G[TP_F_OB]);
+            float* g_af = c.lin_dgrad(g_og, MG, C, P[TP_F_O], C);
+            float* g_qf = c.f32((size_t)MG * C);
+            float* g_kf = c.f32((size_t)MT * C);
+            float* g_vf = c.f32((size_t)MT * C);
+            c.attn_bwd(D, S.qf, S.kf, S.vf, S.af, g_af, B, H, Ng, T, g_qf, g_kf, g_vf);
+            c.lin_wgrad(g_qf, S.nf1_tail, MG, C, C, G[TP_F_Q], nullptr);
+            c.lin_wgrad(g_kf, S.nf1.y, MT, C, C, G[TP_F_K], nullptr);
+            c.lin_wgrad(g_vf, S.nf1.y, MT, C, C, G[TP_F_V], nullptr);
+            g_nf1 = c.lin_dgrad(g_kf, MT, C, P[TP_F_K], C);
+            c.add(g_nf1, c.lin_dgrad(g_vf, MT, C, P[TP_F_V], C), (size_t)MT * C);
+            float* g_tail = c.slice_rows(g_nf1, B, T, N, Ng, C);      // to_q read rows [N, T) only
+            c.add(g_tail, c.lin_dgrad(g_qf, MG, C, P[TP_F_Q], C), (size_t)MG * C);
+            c.put_rows(g_nf1, B, T, N, g_tail, Ng, C);
+        }
         float* g_cat = c.f32((size_t)MT * C);
         c.ln_bwd(g_nf1, S.nf1, P[TP_F_N1_W], MT, C, g_cat, false, G[TP_F_N1_W], G[TP_F_N1_B]);
         c.add(g, c.slice_rows(g_cat, B, T, 0, N, C), nx);
@@ -1338,10 +1411,21 @@ static void block_backward(const Ctx& c, const TrainBlockDims& d, const float* c
     }
 }
 
-static void block_check(const TrainBlockDims& d, const float* const* P) {
+// G (optional): the gradient slots, checked against the kind's key set
+static void block_check(const TrainBlockDims& d, const float* const* P, float* const* G = nullptr) {
     if (d.C % 64 || d.ctx_dim % 64 || d.C % d.heads || d.B < 1 || d.N < 1 || d.Ng < 1) throw GlError(GL_ERR_ARG, "block_train_step: C and ctx_dim must be multiples of 64");
-    for (int i = 0; i < TP_COUNT; ++i)
-        if (!P[i]) throw GlError(GL_ERR_ARG, fmt("block_train_step: parameter slot %d is null", i));
+    if (d.fuser_kind < 0 || d.fuser_kind > 2) throw GlError(GL_ERR_ARG, fmt("block_train_step: fuser_kind %d (0 gatedSA, 1 gatedSA2, 2 gatedCA)", d.fuser_kind));
+    if (d.fuser_kind == 1 && !isqrt_exact(d.Ng))
+        throw GlError(GL_ERR_ARG, fmt("block_train_step: gatedSA2 needs a square number of grounding tokens (attention.py:281-283); Ng = %d", d.Ng));
+    if (d.fuser_kind == 1 && !isqrt_exact(d.N))
+        throw GlError(GL_ERR_ARG, fmt("block_train_step: gatedSA2 needs a square grid of visual tokens (attention.py:280-282); N = %d", d.N));
+    for (int i = 0; i < TP_COUNT; ++i) {
+        const bool absent = d.fuser_kind == 2 && (i == TP_F_LIN_W || i == TP_F_LIN_B);      // GatedCrossAttentionDense has no linear
+        if (absent && (P[i] || (G && G[i])))
+            throw GlError(GL_ERR_ARG, fmt("block_train_step: a gatedCA fuser has no fuser.linear.%s (parameter slot %d must be null in params and grads)",
+                                          i == TP_F_LIN_W ? "weight" : "bias", i));
+        if (!absent && !P[i]) throw GlError(GL_ERR_ARG, fmt("block_train_step: parameter slot %d is null", i));
+    }
 }
 
 int block_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainBlockDims& d, const float* const* P, const float* x, const float* objs,
@@ -1349,7 +1433,7 @@ int block_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainBlockDims
     const size_t nx = (size_t)d.B * d.N * d.C;
     BlockSaved S;
     return with_mse_loss(
-        ar, ws, ws_bytes, s, y, target, nx, loss, dx, nx, [&](const Ctx& c) { block_check(d, P); S = block_forward(c, d, P, x, objs, context, y); },
+        ar, ws, ws_bytes, s, y, target, nx, loss, dx, nx, [&](const Ctx& c) { block_check(d, P, G); S = block_forward(c, d, P, x, objs, context, y); },
         [&](const Ctx& c, float* g) { block_backward(c, d, P, S, objs, g, dobjs, G); return g; });
 }
 
@@ -1357,10 +1441,10 @@ int block_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainBlockDims
 // GroupNorm(32, eps 1e-6) without activation, proj_in / proj_out 1 x 1 convs = Linears over pixel rows. norm / proj_* are SD layers
 // (frozen); gradients: the block's fuser.* parameters, dx, dobjs. P / G: [norm.w, norm.b, proj_in.w, proj_in.b, <37 block slots>,
 // proj_out.w, proj_out.b].
-static void st_check(const TrainBlockDims& d, const float* const* P) {
+static void st_check(const TrainBlockDims& d, const float* const* P, float* const* G = nullptr) {
     for (int i = 0; i < ST_COUNT; ++i)
-        if (!P[i]) throw GlError(GL_ERR_ARG, fmt("st_train_step: parameter slot %d is null", i));
-    block_check(d, P + ST_BLOCK0);
+        if (!P[i] && (i < ST_BLOCK0 || i >= ST_BLOCK0 + TP_COUNT)) throw GlError(GL_ERR_ARG, fmt("st_train_step: parameter slot %d is null", i));
+    block_check(d, P + ST_BLOCK0, G ? G + ST_BLOCK0 : nullptr);
 }
 static STSaved st_forward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const float* x, const float* objs, const float* context, float* y) {
     const int B = d.B, N = d.N, C = d.C, M = B * N;
@@ -2125,6 +2209,11 @@ UNetStep step_dims(const Ctx& c, const Names& nm, const TrainUNetCfg& cfg, const
     u.PWr = u.GK == 3 ? kCnxDims[3] : cfg.gr_dim + 16 * u.NC; u.PW = round_up(u.PWr, 64); u.NBR = u.GK == 1 ? 2 : 1;
     if (u.Ng != u.NB * u.NBR || (u.GK == 2 && u.NB % 17)) throw GlError(GL_ERR_ARG, "unet_train_step: Ng must be the box count (text), twice it (text+image), 17 per person (keypoint)");
     u.MR = u.B * u.Ng;
+    if (cfg.fuser_kind < 0 || cfg.fuser_kind > 2) throw GlError(GL_ERR_ARG, fmt("unet_train_step: fuser_kind %d (0 gatedSA, 1 gatedSA2, 2 gatedCA)", cfg.fuser_kind));
+    if (cfg.fuser_kind == 1 && !isqrt_exact(u.Ng))
+        throw GlError(GL_ERR_ARG, fmt("unet_train_step: gatedSA2 needs a square number of grounding tokens (attention.py:281-283); Ng = %d", u.Ng));
+    if (cfg.fuser_kind == 1 && in.H != in.W)
+        throw GlError(GL_ERR_ARG, fmt("unet_train_step: gatedSA2 needs a square latent (attention.py:280-282: square visual grids); H = %d, W = %d", in.H, in.W));
     u.null_pos = u.GK == 2 ? "position_net.null_xy_feature" : "position_net.null_position_feature";
     u.Cx = cfg.in_channels; u.Ce = u.GK == 3 ? cfg.extra_channels : 0; u.Ci = cfg.inpaint_mode ? u.Cx + 1 : 0; u.Cin0 = u.Cx + u.Ce + u.Ci;
     u.M0 = (size_t)u.B * u.H0 * u.W0;
@@ -2250,6 +2339,11 @@ UNetLayer st_layer(const UNetStep& u, const std::string& p, int C, int H, int W)
     l.P[ST_POUT_W] = nm.w(p + ".proj_out.weight"); l.P[ST_POUT_B] = nm.w(p + ".proj_out.bias");
     for (int i = 0; i < TP_COUNT; ++i) {
         const std::string k = p + ".transformer_blocks.0." + u.block_names[i];
+        if (u.cfg.fuser_kind == 2 && (i == TP_F_LIN_W || i == TP_F_LIN_B)) {      // GatedCrossAttentionDense has no linear: the slots stay null
+            if (nm.has(k) || nm.g(k))
+                throw GlError(GL_ERR_ARG, "unet_train_step: '" + k + "' in the state_dict of a gatedCA model, whose fusers have no linear (attention.py:190-201)");
+            continue;
+        }
         l.P[ST_BLOCK0 + i] = nm.w(k);
         l.G[ST_BLOCK0 + i] = nm.g(k);
     }
@@ -2259,7 +2353,9 @@ UNetLayer st_layer(const UNetStep& u, const std::string& p, int C, int H, int W)
 UNetLayer resample_layer(const Names& nm, Kind kind, const std::string& p, int C, int H, int W) {
     return UNetLayer{kind, p, C, C, H, W, 0, -1, nullptr, {nm.w(p + ".weight"), nm.w(p + ".bias")}, {}, {}, {}};
 }
-TrainBlockDims st_dims(const UNetStep& u, const UNetLayer& l) { return {u.B, l.H * l.W, u.Ng, l.Cout, u.cfg.num_heads, u.in.ctx_T, u.KD, u.in.fuser_scale}; }
+TrainBlockDims st_dims(const UNetStep& u, const UNetLayer& l) {
+    return {u.B, l.H * l.W, u.Ng, l.Cout, u.cfg.num_heads, u.in.ctx_T, u.KD, u.in.fuser_scale, u.cfg.fuser_kind};
+}
 TrainResDims res_dims(const UNetStep& u, const UNetLayer& l) { return {u.B, l.H, l.W, l.Cin, l.Cout, u.ED}; }
 
 // One layer's forward on the stream h; the layer, with what its backward needs, is appended to L.
@@ -2277,7 +2373,7 @@ void run(const UNetStep& u, const float* objs, const float* semb, Act& h, std::v
         l.rs = res_forward(c, res_dims(u, l), l.P.data(), h.p, semb, y);
         if (u.in.checkpoint) c.ar.release(mk);
     } else if (l.kind == K_ST) {
-        st_check(st_dims(u, l), l.P.data());
+        st_check(st_dims(u, l), l.P.data(), l.G.data());
         y = c.f32(rows * l.Cout);
         const size_t mk = c.ar.mark();
         l.ss = st_forward(c, st_dims(u, l), l.P.data(), h.p, objs, u.in.context, y);

@@ -149,7 +149,7 @@ class Engine:
         cfg.inpaint_mode = int(bool(inpaint_mode))
         cfg.grounding_kind = GROUNDING_KINDS[grounding_kind]
         cfg.gr_in_dim, cfg.gr_out_dim, cfg.max_persons = gr_in_dim, gr_out_dim, max_persons
-        cfg.fuser_kind = {"gatedSA": 0, "gatedSA2": 1, "gatedCA": 2}[fuser_type or "gatedSA"]
+        cfg.fuser_kind = _lib.fuser_kind(fuser_type)
         cfg.extra_channels = int(extra_channels)
         cfg.tok_resize, cfg.tok_in_dim = int(tok_resize), int(tok_in_dim)
         check(self.lib.gl_unet_configure(self._ctx, C.byref(cfg)))
@@ -700,7 +700,8 @@ class Engine:
     def unet_train_step(self, cfg: Mapping, state_dict: Mapping[str, torch.Tensor], batch: Mapping[str, torch.Tensor], fuser_scale: float = 1.0,
                         trainable=None, grads: Optional[Mapping[str, torch.Tensor]] = None, checkpoint: bool = False, use_weight_cache: bool = False):
         """One training iteration of the reference (trainer.py:353-392: model(input), mse_loss(model_output, noise), backward) on the
-        device (gl_unet_train_step). cfg: UNetModel kwargs (text tokenizer, gatedSA); state_dict: the model's parameters (fp32, on this
+        device (gl_unet_train_step). cfg: UNetModel kwargs -- any tokenizer; cfg["fuser_type"] gatedSA (default), gatedSA2 (a square number
+        of grounding tokens and H == W) or gatedCA (no fuser.linear.* keys) --; state_dict: the model's parameters (fp32, on this
         device: they are used in place); batch: x [B, 4, H, W] (noised latent), timesteps [B], context [B, 77, 768], boxes, masks,
         positive_embeddings (or, for the text+image tokenizer, text_embeddings, image_embeddings, text_masks, image_masks), target [B, 4, H, W] (the noise).
         A spatial-map model (cfg["grounding_tokenizer"] one of the five *_grounding_net targets; gl_unet_train_step_spatial) takes the map
@@ -731,7 +732,7 @@ class Engine:
         sp = spatial_train_config(cfg)          # a spatial-map tokenizer (canny / depth / normal / hed / sem_grounding_net.py)?
         ti = sp is None and "image_embeddings" in batch     # the text+image tokenizer (text_image_grounding_net.py)
         kp = sp is None and "points" in batch               # the keypoint tokenizer (keypoint_grounding_net.py); else the text tokenizer
-        c.grounding_kind, c.fuser_kind = (3 if sp else 1 if ti else 2 if kp else 0), 0
+        c.grounding_kind, c.fuser_kind = (3 if sp else 1 if ti else 2 if kp else 0), _lib.fuser_kind(cfg.get("fuser_type", "gatedSA"))
         c.max_persons = int(batch["points"].shape[1]) // 17 if kp else 0
         c.gr_in_dim = c.gr_out_dim = 768
         inpaint = bool(cfg.get("inpaint_mode"))
@@ -944,12 +945,28 @@ class Engine:
         names = self.lib.gl_train_block_param_names()
         return [names[i].decode() for i in range(37)]
 
-    def op_block_train(self, state_dict, x, objs, context, target, heads, fuser_scale=1.0):
-        """Training slice (gl_op_block_train): forward + backward of one BasicTransformerBlock (gatedSA fuser) under
-        mse_loss(y, target). state_dict: the block's reference state_dict (fp32). Returns (y, loss, dx, dobjs, grads) with grads
-        a dict over the fuser.* parameter names."""
+    def op_block_train(self, state_dict, x, objs, context, target, heads, fuser_scale=1.0, fuser_type=None):
+        """Training slice (gl_op_block_train): forward + backward of one BasicTransformerBlock under mse_loss(y, target).
+        state_dict: the block's reference state_dict (fp32). Returns (y, loss, dx, dobjs, grads) with grads a dict over the fuser.*
+        parameter names. fuser_type "gatedSA" / "gatedSA2" / "gatedCA" goes through gl_op_block_train_fuser (gatedSA: the same
+        launches and bits as the default entry); a gatedCA block's state_dict has no fuser.linear.* and one that has is refused."""
         dev = self.device
         names = self.block_train_param_names()
+        if fuser_type is not None:
+            kind = _lib.fuser_kind(fuser_type)
+            absent = [n for n in names if n not in state_dict and kind == 2 and n.startswith("fuser.linear.")]
+            params = [(None if n in absent else _f32(state_dict[n], dev)) for n in names]
+            x, objs, context, target = (_f32(t, dev) for t in (x, objs, context, target))
+            B, N, Cc = x.shape
+            dims = TrainBlockDims(int(B), int(N), int(objs.shape[1]), int(Cc), int(heads), int(context.shape[1]), int(context.shape[2]), float(fuser_scale))
+            y, dx, dobjs = torch.empty_like(x), torch.empty_like(x), torch.empty_like(objs)
+            loss = torch.zeros(1, device=dev, dtype=torch.float32)
+            grads = {n: torch.zeros_like(p) for n, p in zip(names, params) if n.startswith("fuser.") and p is not None}
+            parr = (C.c_void_p * 37)(*[(p.data_ptr() if p is not None else None) for p in params])
+            garr = (C.c_void_p * 37)(*[(grads[n].data_ptr() if n in grads else None) for n in names])
+            check(self.lib.gl_op_block_train_fuser(self._ctx, kind, C.byref(dims), parr, _ptr(x), _ptr(objs), _ptr(context), _ptr(target), _ptr(y),
+                                                   _ptr(loss), _ptr(dx), _ptr(dobjs), garr, _stream(self.device)))
+            return y, loss, dx, dobjs, grads
         params = [_f32(state_dict[n], dev) for n in names]
         x, objs, context, target = (_f32(t, dev) for t in (x, objs, context, target))
         B, N, Cc = x.shape
@@ -962,6 +979,28 @@ class Engine:
         check(self.lib.gl_op_block_train(self._ctx, C.byref(dims), parr, _ptr(x), _ptr(objs), _ptr(context), _ptr(target), _ptr(y), _ptr(loss),
                                          _ptr(dx), _ptr(dobjs), garr, _stream(self.device)))
         return y, loss, dx, dobjs, grads
+
+    def op_grid_resize(self, src, sg, sv):
+        """gl_op_grid_resize: src [B, sg*sg, C] fp32 rows -> [B, sv*sv, C], torch's bicubic (align_corners=False) of the square grid:
+        the gatedSA2 fuser's residual on the training path."""
+        src = _f32(src, self.device)
+        B, n, Cc = src.shape
+        if n != sg * sg:
+            raise ValueError(f"op_grid_resize: src holds {n} tokens per sample, sg * sg = {sg * sg}")
+        dst = torch.empty((B, sv * sv, Cc), device=self.device, dtype=torch.float32)
+        check(self.lib.gl_op_grid_resize(self._ctx, _ptr(src), int(B), int(sg), int(sv), int(Cc), _ptr(dst), _stream(self.device)))
+        return dst
+
+    def op_grid_resize_backward(self, g, sg, sv):
+        """gl_op_grid_resize_backward: g [B, sv*sv, C] -> [B, sg*sg, C], the exact transpose of op_grid_resize (a gather, no atomics:
+        two calls give the same bits)."""
+        g = _f32(g, self.device)
+        B, n, Cc = g.shape
+        if n != sv * sv:
+            raise ValueError(f"op_grid_resize_backward: g holds {n} pixels per sample, sv * sv = {sv * sv}")
+        dsrc = torch.empty((B, sg * sg, Cc), device=self.device, dtype=torch.float32)
+        check(self.lib.gl_op_grid_resize_backward(self._ctx, _ptr(g), int(B), int(sg), int(sv), int(Cc), _ptr(dsrc), _stream(self.device)))
+        return dsrc
 
     def op_conv3x3(self, x0, w_oihw, bias, x1=None, stride=1, ups=0, pad_lo=1, res=None):
         B, H, W, C0 = x0.shape

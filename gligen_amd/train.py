@@ -8,7 +8,9 @@ Everything numeric runs in the library: forward + backward in gl_unet_train_step
 the bookkeeping the reference leaves to torch.optim / DDP: the trainable parameters and their gradients are views into a few flat
 fp32 buffers (gligen_amd.dist.GradBuckets), so the backward writes the gradients where the collective reads them, one
 reduce-scatter + all-gather pair per bucket goes over RCCL, and AdamW is one launch per bucket over the flat range.
-The step is built for the three discrete grounding tokenizers and the five spatial-map ones with gatedSA fusers; the batch dict carries
+The step is built for the three discrete grounding tokenizers and the five spatial-map ones with any of the reference's fuser types
+(cfg["fuser_type"]: gatedSA, the default; gatedSA2, which needs a square number of grounding tokens and a square latent; gatedCA, whose
+state_dict has no fuser.linear.*); the batch dict carries
 boxes + masks + positive_embeddings (text), + text_embeddings / image_embeddings / text_masks / image_masks (text+image), points + masks
 (keypoint), or the map under the reference's key (canny_edge, hed_edge, depth, normal, sem) + mask + grounding_extra_input.
 An inpainting model (cfg["inpaint_mode"], discrete tokenizers; trainer.py:189-194, 339-344) trains its 9-channel first conv's weight
@@ -133,7 +135,10 @@ class TrainStep:
     An inpainting model (cfg["inpaint_mode"]): step(batch) takes the reference's keys -- x (the noised latent) and
     inpainting_extra_input = cat(z * mask, mask) [B, 5, H, W] -- or x_rows [B, H, W, 9] / target_rows [B, H, W, 4] as
     Engine.train_step_inputs writes them (no permute copies; any model takes its rows that way); the first conv's weight is part of
-    the trainable set and of the last bucket. The guidance drop leaves all three alone."""
+    the trainable set and of the last bucket. The guidance drop leaves all three alone.
+
+    The fuser type comes from cfg["fuser_type"] (Engine.unet_train_step): a gatedSA2 model has gatedSA's keys and buckets, a gatedCA model
+    has no fuser.linear.* and its fuser.attn.to_k / to_v are [C, context_dim]; the trainable set is name-based and covers both."""
 
     def __init__(self, engine, cfg: Mapping, state_dict: Mapping[str, torch.Tensor], lr: Union[float, Callable[[int], float]] = 5e-5,
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, bucket_mb: float = 128.0, world: Optional[int] = None,

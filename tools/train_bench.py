@@ -7,7 +7,12 @@ iteration fed from the u8 class maps of those planes (gl_unet_train_step_spatial
 (else B = 1, 16 x 16), checkpoint=True, the step inputs made by Engine.train_step_inputs inside the timed region; next to the text
 model's line, and the time of one train_step_inputs launch next to the torch sequence it replaces (q_sample, mask, concat, two
 permutes), medians of 20.
-   PYTHONPATH=. python tools/train_bench.py [--full64] [--spatial {canny,depth,normal,hed,sem} [--class-maps] | --inpaint]"""
+--fuser gatedSA2|gatedCA: the shipped topology with that fuser type, next to the gatedSA text model's line on the same box (with
+--full64: B = 4, 64 x 64 latent, checkpoint=True; else B = 1, 16 x 16): gatedCA with the text tokenizer (30 slots); gatedSA2 with
+--spatial canny (resize 256: an 8 x 8 token grid) or with the text tokenizer and 16 box slots (a 4 x 4 grid). gatedSA2 also prints one
+grid_resize forward + backward (8 -> 64, C 320, B 4) next to torch's F.interpolate forward + backward on the device, medians of 20.
+   PYTHONPATH=. python tools/train_bench.py [--full64] [--spatial {canny,depth,normal,hed,sem} [--class-maps] | --inpaint]
+                                            [--fuser {gatedSA2,gatedCA}]"""
 import json
 import sys
 import time
@@ -18,13 +23,15 @@ from gligen_amd import synthetic as syn
 from gligen_amd.engine import Engine
 
 
-def run(name, cfg, B, hw, reps, eng, checkpoint=False, cache=False):
+def run(name, cfg, B, hw, reps, eng, checkpoint=False, cache=False, max_objs=30):
     model_shapes = None
     from ldm.modules.diffusionmodules.openaimodel import UNetModel
+    if cfg.get("fuser_type", "gatedSA") != "gatedSA":
+        name = f"{name}, {cfg['fuser_type']} fusers, {max_objs} box slots"
     m = UNetModel(**dict(cfg, grounding_tokenizer=syn.GROUNDING_TOKENIZERS["text"], inpaint_mode=False))
     sd = {k: v.float().to(eng.device).contiguous() for k, v in syn.seeded_state_dict({k: tuple(v.shape) for k, v in m.state_dict().items()}, 1234).items()}
     del m
-    b = syn.make_batch("text", B, n_valid=3, seed=5)
+    b = syn.make_batch("text", B, n_valid=3, seed=5, max_objs=max_objs)
     batch = dict(x=syn.make_latent(B, 4, hw, hw, seed=6), timesteps=torch.tensor([981, 441, 300, 77][:B]).float(), context=syn.make_context(B, seed=6),
                  boxes=b["boxes"], masks=b["masks"], positive_embeddings=b["text_embeddings"], target=syn.make_latent(B, 4, hw, hw, seed=7))
     grads = {k: torch.zeros_like(v) for k, v in sd.items() if ".fuser." in k or k.startswith("position_net.")}
@@ -45,7 +52,7 @@ def run(name, cfg, B, hw, reps, eng, checkpoint=False, cache=False):
         eng.train_weight_cache(False)
 
 
-def run_spatial(modality, B, hw, reps, checkpoint=True, class_maps=False):
+def run_spatial(modality, B, hw, reps, checkpoint=True, class_maps=False, fuser="gatedSA"):
     """The shipped topology (syn.UNET_CFG) with a spatial-map tokenizer and its downsampler (configs/cc3m_canny.yaml etc.).
     class_maps: sem's one-hot planes replaced by their u8 class map, argmax over the planes."""
     from ldm.modules.diffusionmodules.openaimodel import UNetModel
@@ -55,7 +62,7 @@ def run_spatial(modality, B, hw, reps, checkpoint=True, class_maps=False):
     tk_params = dict(resize_input=256, out_dim=768)
     if modality == "sem":
         ds_params["in_dim"], tk_params["in_dim"] = 152, 152
-    cfg = dict(syn.UNET_CFG, grounding_downsampler=dict(target=f"ldm.modules.diffusionmodules.{modality}_grounding_downsampler.GroundingDownsampler", params=ds_params),
+    cfg = dict(syn.UNET_CFG, fuser_type=fuser, grounding_downsampler=dict(target=f"ldm.modules.diffusionmodules.{modality}_grounding_downsampler.GroundingDownsampler", params=ds_params),
                grounding_tokenizer=dict(target=f"ldm.modules.diffusionmodules.{modality}_grounding_net.PositionNet", params=tk_params))
     m = UNetModel(**dict(cfg, inpaint_mode=False))
     shapes = {k: tuple(v.shape) for k, v in m.state_dict().items()}
@@ -77,7 +84,7 @@ def run_spatial(modality, B, hw, reps, checkpoint=True, class_maps=False):
         loss, _, _ = eng.unet_train_step(cfg, sd, batch, grads=grads, checkpoint=checkpoint)
     torch.cuda.synchronize()
     dt = (time.time() - t0) / reps
-    print(json.dumps(dict(config=f"shipped topology, {modality} tokenizer + downsampler", inputs="u8 class maps" if class_maps else "fp32 planes", B=B, latent=hw,
+    print(json.dumps(dict(config=f"shipped topology, {modality} tokenizer + downsampler" + ("" if fuser == "gatedSA" else f", {fuser} fusers"), inputs="u8 class maps" if class_maps else "fp32 planes", B=B, latent=hw,
                           tok_resize=256, checkpoint=bool(checkpoint),
                           s_per_iteration=round(dt, 4), loss=float(loss), arena_high_water_gb=round(eng.arena_high_water() / 2 ** 30, 2),
                           trainable_values=sum(int(g.numel()) for g in grads.values()))), flush=True)
@@ -133,22 +140,61 @@ def run_inpaint(B, hw, reps, checkpoint=True):
     out = eng.train_step_inputs(z, noise, t, sched, boxes=boxes, inpaint=True)
     same = bool(torch.equal(out["target_rows"], ref_target) and torch.equal(out["x_rows"][..., 4:], ref_rows[..., 4:]))     # (torch on the GPU may contract a z + s n)
 
-    def median_ms(fn, n=20):
-        ts = []
-        for _ in range(n):
-            torch.cuda.synchronize()
-            t1 = time.perf_counter()
-            fn()
-            torch.cuda.synchronize()
-            ts.append((time.perf_counter() - t1) * 1e3)
-        return sorted(ts)[n // 2]
-
     print(json.dumps(dict(config="step inputs", B=B, latent=hw, train_step_inputs_ms=round(median_ms(lambda: eng.train_step_inputs(z, noise, t, sched, boxes=boxes, inpaint=True)), 4),
                           torch_sequence_ms=round(median_ms(torch_inputs), 4), mask_and_target_equal=same, timing="host wall time around one synchronised call, median of 20")), flush=True)
     eng.close()
 
 
+def median_ms(fn, n=20):
+    ts = []
+    for _ in range(n):
+        torch.cuda.synchronize()
+        t1 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        ts.append((time.perf_counter() - t1) * 1e3)
+    return sorted(ts)[n // 2]
+
+
+def run_grid_resize(B=4, sg=8, sv=64, C=320):
+    """One grid_resize forward + backward (the gatedSA2 residual of the 64 x 64 level) next to F.interpolate(mode="bicubic") forward +
+    backward on the device for the same tensor (NCHW there: torch's layout)."""
+    eng = Engine(0, arena_gb=1.0)
+    dev = eng.device
+    gen = torch.Generator().manual_seed(11)
+    t = torch.randn(B, sg * sg, C, generator=gen).to(dev)
+    g = torch.randn(B, sv * sv, C, generator=gen).to(dev)
+    x = t.permute(0, 2, 1).reshape(B, C, sg, sg).contiguous().requires_grad_(True)
+    gy = g.permute(0, 2, 1).reshape(B, C, sv, sv).contiguous()
+
+    def ours():
+        eng.op_grid_resize(t, sg, sv)
+        eng.op_grid_resize_backward(g, sg, sv)
+
+    def torchs():
+        x.grad = None
+        torch.nn.functional.interpolate(x, (sv, sv), mode="bicubic").backward(gy)
+
+    ours(); torchs()
+    print(json.dumps(dict(config="grid resize forward + backward", B=B, sg=sg, sv=sv, C=C, grid_resize_ms=round(median_ms(ours), 4),
+                          torch_interpolate_ms=round(median_ms(torchs), 4), timing="host wall time around one synchronised forward + backward, median of 20")), flush=True)
+    eng.close()
+
+
 if __name__ == "__main__":
+    fuser = sys.argv[sys.argv.index("--fuser") + 1] if "--fuser" in sys.argv else "gatedSA"
+    if fuser not in ("gatedSA", "gatedSA2", "gatedCA"):
+        raise SystemExit("--fuser gatedSA2 | gatedCA")
+    if fuser == "gatedCA" and "--spatial" in sys.argv:
+        raise SystemExit("--fuser gatedCA: with the text tokenizer")
+    if fuser != "gatedSA" and "--spatial" not in sys.argv:
+        full = "--full64" in sys.argv
+        shape = (4, 64, 1) if full else (1, 16, 2)
+        run("shipped topology", syn.UNET_CFG, *shape, Engine(0, arena_gb=1.0), checkpoint=True)     # the gatedSA text model's line, same box
+        run("shipped topology", dict(syn.UNET_CFG, fuser_type=fuser), *shape, Engine(0, arena_gb=1.0), checkpoint=True, max_objs=16 if fuser == "gatedSA2" else 30)
+        if fuser == "gatedSA2":
+            run_grid_resize()
+        sys.exit(0)
     if "--inpaint" in sys.argv:
         full = "--full64" in sys.argv
         run("shipped topology", syn.UNET_CFG, 4 if full else 1, 64 if full else 16, 1 if full else 2, Engine(0, arena_gb=1.0), checkpoint=True)     # the text model's line, same box
@@ -158,9 +204,11 @@ if __name__ == "__main__":
         modality = sys.argv[sys.argv.index("--spatial") + 1]
         if "--full64" in sys.argv:
             run("shipped topology", syn.UNET_CFG, 4, 64, 1, Engine(0, arena_gb=1.0), checkpoint=True)     # the text model's line, same box
-            run_spatial(modality, 4, 64, 1, class_maps="--class-maps" in sys.argv)
+            run_spatial(modality, 4, 64, 1, class_maps="--class-maps" in sys.argv, fuser=fuser)
         else:
-            run_spatial(modality, 1, 16, 2, class_maps="--class-maps" in sys.argv)
+            run_spatial(modality, 1, 16, 2, class_maps="--class-maps" in sys.argv, fuser=fuser)
+        if fuser == "gatedSA2":
+            run_grid_resize()
         sys.exit(0)
     eng = Engine(0, arena_gb=160.0)
     if "--b4only" in sys.argv:          # the profiled line (tools/gpu_run.sh train with TRAIN_PROF=1): the bench line's train_step shape
