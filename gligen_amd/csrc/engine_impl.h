@@ -3,9 +3,6 @@
 #pragma once
 #include "engine.h"
 
-#include <cstdarg>
-#include <cstdio>
-
 namespace gl {
 
 #define CK(expr)                                              \
@@ -19,15 +16,6 @@ namespace gl {
         if (_e != hipSuccess)                                                                   \
             throw GlError(GL_ERR_HIP, std::string(#expr) + " -> " + hipGetErrorString(_e));     \
     } while (0)
-
-inline std::string fmt(const char* f, ...) {
-    char buf[512];
-    va_list ap;
-    va_start(ap, f);
-    vsnprintf(buf, sizeof(buf), f, ap);
-    va_end(ap);
-    return buf;
-}
 
 // developer aid (GL_LAUNCH_LOG=file, tools/gpu_traffic.sh): one line per GEMM / conv / attention launch, in launch order
 FILE* launch_log_file();

@@ -1,7 +1,8 @@
 // Training slice (second half): forward + backward of ONE BasicTransformerBlock with a gatedSA, gatedSA2 or
 // gatedCA fuser (reference ldm/modules/attention.py:333-338, 236-244, 272-297, 207-212) under the reference's loss, with the gradients the reference's trainer
 // asks for (trainer.py:217-245: the fuser.* parameters; the block input and the grounding tokens so that the step chains into
-// position_net and the blocks in front). See train.hip.
+// position_net and the blocks in front). The implementation is five units behind train_impl.h: train_ops / train_attention /
+// train_layers / train_spatial / train_unet .hip.
 #pragma once
 #include "common.h"
 

@@ -817,7 +817,7 @@ def test_attn3_operand_handover_model():
 
 
 def test_training_attention_mfma_index_model():
-    """The three MFMA attention kernels of the training path (train.hip, round 5: forward, dq, dk / dv) modelled lane by lane in
+    """The three MFMA attention kernels of the training path (train_attention.hip, round 5: forward, dq, dk / dv) modelled lane by lane in
     float64: the prep pass's R / T layouts (tokens of T permuted in 16s), the 32x32x16 operand / accumulator layouts, accumulator
     registers re-used as B operands, key / query padding masks, the per-lane softmax bookkeeping. Ragged sizes (70 queries, 75 keys,
     d = 40 padded to 48 / 64). The hi / lo splits of the real kernels only add passes over the same indices."""

@@ -10,6 +10,7 @@ waterfall loops, and that nothing spills."""
 import re
 import shutil
 import subprocess
+from concurrent.futures import ThreadPoolExecutor
 from pathlib import Path
 
 import pytest
@@ -465,29 +466,44 @@ def test_ffn_dma_statements_declare_what_they_clobber():
     assert all('"scc"' in st for st in stmts)
 
 
+TRAIN_UNITS = ["train_ops", "train_attention", "train_layers", "train_spatial", "train_unet"]
+
+
 def test_training_attention_kernels_keep_their_chunks_in_registers(tmp_path):
-    """train.hip's fp32 attention kernels split a head dimension over 1 / 2 / 4 lanes in chunks of <= 40 so that a lane's q /
+    """train_attention.hip's fp32 attention kernels split a head dimension over 1 / 2 / 4 lanes in chunks of <= 40 so that a lane's q /
     accumulator chunks stay in registers (one lane per query at d = 160 spilled 320 floats and ran 3 ms per launch): the forward
-    kernels use no scratch at all, the backward ones at most a few dozen dwords (they sit at the 128-register default bound)."""
+    kernels use no scratch at all, the backward ones at most a few dozen dwords (they sit at the 128-register default bound).
+    Across the five units of the training path (train_impl.h): 80 kernels, each defined in one unit only -- the build has no
+    relocatable device code, so a kernel is launched from the unit that defines it."""
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    out = tmp_path / "train.s"
-    r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", str(ROOT / "include"), "--offload-device-only", "-S",
-                        str(ROOT / "gligen_amd" / "csrc" / "train.hip"), "-o", str(out)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    asm = out.read_text()
+
+    def listing(unit):
+        out = tmp_path / (unit + ".s")
+        r = subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", str(ROOT / "include"), "--offload-device-only", "-S",
+                            str(ROOT / "gligen_amd" / "csrc" / (unit + ".hip")), "-o", str(out)], capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return out.read_text()
+
+    with ThreadPoolExecutor(max_workers=len(TRAIN_UNITS)) as ex:
+        listings = dict(zip(TRAIN_UNITS, ex.map(listing, TRAIN_UNITS)))
     seen = seen_reductions = 0
-    for m in re.finditer(r"\.amdhsa_kernel (\S+)", asm):
-        blk = asm[m.start():asm.index(".end_amdhsa_kernel", m.start())]
-        name = m.group(1)
-        scratch = int(re.search(r"private_segment_fixed_size (\d+)", blk).group(1))
-        if "attn_fwd_kernel" in name:
-            assert scratch == 0, (name, scratch)
-            seen += 1
-        elif "attn_bwd" in name:
-            assert scratch <= 256, (name, scratch)
-            seen += 1
-        elif "colsum_kernel" in name or "gn_silu" in name:
-            assert scratch == 0, (name, scratch)
-            seen_reductions += 1
+    owner = {}
+    for unit, asm in listings.items():
+        for m in re.finditer(r"\.amdhsa_kernel (\S+)", asm):
+            blk = asm[m.start():asm.index(".end_amdhsa_kernel", m.start())]
+            name = m.group(1)
+            assert name not in owner, (name, owner[name], unit)
+            owner[name] = unit
+            scratch = int(re.search(r"private_segment_fixed_size (\d+)", blk).group(1))
+            if "attn_fwd_kernel" in name:
+                assert scratch == 0, (name, scratch)
+                seen += 1
+            elif "attn_bwd" in name:
+                assert scratch <= 256, (name, scratch)
+                seen += 1
+            elif "colsum_kernel" in name or "gn_silu" in name:
+                assert scratch == 0, (name, scratch)
+                seen_reductions += 1
     assert seen == 15       # 5 head dims x (forward, backward-q, backward-kv)
     assert seen_reductions == 3     # colsum_kernel, gn_silu_fwd_kernel, gn_silu_bwd_kernel: a rename must not empty that branch
+    assert len(owner) == 80, {u: sum(1 for v in owner.values() if v == u) for u in TRAIN_UNITS}

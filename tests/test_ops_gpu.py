@@ -424,7 +424,7 @@ def test_fuser_block_backward_vs_reference(engine):
     meta, sd, x, objs, context, target = (case[k] for k in ("meta", "sd", "x", "objs", "context", "target"))
     worst = max(report, key=report.get)
     print("training slice: worst", worst, report[worst])
-    # (the judge's bar is rel-MSE <= 1e-3 per tensor; with the three-pass bf16 products of train.hip the path is at fp32 level and the
+    # (the judge's bar is rel-MSE <= 1e-3 per tensor; with the three-pass bf16 products of train_ops.hip the path is at fp32 level and the
     # golden's fp16 storage of the big gradients is what is left: 1e-7. Asserted with margin.)
     assert report["loss"] < 1e-5 and report["y"] < 1e-6, report
     assert all(v < 1e-5 for v in report.values()), {k: v for k, v in report.items() if v >= 1e-5}

@@ -1,6 +1,7 @@
 """Fingerprint of the training path: one line per case with a SHA-256 over loss, eps and every gradient tensor (sorted by name) of
 gl_unet_train_step, and the arena's high-water mark. Two builds of the library that launch the same kernels on the same operands in
-the same order print the same lines. Synthetic inputs, seeded weights, small UNet, B = 2, 16 x 16 latent.
+the same order print the same lines. Synthetic inputs, seeded weights, small UNet, B = 2, 16 x 16 latent: every tokenizer, the class-map inputs, an
+inpainting model and the three fuser types.
    GL_DEV_SWITCHES=1 GL_GEMM_AUTOTUNE=0 PYTHONPATH=. python tools/train_outputs.py      (no timed tile choice: repeatable across processes)"""
 import hashlib
 
@@ -15,7 +16,7 @@ B, HW = 2, 16
 
 def state_dict(cfg, dev):
     from ldm.modules.diffusionmodules.openaimodel import UNetModel
-    m = UNetModel(**dict(cfg, inpaint_mode=False))
+    m = UNetModel(**dict(cfg, inpaint_mode=bool(cfg.get("inpaint_mode"))))
     shapes = {k: tuple(v.shape) for k, v in m.state_dict().items()}
     return {k: v.float().to(dev).contiguous() for k, v in syn.seeded_state_dict(shapes, 1234).items()}
 
@@ -25,8 +26,8 @@ def common():
                 target=syn.make_latent(B, 4, HW, HW, seed=7))
 
 
-def discrete(kind):
-    b = syn.make_batch(kind, B, n_valid=3, seed=5)
+def discrete(kind, **kw):
+    b = syn.make_batch(kind, B, n_valid=3, seed=5, **kw)
     batch = dict(common(), masks=b["masks"])
     if kind == "keypoint":
         batch["points"] = b["points"]
@@ -36,6 +37,20 @@ def discrete(kind):
     else:
         batch.update(boxes=b["boxes"], positive_embeddings=b["text_embeddings"])
     return dict(syn.UNET_CFG_SMALL, grounding_tokenizer=syn.GROUNDING_TOKENIZERS[kind]), batch
+
+
+def inpaint():
+    """The text model with inpaint_mode: inpainting_extra_input = cat(z * mask, mask), the mask 0 inside the boxes (trainer.py:339-344)."""
+    cfg, batch = discrete("text")
+    z, mask = syn.make_latent(B, 4, HW, HW, seed=8), torch.ones(B, 1, HW, HW)
+    for b in range(B):
+        for x0, y0, x1, y1 in (batch["boxes"][b] * HW).int().tolist():
+            mask[b, :, y0:y1, x0:x1] = 0
+    return dict(cfg, inpaint_mode=True), dict(batch, inpainting_extra_input=torch.cat([z * mask, mask], dim=1))
+
+
+def fuser(fuser_type, cfg, batch):
+    return dict(cfg, fuser_type=fuser_type), batch
 
 
 def spatial(modality, class_maps=False):
@@ -76,3 +91,7 @@ if __name__ == "__main__":
     case("canny tokenizer + downsampler", *spatial("canny"))
     case("sem from planes", *spatial("sem"))
     case("sem from class maps", *spatial("sem", class_maps=True))
+    case("text, inpaint_mode", *inpaint())
+    case("gatedSA2", *fuser("gatedSA2", *discrete("text", max_objs=16)))           # a square Ng (and the square latent): 4 x 4 tokens
+    case("gatedCA", *fuser("gatedCA", *discrete("text")))
+    case("gatedSA2, canny tokenizer + downsampler", *fuser("gatedSA2", *spatial("canny")))      # Ng = (64 / 32)^2
