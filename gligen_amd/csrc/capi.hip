@@ -7,6 +7,7 @@
 #include "../../include/gligen_amd_train_maps.h"
 #include "../../include/gligen_amd_train_inputs.h"
 #include "../../include/gligen_amd_train_fusers.h"
+#include "../../include/gligen_amd_trainer.h"
 
 #include <cstdlib>
 
@@ -696,6 +697,16 @@ int gl_op_adamw_step(gl_ctx* ctx, float* p, const float* g, float* m, float* v, 
     NEED(ctx);
     if (!p || !g || !m || !v || n < 0) return gl::set_error(GL_ERR_ARG, "gl_op_adamw_step: null pointer");
     return gl::adamw_step(p, g, m, v, (size_t)n, lr, beta1, beta2, eps, weight_decay, step, S(s));
+}
+
+int gl_op_adamw_ema_step(gl_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, int64_t n, double lr, double beta1, double beta2,
+                         double eps, double weight_decay, double ema_rate, int step, gl_stream s) {
+    NEED(ctx);
+    if (!p || !g || !m || !v || !ema) return gl::set_error(GL_ERR_ARG, "gl_op_adamw_ema_step: null pointer");
+    if (n < 0) return gl::set_error(GL_ERR_ARG, "gl_op_adamw_ema_step: n = %lld is negative", (long long)n);
+    if (step < 1) return gl::set_error(GL_ERR_ARG, "gl_op_adamw_ema_step: step = %d, steps count from 1", step);
+    if (!(ema_rate >= 0.0 && ema_rate <= 1.0)) return gl::set_error(GL_ERR_ARG, "gl_op_adamw_ema_step: ema_rate %g is outside [0, 1]", ema_rate);
+    return gl::adamw_ema_step(p, g, m, v, ema, (size_t)n, lr, beta1, beta2, eps, weight_decay, ema_rate, step, S(s));
 }
 
 static const char* const k_train_block_names[GL_TRAIN_BLOCK_PARAMS] = {

@@ -134,5 +134,8 @@ int train_step_inputs_launch(const TrainStepInputs& a, hipStream_t s);
 
 // One AdamW update of a flat fp32 parameter range, in place (torch.optim.AdamW semantics: trainer.py:245, :384 opt.step()); step = 1, 2, ...
 int adamw_step(float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps, double wd, int step, hipStream_t s);
+// The same update (the same bits for p, m, v) and ema = ema_rate * ema + (1 - ema_rate) * p_new in one pass (train_optim.hip; trainer.py:121-123, 388-391)
+int adamw_ema_step(float* p, const float* g, float* m, float* v, float* ema, size_t n, double lr, double b1, double b2, double eps, double wd, double ema_rate,
+                   int step, hipStream_t s);
 
 }  // namespace gl

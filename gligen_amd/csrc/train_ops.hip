@@ -8,6 +8,7 @@
 // everything else is fp32, as the reference trains in fp32). Every reduction is a fixed-order sum: no float atomics.
 #include "train_impl.h"
 
+#include "adamw_update.h"
 #include "gemm.h"
 #include "misc.h"
 
@@ -262,17 +263,16 @@ __global__ void mse_grad_kernel(const float* __restrict__ y, const float* __rest
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v, size_t n, float lr,
                              float b1, float omb1, float b2, float omb2, float eps, float decay, float step_size, float bc2_sqrt) {
     // torch.optim.AdamW (_single_tensor_adamw): every scalar below is formed in double on the host, as torch forms them from Python
-    // floats, and rounded to fp32 once: decay = 1 - lr wd, omb = 1 - beta, step_size = lr / (1 - beta1^t), bc2_sqrt = sqrt(1 - beta2^t)
+    // floats, and rounded to fp32 once (adamw_update.h: adamw_scalars); the update itself is adamw_update, which train_optim.hip's
+    // fused AdamW + EMA kernel shares
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= n) return;
     (void)lr;
-    const float gi = g[i];
-    const float mi = b1 * m[i] + omb1 * gi;
-    const float vi = b2 * v[i] + omb2 * gi * gi;
+    float pi = p[i], mi = m[i], vi = v[i];
+    adamw_update(pi, g[i], mi, vi, b1, omb1, b2, omb2, eps, decay, step_size, bc2_sqrt);
     m[i] = mi;
     v[i] = vi;
-    const float denom = sqrtf(vi) / bc2_sqrt + eps;
-    p[i] = p[i] * decay - step_size * (mi / denom);
+    p[i] = pi;
 }
 
 // ---- ResBlock pieces (openaimodel.py:154-232): GroupNorm32 + SiLU over pixel rows [B][HW][C] (fp32), and their backward.
@@ -647,9 +647,9 @@ float* conv3x3_direct(const Ctx& c, const float* x, const float* w, const float*
 
 int adamw_step(float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps, double wd, int step, hipStream_t s) {
     if (step < 1) return set_error(GL_ERR_ARG, "adamw_step: step counts from 1");
-    const double bc1 = 1.0 - pow(b1, (double)step), bc2 = 1.0 - pow(b2, (double)step);
-    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, n, (float)lr, (float)b1, (float)(1.0 - b1), (float)b2,
-                       (float)(1.0 - b2), (float)eps, (float)(1.0 - lr * wd), (float)(lr / bc1), (float)sqrt(bc2));
+    const AdamwScalars k = adamw_scalars(lr, b1, b2, eps, wd, step);
+    hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, p, g, m, v, n, (float)lr, k.b1, k.omb1, k.b2, k.omb2, k.eps, k.decay,
+                       k.step_size, k.bc2_sqrt);
     GL_LAUNCH_CHECK();
     return GL_OK;
 }

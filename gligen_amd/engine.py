@@ -690,6 +690,35 @@ class Engine:
         check(self.lib.gl_op_adamw_step(self._ctx, _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(lr), float(betas[0]), float(betas[1]),
                                         float(eps), float(weight_decay), int(step), _stream(self.device)))
 
+    ADAMW_EMA_GRID = (16384, 256, 4)     # adamw_ema_kernel's grid cap, block size and elements per lane (train_optim.hip)
+
+    def op_adamw_ema_step(self, p, g, m, v, ema, step, *, ema_rate, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        """op_adamw_step's update of p, m, v (the same bits) and ema = ema_rate * ema + (1 - ema_rate) * p_new in the same pass
+        (gl_op_adamw_ema_step; trainer.py:388-391: opt.step(), then update_ema). Flat fp32 tensors of one length; views at any 4-byte
+        offset are taken (the kernel's scalar path)."""
+        for t in (p, g, m, v, ema):
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == p.numel()
+        check(self.lib.gl_op_adamw_ema_step(self._ctx, _ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), p.numel(), float(lr), float(betas[0]), float(betas[1]),
+                                            float(eps), float(weight_decay), float(ema_rate), int(step), _stream(self.device)))
+
+    @staticmethod
+    def count_spatial_transformers(cfg: Mapping) -> int:
+        """The number of SpatialTransformers of a UNetModel config, walked as gl_unet_train_step numbers them (openaimodel.py:307-383):
+        one behind every ResBlock of the input and output paths whose level's downsampling rate is in attention_resolutions, and the
+        middle block's. 16 for the shipped topology."""
+        levels, nres, attn = len(cfg["channel_mult"]), int(cfg["num_res_blocks"]), {int(a) for a in cfg["attention_resolutions"]}
+        n, ds = 0, 1
+        for level in range(levels):
+            n += nres * (ds in attn)
+            if level != levels - 1:
+                ds *= 2
+        n += 1
+        for level in reversed(range(levels)):
+            n += (nres + 1) * (ds in attn)
+            if level:
+                ds //= 2
+        return n
+
     def train_weight_cache(self, enable: bool = True) -> int:
         """Keep the bf16 operand copies of the frozen parameters across unet_train_step calls (gl_train_weight_cache); returns the bytes
         held. Only for callers that change nothing but the parameters they ask gradients for (TrainStep does); enable=False frees them."""

@@ -14,7 +14,10 @@ state_dict has no fuser.linear.*); the batch dict carries
 boxes + masks + positive_embeddings (text), + text_embeddings / image_embeddings / text_masks / image_masks (text+image), points + masks
 (keypoint), or the map under the reference's key (canny_edge, hed_edge, depth, normal, sem) + mask + grounding_extra_input.
 An inpainting model (cfg["inpaint_mode"], discrete tokenizers; trainer.py:189-194, 339-344) trains its 9-channel first conv's weight
-as well; its batch carries inpainting_extra_input [B, 5, H, W] next to x, or x_rows / target_rows from Engine.train_step_inputs."""
+as well; its batch carries inpainting_extra_input [B, 5, H, W] next to x, or x_rows / target_rows from Engine.train_step_inputs.
+With ema_rate the update is gl_op_adamw_ema_step: AdamW and the reference's EMA of the parameters (trainer.py:121-123, 390-391) in one
+launch per bucket. The optimizer state travels in torch.optim.AdamW's own layout (torch_optimizer_state_dict), so a checkpoint crosses
+to the reference's trainer and back; the loop, the checkpoint files and resuming are gligen_amd.trainer.Trainer."""
 from __future__ import annotations
 
 import math
@@ -138,12 +141,20 @@ class TrainStep:
     the trainable set and of the last bucket. The guidance drop leaves all three alone.
 
     The fuser type comes from cfg["fuser_type"] (Engine.unet_train_step): a gatedSA2 model has gatedSA's keys and buckets, a gatedCA model
-    has no fuser.linear.* and its fuser.attn.to_k / to_v are [C, context_dim]; the trainable set is name-based and covers both."""
+    has no fuser.linear.* and its fuser.attn.to_k / to_v are [C, context_dim]; the trainable set is name-based and covers both.
+
+    ema_rate (None: no average, the calls and buffers above and nothing else): the reference's EMA of the model (trainer.py:121-123,
+    251-256, 390-391; --enable_ema, --ema_rate). One more flat buffer set `self.ema` in the bucket layout, initialised to the
+    parameters (deepcopy(self.model)); every bucket update is then Engine.op_adamw_ema_step, AdamW and the average of the updated
+    parameters in one pass on the stream the update ran on before: the same parameter bits, and the same EMA bits from both schedules.
+
+    state_dict should be in module order (what UNetModel.state_dict() gives): the order of its trainable names is the parameter
+    numbering of torch_optimizer_state_dict."""
 
     def __init__(self, engine, cfg: Mapping, state_dict: Mapping[str, torch.Tensor], lr: Union[float, Callable[[int], float]] = 5e-5,
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, bucket_mb: float = 128.0, world: Optional[int] = None,
                  checkpoint: bool = True, drop_prob: float = 0.0, rng: Optional[random.Random] = None, broadcast: bool = True, overlap: bool = True,
-                 cache_frozen: bool = True, exchange_even_alone: bool = False):
+                 cache_frozen: bool = True, exchange_even_alone: bool = False, ema_rate: Optional[float] = None):
         self.engine, self.cfg = engine, dict(cfg)
         # (a world of one rank issues no collective; True sends the buckets through the collectives anyway -- the one-GPU test of the
         # overlapped schedule with RCCL's kernels on the communication stream, tests/test_ops_gpu.py)
@@ -154,6 +165,7 @@ class TrainStep:
         self.drop_prob, self.rng = float(drop_prob), rng or random.Random()
         self.checkpoint = bool(checkpoint)       # activation checkpointing per block (the reference: use_checkpoint=True in every shipped config)
         names = trainable_names(state_dict, self.cfg)
+        self.param_order = list(names)      # torch.optim.AdamW's parameter numbering: the reference's named_parameters() order
         self.milestone = gradient_milestones(names)
         n_blocks = max(self.milestone.values(), default=0)
         # the engine numbers SpatialTransformers by walking the config; both counts must agree or bucket_ready waits on the wrong events
@@ -179,6 +191,10 @@ class TrainStep:
         if broadcast and tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
             for b in self.pbuf.buckets:            # the views alias the buckets: one collective per bucket moves every trainable tensor
                 tdist.broadcast(b, src=0)
+        if ema_rate is not None and not 0.0 <= float(ema_rate) <= 1.0:
+            raise ValueError(f"TrainStep: ema_rate {ema_rate!r} is outside [0, 1]")
+        self.ema_rate = None if ema_rate is None else float(ema_rate)
+        self.ema = None if ema_rate is None else [b.clone() for b in self.pbuf.buckets]       # (after the broadcast: deepcopy(self.model))
         # a bucket may go out once the LAST of its gradients is written: its lowest block number -- or the end of the backward
         self.bucket_ready = []
         for items in self.gbuf.layout:
@@ -205,8 +221,12 @@ class TrainStep:
         loss, eps, _ = self.engine.unet_train_step(self.cfg, self.params, batch, fuser_scale=fuser_scale, grads=self.gbuf.views, checkpoint=self.checkpoint, **kw)
         self.steps += 1
         lr = self.lr_at(self.steps)
-        upd = lambda i: self.engine.op_adamw_step(self.pbuf.buckets[i], self.gbuf.buckets[i], self.m[i], self.v[i], self.steps, lr=lr, betas=self.betas,
-                                                  eps=self.eps, weight_decay=self.wd)
+        if self.ema is None:
+            upd = lambda i: self.engine.op_adamw_step(self.pbuf.buckets[i], self.gbuf.buckets[i], self.m[i], self.v[i], self.steps, lr=lr, betas=self.betas,
+                                                      eps=self.eps, weight_decay=self.wd)
+        else:       # AdamW and the EMA of the updated parameters in one pass over the bucket
+            upd = lambda i: self.engine.op_adamw_ema_step(self.pbuf.buckets[i], self.gbuf.buckets[i], self.m[i], self.v[i], self.ema[i], self.steps,
+                                                          ema_rate=self.ema_rate, lr=lr, betas=self.betas, eps=self.eps, weight_decay=self.wd)
         nb = len(self.gbuf.buckets)
         alone = self.exchange_even_alone
         if not self.overlap:                        # backward, every collective, every update: one stream
@@ -248,6 +268,90 @@ class TrainStep:
                 mb[off:off + n].view(shape).copy_(state["exp_avg"][name])
                 vb[off:off + n].view(shape).copy_(state["exp_avg_sq"][name])
         self.steps = int(state["steps"])
+
+    def _slices(self, bufs):
+        """name -> the view of `bufs` (a buffer set in the bucket layout) that belongs to that trainable tensor."""
+        return {name: b[off:off + n].view(shape) for items, b in zip(self.pbuf.layout, bufs) for name, off, n, shape in items}
+
+    def ema_state_dict(self) -> Dict[str, torch.Tensor]:
+        """The reference's ckpt["ema"] (trainer.py:481-482): a full state_dict in the order of the parameters; the trainable tensors
+        come from the EMA buffers. Deviation from the reference: it averages the frozen tensors too, which never change, so their
+        average is themselves up to the rounding jitter of rate * x + (1 - rate) * x; here the frozen tensors ARE the parameters."""
+        if self.ema is None:
+            raise ValueError("ema_state_dict: this TrainStep keeps no EMA (ema_rate=None)")
+        ema = self._slices(self.ema)
+        return {k: (ema[k] if k in ema else v).clone() for k, v in self.params.items()}
+
+    def load_ema_state_dict(self, state_dict: Mapping[str, torch.Tensor]) -> None:
+        """The inverse of ema_state_dict: the trainable tensors of `state_dict` into the EMA buffers (the frozen ones are not kept)."""
+        if self.ema is None:
+            raise ValueError("load_ema_state_dict: this TrainStep keeps no EMA (ema_rate=None)")
+        for k, view in self._slices(self.ema).items():
+            if k not in state_dict:
+                raise ValueError(f"load_ema_state_dict: '{k}' is missing")
+            if tuple(state_dict[k].shape) != tuple(view.shape):
+                raise ValueError(f"load_ema_state_dict: '{k}' is {tuple(state_dict[k].shape)}, the model's is {tuple(view.shape)}")
+            view.copy_(state_dict[k].to(device=view.device, dtype=torch.float32))
+
+    def torch_optimizer_state_dict(self, initial_lr: Optional[float] = None) -> Dict[str, object]:
+        """The optimizer in the layout of torch.optim.AdamW.state_dict(), the reference's ckpt["opt"] (trainer.py:245, 476):
+        state[i] = {step, exp_avg, exp_avg_sq} (CPU tensors) and one param group with params = [0 .. n-1], where i numbers the
+        trainable tensors in the order of the state_dict this step was built from (the reference's named_parameters() order). The
+        keys and the type of `step` are read off a real torch.optim.AdamW over stand-in tensors, so they follow the installed
+        torch. lr is the rate of the NEXT step (what a LambdaLR has left in the group after its scheduler.step()); initial_lr, when
+        given, is added as the schedulers do. Before the first step `state` is empty, as torch's is."""
+        n = len(self.param_order)
+        stand = [torch.nn.Parameter(torch.zeros(1)) for _ in range(n)]
+        opt = torch.optim.AdamW(stand, lr=self.lr_at(self.steps + 1), betas=self.betas, eps=self.eps, weight_decay=self.wd)
+        if self.steps > 0:
+            for q in stand:
+                q.grad = torch.zeros(1)
+            opt.step()          # materialises every state entry with this torch's keys
+        out = opt.state_dict()
+        m, v = self._slices(self.m), self._slices(self.v)
+        for i, name in enumerate(self.param_order):
+            st = out["state"].get(i)
+            if st is None:
+                continue
+            extra = set(st) - {"step", "exp_avg", "exp_avg_sq"}
+            if extra:
+                raise RuntimeError(f"torch_optimizer_state_dict: this torch's AdamW keeps {sorted(extra)}, which the step does not have")
+            st["step"] = torch.full_like(st["step"], self.steps) if torch.is_tensor(st["step"]) else int(self.steps)
+            st["exp_avg"], st["exp_avg_sq"] = m[name].detach().cpu().clone(), v[name].detach().cpu().clone()
+        if initial_lr is not None:
+            out["param_groups"][0]["initial_lr"] = float(initial_lr)
+        return out
+
+    def load_torch_optimizer_state_dict(self, state: Mapping[str, object]) -> None:
+        """The inverse: what torch.optim.AdamW.state_dict() of the reference's trainer, or torch_optimizer_state_dict, holds. As
+        torch's load_state_dict does, the group's betas / eps / weight_decay replace this step's, and its lr when this step's rate is
+        a constant (a schedule stays: `steps` positions it). A count or shape mismatch is a ValueError that names the tensor."""
+        groups = state["param_groups"]
+        ids = [i for g in groups for i in g["params"]]
+        n = len(self.param_order)
+        if len(ids) != n:
+            odd = self.param_order[len(ids)] if len(ids) < n else f"parameter {n} of the saved optimizer"
+            raise ValueError(f"load_torch_optimizer_state_dict: {len(ids)} parameters saved, {n} trainable tensors here (first without a partner: {odd})")
+        saved = state["state"]
+        m, v = self._slices(self.m), self._slices(self.v)
+        steps = set()
+        for name, i in zip(self.param_order, ids):
+            st = saved.get(i)
+            if st is None:          # torch keeps no entry for a parameter that never had a gradient
+                m[name].zero_(); v[name].zero_()
+                continue
+            for key, dst in (("exp_avg", m[name]), ("exp_avg_sq", v[name])):
+                if tuple(st[key].shape) != tuple(dst.shape):
+                    raise ValueError(f"load_torch_optimizer_state_dict: {key} of parameter {i} is {tuple(st[key].shape)}, '{name}' is {tuple(dst.shape)}")
+                dst.copy_(st[key].to(device=dst.device, dtype=torch.float32))
+            steps.add(int(float(st["step"])))
+        if len(steps) > 1:
+            raise ValueError(f"load_torch_optimizer_state_dict: the parameters are at different steps {sorted(steps)}; this step keeps one count")
+        self.steps = steps.pop() if steps else 0
+        g0 = groups[0]
+        self.betas, self.eps, self.wd = tuple(float(b) for b in g0["betas"]), float(g0["eps"]), float(g0["weight_decay"])
+        if not callable(self.lr):
+            self.lr = float(g0["lr"])
 
     def load_state_dict(self, state_dict: Mapping[str, torch.Tensor]) -> None:
         """Parameters back into the flat buffers (trainable) / the frozen set, in place: the views the engine reads stay the same."""

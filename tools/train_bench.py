@@ -11,8 +11,12 @@ permutes), medians of 20.
 --full64: B = 4, 64 x 64 latent, checkpoint=True; else B = 1, 16 x 16): gatedCA with the text tokenizer (30 slots); gatedSA2 with
 --spatial canny (resize 256: an 8 x 8 token grid) or with the text tokenizer and 16 box slots (a 4 x 4 grid). gatedSA2 also prints one
 grid_resize forward + backward (8 -> 64, C 320, B 4) next to torch's F.interpolate forward + backward on the device, medians of 20.
+--ema: whole TrainStep iterations (forward, loss, backward, AdamW over the buckets) of the shipped text model, B = 4, 64 x 64 latent,
+checkpoint=True, in three settings run in alternation on one box: no EMA, the EMA fused into the optimizer launch
+(gl_op_adamw_ema_step), and the EMA as the two torch ops per bucket (mul_, add_: the reference's update_ema) behind gl_op_adamw_step
+on the communication stream; then the two optimizer kernels alone on the largest bucket (HIP events, median of 20, bytes / time).
    PYTHONPATH=. python tools/train_bench.py [--full64] [--spatial {canny,depth,normal,hed,sem} [--class-maps] | --inpaint]
-                                            [--fuser {gatedSA2,gatedCA}]"""
+                                            [--fuser {gatedSA2,gatedCA}] | --ema"""
 import json
 import sys
 import time
@@ -145,6 +149,76 @@ def run_inpaint(B, hw, reps, checkpoint=True):
     eng.close()
 
 
+def run_ema(B=4, hw=64, reps=5, rate=0.9999):
+    """One TrainStep, switched between the three settings from iteration to iteration: the same parameters, buckets and cached
+    operand copies under all of them."""
+    from gligen_amd.train import TrainStep
+    from gligen_amd.trainer import synthetic_state_dict
+    cfg = dict(syn.UNET_CFG, grounding_tokenizer=syn.GROUNDING_TOKENIZERS["text"], inpaint_mode=False)
+    eng = Engine(0, arena_gb=24.0)
+    dev = eng.device
+    ts = TrainStep(eng, cfg, synthetic_state_dict(cfg), lr=5e-5, weight_decay=0.0, world=1, checkpoint=True, ema_rate=rate)
+    b = syn.make_batch("text", B, n_valid=3, seed=5)
+    batch = {k: v.to(dev) for k, v in dict(x=syn.make_latent(B, 4, hw, hw, seed=6), timesteps=torch.tensor([981, 441, 300, 77][:B]).float(),
+                                           context=syn.make_context(B, seed=6), boxes=b["boxes"], masks=b["masks"], positive_embeddings=b["text_embeddings"],
+                                           target=syn.make_latent(B, 4, hw, hw, seed=7)).items()}
+    bufs = ts.ema
+    ema_of = {p.data_ptr(): e for p, e in zip(ts.pbuf.buckets, bufs)}
+    plain_step = eng.op_adamw_step
+
+    def adamw_then_torch_ema(p, g, m, v, step, **kw):        # update_ema (trainer.py:121-123) behind the update, on the stream it ran on
+        plain_step(p, g, m, v, step, **kw)
+        ema_of[p.data_ptr()].mul_(rate).add_(p, alpha=1 - rate)
+
+    def setting(name):
+        ts.ema = bufs if name == "fused" else None
+        eng.op_adamw_step = adamw_then_torch_ema if name == "torch_ops" else plain_step
+
+    names = ("off", "fused", "torch_ops")
+    times = {n: [] for n in names}
+    for n in names:                                          # warm-up: GEMM tile selection, the operand cache, the allocator
+        setting(n)
+        ts.step(batch)
+    torch.cuda.synchronize()
+    for _ in range(reps):
+        for n in names:
+            setting(n)
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            loss, _ = ts.step(batch)
+            torch.cuda.synchronize()
+            times[n].append(time.perf_counter() - t0)
+    setting("off")
+    med = {n: sorted(v)[len(v) // 2] for n, v in times.items()}
+    print(json.dumps(dict(config="shipped topology, TrainStep iteration (forward + loss + backward + AdamW), EMA off / fused / two torch ops per bucket", B=B, latent=hw,
+                          checkpoint=True, ema_rate=rate, buckets=len(ts.pbuf.buckets), trainable_values=sum(int(x.numel()) for x in ts.pbuf.buckets),
+                          s_per_iteration={n: round(med[n], 4) for n in names}, s_per_iteration_min={n: round(min(times[n]), 4) for n in names},
+                          timing=f"host wall time around one synchronised iteration, median of {reps}, the three settings in alternation", loss=float(loss))), flush=True)
+    i = max(range(len(ts.pbuf.buckets)), key=lambda k: ts.pbuf.buckets[k].numel())
+    p, g, m, v, e = ts.pbuf.buckets[i], ts.gbuf.buckets[i], ts.m[i], ts.v[i], bufs[i]
+    n = int(p.numel())
+
+    def event_ms(fn, reps=20):
+        out = []
+        for _ in range(reps):
+            a, z = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record(); fn(); z.record()
+            torch.cuda.synchronize()
+            out.append(a.elapsed_time(z))
+        return sorted(out)[reps // 2]
+
+    kw = dict(lr=5e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0)
+    t_fused = event_ms(lambda: eng.op_adamw_ema_step(p, g, m, v, e, 3, ema_rate=rate, **kw))
+    t_adamw = event_ms(lambda: plain_step(p, g, m, v, 3, **kw))
+    t_torch = event_ms(lambda: e.mul_(rate).add_(p, alpha=1 - rate))
+    print(json.dumps(dict(config="optimizer kernels on the largest bucket", elements=n, adamw_ema_us=round(t_fused * 1e3, 1), adamw_ema_GBps=round(36.0 * n / t_fused / 1e6, 1),
+                          adamw_us=round(t_adamw * 1e3, 1), adamw_GBps=round(28.0 * n / t_adamw / 1e6, 1), torch_mul_add_us=round(t_torch * 1e3, 1),
+                          torch_mul_add_GBps=round(20.0 * n / t_torch / 1e6, 1), timing="HIP events around one launch (torch: two), median of 20",
+                          bytes="36 B / 28 B / 20 B per element")), flush=True)
+    eng.train_weight_cache(False)
+    eng.close()
+
+
 def median_ms(fn, n=20):
     ts = []
     for _ in range(n):
@@ -187,6 +261,9 @@ if __name__ == "__main__":
         raise SystemExit("--fuser gatedSA2 | gatedCA")
     if fuser == "gatedCA" and "--spatial" in sys.argv:
         raise SystemExit("--fuser gatedCA: with the text tokenizer")
+    if "--ema" in sys.argv:
+        run_ema()
+        sys.exit(0)
     if fuser != "gatedSA" and "--spatial" not in sys.argv:
         full = "--full64" in sys.argv
         shape = (4, 64, 1) if full else (1, 16, 2)
