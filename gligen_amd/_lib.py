@@ -1,5 +1,5 @@
 """ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
-include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h, include/gligen_amd_train_fusers.h and include/gligen_amd_trainer.h).
+include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h, include/gligen_amd_train_fusers.h, include/gligen_amd_train_prims.h and include/gligen_amd_trainer.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -206,6 +206,17 @@ TRAIN_FUSER_SYMBOLS = {
     "gl_op_grid_resize_backward": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
 }
 
+# every symbol include/gligen_amd_train_prims.h declares (the training path's primitives one by one)
+_F = C.c_float
+TRAIN_PRIM_SYMBOLS = {
+    "gl_op_train_attention": (_I, [_P, _I, _I, _I, _I, _I] + [_P] * 9 + [_P]),
+    "gl_op_train_linear": (_I, [_P, _I, _I, _I] + [_P] * 8 + [_P]),
+    "gl_op_train_layernorm": (_I, [_P, _I, _I, _F, _P, _P, _P, _P, _I] + [_P] * 6 + [_P]),
+    "gl_op_train_groupnorm": (_I, [_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _I] + [_P] * 4 + [_P]),
+    "gl_op_train_geglu": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
+    "gl_op_train_dot": (_I, [_P, C.c_int64, _P, _P, _P, _F, _I, _P, _P]),
+}
+
 # every symbol include/gligen_amd_trainer.h declares (the optimizer unit of a training run: AdamW + EMA in one pass)
 TRAINER_SYMBOLS = {
     "gl_op_adamw_ema_step": (_I, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _I, _P]),
@@ -240,7 +251,8 @@ def load() -> C.CDLL:
     # torch.cuda.is_available() is True) -- seen with build() called before the first `import torch` of the process.
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
-    for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS, **TRAINER_SYMBOLS}.items():
+    for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS, **TRAIN_PRIM_SYMBOLS,
+                              **TRAINER_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

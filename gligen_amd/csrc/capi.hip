@@ -7,6 +7,7 @@
 #include "../../include/gligen_amd_train_maps.h"
 #include "../../include/gligen_amd_train_inputs.h"
 #include "../../include/gligen_amd_train_fusers.h"
+#include "../../include/gligen_amd_train_prims.h"
 #include "../../include/gligen_amd_trainer.h"
 
 #include <cstdlib>
@@ -775,6 +776,66 @@ int gl_op_grid_resize_backward(gl_ctx* ctx, const float* g, int B, int sg, int s
     ++ctx->eng->n_launches;
     GL_API_END
 }
+
+// ---- include/gligen_amd_train_prims.h: the training path's primitives one by one, over the arena and workspace the slices above use
+#define TRAIN_PRIM(call)                                                        \
+    GL_API_BEGIN                                                                \
+    Engine& eng = *ctx->eng;                                                    \
+    eng.arena().reset();                                                        \
+    Arena& ar = eng.arena();                                                    \
+    float* ws = eng.splitk_ws();                                                \
+    const size_t ws_bytes = eng.splitk_ws_bytes();                              \
+    const int rc = (call);                                                      \
+    if (rc != GL_OK) throw GlError(rc, gl::last_error());                       \
+    GL_API_END
+
+int gl_op_train_attention(gl_ctx* ctx, int B, int H, int D, int Nq, int Nk, const float* q, const float* k, const float* v, const float* dout, float* o,
+                          float* lse, float* dq, float* dk, float* dv, gl_stream s) {
+    NEED(ctx);
+    if (!q || !k || !v || !o || !lse) return gl::set_error(GL_ERR_ARG, "gl_op_train_attention: null pointer (q, k, v, o and lse are required)");
+    if (!dk != !dv) return gl::set_error(GL_ERR_ARG, "gl_op_train_attention: dk and dv come together (both NULL: the dq-only call)");
+    if (!dout && (dq || dk)) return gl::set_error(GL_ERR_ARG, "gl_op_train_attention: a gradient was asked for without dout");
+    TRAIN_PRIM(gl::train_prim_attention(ar, ws, ws_bytes, B, H, D, Nq, Nk, q, k, v, dout, o, lse, dq, dk, dv, S(s)))
+}
+
+int gl_op_train_linear(gl_ctx* ctx, int M, int N, int K, const float* x, const float* W, const float* b, const float* dy, float* y, float* dx, float* dW,
+                       float* db, gl_stream s) {
+    NEED(ctx);
+    if (!x || !W) return gl::set_error(GL_ERR_ARG, "gl_op_train_linear: null pointer (x and W are required)");
+    if (!dy && (dx || dW || db)) return gl::set_error(GL_ERR_ARG, "gl_op_train_linear: a gradient was asked for without dy");
+    TRAIN_PRIM(gl::train_prim_linear(ar, ws, ws_bytes, M, N, K, x, W, b, dy, y, dx, dW, db, S(s)))
+}
+
+int gl_op_train_layernorm(gl_ctx* ctx, int R, int C, float eps, const float* x, const float* g, const float* b, const float* dy, int accumulate, float* y,
+                          float* xhat, float* rstd, float* dx, float* dgamma, float* dbeta, gl_stream s) {
+    NEED(ctx);
+    if (!x || !g || !b) return gl::set_error(GL_ERR_ARG, "gl_op_train_layernorm: null pointer (x, g and b are required)");
+    if (!dy && (dx || dgamma || dbeta)) return gl::set_error(GL_ERR_ARG, "gl_op_train_layernorm: a gradient was asked for without dy");
+    TRAIN_PRIM(gl::train_prim_layernorm(ar, ws, ws_bytes, R, C, eps, x, g, b, dy, accumulate, y, xhat, rstd, dx, dgamma, dbeta, S(s)))
+}
+
+int gl_op_train_groupnorm(gl_ctx* ctx, int B, int HW, int C, int silu, float eps, const float* x, const float* g, const float* b, const float* da,
+                          int accumulate, float* a, float* xhat, float* rstd, float* dx, gl_stream s) {
+    NEED(ctx);
+    if (!x || !g || !b) return gl::set_error(GL_ERR_ARG, "gl_op_train_groupnorm: null pointer (x, g and b are required)");
+    if (!da && dx) return gl::set_error(GL_ERR_ARG, "gl_op_train_groupnorm: dx was asked for without da");
+    TRAIN_PRIM(gl::train_prim_groupnorm(ar, ws, ws_bytes, B, HW, C, silu, eps, x, g, b, da, accumulate, a, xhat, rstd, dx, S(s)))
+}
+
+int gl_op_train_geglu(gl_ctx* ctx, int R, int I, const float* u, const float* dh, float* h, float* du, gl_stream s) {
+    NEED(ctx);
+    if (!u) return gl::set_error(GL_ERR_ARG, "gl_op_train_geglu: null pointer (u is required)");
+    if (!dh && du) return gl::set_error(GL_ERR_ARG, "gl_op_train_geglu: du was asked for without dh");
+    TRAIN_PRIM(gl::train_prim_geglu(ar, ws, ws_bytes, R, I, u, dh, h, du, S(s)))
+}
+
+int gl_op_train_dot(gl_ctx* ctx, int64_t n, const float* a, const float* b, const float* alpha, float scale, int mode, float* out, gl_stream s) {
+    NEED(ctx);
+    if (!a || !b || !out || (mode == 0 && !alpha)) return gl::set_error(GL_ERR_ARG, "gl_op_train_dot: null pointer (a, b and out are required; alpha in mode 0)");
+    if (n < 1 || mode < 0 || mode > 1) return gl::set_error(GL_ERR_ARG, "gl_op_train_dot: n = %lld, mode = %d (0 gate gradient, 1 mean squared difference)", (long long)n, mode);
+    TRAIN_PRIM(gl::train_prim_dot(ar, ws, ws_bytes, (size_t)n, a, b, alpha, scale, mode, out, S(s)))
+}
+#undef TRAIN_PRIM
 
 static_assert(GL_TRAIN_ST_PARAMS == gl::ST_COUNT, "parameter table out of step with train.h");
 const char* const* gl_train_st_param_names(void) {

@@ -132,6 +132,21 @@ struct TrainStepInputs {
 };
 int train_step_inputs_launch(const TrainStepInputs& a, hipStream_t s);
 
+// ---- The primitives by themselves (include/gligen_amd_train_prims.h; the argument lists are the entry points'): a Ctx over the arena
+// as the slices above build it -- no weight cache --, the Ctx methods the step is composed of, results copied to the caller on `s`.
+// train_prim_attention is in train_attention.hip, the others in train_ops.hip.
+int train_prim_attention(Arena& ar, float* ws, size_t ws_bytes, int B, int H, int D, int Nq, int Nk, const float* q, const float* k, const float* v,
+                         const float* dout, float* o, float* lse, float* dq, float* dk, float* dv, hipStream_t s);
+int train_prim_linear(Arena& ar, float* ws, size_t ws_bytes, int M, int N, int K, const float* x, const float* W, const float* b, const float* dy, float* y,
+                      float* dx, float* dW, float* db, hipStream_t s);
+int train_prim_layernorm(Arena& ar, float* ws, size_t ws_bytes, int R, int C, float eps, const float* x, const float* g, const float* b, const float* dy,
+                         int accumulate, float* y, float* xhat, float* rstd, float* dx, float* dgamma, float* dbeta, hipStream_t s);
+int train_prim_groupnorm(Arena& ar, float* ws, size_t ws_bytes, int B, int HW, int C, int silu, float eps, const float* x, const float* g, const float* b,
+                         const float* da, int accumulate, float* a, float* xhat, float* rstd, float* dx, hipStream_t s);
+int train_prim_geglu(Arena& ar, float* ws, size_t ws_bytes, int R, int I, const float* u, const float* dh, float* h, float* du, hipStream_t s);
+int train_prim_dot(Arena& ar, float* ws, size_t ws_bytes, size_t n, const float* a, const float* b, const float* alpha, float scale, int mode, float* out,
+                   hipStream_t s);
+
 // One AdamW update of a flat fp32 parameter range, in place (torch.optim.AdamW semantics: trainer.py:245, :384 opt.step()); step = 1, 2, ...
 int adamw_step(float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps, double wd, int step, hipStream_t s);
 // The same update (the same bits for p, m, v) and ema = ema_rate * ema + (1 - ema_rate) * p_new in one pass (train_optim.hip; trainer.py:121-123, 388-391)

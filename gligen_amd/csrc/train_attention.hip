@@ -510,4 +510,24 @@ void Ctx::attn_bwd(int D, const float* q, const float* k, const float* v, const 
 
 }  // namespace train
 
+// attn_fwd, then attn_bwd when dout is given (train.h). o and lse are the forward's arena buffers copied out; the backward writes dq,
+// dk, dv where the caller points, as the step's own calls do.
+int train_prim_attention(Arena& ar, float* ws, size_t ws_bytes, int B, int H, int D, int Nq, int Nk, const float* q, const float* k, const float* v,
+                         const float* dout, float* o, float* lse, float* dq, float* dk, float* dv, hipStream_t s) {
+    if (B < 1 || H < 1 || Nq < 1 || Nk < 1) return set_error(GL_ERR_ARG, "gl_op_train_attention: B=%d H=%d Nq=%d Nk=%d", B, H, Nq, Nk);
+    if (!with_valu_dims(D, [](auto, auto) {})) return set_error(GL_ERR_ARG, "gl_op_train_attention: head dim %d (32, 40, 64, 80, 160 are built)", D);
+    try {
+        Ctx c{ar, ws, ws_bytes, s};
+        const size_t nq = (size_t)B * Nq * H * D;
+        const Ctx::Attn f = c.attn_fwd(D, q, k, v, B, H, Nq, Nk);
+        c.hip(hipMemcpyAsync(o, f.o, nq * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
+        c.hip(hipMemcpyAsync(lse, f.lse, (size_t)B * H * Nq * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
+        if (dout) c.attn_bwd(D, q, k, v, f, dout, B, H, Nq, Nk, dq ? dq : c.f32(nq), dk, dv);
+        c.hip(hipGetLastError(), "training attention kernel launch");
+    } catch (const GlError& e) {
+        return set_error(e.code, "%s", e.what());
+    }
+    return GL_OK;
+}
+
 }  // namespace gl

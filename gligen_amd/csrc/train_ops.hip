@@ -146,12 +146,27 @@ __global__ void ln_fwd_kernel(const float* __restrict__ x, const float* __restri
     const int row = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6), lane = threadIdx.x & 63;
     if (row >= R) return;
     const float* xr = x + (size_t)row * Cc;
+    // One pass (sum, sum of squares) while the row is well conditioned: E[x^2] - mean^2 loses mean^2 / var of the fp32 digits, nothing
+    // to speak of while mean^2 <= var. Otherwise -- rows N(30, 1) were off by 1e-4 of xhat, a constant row got a wrong rstd -- the
+    // statistics are taken again without cancellation, relative to the row's first element p (x - p is exact or rounded at the size of
+    // the spread, not of the mean): the mean of x - p, then the sum of squared deviations from it. The choice is per row and the sums are
+    // in a fixed order either way.
     float s = 0.f, ss = 0.f;
     for (int c = lane; c < Cc; c += 64) { const float v = xr[c]; s += v; ss += v * v; }
     s = wave_sum(s); ss = wave_sum(ss);
-    const float mean = s / Cc, var = fmaxf(ss / Cc - mean * mean, 0.f), rstd = rsqrtf(var + eps);
+    float p = s / Cc, md = 0.f;                            // xhat = ((x - p) - md) rstd; one pass: p = mean
+    float var = fmaxf(ss / Cc - p * p, 0.f);
+    if (p * p > var) {
+        p = xr[0];
+        s = 0.f; ss = 0.f;
+        for (int c = lane; c < Cc; c += 64) s += xr[c] - p;
+        md = wave_sum(s) / Cc;                             // mean - p
+        for (int c = lane; c < Cc; c += 64) { const float d = (xr[c] - p) - md; ss += d * d; }
+        var = wave_sum(ss) / Cc;
+    }
+    const float rstd = rsqrtf(var + eps);
     for (int c = lane; c < Cc; c += 64) {
-        const float h = (xr[c] - mean) * rstd;
+        const float h = ((xr[c] - p) - md) * rstd;
         xhat[(size_t)row * Cc + c] = h;
         y[(size_t)row * Cc + c] = h * g[c] + b[c];
     }
@@ -276,7 +291,7 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
 }
 
 // ---- ResBlock pieces (openaimodel.py:154-232): GroupNorm32 + SiLU over pixel rows [B][HW][C] (fp32), and their backward.
-// One workgroup per (group, sample); the group's HW x cpg slab is read twice (statistics, then apply), sums in a fixed order.
+// One workgroup per (group, sample); the group's HW x cpg slab is read twice (statistics, then apply; twice more for an ill-conditioned slab), sums in a fixed order.
 __device__ __forceinline__ float block_sum_256(float v, float* red) {
     v = wave_sum(v);
     __syncthreads();
@@ -290,15 +305,27 @@ __global__ void __launch_bounds__(256) gn_silu_fwd_kernel(const float* __restric
     __shared__ float red[4];
     const int g = blockIdx.x, b = blockIdx.y, cpg = Cc / 32, n = HW * cpg;
     const float* xb = x + (size_t)b * HW * Cc + g * cpg;
+    // one pass while mean^2 <= var, else again relative to the slab's first element, mean first, then the squared deviations from it
+    // (ln_fwd_kernel's comment); the choice is the same for every thread of the workgroup
     float s = 0.f, q = 0.f;
     for (int i = threadIdx.x; i < n; i += 256) { const float v = xb[(size_t)(i / cpg) * Cc + i % cpg]; s += v; q += v * v; }
     s = block_sum_256(s, red);
     q = block_sum_256(q, red);
-    const float mean = s / n, rstd = rsqrtf(fmaxf(q / n - mean * mean, 0.f) + eps);
+    float p = s / n, md = 0.f;                             // xhat = ((x - p) - md) rstd; one pass: p = mean
+    float var = fmaxf(q / n - p * p, 0.f);
+    if (p * p > var) {
+        p = xb[0];
+        s = 0.f; q = 0.f;
+        for (int i = threadIdx.x; i < n; i += 256) s += xb[(size_t)(i / cpg) * Cc + i % cpg] - p;
+        md = block_sum_256(s, red) / n;                    // mean - p
+        for (int i = threadIdx.x; i < n; i += 256) { const float d = (xb[(size_t)(i / cpg) * Cc + i % cpg] - p) - md; q += d * d; }
+        var = block_sum_256(q, red) / n;
+    }
+    const float rstd = rsqrtf(var + eps);
     for (int i = threadIdx.x; i < n; i += 256) {
         const int c = g * cpg + i % cpg;
         const size_t o = ((size_t)b * HW + i / cpg) * Cc + c;
-        const float h = (x[o] - mean) * rstd, u = h * gam[c] + bet[c];
+        const float h = ((x[o] - p) - md) * rstd, u = h * gam[c] + bet[c];
         xhat[o] = h;
         a[o] = silu ? u / (1.f + __expf(-u)) : u;
     }
@@ -644,6 +671,78 @@ float* conv3x3_direct(const Ctx& c, const float* x, const float* w, const float*
 }
 
 }  // namespace train
+
+// ---- the primitives by themselves (train.h; include/gligen_amd_train_prims.h): what a Ctx method returns in the arena is copied to
+// the caller; what a method writes through a pointer (ln_bwd's dx / dgamma / dbeta, gn_silu_bwd's dx, the weight gradient, the dot) is
+// written where the caller points
+namespace {
+template <class F>
+int run_prim(Arena& ar, float* ws, size_t ws_bytes, hipStream_t s, F&& body) {
+    try {
+        Ctx c{ar, ws, ws_bytes, s};
+        body(c);
+        c.hip(hipGetLastError(), "training primitive kernel launch");
+    } catch (const GlError& e) {
+        return set_error(e.code, "%s", e.what());
+    }
+    return GL_OK;
+}
+void copy_out(const Ctx& c, float* dst, const float* src, size_t n) {
+    if (dst) c.hip(hipMemcpyAsync(dst, src, n * 4, hipMemcpyDeviceToDevice, c.s), "hipMemcpyAsync");
+}
+}  // namespace
+
+int train_prim_linear(Arena& ar, float* ws, size_t ws_bytes, int M, int N, int K, const float* x, const float* W, const float* b, const float* dy, float* y,
+                      float* dx, float* dW, float* db, hipStream_t s) {
+    if (M < 1 || N < 1 || K < 1) return set_error(GL_ERR_ARG, "gl_op_train_linear: M=%d N=%d K=%d", M, N, K);
+    return run_prim(ar, ws, ws_bytes, s, [&](const Ctx& c) {
+        if (y) copy_out(c, y, lin_fwd_any(c, x, M, K, W, b, N), (size_t)M * N);
+        if (!dy) return;
+        if (dx) copy_out(c, dx, lin_dgrad_any(c, dy, M, N, W, K), (size_t)M * K);
+        const int Kp = round_up(K, 64);
+        if (dW || db) lin_wgrad_unpad(c, dy, dW && Kp != K ? pad_cols(c, x, M, K, Kp) : x, M, N, K, Kp, dW, db);
+    });
+}
+
+int train_prim_layernorm(Arena& ar, float* ws, size_t ws_bytes, int R, int C, float eps, const float* x, const float* g, const float* b, const float* dy,
+                         int accumulate, float* y, float* xhat, float* rstd, float* dx, float* dgamma, float* dbeta, hipStream_t s) {
+    if (R < 1 || C < 1) return set_error(GL_ERR_ARG, "gl_op_train_layernorm: R=%d C=%d", R, C);
+    return run_prim(ar, ws, ws_bytes, s, [&](const Ctx& c) {
+        const size_t n = (size_t)R * C;
+        const Ctx::LN f = c.ln_fwd(x, R, C, g, b, eps);
+        copy_out(c, y, f.y, n);
+        copy_out(c, xhat, f.xhat, n);
+        copy_out(c, rstd, f.rstd, (size_t)R);
+        if (dy) c.ln_bwd(dy, f, g, R, C, dx ? dx : c.f32(n), dx && accumulate, dgamma, dbeta);
+    });
+}
+
+int train_prim_groupnorm(Arena& ar, float* ws, size_t ws_bytes, int B, int HW, int C, int silu, float eps, const float* x, const float* g, const float* b,
+                         const float* da, int accumulate, float* a, float* xhat, float* rstd, float* dx, hipStream_t s) {
+    if (B < 1 || HW < 1 || C < 1) return set_error(GL_ERR_ARG, "gl_op_train_groupnorm: B=%d HW=%d C=%d", B, HW, C);
+    if (C % 32) return set_error(GL_ERR_ARG, "gl_op_train_groupnorm: C=%d is no multiple of the 32 groups", C);
+    return run_prim(ar, ws, ws_bytes, s, [&](const Ctx& c) {
+        const size_t n = (size_t)B * HW * C;
+        const Ctx::GN f = c.gn_silu_fwd(x, B, HW, C, g, b, silu != 0, eps);
+        copy_out(c, a, f.a, n);
+        copy_out(c, xhat, f.xhat, n);
+        copy_out(c, rstd, f.rstd, (size_t)B * 32);
+        if (da && dx) c.gn_silu_bwd(da, f, g, b, B, HW, C, dx, accumulate != 0, silu != 0);
+    });
+}
+
+int train_prim_geglu(Arena& ar, float* ws, size_t ws_bytes, int R, int I, const float* u, const float* dh, float* h, float* du, hipStream_t s) {
+    if (R < 1 || I < 1) return set_error(GL_ERR_ARG, "gl_op_train_geglu: R=%d I=%d", R, I);
+    return run_prim(ar, ws, ws_bytes, s, [&](const Ctx& c) {
+        if (h) copy_out(c, h, c.geglu_fwd(u, R, I), (size_t)R * I);
+        if (dh && du) copy_out(c, du, c.geglu_bwd(dh, u, R, I), (size_t)R * 2 * I);
+    });
+}
+
+int train_prim_dot(Arena& ar, float* ws, size_t ws_bytes, size_t n, const float* a, const float* b, const float* alpha, float scale, int mode, float* out,
+                   hipStream_t s) {
+    return run_prim(ar, ws, ws_bytes, s, [&](const Ctx& c) { c.dot_reduce(a, b, n, alpha, scale, mode, out); });
+}
 
 int adamw_step(float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps, double wd, int step, hipStream_t s) {
     if (step < 1) return set_error(GL_ERR_ARG, "adamw_step: step counts from 1");

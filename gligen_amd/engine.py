@@ -1031,6 +1031,119 @@ class Engine:
         check(self.lib.gl_op_grid_resize_backward(self._ctx, _ptr(g), int(B), int(sg), int(sv), int(Cc), _ptr(dsrc), _stream(self.device)))
         return dsrc
 
+    # ---- include/gligen_amd_train_prims.h: the training path's primitives one by one. Each returns a dict of fp32 tensors by output
+    # name. out=None produces every output the inputs allow; out={name: tensor} produces those and writes them into the caller's tensors
+    # (contiguous fp32 on the engine's device, views included), which is how a test puts guard zones round them.
+    def _prim_outs(self, shapes, out, required=()):
+        if out is None:
+            return {k: torch.empty(shape, device=self.device, dtype=torch.float32) for k, shape in shapes.items()}
+        for k, t in out.items():
+            if k not in shapes:
+                raise ValueError(f"no output {k!r} for these inputs (one of {sorted(shapes)})")
+            if t.dtype != torch.float32 or not t.is_contiguous() or tuple(t.shape) != tuple(shapes[k]) or t.device != torch.device(self.device):
+                raise ValueError(f"output {k!r}: a contiguous fp32 tensor of shape {tuple(shapes[k])} on {self.device} is needed")
+        missing = [k for k in required if k not in out]
+        if missing:
+            raise ValueError(f"outputs {missing} are required")
+        return dict(out)
+
+    def op_train_attention(self, q, k, v, heads, dout=None, out=None):
+        """gl_op_train_attention: q [B, Nq, H D], k / v [B, Nk, H D] -> o, lse [B, H, Nq]; with dout also dq, dk, dv. out without
+        dk / dv is the training step's dq-only call."""
+        dev = self.device
+        q, k, v = (_f32(t, dev) for t in (q, k, v))
+        dout = None if dout is None else _f32(dout, dev)
+        B, Nq, HD = q.shape
+        Nk = k.shape[1]
+        if HD % heads or k.shape != (B, Nk, HD) or v.shape != k.shape or (dout is not None and dout.shape != q.shape):
+            raise ValueError("op_train_attention: q / dout [B, Nq, H D], k / v [B, Nk, H D]")
+        shapes = {"o": q.shape, "lse": (B, heads, Nq)}
+        if dout is not None:
+            shapes.update(dq=q.shape, dk=k.shape, dv=k.shape)
+        o = self._prim_outs(shapes, out, required=("o", "lse"))
+        check(self.lib.gl_op_train_attention(self._ctx, int(B), int(heads), int(HD // heads), int(Nq), int(Nk), _ptr(q), _ptr(k), _ptr(v), _ptr(dout),
+                                             *[_ptr(o.get(n)) for n in ("o", "lse", "dq", "dk", "dv")], _stream(dev)))
+        return o
+
+    def op_train_linear(self, x, W, b=None, dy=None, out=None):
+        """gl_op_train_linear: x [M, K], W [N, K], b [N] -> y [M, N]; with dy [M, N] also dx, dW, db."""
+        dev = self.device
+        x, W = _f32(x, dev), _f32(W, dev)
+        b, dy = (None if t is None else _f32(t, dev) for t in (b, dy))
+        (M, K), N = x.shape, W.shape[0]
+        if W.shape != (N, K) or (b is not None and b.shape != (N,)) or (dy is not None and dy.shape != (M, N)):
+            raise ValueError("op_train_linear: x [M, K], W [N, K], b [N], dy [M, N]")
+        shapes = {"y": (M, N)}
+        if dy is not None:
+            shapes.update(dx=(M, K), dW=(N, K), db=(N,))
+        o = self._prim_outs(shapes, out)
+        check(self.lib.gl_op_train_linear(self._ctx, int(M), int(N), int(K), _ptr(x), _ptr(W), _ptr(b), _ptr(dy),
+                                          *[_ptr(o.get(n)) for n in ("y", "dx", "dW", "db")], _stream(dev)))
+        return o
+
+    def op_train_layernorm(self, x, g, b, eps=1e-5, dy=None, accumulate=False, out=None):
+        """gl_op_train_layernorm: x [R, C] -> y, xhat, rstd [R]; with dy also dx (added to out["dx"] when accumulate), dgamma, dbeta."""
+        dev = self.device
+        x, g, b = (_f32(t, dev) for t in (x, g, b))
+        dy = None if dy is None else _f32(dy, dev)
+        R, Cc = x.shape
+        if g.shape != (Cc,) or b.shape != (Cc,) or (dy is not None and dy.shape != x.shape):
+            raise ValueError("op_train_layernorm: x / dy [R, C], g / b [C]")
+        shapes = {"y": x.shape, "xhat": x.shape, "rstd": (R,)}
+        if dy is not None:
+            shapes.update(dx=x.shape, dgamma=(Cc,), dbeta=(Cc,))
+        o = self._prim_outs(shapes, out, required=("dx",) if accumulate else ())
+        if accumulate and out is None:
+            raise ValueError("op_train_layernorm: accumulate adds to out['dx']")
+        check(self.lib.gl_op_train_layernorm(self._ctx, int(R), int(Cc), C.c_float(eps), _ptr(x), _ptr(g), _ptr(b), _ptr(dy), 1 if accumulate else 0,
+                                             *[_ptr(o.get(n)) for n in ("y", "xhat", "rstd", "dx", "dgamma", "dbeta")], _stream(dev)))
+        return o
+
+    def op_train_groupnorm(self, x, g, b, silu=True, eps=1e-5, da=None, accumulate=False, out=None):
+        """gl_op_train_groupnorm: pixel rows x [B, HW, C], 32 groups -> a, xhat, rstd [B, 32]; with da also dx (added to out["dx"] when
+        accumulate)."""
+        dev = self.device
+        x, g, b = (_f32(t, dev) for t in (x, g, b))
+        da = None if da is None else _f32(da, dev)
+        B, HW, Cc = x.shape
+        if g.shape != (Cc,) or b.shape != (Cc,) or (da is not None and da.shape != x.shape):
+            raise ValueError("op_train_groupnorm: x / da [B, HW, C], g / b [C]")
+        shapes = {"a": x.shape, "xhat": x.shape, "rstd": (B, 32)}
+        if da is not None:
+            shapes.update(dx=x.shape)
+        o = self._prim_outs(shapes, out, required=("dx",) if accumulate else ())
+        if accumulate and out is None:
+            raise ValueError("op_train_groupnorm: accumulate adds to out['dx']")
+        check(self.lib.gl_op_train_groupnorm(self._ctx, int(B), int(HW), int(Cc), 1 if silu else 0, C.c_float(eps), _ptr(x), _ptr(g), _ptr(b), _ptr(da),
+                                             1 if accumulate else 0, *[_ptr(o.get(n)) for n in ("a", "xhat", "rstd", "dx")], _stream(dev)))
+        return o
+
+    def op_train_geglu(self, u, dh=None, out=None):
+        """gl_op_train_geglu: u [R, 2 I] = (val | gate) -> h [R, I]; with dh also du [R, 2 I]."""
+        dev = self.device
+        u = _f32(u, dev)
+        dh = None if dh is None else _f32(dh, dev)
+        R, I2 = u.shape
+        if I2 % 2 or (dh is not None and dh.shape != (R, I2 // 2)):
+            raise ValueError("op_train_geglu: u [R, 2 I], dh [R, I]")
+        shapes = {"h": (R, I2 // 2)}
+        if dh is not None:
+            shapes.update(du=u.shape)
+        o = self._prim_outs(shapes, out)
+        check(self.lib.gl_op_train_geglu(self._ctx, int(R), int(I2 // 2), _ptr(u), _ptr(dh), _ptr(o.get("h")), _ptr(o.get("du")), _stream(dev)))
+        return o
+
+    def op_train_dot(self, a, b, mode, alpha=None, scale=1.0, out=None):
+        """gl_op_train_dot: mode 0: scale (1 - tanh(alpha)^2) sum(a b); mode 1: mean((a - b)^2). Returns {"out": [1]}."""
+        dev = self.device
+        a, b = _f32(a, dev).reshape(-1), _f32(b, dev).reshape(-1)
+        alpha = None if alpha is None else _f32(alpha, dev)
+        if a.shape != b.shape:
+            raise ValueError("op_train_dot: a and b hold the same number of elements")
+        o = self._prim_outs({"out": (1,)}, out, required=("out",))
+        check(self.lib.gl_op_train_dot(self._ctx, int(a.numel()), _ptr(a), _ptr(b), _ptr(alpha), C.c_float(scale), int(mode), _ptr(o["out"]), _stream(dev)))
+        return o
+
     def op_conv3x3(self, x0, w_oihw, bias, x1=None, stride=1, ups=0, pad_lo=1, res=None):
         B, H, W, C0 = x0.shape
         C1 = 0 if x1 is None else x1.shape[3]
