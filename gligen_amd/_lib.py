@@ -222,6 +222,11 @@ TRAINER_SYMBOLS = {
     "gl_op_adamw_ema_step": (_I, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _I, _P]),
 }
 
+# every symbol include/gligen_amd_sampler.h declares (how the sampler schedules the guidance pair)
+SAMPLER_SYMBOLS = {
+    "gl_set_cfg_shared_prefix": (_I, [_I]),
+}
+
 # gl_unet_config.fuser_kind / the fuser_kind of gl_op_block_train_fuser, by the reference's fuser_type
 FUSER_KINDS = {"gatedSA": 0, "gatedSA2": 1, "gatedCA": 2}
 
@@ -252,7 +257,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS, **TRAIN_PRIM_SYMBOLS,
-                              **TRAINER_SYMBOLS}.items():
+                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -9,6 +9,7 @@
 #include "../../include/gligen_amd_train_fusers.h"
 #include "../../include/gligen_amd_train_prims.h"
 #include "../../include/gligen_amd_trainer.h"
+#include "../../include/gligen_amd_sampler.h"
 
 #include <cstdlib>
 
@@ -446,6 +447,9 @@ int gl_launch_count(gl_ctx* ctx, int64_t* n) {
 int gl_set_ff_rows_policy(int mode) { return gl::ff_rows_policy_set(mode); }
 
 int gl_ff_rows_policy_report(char* buf, size_t cap) { return gl::ff_rows_policy_report(buf, cap); }
+
+// ---- include/gligen_amd_sampler.h
+int gl_set_cfg_shared_prefix(int on) { return gl::cfg_shared_prefix_set(on); }
 
 int gl_box_calibrate(gl_ctx* ctx, gl_box_calibration* out, gl_stream s) {
     NEED(ctx);

@@ -124,6 +124,11 @@ struct TRef { const bf16* p0 = nullptr; int C0 = 0; const bf16* p1 = nullptr; in
 // 2 = by the static rule on the row count
 int ff_rows_policy_set(int mode);
 int ff_rows_policy_report(char* buf, size_t cap);
+// The two halves of a classifier-free-guidance evaluation share every layer in front of the first conditioning-dependent one
+// (Engine::unet_forward): 1 = those layers run once, at the latent batch (default), 0 = at the full batch like the rest. Process-wide;
+// a change drops captured sampler graphs like a policy change does. GL_CFG_SHARED_PREFIX=0 (developer A/B) presets 0.
+int cfg_shared_prefix_set(int on);
+bool cfg_shared_prefix();
 // the attention kernel's arguments over q / k / v^T in their head layouts, o [B][Nq][H * d]
 AttnParams attn_params(const bf16* q, const bf16* k, const bf16* vt, bf16* o, int H, int d, int Nq, int Nk, int Tq_pad, int Tk_pad, int vt_layout);
 
@@ -262,7 +267,10 @@ class Engine {
     bf16* layernorm(const bf16* x, int B, int N, int C, const NormW& n, bool pad64, hipStream_t s);
     bf16* conv3x3_small(const ConvW& c, Im2colParams P, int reps, hipStream_t s);
     void gn_silu_conv3x3_nchw(const bf16* x, int C, int B, int H, int W, const NormW& n, float eps, const ConvW& c, int n_real, float* out, hipStream_t s);
-    bf16* resblock(const ResW& r, const TRef& x, int B, int H, int W, const float* embout, int emb_ld, float eps, hipStream_t s);
+    bf16* resblock(const ResW& r, const TRef& x, int B, int H, int W, const float* embout, int emb_ld, float eps, hipStream_t s, bf16* out = nullptr);
+    // `reps` copies of src [n] behind each other into dst (misc.h replicate_launch): a tensor of the guidance pair's shared prefix
+    // becomes the full-batch tensor its consumer reads
+    void replicate(const bf16* src, bf16* dst, size_t n, int reps, hipStream_t s);
     // one attention launch over q / k / v^T in their head layouts (profile scope, launch log, launch counter)
     void attention(const bf16* q, const bf16* k, const bf16* vt, bf16* o, int B, int H, int d, int Nq, int Nk, int Tq_pad, int Tk_pad, int vt_layout,
                    hipStream_t s);
@@ -340,7 +348,9 @@ class Engine {
     uint64_t cond_epoch_ = 0;
 
     // ---- UNet, the transformer block (engine_unet.hip)
-    bf16* transformer(const STW& t, const bf16* x, int B, int H, int W, hipStream_t s);
+    // Bp: the prefix batch. Bp < B (a divisor): samples b and b % Bp of x [B] are equal, so GroupNorm, proj_in, norm1 and attn1 -- the
+    // layers in front of the fuser, the first to read conditioning -- run on the first Bp samples only
+    bf16* transformer(const STW& t, const bf16* x, int B, int Bp, int H, int W, hipStream_t s);
     // in_stats: `ln` holds RAW rows whose statistics are in_stats (folded LayerNorm applied by the GEMM); out_stats: statistics of the result
     // raw_rows: with a folded LayerNorm, `ln` may be the RAW rows (no in_stats needed) when ff_rows(f, M) says the row-local kernel runs
     // use_rows: run the row-local kernel (the caller asked ff_rows_for)
@@ -371,8 +381,9 @@ class Engine {
     // of attention `a` into its head-layout buffers; T tokens per sample, Nk keys decide the V^T form (attn_vt_layout)
     bool qkv_rows_ok(const SelfAttnW& a, int B, int T, int Nk, int C, int d) const;
     void qkv_project_gemm(const SelfAttnW& a, const bf16* ln, int B, int T, int Nk, int C, int d, hipStream_t s, const RowStats* in_stats, int Tbuf, int slot);
+    // Bin: x and pre_res hold Bin samples (0: B); sample b reads sample b % Bin (QkvRowsParams::in_period)
     void qkv_rows_project(const SelfAttnW& a, const bf16* x, int B, int T, int Nk, int C, int d, const LinW& pre, const bf16* pre_res, bf16* mid,
-                          RowStats* mid_stats, int Tbuf, int slot, hipStream_t s);
+                          RowStats* mid_stats, int Tbuf, int slot, hipStream_t s, int Bin = 0);
     // time_embed + every ResBlock's emb_layers (openaimodel.py:436-437, 220-221) depend on the timestep alone, and a sampling run knows
     // its timesteps: one batched pass over the whole schedule at the start of gl_sample_plms instead of 4 tiny GEMM chains per evaluation
     float* emb_rows(const int64_t* t_dev, int R, float* out, hipStream_t s);

@@ -646,9 +646,15 @@ bf16* Engine::conv3x3(const TRef& x, int B, int Hin, int Win, const ConvW& c, in
 }
 
 // ResBlock._forward (openaimodel.py:212-232) / VAE ResnetBlock.forward (model.py:118-141)
-bf16* Engine::resblock(const ResW& r, const TRef& x, int B, int H, int W, const float* embout, int emb_ld, float eps, hipStream_t s) {
+void Engine::replicate(const bf16* src, bf16* dst, size_t n, int reps, hipStream_t s) {
+    ProfScope ps(this, s, "replicate_kernel", 0.0, (1.0 + reps) * n * 2);
+    CK(replicate_launch(src, dst, n * sizeof(bf16), reps, s));
+    ++n_launches;
+}
+
+bf16* Engine::resblock(const ResW& r, const TRef& x, int B, int H, int W, const float* embout, int emb_ld, float eps, hipStream_t s, bf16* out) {
     const int HW = H * W, M = B * HW;
-    bf16* out = arena_.get<bf16>((size_t)M * r.Cout);
+    if (!out) out = arena_.get<bf16>((size_t)M * r.Cout);
     const size_t mk = arena_.mark();
     bf16* h = gn_silu_conv3x3(x, B, H, W, r.n1, eps, r.c1, embout ? embout + r.emb_off : nullptr, emb_ld, nullptr, nullptr, s);
     const bf16* sk;

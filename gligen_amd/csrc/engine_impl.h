@@ -22,6 +22,16 @@ FILE* launch_log_file();
 
 unsigned ff_rows_policy_epoch();   // bumped when the kernel-form policy's mode changes: captured graphs of another epoch are dropped
 
+// counters of the guidance pair's shared prefix (tail of gl_ff_rows_policy_report): 0 = an evaluation shared its prefix, 1 = a row-local
+// projection ran at the prefix batch, 2 = a row-local projection read prefix-batch rows through an input period
+void cfg_shared_prefix_note(int what);
+
+// RAII over gemm_set_plan_batch_scale: the launches in its scope run at 1 / scale of the batch they are planned for
+struct PlanAsBatch {
+    explicit PlanAsBatch(int scale) { gemm_set_plan_batch_scale(scale); }
+    ~PlanAsBatch() { gemm_set_plan_batch_scale(1); }
+};
+
 // ---- the recurring GEMM operand / epilogue shapes: a call site states only what differs from these
 inline AOperand a_rows(const bf16* x, int K) {
     AOperand A;

@@ -40,17 +40,49 @@ int ff_rows_policy_set(int mode) {
     return GL_OK;
 }
 unsigned ff_rows_policy_epoch() { return ff_policy::epoch.load(); }
+
+// ---------------------------------------------------------------- the guidance pair's shared prefix (Engine::unet_forward)
+namespace cfg_prefix {
+static std::atomic<int> on{-1};            // -1: not decided yet (GL_CFG_SHARED_PREFIX, default on)
+static int current() {
+    int v = on.load();
+    if (v < 0) {
+        const char* e = dev_env("GL_CFG_SHARED_PREFIX");     // developer A/B: 0 = every layer at the full batch
+        const int want = (e && atoi(e) == 0) ? 0 : 1;
+        int expect = -1;
+        on.compare_exchange_strong(expect, want);
+        v = on.load();
+    }
+    return v;
+}
+// what the host issued in shared form so far (eager passes and captures, not graph replays): evaluations, row-local projections at the
+// prefix batch, row-local projections that read prefix-batch rows through an input period
+static std::atomic<long long> count[3];
+}  // namespace cfg_prefix
+bool cfg_shared_prefix() { return cfg_prefix::current() != 0; }
+void cfg_shared_prefix_note(int what) { cfg_prefix::count[what].fetch_add(1); }
+int cfg_shared_prefix_set(int on) {
+    if (on != 0 && on != 1) return set_error(GL_ERR_ARG, "cfg shared prefix %d (expected 0 or 1)", on);
+    if (cfg_prefix::current() != on) {
+        cfg_prefix::on.store(on);
+        ff_policy::epoch.fetch_add(1);      // captured sampler graphs hold the other form's launches
+    }
+    return GL_OK;
+}
 int ff_rows_policy_report(char* buf, size_t cap) {
     if (!buf || !cap) return set_error(GL_ERR_ARG, "ff_rows_policy_report: no buffer");
     std::lock_guard<std::mutex> lk(ff_policy::mu);
     size_t n = (size_t)snprintf(buf, cap, "mode=%d", ff_policy::mode.load());
     for (const auto& kv : ff_policy::table) {
-        if (n + 96 >= cap) break;
+        if (n + 96 + 128 >= cap) break;       // (room for the shared-prefix tail)
         const uint64_t k = kv.first;
         n += (size_t)snprintf(buf + n, cap - n, ";dev%d %s form%d C%d M%d -> %s (rows %.1f us, gemm %.1f us)", (int)(k >> 56),
                               ((k >> 52) & 15) == 1 ? "fuser.ff" : ((k >> 52) & 15) == 2 ? "ff" : ((k >> 52) & 15) == 3 ? "proj_in+attn1.qkv" : "attn1.to_out+fuser.qkv", (int)((k >> 48) & 15), (int)((k >> 32) & 0xffff), (int)(k & 0xffffffffu),
                               kv.second.rows ? "rows" : "gemm", kv.second.us_rows, kv.second.us_gemm);
     }
+    if (n + 128 < cap)
+        snprintf(buf + n, cap - n, ";cfg_shared_prefix=%d evals=%lld rows_at_prefix=%lld rows_periodic=%lld", cfg_prefix::current(),
+                 cfg_prefix::count[0].load(), cfg_prefix::count[1].load(), cfg_prefix::count[2].load());
     return GL_OK;
 }
 

@@ -326,14 +326,16 @@ bool Engine::qkv_rows_ok(const SelfAttnW& a, int B, int T, int Nk, int C, int d)
 }
 
 void Engine::qkv_rows_project(const SelfAttnW& a, const bf16* x, int B, int T, int Nk, int C, int d, const LinW& pre, const bf16* pre_res, bf16* mid,
-                              RowStats* mid_stats, int Tbuf, int slot, hipStream_t s) {
+                              RowStats* mid_stats, int Tbuf, int slot, hipStream_t s, int Bin) {
     const int H = C / d, M = B * T;
+    if (Bin < 0 || (Bin && B % Bin != 0)) throw GlError(GL_ERR_STATE, fmt("qkv_rows_project: %d input samples for a batch of %d", Bin, B));
     int dp, dpv;
     CK(attn_dims(d, &dp, &dpv));
     const int vt_layout = attn_vt_layout(d, Nk, &dpv);
     AttnBufs& bufs = attn_bufs(B, H, d, Tbuf ? Tbuf : T, Tbuf ? Tbuf : T, dpv, slot);
     QkvRowsParams P{};
     P.x = x; P.ldx = C; P.eps = 1e-5f; P.stream = a.rows_stream; P.M = M;
+    P.in_period = (Bin && Bin != B) ? Bin * T : 0;
     P.pre = 1; P.pre_b = pre.b; P.pre_res = pre_res; P.ld_pre_res = C; P.mid_out = mid; P.ld_mid = C;
     if (mid_stats) {
         *mid_stats = RowStats{};
@@ -569,13 +571,18 @@ bf16* Engine::concat_layernorm(const STW& t, const bf16* x, int B, int HW, int T
 
 // SpatialTransformer.forward + BasicTransformerBlock._forward + GatedSelfAttentionDense.forward
 // (attention.py:366-376, 333-338, 236-244)
-bf16* Engine::transformer(const STW& t, const bf16* x, int B, int H, int W, hipStream_t s) {
+bf16* Engine::transformer(const STW& t, const bf16* x, int B, int Bp, int H, int W, hipStream_t s) {
     const int HW = H * W, M = B * HW, C = t.C, d = t.d, heads = C / d;
     bf16* out = arena_.get<bf16>((size_t)M * C);
     const size_t mk = arena_.mark();
     if (cond_.Beff != B) throw GlError(GL_ERR_STATE, fmt("unet_forward batch %d != batch %d of the conditioning set by gl_unet_set_cond", B, cond_.Beff));
+    if (Bp <= 0 || B % Bp != 0) throw GlError(GL_ERR_STATE, fmt("transformer: prefix batch %d does not divide batch %d", Bp, B));
+    // Everything in front of attn1.to_out sees x alone: with Bp < B it runs on the first Bp samples (Mp rows), and what reads its
+    // results (o, t0) at B samples reads sample b % Bp
+    const bool shared = Bp < B;
+    const int Mp = Bp * HW;
 
-    bf16* n = groupnorm(TRef{x, C, nullptr, 0}, B, HW, t.gn, 1e-6f, false, s);
+    bf16* n = groupnorm(TRef{x, C, nullptr, 0}, Bp, HW, t.gn, 1e-6f, false, s);
     // Folded LayerNorms (gemm.h Epilogue::ln_stats): every GEMM that writes the residual stream also writes its rows' partial
     // (sum, sum of squares); the projection behind the next LayerNorm then reads the RAW rows and normalises in its epilogue.
     // Where no statistics exist (split-K producer, the [x ; objs] concatenation, an epilogue without the fold) the rows go
@@ -584,32 +591,43 @@ bf16* Engine::transformer(const STW& t, const bf16* x, int B, int H, int W, hipS
     const bool aligned = Tp == HW;
     auto normed = [&](const bf16* rows, const NormW& nw, bool folded, bool fuse, bool pad64) -> const bf16* {
         if (fuse) return rows;
-        return folded ? layernorm_plain(rows, B, HW, C, pad64, s) : layernorm(rows, B, HW, C, nw, pad64, s);
+        return folded ? layernorm_plain(rows, Bp, HW, C, pad64, s) : layernorm(rows, Bp, HW, C, nw, pad64, s);   // (norm1: the prefix batch)
     };
     RowStats st0, st1, st2, st3;
     // the row-local feed-forward kernel normalises its raw input rows itself: their producers need not write statistics
     const bool r2 = !fuser_off_ && ff_rows_for(t, 1, B, HW, s), r4 = ff_rows_for(t, 2, B, HW, s);
     // proj_in -> norm1 -> attn1's q,k,v^T: one row-local launch where that kernel exists and fills the chip (ffn.h qkv_rows_kernel)
-    const bool rq1 = aligned && qkv_rows_for(t, 0, B, HW, HW, s);
     bf16* t0;
     const bf16* ln = nullptr;
-    bf16* o = nullptr;
+    bf16* o = arena_.get<bf16>((size_t)M * C);         // (B samples: the later attentions write it whole)
+    bool rq1;
+    {
+    // the prefix's GEMMs take the plans of their full-batch forms: the same bits as without sharing (gemm.h gemm_set_plan_batch_scale)
+    PlanAsBatch plan_as(B / Bp);
+    rq1 = aligned && qkv_rows_for(t, 0, Bp, HW, HW, s);
     if (rq1) {
-        t0 = arena_.get<bf16>((size_t)M * C);
-        o = arena_.get<bf16>((size_t)M * C);
-        qkv_rows_project(t.a1, n, B, HW, HW, C, d, t.proj_in, nullptr, t0, nullptr, 0, 0, s);
-        self_attention(t.a1, nullptr, B, Tp, HW, HW, C, d, o, s, nullptr, 0, 0, true);
+        t0 = arena_.get<bf16>((size_t)Mp * C);
+        qkv_rows_project(t.a1, n, Bp, HW, HW, C, d, t.proj_in, nullptr, t0, nullptr, 0, 0, s);
+        self_attention(t.a1, nullptr, Bp, Tp, HW, HW, C, d, o, s, nullptr, 0, 0, true);
+        if (shared) cfg_shared_prefix_note(1);
     } else {
-        t0 = linear_rows(n, M, t.proj_in, ACT_NONE, nullptr, nullptr, s, &st0);
+        t0 = linear_rows(n, Mp, t.proj_in, ACT_NONE, nullptr, nullptr, s, &st0);
         // x = attn1(norm1(x)) + x
-        const bool f1 = t.a1.folded && can_fold(st0, M, C, 3 * C, EPI_QKV_HEADS, ACT_NONE, aligned);
+        const bool f1 = t.a1.folded && can_fold(st0, Mp, C, 3 * C, EPI_QKV_HEADS, ACT_NONE, aligned);
         ln = normed(t0, t.ln1, t.a1.folded, f1, true);
-        o = arena_.get<bf16>((size_t)M * C);
-        self_attention(t.a1, ln, B, Tp, HW, HW, C, d, o, s, f1 ? &st0 : nullptr);
+        self_attention(t.a1, ln, Bp, Tp, HW, HW, C, d, o, s, f1 ? &st0 : nullptr);
+    }
     }
     const int Ng = cond_.Ng;
     // attn1.to_out + residual -> fuser.norm1 -> the fuser's q,k,v^T over the visual rows: the same launch shape
     const bool rq2 = !fuser_off_ && unet_.cfg.fuser_kind == 0 && fuser_hoist_ && aligned && cond_.Ng > 0 && qkv_rows_for(t, 1, B, HW, HW + Ng, s);
+    if (shared && !rq2) {
+        // every form but the row-local launch below reads o and t0 at B samples: one copy kernel each, then the code is the unshared one
+        replicate(o, o + (size_t)Mp * C, (size_t)Mp * C, B / Bp - 1, s);
+        bf16* t0b = arena_.get<bf16>((size_t)M * C);
+        replicate(t0, t0b, (size_t)Mp * C, B / Bp, s);
+        t0 = t0b;
+    }
     bf16* t1 = rq2 ? arena_.get<bf16>((size_t)M * C) : linear_rows(o, M, t.a1.out, ACT_NONE, t0, nullptr, s, &st1);
 
     bf16* t3;
@@ -622,7 +640,9 @@ bf16* Engine::transformer(const STW& t, const bf16* x, int B, int H, int W, hipS
         const int Tf = round_up(HW + Ng, 64);
         if (rq2) {
             ensure_fuser_kv(t, B, HW, s);
-            qkv_rows_project(t.fa, o, B, HW, HW + Ng, C, d, t.a1.out, t0, t1, nullptr, Tf, t.idx + 1, s);
+            // (shared prefix: o and t0 hold Bp samples, the launch reads row m % Mp of both and writes t1 and q, k, v^T for all B)
+            qkv_rows_project(t.fa, o, B, HW, HW + Ng, C, d, t.a1.out, t0, t1, nullptr, Tf, t.idx + 1, s, shared ? Bp : 0);
+            if (shared) cfg_shared_prefix_note(2);
             self_attention(t.fa, nullptr, B, HW, HW, HW + Ng, C, d, o, s, nullptr, Tf, t.idx + 1, true);
         } else if (fuser_hoist_ && t.fa.fused && t.fa.folded && aligned) {
             // the grounding tokens' keys / values are in this block's buffers since the prompt was set (fuser_kv_fill); only the visual
@@ -912,7 +932,32 @@ void Engine::unet_forward(int Beff, int h, int w, const float* x, int xB, const 
     std::vector<Act> hs;
     Act cur{nullptr, 0, h, w};
 
-    auto run_layer = [&](const Layer& L, const TRef& in) {
+    // The guidance pair's shared prefix. With one time-embedding row for every sample and x (and the extra first-conv input) of xB
+    // samples serving Beff = R xB, samples b and b % xB are bit-identical until the first layer that reads conditioning: the first
+    // transformer's fuser / cross-attention. The layers between conv_in and that transformer, and the transformer's own head (its
+    // GroupNorm, proj_in, norm1, attn1), run on the first xB samples only. conv_in stays at Beff: its output is hs[0], which the last
+    // output block concatenates at Beff. Per-sample timesteps (emb_row == nullptr) never share: whether they are equal is not
+    // known on the host.
+    int Bp = Beff;
+    if (emb_row && Beff / xB > 1 && cfg_shared_prefix()) {
+        bool has_st = false;
+        for (const UNetBlock& b : unet_.in_blocks)
+            for (const Layer& L : b.layers) has_st = has_st || L.kind == L_ST;
+        if (has_st) {
+            Bp = xB;
+            cfg_shared_prefix_note(0);
+        }
+    }
+    bool in_prefix = Bp < Beff;      // until the first transformer has run
+
+    // Bl: the batch the layer runs at. full (Bl < Beff): its result is needed at Beff -- a skip connection, or the transformer's
+    // residual behind proj_out -- so it is written into a Beff-sample buffer and copied behind itself
+    auto run_layer = [&](const Layer& L, const TRef& in, int Bl, bool full) {
+        PlanAsBatch plan_as(L.kind == L_ST ? 1 : Beff / Bl);    // a prefix layer's GEMMs / convs: planned as at Beff, the same bits (the transformer scopes its own)
+        auto out_for = [&](int HWo, int Co) { return full ? arena_.get<bf16>((size_t)Beff * HWo * Co) : nullptr; };
+        auto fill = [&](bf16* o, int HWo, int Co) {
+            if (full) replicate(o, o + (size_t)Bl * HWo * Co, (size_t)Bl * HWo * Co, Beff / Bl - 1, s);
+        };
         switch (L.kind) {
             case L_CONV_IN: {
                 if (extra && extraB != xB) throw GlError(GL_ERR_ARG, "extra first-conv input batch must equal x batch");
@@ -926,19 +971,22 @@ void Engine::unet_forward(int Beff, int h, int w, const float* x, int xB, const 
             }
             case L_RES: {
                 const ResW& r = unet_.res[L.idx];
-                cur.p = resblock(r, in, Beff, cur.H, cur.W, embout, emb_ld, 1e-5f, s);
+                cur.p = resblock(r, in, Bl, cur.H, cur.W, embout, emb_ld, 1e-5f, s, out_for(cur.H * cur.W, r.Cout));
                 cur.C = r.Cout;
+                fill(cur.p, cur.H * cur.W, cur.C);
                 break;
             }
             case L_ST: {
                 if (in.p1) throw GlError(GL_ERR_STATE, "transformer over concatenated input");
-                cur.p = transformer(unet_.st[L.idx], in.p0, Beff, cur.H, cur.W, s);
+                cur.p = transformer(unet_.st[L.idx], in.p0, Beff, Bl, cur.H, cur.W, s);   // (its input holds Beff samples either way)
                 break;
             }
             case L_DOWN: {
-                cur.p = conv3x3(in, Beff, cur.H, cur.W, unet_.updown[L.idx], 2, 0, 1, nullptr, 0, nullptr, s);
-                cur.H = (cur.H + 2 - 3) / 2 + 1;
-                cur.W = (cur.W + 2 - 3) / 2 + 1;
+                const int Ho = (cur.H + 2 - 3) / 2 + 1, Wo = (cur.W + 2 - 3) / 2 + 1;
+                cur.p = conv3x3(in, Bl, cur.H, cur.W, unet_.updown[L.idx], 2, 0, 1, nullptr, 0, nullptr, s, out_for(Ho * Wo, unet_.updown[L.idx].Cout));
+                cur.H = Ho;
+                cur.W = Wo;
+                fill(cur.p, Ho * Wo, unet_.updown[L.idx].Cout);
                 break;
             }
             case L_UP: {
@@ -951,18 +999,24 @@ void Engine::unet_forward(int Beff, int h, int w, const float* x, int xB, const 
     };
 
     for (const UNetBlock& b : unet_.in_blocks) {
-        for (const Layer& L : b.layers) run_layer(L, TRef{cur.p, cur.C, nullptr, 0});
+        for (size_t i = 0; i < b.layers.size(); ++i) {
+            const Layer& L = b.layers[i];
+            const bool pre = in_prefix && L.kind != L_CONV_IN;
+            const bool last = i + 1 == b.layers.size();
+            run_layer(L, TRef{cur.p, cur.C, nullptr, 0}, pre ? Bp : Beff, pre && L.kind != L_ST && (last || b.layers[i + 1].kind == L_ST));
+            if (L.kind == L_ST) in_prefix = false;
+        }
         hs.push_back(cur);
     }
-    for (const Layer& L : unet_.mid_block.layers) run_layer(L, TRef{cur.p, cur.C, nullptr, 0});
+    for (const Layer& L : unet_.mid_block.layers) run_layer(L, TRef{cur.p, cur.C, nullptr, 0}, Beff, false);
     for (const UNetBlock& b : unet_.out_blocks) {
         Act sk = hs.back();
         hs.pop_back();
         if (sk.H != cur.H || sk.W != cur.W) throw GlError(GL_ERR_ARG, "latent size must be divisible by the UNet's total stride");
         bool first = true;
         for (const Layer& L : b.layers) {
-            if (first) run_layer(L, TRef{cur.p, cur.C, sk.p, sk.C});  // th.cat([h, hs.pop()], dim=1)
-            else run_layer(L, TRef{cur.p, cur.C, nullptr, 0});
+            if (first) run_layer(L, TRef{cur.p, cur.C, sk.p, sk.C}, Beff, false);  // th.cat([h, hs.pop()], dim=1)
+            else run_layer(L, TRef{cur.p, cur.C, nullptr, 0}, Beff, false);
             first = false;
         }
     }

@@ -83,6 +83,8 @@ struct QkvRowsParams {
     bf16* k;                // key-tile layout (gemm.h ktile_off), [B*H][Tpad_k / 64][DP / 8][64][8]
     bf16* vt;               // [B*H][DPV][Tpad_k], tokens permuted within groups of 32 (vt_perm32 = 1)
     int H, d, DP, DPV, T, Tpad_q, Tpad_k, vt_perm32;   // T = rows per sample (a multiple of 128)
+    int in_period;          // 0: none. Else x and pre_res hold in_period rows (a multiple of T dividing M) and output row m reads input
+                            // row m % in_period: the classifier-free-guidance pair's shared prefix (Engine::transformer)
 };
 bool qkv_rows_supported(int M, int C, int d, int T);
 size_t qkv_rows_stream_bytes(int C, bool pre, int np);

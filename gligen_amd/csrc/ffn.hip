@@ -785,6 +785,8 @@ __global__ void __launch_bounds__(256, 1) qkv_rows_kernel(QkvRowsParams p) {
     const int h = lane >> 5, l31 = lane & 31;
     const int row0 = blockIdx.x * 128 + wave * 32;     // the wave's first row (32 consecutive tokens of one sample: T % 32 == 0)
     const int row = row0 + l31;
+    // the row this lane LOADS (p.in_period): a period is whole samples, so the wave's 32 rows stay consecutive -- another base address
+    const int row_in = (p.in_period ? row0 % p.in_period : row0) + l31;
     const unsigned lane16 = (unsigned)lane * 16u;
 
     u32x4 rs;
@@ -807,7 +809,7 @@ __global__ void __launch_bounds__(256, 1) qkv_rows_kernel(QkvRowsParams p) {
     // wait vmcnt(0) per feature block, i.e. for every store issued before it (measured: 65 us per launch instead of 3 x 5 + epilogues).
     bf16x8 xf[KS];
     {
-        const bf16* src = p.x + (size_t)row * p.ldx + h * 8;
+        const bf16* src = p.x + (size_t)row_in * p.ldx + h * 8;
 #pragma unroll
         for (int ks = 0; ks < KS; ++ks) xf[ks] = *reinterpret_cast<const bf16x8*>(src + ks * 16);
     }
@@ -815,7 +817,7 @@ __global__ void __launch_bounds__(256, 1) qkv_rows_kernel(QkvRowsParams p) {
     const bool has_res = PRE && p.pre_res != nullptr;
     if constexpr (PRE) {
         if (has_res) {
-            const bf16* src = p.pre_res + (size_t)row * p.ld_pre_res + h * 4;
+            const bf16* src = p.pre_res + (size_t)row_in * p.ld_pre_res + h * 4;
 #pragma unroll
             for (int cb = 0; cb < NCB; ++cb)
 #pragma unroll
@@ -1165,6 +1167,7 @@ int qkv_rows_launch(const QkvRowsParams& p, int C, hipStream_t s) {
     if (p.np == 3 && (p.vt_perm32 != 1 || p.Tpad_k % 32)) return set_error(GL_ERR_UNSUPPORTED, "qkv_rows: v^T is written in the 32-token form only (attn3_kernel)");
     if (p.H * p.d != C || p.DP < p.d || p.DP % 8 || (p.np == 3 && p.DPV < p.d)) return set_error(GL_ERR_ARG, "qkv_rows: head geometry");
     if (p.pre && (!p.pre_b || !p.mid_out || p.ld_mid % 4 || (p.pre_res && p.ld_pre_res % 4))) return set_error(GL_ERR_ARG, "qkv_rows: the leading projection needs its bias and the buffer for its result");
+    if (p.in_period < 0 || (p.in_period && (p.in_period % p.T || p.M % p.in_period))) return set_error(GL_ERR_ARG, "qkv_rows: the input period must be whole samples and divide M");
     using G = FFGeom<320>;
     constexpr int LDS = 3 * G::PJ_BLK * 1024 + 4 * 320 * (int)sizeof(float);
     // (125 KB of LDS: the attribute is set at the first launch of each form, as before)

@@ -120,6 +120,10 @@ void gemm_set_autotune(int on);                    // 1 (default): time candidat
 // output element is then one sequential fp32 accumulation over K whatever M is, so a row of the result does not depend on how
 // many other rows the call carries (the CLIP vision tower: an image's feature must not depend on the batch it was encoded in).
 void gemm_set_no_split(int on);
+// scale > 1: the GEMMs / convs this THREAD launches from now on are planned as the same problem with `scale` times the rows -- kernel
+// family, tile and K split of the larger launch, grid and item counts of the real one -- so a row comes out with the bits it has when
+// it is one of the larger launch's rows (the guidance pair's shared prefix, Engine::unet_forward). 1: off.
+void gemm_set_plan_batch_scale(int scale);
 void gemm_last_cfg(int* tm, int* tn, int* splits);
 const char* gemm_last_kernel_name();  // kernel symbol (template arguments included) of the most recent gemm_launch
 bool gemm_gn_prologue_supported(const AOperand& A, int M, int N, int K, const Epilogue& E);   // may this launch take AOperand::gn?

@@ -35,6 +35,8 @@ void gemm_force_cfg(int tm, int tn, int splits) { gemm_knobs().force_tm = tm; ge
 void gemm_force_grid(int g) { gemm_knobs().force_grid = g; }
 static thread_local int t_no_split = 0;
 void gemm_set_no_split(int on) { t_no_split = on; }
+static thread_local int t_plan_scale = 1;
+void gemm_set_plan_batch_scale(int scale) { t_plan_scale = scale > 1 ? scale : 1; }
 
 // GEGLU weight-row packing the current main-loop variant expects (pack_geglu_launch layout argument)
 int gemm_geglu_layout() { return gemm_knobs().variant >= 2 ? 1 : 0; }
@@ -194,8 +196,10 @@ int split_units(const GemmProblem& pb, int want, int tiles, int units, int min_u
     return per;
 }
 
-void plan_glds(const GemmProblem& pb, GemmPlan& p) {
-    const int M = pb.M, N = pb.N;
+// ph (here and below): the problem the CHOICES are made for -- pb itself, or pb with gemm_set_plan_batch_scale's row count. Tile and
+// K split come from ph, every size of the launch (tiles, items, grid) from pb.
+void plan_glds(const GemmProblem& pb, const GemmProblem& ph, GemmPlan& p) {
+    const int M = ph.M, N = pb.N;
     // pick the tile: padding efficiency x relative tile speed x chip fill
     int best = 0;
     float best_score = -1.f;
@@ -211,11 +215,11 @@ void plan_glds(const GemmProblem& pb, GemmPlan& p) {
     }
     const Cfg& cf = kCfgs[best];
     snprintf(p.name, sizeof p.name, "gemm_glds_kernel<%dx%d, %d>", cf.bm, cf.bn, pb.A.mode);   // (the split is not named here)
-    const int tiles = cdiv(M, cf.bm) * cdiv(N, cf.bn);
+    const int tiles_h = cdiv(M, cf.bm) * cdiv(N, cf.bn), tiles = cdiv(pb.M, cf.bm) * cdiv(N, cf.bn);
     const int nk = pb.K / 64;
     int splits = 1;
-    if (pb.has_ws && !t_no_split && tiles < 256 && nk >= 8) {
-        splits = std::min(std::min(cdiv(512, tiles), nk / 4), 16);
+    if (pb.has_ws && !t_no_split && tiles_h < 256 && nk >= 8) {
+        splits = std::min(std::min(cdiv(512, tiles_h), nk / 4), 16);
         while (splits > 1 && (size_t)splits * M * N * sizeof(float) > pb.ws_bytes) --splits;
     }
     const int kps = cdiv(nk, splits);
@@ -224,27 +228,27 @@ void plan_glds(const GemmProblem& pb, GemmPlan& p) {
     p.work = WorkDesc{cdiv(N, cf.bn), p.splits, kps, tiles, -1, 0, p.splits};
 }
 
-void plan_halo(const GemmProblem& pb, GemmPlan& p) {
+void plan_halo(const GemmProblem& pb, const GemmProblem& ph, GemmPlan& p) {
     const AOperand& A = pb.A;
     const int M = pb.M, N = pb.N, tn = N % 160 == 0 ? 5 : 4;
     HaloDesc& hd = p.halo;
     hd.lgW = ilog2_exact(A.Win); hd.lgH = ilog2_exact(A.Hin);
     hd.tiles_n = cdiv(N, tn * 32);
     const int tiles = (M / 256) * hd.tiles_n;
-    hd.chunks_per_split = split_units(pb, gemm_knobs().halo_splits, tiles, (A.C0 + A.C1) / 64, 2, true, hd.splits);
+    hd.chunks_per_split = split_units(ph, gemm_knobs().halo_splits, (ph.M / 256) * hd.tiles_n, (A.C0 + A.C1) / 64, 2, true, hd.splits);
     hd.n_items = tiles * hd.splits;
     p.tm = 8; p.tn = tn; p.gn = A.gn != nullptr; p.splits = hd.splits;
     p.grid = std::min(hd.n_items, 256);
     snprintf(p.name, sizeof p.name, "conv_halo_kernel<%d, %d%s>%s", tn, 8, p.gn ? ", gn" : "", reduce_suffix(p.splits));
 }
 
-void plan_wide(const GemmProblem& pb, GemmPlan& p) {
+void plan_wide(const GemmProblem& pb, const GemmProblem& ph, GemmPlan& p) {
     const Epilogue& E = pb.E;
     const int M = pb.M, N = pb.N, tn = (E.act != ACT_GEGLU && N % 160 == 0) ? 5 : 4;
     WideDesc& wd = p.wide;
     wd.tiles_n = N / (tn * 32);
     const int tiles = (M / 256) * wd.tiles_n;
-    wd.kt_per_split = split_units(pb, gemm_knobs().wide_splits, tiles, pb.K / 64, 4, E.act != ACT_GEGLU, wd.splits);
+    wd.kt_per_split = split_units(ph, gemm_knobs().wide_splits, (ph.M / 256) * wd.tiles_n, pb.K / 64, 4, E.act != ACT_GEGLU, wd.splits);
     wd.n_items = tiles * wd.splits;
     // Item order against the 8 XCD L2s (profiles/r3/wide_ring_kbench.txt, per-problem fabric traffic in profiles/r3_final/).
     // Linear order with tiles_n a multiple of 8 is weight-stationary by accident: XCD x only ever sees the column tiles = x mod 8,
@@ -434,22 +438,35 @@ static bool tuned_lookup(const char* key, bool use_u, GemmCand& out) {   // (cal
 int gemm_plan(const AOperand& A, int M, int N, int K, Epilogue& E, bool has_ws, size_t ws_bytes, GemmPlan& p, const GemmTuner& tuner) {
     GL_TRY(gemm_validate(A, M, N, K, E));
     const GemmProblem pb{A, M, N, K, E, has_ws, ws_bytes};
-    p = GemmPlan{gemm_route(A, M, N, K, E), 0, 0, A.mode};
-    if (p.family == GEMM_GLDS) { plan_glds(pb, p); return GL_OK; }
-    if (p.family == GEMM_HALO) { plan_halo(pb, p); return GL_OK; }
-    if (p.family == GEMM_WIDE) { plan_wide(pb, p); return GL_OK; }
+    // gemm_set_plan_batch_scale: family, tile and K split are those of the same problem with `scale` times the rows (what the tuned
+    // table / an earlier tuning pass holds for it, else the model's choice; never timed here: the buffers hold M rows), so a row of
+    // the result has the bits it has in the larger launch. Taken only where the larger problem's kernel family runs this one too.
+    int Mh = (t_plan_scale > 1 && M <= 0x7fffffff / t_plan_scale) ? M * t_plan_scale : M;
+    int family = gemm_route(A, Mh, N, K, E);
+    if (Mh != M) {
+        const int own = gemm_route(A, M, N, K, E);
+        if (family != own && !(family == GEMM_HALO && halo_eligible(A, M, N, K, E)) && !(family == GEMM_WIDE && wide_eligible(A, M, N, K, E))) {
+            Mh = M;
+            family = own;
+        }
+    }
+    const GemmProblem ph{A, Mh, N, K, E, has_ws, ws_bytes};
+    p = GemmPlan{family, 0, 0, A.mode};
+    if (p.family == GEMM_GLDS) { plan_glds(pb, ph, p); return GL_OK; }
+    if (p.family == GEMM_HALO) { plan_halo(pb, ph, p); return GL_OK; }
+    if (p.family == GEMM_WIDE) { plan_wide(pb, ph, p); return GL_OK; }
     const bool use_u = p.family == GEMM_U;
     GemmCand pick;
     if (forced_choice(pb, use_u, pick)) return gemm_plan_tile(pb, use_u, pick, p);
     char key[160];
-    tuned_key(pb, use_u, key, sizeof key);
+    tuned_key(ph, use_u, key, sizeof key);
     {
         std::lock_guard<std::mutex> lock(g_tune_mu);
         if (!tuned_lookup(key, use_u, pick)) {
             GemmCand model;
-            if (!model_choice(pb, use_u, model)) return set_error(GL_ERR_ARG, "gemm: no tile configuration for M=%d N=%d K=%d", M, N, K);
+            if (!model_choice(ph, use_u, model)) return set_error(GL_ERR_ARG, "gemm: no tile configuration for M=%d N=%d K=%d", M, N, K);
             pick = model;
-            if (tuner && gemm_knobs().autotune) {
+            if (tuner && gemm_knobs().autotune && Mh == M) {
                 // the lock is held across the pass: two threads tuning at once would time each other's launches
                 bool cache = false;
                 GL_TRY(tuner(pb, use_u, key, model, &pick, &cache));

@@ -129,5 +129,8 @@ int box_calibrate_launch(void* scratch, size_t scratch_bytes, float* out3, hipSt
 // gl_mfma_calibrate: out4 = {TFLOP/s, shader clock in MHz measured inside the loop, ms, SIMD cycles per MFMA at that clock}; scratch >= 4 KiB
 int mfma_calibrate_launch(int shape, int waves_per_simd, int n_acc, int zero_data, float target_ms, void* scratch, float* out4, hipStream_t stream);
 int zero_launch(void* dst, size_t bytes, hipStream_t stream);
+// dst[r * bytes + i] = src[i] for r < reps: `reps` copies of one block behind each other (bytes a multiple of 16, both 16-byte aligned;
+// dst may start right behind src, it must not overlap it)
+int replicate_launch(const void* src, void* dst, size_t bytes, int reps, hipStream_t stream);
 
 }  // namespace gl

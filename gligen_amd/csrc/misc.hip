@@ -516,6 +516,19 @@ int zero_launch(void* dst, size_t bytes, hipStream_t stream) {
     return GL_OK;
 }
 
+__global__ void replicate_kernel(const uint4* __restrict__ s, uint4* __restrict__ d, int64_t n16, int reps) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n16; i += (int64_t)gridDim.x * blockDim.x) {
+        const uint4 v = s[i];
+        for (int r = 0; r < reps; ++r) d[(int64_t)r * n16 + i] = v;
+    }
+}
+int replicate_launch(const void* src, void* dst, size_t bytes, int reps, hipStream_t stream) {
+    if (bytes % 16 != 0 || ((uintptr_t)src | (uintptr_t)dst) % 16 != 0 || reps < 1) return set_error(GL_ERR_ARG, "replicate: %zu bytes x %d, 16-byte units only", bytes, reps);
+    hipLaunchKernelGGL(replicate_kernel, dim3(grid_for(bytes / 16)), dim3(256), 0, stream, (const uint4*)src, (uint4*)dst, (int64_t)(bytes / 16), reps);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
 
 // ---- GroundingDownsampler of the spatial-map modalities (reference canny/depth/normal/sem/hed_grounding_downsampler.py):
 // F.interpolate of the first n channels of the conditioning image to R x R (bicubic, align_corners=False, A = -0.75, taps

@@ -627,6 +627,11 @@ class Engine:
         rank and run -- the timed default may pick the other form, which differs in the last bits). Process-wide."""
         check(self.lib.gl_set_ff_rows_policy(int(mode)))
 
+    def set_cfg_shared_prefix(self, on: bool) -> None:
+        """gl_set_cfg_shared_prefix: run the layers in front of the first conditioning-dependent one once per [cond ; uncond]
+        evaluation of the sampler (default) or at the full batch like the rest. Process-wide; captured graphs are dropped."""
+        check(self.lib.gl_set_cfg_shared_prefix(int(bool(on))))
+
     def ff_rows_policy_report(self) -> str:
         buf = C.create_string_buffer(4096)
         check(self.lib.gl_ff_rows_policy_report(buf, 4096))
