@@ -1,5 +1,6 @@
 """ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
-include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h, include/gligen_amd_train_fusers.h, include/gligen_amd_train_prims.h and include/gligen_amd_trainer.h).
+include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h, include/gligen_amd_train_fusers.h, include/gligen_amd_train_prims.h,
+include/gligen_amd_trainer.h, include/gligen_amd_sampler.h and include/gligen_amd_gemm_plans.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -227,6 +228,25 @@ SAMPLER_SYMBOLS = {
     "gl_set_cfg_shared_prefix": (_I, [_I]),
 }
 
+class GemmPlanRecord(C.Structure):   # = gl_gemm_plan_record
+    _fields_ = [("kernel", C.c_char * 96)] + [(n, C.c_int) for n in ("family", "M", "N", "K", "tm", "tn", "splits", "grid", "n_items", "box", "rm", "rz",
+                                                                     "units_per_split", "xcd")]
+
+
+class AttnProjLayout(C.Structure):   # = gl_attn_proj_layout
+    _fields_ = [(n, C.c_int) for n in ("d", "dp", "dpv", "tq", "tk", "tq_pad", "tk_pad", "vt_perm32")]
+
+
+# every symbol include/gligen_amd_gemm_plans.h declares (one named GEMM plan at a time, and the log of what ran)
+GEMM_PLAN_SYMBOLS = {
+    "gl_gemm_force_plan": (_I, [_I, _I, _I, _I]),
+    "gl_gemm_force_knobs": (_I, [_I, _I, _I, _I, _I, _I]),
+    "gl_gemm_force_clear": (_I, []),
+    "gl_gemm_plan_log_clear": (_I, []),
+    "gl_gemm_plan_log": (_I, [C.POINTER(GemmPlanRecord), _I, C.POINTER(_I), C.POINTER(_I)]),
+    "gl_op_attention_project": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, C.POINTER(AttnProjLayout), _P]),
+}
+
 # gl_unet_config.fuser_kind / the fuser_kind of gl_op_block_train_fuser, by the reference's fuser_type
 FUSER_KINDS = {"gatedSA": 0, "gatedSA2": 1, "gatedCA": 2}
 
@@ -257,7 +277,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS, **TRAIN_PRIM_SYMBOLS,
-                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS}.items():
+                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **GEMM_PLAN_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -10,6 +10,8 @@
 #include "../../include/gligen_amd_train_prims.h"
 #include "../../include/gligen_amd_trainer.h"
 #include "../../include/gligen_amd_sampler.h"
+#include "../../include/gligen_amd_gemm_plans.h"
+#include "gemm_plan.h"
 
 #include <cstdlib>
 
@@ -450,6 +452,46 @@ int gl_ff_rows_policy_report(char* buf, size_t cap) { return gl::ff_rows_policy_
 
 // ---- include/gligen_amd_sampler.h
 int gl_set_cfg_shared_prefix(int on) { return gl::cfg_shared_prefix_set(on); }
+
+// ---- include/gligen_amd_gemm_plans.h
+int gl_gemm_force_plan(int tm, int tn, int splits, int grid_cap) {
+    bool tile = tm == 0 && tn == 0;
+    for (int c = 0; c < kGemmTiles; ++c) tile |= kGemmTm[c] == tm && kGemmTn[c] == tn;
+    if (!tile || splits < 0 || splits > 32 || grid_cap < 0)
+        return gl::set_error(GL_ERR_ARG, "gl_gemm_force_plan: tile %dx%d / %d splits / cap %d (tiles 4x5 4x4 2x5 2x4 2x2 or 0x0, splits 0..32, cap >= 0)", tm, tn, splits, grid_cap);
+    gemm_force_cfg(tm, tn, tm ? splits : 0);
+    gemm_force_grid(grid_cap);
+    return GL_OK;
+}
+int gl_gemm_force_knobs(int halo_splits, int wide_splits, int wide_xcd, int xcd_boxes, int halo, int wide) {
+    if (halo_splits < 0 || wide_splits < 0 || wide_xcd < -1 || wide_xcd > 1 || xcd_boxes < 0 || xcd_boxes > 1 || halo < 0 || wide < 0 || wide > 2)
+        return gl::set_error(GL_ERR_ARG, "gl_gemm_force_knobs: halo_splits %d, wide_splits %d, wide_xcd %d, xcd_boxes %d, halo %d, wide %d", halo_splits, wide_splits, wide_xcd, xcd_boxes, halo, wide);
+    gemm_force_knobs(halo_splits, wide_splits, wide_xcd, xcd_boxes, halo, wide);
+    return GL_OK;
+}
+int gl_gemm_force_clear(void) { gemm_force_clear(); return GL_OK; }
+int gl_gemm_plan_log_clear(void) { gemm_plan_log_clear(); return GL_OK; }
+int gl_gemm_plan_log(gl_gemm_plan_record* out, int max, int* n_written, int* n_launches) {
+    if (!out || !n_written || !n_launches || max < 0) return gl::set_error(GL_ERR_ARG, "gl_gemm_plan_log: null pointer or negative max");
+    GemmLogEntry e[kGemmLogSize];
+    const int n = gemm_plan_log(e, std::min(max, (int)kGemmLogSize), n_launches);
+    for (int i = 0; i < n; ++i) {
+        const GemmPlan& p = e[i].plan;
+        gl_gemm_plan_record& r = out[i];
+        r = gl_gemm_plan_record{};
+        snprintf(r.kernel, sizeof r.kernel, "%s", p.name);
+        r.family = p.family; r.M = e[i].M; r.N = e[i].N; r.K = e[i].K;
+        r.tm = p.tm; r.tn = p.tn; r.splits = p.splits; r.grid = p.grid;
+        if (p.family == GEMM_HALO) { r.n_items = p.halo.n_items; r.units_per_split = p.halo.chunks_per_split; }
+        else if (p.family == GEMM_WIDE) { r.n_items = p.wide.n_items; r.units_per_split = p.wide.kt_per_split; r.xcd = p.wide.xcd; }
+        else {
+            r.n_items = p.work.n_items; r.units_per_split = p.work.kt_per_split;
+            if (p.family != GEMM_GLDS) { r.box = p.work.box; r.rm = p.work.rm; r.rz = p.work.rz; }
+        }
+    }
+    *n_written = n;
+    return GL_OK;
+}
 
 int gl_box_calibrate(gl_ctx* ctx, gl_box_calibration* out, gl_stream s) {
     NEED(ctx);
@@ -1149,13 +1191,58 @@ int gl_op_layernorm(gl_ctx* ctx, const void* x, const void* x2, int B, int N1, i
     GL_API_END
 }
 
+// The projections of gl_op_attention into the head-layout buffers q, k, vt (one fused EPI_QKV_HEADS launch for self-attention, else
+// q scatter, k scatter into the key-tile layout and v^T): shared by gl_op_attention and gl_op_attention_project.
+static void attention_project(Engine& eng, const void* xq, const void* xkv, int B, int Nq, int Nk, int C, int Ck, int H, const float* wq,
+                              const float* wk, const float* wv, bf16* q, bf16* k, bf16* vt, int Tq_pad, int Tk_pad, int dp, int dpv, int vt_layout,
+                              hipStream_t s) {
+    Arena& ar = eng.arena();
+    const int d = C / H, Tq = round_up(Nq, 64), Tk = round_up(Nk, 64);
+    bf16* wqb = ar.get<bf16>((size_t)C * C);
+    bf16* wkb = ar.get<bf16>((size_t)C * Ck);
+    bf16* wvb = ar.get<bf16>((size_t)C * Ck);
+    bf16* xqp = ar.get<bf16>((size_t)B * Tq * C);
+    bf16* xkp = ar.get<bf16>((size_t)B * Tk * Ck);
+    auto ck = [&](int rc) { if (rc != GL_OK) throw GlError(rc, gl::last_error()); };
+    ck(cast_f32_bf16_launch(wq, wqb, (int64_t)C * C, s));
+    ck(cast_f32_bf16_launch(wk, wkb, (int64_t)C * Ck, s));
+    ck(cast_f32_bf16_launch(wv, wvb, (int64_t)C * Ck, s));
+    ck(pad_rows_bf16_launch((const bf16*)xq, xqp, B, Nq, Tq, C, s));
+    ck(pad_rows_bf16_launch((const bf16*)xkv, xkp, B, Nk, Tk, Ck, s));
+    // self-attention (same rows for q, k, v): the engine's fused projection, one EPI_QKV_HEADS GEMM (GL_QKV_FUSED=0: off)
+    const bool fused = xq == xkv && C == Ck && Nq == Nk && gemm_supports_qkv() && (2 * C) % 128 == 0 &&
+                       !(dev_env("GL_QKV_FUSED") && atoi(dev_env("GL_QKV_FUSED")) == 0);
+    if (fused) {
+        bf16* wqkv = ar.get<bf16>((size_t)3 * C * C);
+        ck(cast_f32_bf16_launch(wq, wqkv, (int64_t)C * C, s));
+        ck(cast_f32_bf16_launch(wk, wqkv + (size_t)C * C, (int64_t)C * C, s));
+        ck(cast_f32_bf16_launch(wv, wqkv + (size_t)2 * C * C, (int64_t)C * C, s));
+        Epilogue E = e_heads(EPI_QKV_HEADS, q, k, C, H, d, dp, Tq, Tq_pad, Tk_pad);
+        E.vt = vt; E.DPV = dpv; E.vt_perm32 = vt_layout;
+        ck(gemm_launch(a_rows(xqp, C), wqkv, B * Tq, 3 * C, C, E, nullptr, 0, s));
+    } else {
+        ck(gemm_launch(a_rows(xqp, C), wqb, B * Tq, C, C, e_heads(EPI_QK_HEADS, q, nullptr, C, H, d, dp, Tq, Tq_pad, 0), eng.splitk_ws(),
+                       eng.splitk_ws_bytes(), s));
+        {
+            Epilogue E = e_heads(EPI_QK_HEADS, k, nullptr, C, H, d, dp, Tk, Tk_pad, 0);
+            E.q_tiled = 1;
+            ck(gemm_launch(a_rows(xkp, Ck), wkb, B * Tk, C, Ck, E, eng.splitk_ws(), eng.splitk_ws_bytes(), s));
+        }
+        {
+            Epilogue E;
+            epilogue_defaults(E);
+            E.mode = EPI_VT_HEADS; E.out = vt; E.H = H; E.d = d; E.DPV = dpv; E.T = Tk; E.Tpad_k = Tk_pad; E.vt_perm32 = vt_layout;
+            ck(gemm_launch_t(wvb, C, xkp, B * Tk, Ck, E, s));
+        }
+    }
+}
+
 int gl_op_attention(gl_ctx* ctx, const void* xq, const void* xkv, int B, int Nq, int Nk, int C, int Ck, int H,
                     const float* wq, const float* wk, const float* wv, void* o, gl_stream s) {
     NEED(ctx);
     GL_API_BEGIN
     Engine& eng = *ctx->eng;
-    Arena& ar = eng.arena();
-    ar.reset();
+    eng.arena().reset();
     if (C % H != 0) throw GlError(GL_ERR_ARG, "C must be divisible by H");
     const int d = C / H;
     int dp, dpv;
@@ -1164,46 +1251,32 @@ int gl_op_attention(gl_ctx* ctx, const void* xq, const void* xkv, int B, int Nq,
     const int Tq = round_up(Nq, 64), Tk = round_up(Nk, 64);
     const int vt_layout = attn_vt_layout(d, Nk, &dpv);
     AttnBufs& bufs = eng.attn_bufs(B, H, d, Tq, Tk, dpv);
-    bf16* wqb = ar.get<bf16>((size_t)C * C);
-    bf16* wkb = ar.get<bf16>((size_t)C * Ck);
-    bf16* wvb = ar.get<bf16>((size_t)C * Ck);
-    bf16* xqp = ar.get<bf16>((size_t)B * Tq * C);
-    bf16* xkp = ar.get<bf16>((size_t)B * Tk * Ck);
-    auto ck = [&](int rc) { if (rc != GL_OK) throw GlError(rc, gl::last_error()); };
-    ck(cast_f32_bf16_launch(wq, wqb, (int64_t)C * C, S(s)));
-    ck(cast_f32_bf16_launch(wk, wkb, (int64_t)C * Ck, S(s)));
-    ck(cast_f32_bf16_launch(wv, wvb, (int64_t)C * Ck, S(s)));
-    ck(pad_rows_bf16_launch((const bf16*)xq, xqp, B, Nq, Tq, C, S(s)));
-    ck(pad_rows_bf16_launch((const bf16*)xkv, xkp, B, Nk, Tk, Ck, S(s)));
-    // self-attention (same rows for q, k, v): the engine's fused projection, one EPI_QKV_HEADS GEMM (GL_QKV_FUSED=0: off)
-    const bool fused = xq == xkv && C == Ck && Nq == Nk && gemm_supports_qkv() && (2 * C) % 128 == 0 &&
-                       !(dev_env("GL_QKV_FUSED") && atoi(dev_env("GL_QKV_FUSED")) == 0);
-    if (fused) {
-        bf16* wqkv = ar.get<bf16>((size_t)3 * C * C);
-        ck(cast_f32_bf16_launch(wq, wqkv, (int64_t)C * C, S(s)));
-        ck(cast_f32_bf16_launch(wk, wqkv + (size_t)C * C, (int64_t)C * C, S(s)));
-        ck(cast_f32_bf16_launch(wv, wqkv + (size_t)2 * C * C, (int64_t)C * C, S(s)));
-        Epilogue E = e_heads(EPI_QKV_HEADS, bufs.q, bufs.k, C, H, d, dp, Tq, bufs.Tq_pad, bufs.Tk_pad);
-        E.vt = bufs.vt; E.DPV = dpv; E.vt_perm32 = vt_layout;
-        ck(gemm_launch(a_rows(xqp, C), wqkv, B * Tq, 3 * C, C, E, nullptr, 0, S(s)));
-    } else {
-        ck(gemm_launch(a_rows(xqp, C), wqb, B * Tq, C, C, e_heads(EPI_QK_HEADS, bufs.q, nullptr, C, H, d, dp, Tq, bufs.Tq_pad, 0), eng.splitk_ws(),
-                       eng.splitk_ws_bytes(), S(s)));
-        {
-            Epilogue E = e_heads(EPI_QK_HEADS, bufs.k, nullptr, C, H, d, dp, Tk, bufs.Tk_pad, 0);
-            E.q_tiled = 1;
-            ck(gemm_launch(a_rows(xkp, Ck), wkb, B * Tk, C, Ck, E, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s)));
-        }
-        {
-            Epilogue E;
-            epilogue_defaults(E);
-            E.mode = EPI_VT_HEADS; E.out = bufs.vt; E.H = H; E.d = d; E.DPV = dpv; E.T = Tk; E.Tpad_k = bufs.Tk_pad; E.vt_perm32 = vt_layout;
-            ck(gemm_launch_t(wvb, C, xkp, B * Tk, Ck, E, S(s)));
-        }
-    }
+    attention_project(eng, xq, xkv, B, Nq, Nk, C, Ck, H, wq, wk, wv, bufs.q, bufs.k, bufs.vt, bufs.Tq_pad, bufs.Tk_pad, dp, dpv, vt_layout, S(s));
     AttnParams P = attn_params(bufs.q, bufs.k, bufs.vt, (bf16*)o, H, d, Nq, Nk, bufs.Tq_pad, bufs.Tk_pad, vt_layout);
     P.counters = eng.attn_counters();     // nullptr unless gl_attn_regime_counters switched counting on
-    ck(attn_launch(P, B, S(s)));
+    r = attn_launch(P, B, S(s));
+    if (r != GL_OK) throw GlError(r, gl::last_error());
+    GL_API_END
+}
+
+// include/gligen_amd_gemm_plans.h: the same projections into the caller's buffers
+int gl_op_attention_project(gl_ctx* ctx, const void* xq, const void* xkv, int B, int Nq, int Nk, int C, int Ck, int H, const float* wq,
+                            const float* wk, const float* wv, void* q, void* k, void* vt, gl_attn_proj_layout* layout, gl_stream s) {
+    NEED(ctx);
+    if (!layout) return gl::set_error(GL_ERR_ARG, "gl_op_attention_project: null layout");
+    GL_API_BEGIN
+    Engine& eng = *ctx->eng;
+    if (H <= 0 || C % H != 0) throw GlError(GL_ERR_ARG, "C must be divisible by H");
+    const int d = C / H;
+    int dp, dpv;
+    int r = attn_dims(d, &dp, &dpv);
+    if (r != GL_OK) throw GlError(r, gl::last_error());
+    const int vt_layout = attn_vt_layout(d, Nk, &dpv);
+    *layout = gl_attn_proj_layout{d, dp, dpv, round_up(Nq, 64), round_up(Nk, 64), round_up(round_up(Nq, 64), 128), round_up(Nk, 64), vt_layout};
+    if (!q && !k && !vt) return GL_OK;
+    if (!xq || !xkv || !wq || !wk || !wv || !q || !k || !vt) throw GlError(GL_ERR_ARG, "gl_op_attention_project: null pointer");
+    eng.arena().reset();
+    attention_project(eng, xq, xkv, B, Nq, Nk, C, Ck, H, wq, wk, wv, (bf16*)q, (bf16*)k, (bf16*)vt, layout->tq_pad, layout->tk_pad, dp, dpv, vt_layout, S(s));
     GL_API_END
 }
 

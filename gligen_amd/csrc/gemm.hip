@@ -27,6 +27,7 @@
 #include "gemm_plan.h"
 
 #include <algorithm>
+#include <climits>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -2492,6 +2493,16 @@ static thread_local GemmPlan t_last = [] { GemmPlan p{}; strcpy(p.name, "gemm");
 int gemm_last_stats_nb() { return t_last.stats_nb; }
 const char* gemm_last_kernel_name() { return t_last.name; }
 void gemm_last_cfg(int* tm, int* tn, int* splits) { *tm = t_last.tm; *tn = t_last.tn; *splits = t_last.splits; }
+// the plan log: a ring of the calling thread's last kGemmLogSize launches (ops such as gl_op_attention make several)
+static thread_local GemmLogEntry t_log[kGemmLogSize];
+static thread_local int t_log_n = 0;   // launches since the last clear
+void gemm_plan_log_clear() { t_log_n = 0; }
+int gemm_plan_log(GemmLogEntry* out, int max, int* launches) {
+    if (launches) *launches = t_log_n;
+    const int n = std::max(0, std::min(std::min(t_log_n, kGemmLogSize), max));
+    for (int i = 0; i < n; ++i) out[i] = t_log[(t_log_n - n + i) % kGemmLogSize];
+    return n;
+}
 
 namespace {
 
@@ -2635,6 +2646,8 @@ int gemm_launch(const AOperand& A, const bf16* W, int M, int N, int K, const Epi
     GemmPlan plan;
     GL_TRY(gemm_plan(A, M, N, K, E, ws != nullptr, ws_bytes, plan, [&](auto&&... a) { return tune(W, ws, stream, a...); }));
     t_last = plan;
+    t_log[t_log_n % kGemmLogSize] = GemmLogEntry{plan, M, N, K};
+    t_log_n = t_log_n == INT_MAX ? kGemmLogSize : t_log_n + 1;   // (the ring position survives the wrap: kGemmLogSize divides 2^31)
     return execute(plan, A, W, M, N, K, E, ws, stream);
 }
 

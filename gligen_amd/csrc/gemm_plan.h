@@ -38,9 +38,13 @@ struct GemmKnobs {
     int xcd_boxes = 1, wide_xcd = -1;             // GL_GEMM_XCD_BOXES, GL_WIDE_XCD (-1 = by column-tile count)
     int autotune = 1, tune_reps = 3, corun = 0;   // GL_GEMM_AUTOTUNE / gemm_set_autotune, GL_GEMM_TUNE_REPS, GL_GEMM_TUNE_CORUN
     bool no_table = false, tune_log = false;      // GL_GEMM_NO_TABLE, GL_GEMM_TUNE_LOG (set = on)
-    int force_tm = 0, force_tn = 0, force_splits = 0, force_grid = 0;   // gemm_force_cfg / gemm_force_grid (kbench sweeps)
+    int force_tm = 0, force_tn = 0, force_splits = 0, force_grid = 0;   // gemm_force_cfg / gemm_force_grid (kbench sweeps, gl_gemm_force_plan)
 };
 GemmKnobs& gemm_knobs();
+// The knobs a test sets through include/gligen_amd_gemm_plans.h that otherwise only the environment reaches; gemm_force_clear puts
+// them back to what the environment / the defaults say and drops gemm_force_cfg / gemm_force_grid.
+void gemm_force_knobs(int halo_splits, int wide_splits, int wide_xcd, int xcd_boxes, int halo, int wide);
+void gemm_force_clear();
 
 struct GemmProblem {
     const AOperand& A;
@@ -67,6 +71,12 @@ struct GemmPlan {
     int stats_nb;         // column blocks of row statistics this launch writes to Epilogue::stats_out (0: none)
     char name[96];
 };
+
+// ---- the plan log (gemm.hip): what gemm_launch executed on the calling thread since the last clear, newest kGemmLogSize kept
+struct GemmLogEntry { GemmPlan plan; int M, N, K; };
+constexpr int kGemmLogSize = 32;
+void gemm_plan_log_clear();
+int gemm_plan_log(GemmLogEntry* out, int max, int* launches);   // oldest first; returns the entries written, *launches = launches since the clear
 
 // ---- the p / u family, for the tuner: what it times, and the plan of one candidate
 std::vector<GemmCand> gemm_tune_candidates(const GemmProblem& pb, bool use_u);

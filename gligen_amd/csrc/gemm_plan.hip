@@ -33,6 +33,16 @@ void gemm_set_variant(int v) { gemm_knobs().variant = v < 0 ? read_knobs().varia
 void gemm_set_autotune(int on) { gemm_knobs().autotune = on < 0 ? read_knobs().autotune : on; }
 void gemm_force_cfg(int tm, int tn, int splits) { gemm_knobs().force_tm = tm; gemm_knobs().force_tn = tn; gemm_knobs().force_splits = splits; }
 void gemm_force_grid(int g) { gemm_knobs().force_grid = g; }
+void gemm_force_knobs(int halo_splits, int wide_splits, int wide_xcd, int xcd_boxes, int halo, int wide) {
+    GemmKnobs& k = gemm_knobs();
+    k.halo_splits = halo_splits; k.wide_splits = wide_splits; k.wide_xcd = wide_xcd; k.xcd_boxes = xcd_boxes; k.halo = halo; k.wide = wide;
+}
+void gemm_force_clear() {
+    const GemmKnobs d = read_knobs();
+    gemm_force_cfg(0, 0, 0);
+    gemm_force_grid(0);
+    gemm_force_knobs(d.halo_splits, d.wide_splits, d.wide_xcd, d.xcd_boxes, d.halo, d.wide);
+}
 static thread_local int t_no_split = 0;
 void gemm_set_no_split(int on) { t_no_split = on; }
 static thread_local int t_plan_scale = 1;
@@ -300,7 +310,8 @@ static void tuned_key(const GemmProblem& pb, bool use_u, char* key, size_t n) {
 static bool forced_choice(const GemmProblem& pb, bool use_u, GemmCand& out) {
     const GemmKnobs& kn = gemm_knobs();
     const int want = kn.force_splits ? kn.force_splits : 1;   // no split given: unsplit
-    if (!kn.force_tm || std::find(kSp, kSp + 10, want) == kSp + 10) return false;
+    // any split count that is its own normal form (nk = 10: 5 = cdiv(10, cdiv(10, 6)) is what the tuner's 6 runs as), not kSp alone
+    if (!kn.force_tm || want < 1 || want > kSp[9]) return false;
     for (int c = 0; c < kGemmTiles; ++c) {
         int sp = want;
         if (kGemmTm[c] != kn.force_tm || kGemmTn[c] != kn.force_tn || !feasible(pb, use_u, c, sp) || sp != want) continue;

@@ -632,6 +632,32 @@ class Engine:
         evaluation of the sampler (default) or at the full batch like the rest. Process-wide; captured graphs are dropped."""
         check(self.lib.gl_set_cfg_shared_prefix(int(bool(on))))
 
+    # ---- one named GEMM plan at a time (include/gligen_amd_gemm_plans.h; process-wide forcing, per-thread log)
+    def gemm_force_plan(self, tm=0, tn=0, splits=0, grid_cap=0) -> None:
+        """gl_gemm_force_plan: tile (units of 32), K split and resident-grid cap of the p / u kernels. A choice that does not fit a
+        problem is planned as usual: gemm_plan_log tells what ran."""
+        check(self.lib.gl_gemm_force_plan(int(tm), int(tn), int(splits), int(grid_cap)))
+
+    def gemm_force_knobs(self, halo_splits, wide_splits, wide_xcd, xcd_boxes, halo, wide) -> None:
+        """gl_gemm_force_knobs; every knob is given (gemm_force_clear puts the library's own defaults back)."""
+        check(self.lib.gl_gemm_force_knobs(int(halo_splits), int(wide_splits), int(wide_xcd), int(xcd_boxes), int(halo), int(wide)))
+
+    def gemm_force_clear(self) -> None:
+        check(self.lib.gl_gemm_force_clear())
+
+    def gemm_plan_log_clear(self) -> None:
+        check(self.lib.gl_gemm_plan_log_clear())
+
+    def gemm_plan_log(self):
+        """(records, launches): the calling thread's GEMM launches since gemm_plan_log_clear as dicts (the newest 32, in launch
+        order), and how many there were."""
+        from ._lib import GemmPlanRecord
+        recs = (GemmPlanRecord * 32)()
+        n, total = C.c_int(0), C.c_int(0)
+        check(self.lib.gl_gemm_plan_log(recs, 32, C.byref(n), C.byref(total)))
+        out = [{f: (getattr(r, f).decode() if f == "kernel" else getattr(r, f)) for f, _ in GemmPlanRecord._fields_} for r in recs[:n.value]]
+        return out, total.value
+
     def ff_rows_policy_report(self) -> str:
         buf = C.create_string_buffer(4096)
         check(self.lib.gl_ff_rows_policy_report(buf, 4096))

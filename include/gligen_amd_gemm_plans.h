@@ -1,0 +1,66 @@
+/* gligen_amd_gemm_plans.h -- run the GEMM / conv launcher of libgligen_amd.so with one named plan, and read back what it ran.
+ * Which tile, K split, resident grid and XCD item order a problem gets is decided at run time (shipped table, analytic model,
+ * on-device tuner); these entries exist so that every plan the planner can choose is held to a reference by itself
+ * (tests/test_gemm_candidates_gpu.py) -- the engine does not go through them. They mirror the GL_GEMM_* / GL_CONV_HALO* / GL_WIDE_XCD
+ * developer switches (tools/README.md) as calls. Conventions as in gligen_amd.h. The forcing is process-wide: set it before
+ * launching, not while other threads launch; the log is per calling thread. */
+#ifndef GLIGEN_AMD_GEMM_PLANS_H
+#define GLIGEN_AMD_GEMM_PLANS_H
+#include "gligen_amd.h"
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+/* The tile (tm, tn in units of 32 rows / columns: 4x5, 4x4, 2x5, 2x4, 2x2), the K split (1 .. 32) and the cap on resident
+ * workgroups (0: 512) of gemm_p_kernel / gemm_u_kernel. tm = 0: no forced tile (the cap still holds). While a tile is forced, the
+ * problems that would go to conv_halo_kernel / gemm_wide_kernel run on gemm_u_kernel. A choice that does not fit a problem (the
+ * split leaves fewer than two K tiles per part, the workspace is too small, a tile the epilogue has no form for, a split count such
+ * as 6 of 10 K tiles that is the same launch as 5) is NOT an error: that problem is planned as usual -- read the log. */
+int gl_gemm_force_plan(int tm, int tn, int splits, int grid_cap);
+
+/* halo_splits / wide_splits: K split of conv_halo_kernel / gemm_wide_kernel (0: automatic). wide_xcd: the wide kernel's item order
+ * (-1: by column-tile count, 0 linear, 1 contiguous ranges per XCD). xcd_boxes: gemm_u_kernel's XCD box partition (1 on, 0 linear
+ * ranges). halo: eligible 3x3 convs with M >= 256 * halo go to conv_halo_kernel (8; 0: never). wide: what gemm_wide_kernel takes (0
+ * nothing, 1 the GEGLU projections, 2 every row GEMM it is eligible for). */
+int gl_gemm_force_knobs(int halo_splits, int wide_splits, int wide_xcd, int xcd_boxes, int halo, int wide);
+
+/* Drop gl_gemm_force_plan and put the six knobs back to their defaults (with GL_DEV_SWITCHES=1: to what the environment says). */
+int gl_gemm_force_clear(void);
+
+typedef struct gl_gemm_plan_record {
+    char kernel[96];      /* kernel name with template arguments, " + splitk_reduce_kernel" behind a split launch */
+    int family;           /* 0 gemm_glds_kernel, 1 gemm_p_kernel, 2 gemm_u_kernel, 3 conv_halo_kernel, 4 gemm_wide_kernel */
+    int M, N, K;
+    int tm, tn;           /* tile in units of 32 (halo / wide: tm = 8) */
+    int splits;
+    int grid;             /* workgroups launched (gemm_glds_kernel: tiles, times splits in z) */
+    int n_items;          /* work items: tiles x splits (gemm_glds_kernel: tiles) */
+    int box, rm, rz;      /* p / u: XCD partition (box < 0: linear ranges; else lgm | lgn << 4, rows and splits per box); else 0 */
+    int units_per_split;  /* K tiles of 64 per split; conv_halo_kernel: chunks of 64 channels per split */
+    int xcd;              /* gemm_wide_kernel: item order (1: contiguous ranges per XCD); else 0 */
+} gl_gemm_plan_record;
+
+#define GL_GEMM_PLAN_LOG_SIZE 32
+
+/* The launches gemm_launch made on the calling thread since gl_gemm_plan_log_clear: the newest min(launches, 32, max) in launch
+ * order into out, their number into *n_written, the launches since the clear into *n_launches (more than 32: the oldest fell out). */
+int gl_gemm_plan_log_clear(void);
+int gl_gemm_plan_log(gl_gemm_plan_record* out, int max, int* n_written, int* n_launches);
+
+/* The projections of gl_op_attention alone, into the caller's buffers, so that a test can hold q, k and v^T to a reference and see what
+ * is not written: one fused launch when xq == xkv (same pointer, C == Ck, Nq == Nk), else the q scatter, the k scatter and the v^T
+ * projection. Tokens are padded with zero rows to tq / tk (multiples of 64), and those rows are written.
+ *   q  [B H][tq_pad][dp]        row-major; rows >= tq and columns >= d are not written
+ *   k  [B H][tk_pad / 64][dp / 8][64][8]   the key-tile layout (element (t, c) at (t / 64, c / 8, t % 64, c % 8)); columns >= d not written
+ *   vt [B H][dpv][tk_pad]       feature rows >= d not written; inside every group of 16 tokens (32 when vt_perm32) the quads of 4 tokens
+ *                               are stored in the order 0 2 1 3 (0 2 4 6 1 3 5 7)
+ * With q, k and vt all NULL only *layout is filled (the sizes to allocate). */
+typedef struct gl_attn_proj_layout { int d, dp, dpv, tq, tk, tq_pad, tk_pad, vt_perm32; } gl_attn_proj_layout;
+int gl_op_attention_project(gl_ctx* ctx, const void* xq, const void* xkv, int B, int Nq, int Nk, int C, int Ck, int H, const float* wq,
+                            const float* wk, const float* wv, void* q, void* k, void* vt, gl_attn_proj_layout* layout, gl_stream s);
+
+#ifdef __cplusplus
+}
+#endif
+#endif
