@@ -1,6 +1,6 @@
 """ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
 include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h, include/gligen_amd_train_fusers.h, include/gligen_amd_train_prims.h,
-include/gligen_amd_trainer.h, include/gligen_amd_sampler.h and include/gligen_amd_gemm_plans.h).
+include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_gemm_plans.h and include/gligen_amd_attention_core.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -247,6 +247,13 @@ GEMM_PLAN_SYMBOLS = {
     "gl_op_attention_project": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, C.POINTER(AttnProjLayout), _P]),
 }
 
+# every symbol include/gligen_amd_attention_core.h declares (one attention kernel on the caller's q, k, v^T buffers)
+ATTENTION_CORE_SYMBOLS = {
+    "gl_op_attention_core": (_I, [_P, _P, _P, _P, C.POINTER(AttnProjLayout), _I, _I, _I, _I, _P, _I, _I, _I, _P]),
+}
+ATTN_CORE_KERNELS = {"auto": 0, "attn_kernel": 1, "attn2_kernel_w4": 2, "attn2_kernel_w8": 3, "attn3_kernel": 4}   # = GL_ATTN_CORE_*
+GL_ERR_UNSUPPORTED = 5
+
 # gl_unet_config.fuser_kind / the fuser_kind of gl_op_block_train_fuser, by the reference's fuser_type
 FUSER_KINDS = {"gatedSA": 0, "gatedSA2": 1, "gatedCA": 2}
 
@@ -277,7 +284,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS, **TRAIN_PRIM_SYMBOLS,
-                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **GEMM_PLAN_SYMBOLS}.items():
+                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -31,6 +31,10 @@ int attn_dims(int d, int* DP, int* DPV);
 // 64, tokens permuted inside groups of 32 as [0-3, 8-11, 16-19, 24-27, 4-7, 12-15, 20-23, 28-31].
 int attn_vt_layout(int d, int Nk, int* DPV);
 int attn_launch(const AttnParams& P, int B, hipStream_t stream);
+// One named kernel on the caller's buffers (gl_op_attention_core; = the GL_ATTN_CORE_* of include/gligen_amd_attention_core.h): AUTO is
+// attn_launch; a kernel without an instantiation for (d, vt_layout, DPV rows of V^T), or a pipelined one with Nk <= 128: GL_ERR_UNSUPPORTED
+enum { ATTN_SEL_AUTO = 0, ATTN_SEL_V1 = 1, ATTN_SEL_V2_W4 = 2, ATTN_SEL_V2_W8 = 3, ATTN_SEL_V3 = 4 };
+int attn_launch_select(const AttnParams& P, int B, int DPV, int kernel, hipStream_t stream);
 const char* attn_kernel_name(int d, int Nk, int vt_layout = -1);  // kernel symbol attn_launch uses for head dim d and Nk keys (buffers laid out per attn_vt_layout)
 // one-time init of a V^T buffer [BH][DPV][Tk_pad]: padding row d := 1.0 (the softmax denominator row)
 int attn_vt_ones_launch(bf16* vt, int BH, int d, int Tk_pad, hipStream_t stream, int DPV = 0);   // DPV 0: attn_dims'

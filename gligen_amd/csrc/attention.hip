@@ -1183,4 +1183,35 @@ int attn_launch(const AttnParams& P, int B, hipStream_t stream) {
     }
 }
 
+// gl_op_attention_core (include/gligen_amd_attention_core.h): one named kernel instead of attn_launch's choice -- the same launch
+// helpers, nothing else. DPV: the row count of the caller's V^T buffer (it has to be the instantiation's).
+int attn_launch_select(const AttnParams& P, int B, int DPV, int kernel, hipStream_t stream) {
+    if (kernel == ATTN_SEL_AUTO) return attn_launch(P, B, stream);
+    if (P.Nq <= 0 || P.Nk <= 0) return set_error(GL_ERR_ARG, "attention: empty Nq=%d Nk=%d", P.Nq, P.Nk);
+    if (P.Tq_pad % 128 != 0 || P.Tk_pad % 64 != 0 || P.Tq_pad < P.Nq || P.Tk_pad < P.Nk)
+        return set_error(GL_ERR_ARG, "attention: bad padding Tq_pad=%d Tk_pad=%d (Nq=%d Nk=%d)", P.Tq_pad, P.Tk_pad, P.Nq, P.Nk);
+    const bool pipelined = kernel != ATTN_SEL_V1;
+    if (pipelined && P.Nk <= 128)
+        return set_error(GL_ERR_UNSUPPORTED, "attention: the pipelined kernels run with more than two key tiles (Nk = %d)", P.Nk);
+    switch (kernel) {
+        case ATTN_SEL_V1:
+            if (P.vt_layout == 0 && P.d == 40 && DPV == 64) return launch_attn<48, 64, true>(P, B, stream);
+            if (P.vt_layout == 0 && P.d == 80 && DPV == 96) return launch_attn<80, 96, true>(P, B, stream);
+            if (P.vt_layout == 0 && P.d == 160 && DPV == 160) return launch_attn<160, 160, false>(P, B, stream);
+            break;
+        case ATTN_SEL_V2_W4:
+            if (P.vt_layout == 0 && P.d == 40 && DPV == 64) return launch_attn2<48, 64, true, 4>(P, B, stream);
+            break;
+        case ATTN_SEL_V2_W8:
+            if (P.vt_layout == 0 && P.d == 40 && DPV == 64) return launch_attn2<48, 64, true, 8>(P, B, stream);
+            break;
+        case ATTN_SEL_V3:
+            if (P.vt_layout == 1 && P.d == 40 && DPV == 48) return launch_attn3<48, 48, true, 4>(P, B, stream);
+            if (P.vt_layout == 1 && P.d == 80 && DPV == 96) return launch_attn3<80, 96, false, 4>(P, B, stream);
+            break;
+        default: return set_error(GL_ERR_ARG, "attention: kernel selector %d (0 .. 4)", kernel);
+    }
+    return set_error(GL_ERR_UNSUPPORTED, "attention: kernel %d has no instantiation for d = %d, vt layout %d, %d V^T rows", kernel, P.d, P.vt_layout, DPV);
+}
+
 }  // namespace gl

@@ -11,6 +11,7 @@
 #include "../../include/gligen_amd_trainer.h"
 #include "../../include/gligen_amd_sampler.h"
 #include "../../include/gligen_amd_gemm_plans.h"
+#include "../../include/gligen_amd_attention_core.h"
 #include "gemm_plan.h"
 
 #include <cstdlib>
@@ -1277,6 +1278,34 @@ int gl_op_attention_project(gl_ctx* ctx, const void* xq, const void* xkv, int B,
     if (!xq || !xkv || !wq || !wk || !wv || !q || !k || !vt) throw GlError(GL_ERR_ARG, "gl_op_attention_project: null pointer");
     eng.arena().reset();
     attention_project(eng, xq, xkv, B, Nq, Nk, C, Ck, H, wq, wk, wv, (bf16*)q, (bf16*)k, (bf16*)vt, layout->tq_pad, layout->tk_pad, dp, dpv, vt_layout, S(s));
+    GL_API_END
+}
+
+// include/gligen_amd_attention_core.h: one attention kernel on the caller's q, k, v^T (no projection in front, no buffer of the engine's)
+int gl_op_attention_core(gl_ctx* ctx, const void* q, const void* k, const void* vt, const gl_attn_proj_layout* layout, int B, int H, int Nq,
+                         int Nk, void* o, int ldo, int o_rows_per_b, int kernel, gl_stream s) {
+    NEED(ctx);
+    if (!q || !k || !vt || !o || !layout) return gl::set_error(GL_ERR_ARG, "gl_op_attention_core: null pointer");
+    GL_API_BEGIN
+    const gl_attn_proj_layout& L = *layout;
+    int dp, dpv;
+    int r = attn_dims(L.d, &dp, &dpv);
+    if (r != GL_OK) throw GlError(r, gl::last_error());
+    if (B <= 0 || H <= 0 || L.dp != dp) throw GlError(GL_ERR_ARG, "gl_op_attention_core: B, H > 0 and dp = 48 / 80 / 160 for d = 40 / 80 / 160");
+    if (ldo < H * L.d || ldo % 4 != 0 || o_rows_per_b < Nq || (reinterpret_cast<uintptr_t>(o) & 7) != 0)
+        throw GlError(GL_ERR_ARG, "gl_op_attention_core: ldo >= H d, ldo % 4 == 0, o_rows_per_b >= Nq, o 8-byte aligned");
+    if (((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(vt)) & 15) != 0)
+        throw GlError(GL_ERR_ARG, "gl_op_attention_core: q, k and vt are 16-byte aligned");
+    if (L.vt_perm32 != 0 && L.vt_perm32 != 1) throw GlError(GL_ERR_ARG, "gl_op_attention_core: vt_perm32 is 0 or 1");
+    // (the selector checks dpv against the named instantiation; attn_launch's own choice follows vt_perm32 alone)
+    if (kernel == ATTN_SEL_AUTO && L.dpv != (L.vt_perm32 && L.d == 40 ? 48 : dpv))
+        throw GlError(GL_ERR_ARG, "gl_op_attention_core: dpv does not belong to (d, vt_perm32)");
+    AttnParams P = attn_params((const bf16*)q, (const bf16*)k, (const bf16*)vt, (bf16*)o, H, L.d, Nq, Nk, L.tq_pad, L.tk_pad, L.vt_perm32);
+    P.ldo = ldo;
+    P.o_rows_per_b = o_rows_per_b;
+    P.counters = ctx->eng->attn_counters();     // as gl_op_attention: nullptr unless gl_attn_regime_counters switched counting on
+    r = attn_launch_select(P, B, L.dpv, kernel, S(s));
+    if (r != GL_OK) throw GlError(r, gl::last_error());
     GL_API_END
 }
 

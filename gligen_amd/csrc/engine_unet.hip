@@ -313,7 +313,10 @@ void Engine::fuser_kv_fill(const STW& t, int B, int HW, hipStream_t s) {
     Epilogue E = e_heads(EPI_QKV_HEADS, bufs.q, bufs.k, C, H, d, dp, Ng64, bufs.Tq_pad, bufs.Tk_pad);
     E.vt = bufs.vt; E.DPV = dpv; E.tok_off = HW; E.vt_perm32 = vt_layout;
     E.bias = t.fa.b;          // W beta of the folded LayerNorm
-    CK(gemm_launch(a_rows(lno, C), t.fa.wqk, B * Ng64, 3 * C, C, E, ws_, ws_bytes_, s));   // (its q rows land behind the last query: never read)
+    // Its q rows land behind the last query, and the K / V^T rows Ng .. Ng64 - 1 hold the bias W beta, not zero: where they share a
+    // query block or key tile with real rows the attention kernels load them, without effect on the real rows -- the query guard and the
+    // `kv >= Nk` mask alone keep them out (include/gligen_amd_attention_core.h; tests/test_attention_core_gpu.py fills both places)
+    CK(gemm_launch(a_rows(lno, C), t.fa.wqk, B * Ng64, 3 * C, C, E, ws_, ws_bytes_, s));
     arena_.release(mk);
     if (fuser_kv_.size() < unet_.st.size()) fuser_kv_.resize(unet_.st.size());
     fuser_kv_[t.idx] = FuserKV{cond_epoch_, B, HW};

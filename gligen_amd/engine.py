@@ -1249,6 +1249,16 @@ class Engine:
                                        _ptr(o), _stream(self.device)))
         return o
 
+    def op_attention_core(self, q, k, vt, layout, B, heads, Nq, Nk, o, ldo, o_rows_per_b, kernel="auto"):
+        """One attention kernel on the caller's bf16 buffers (gl_op_attention_core; layouts and the buffer contract:
+        include/gligen_amd_attention_core.h). layout: an AttnProjLayout (d, dp, dpv, tq_pad, tk_pad, vt_perm32); kernel: a key of
+        _lib.ATTN_CORE_KERNELS. Writes rows < Nq, columns < heads * d of every sample of o [B][o_rows_per_b][ldo] and returns o; a
+        kernel with no instantiation for the layout raises GligenAmdError('libgligen_amd error 5: ...')."""
+        from ._lib import ATTN_CORE_KERNELS
+        check(self.lib.gl_op_attention_core(self._ctx, _ptr(q), _ptr(k), _ptr(vt), C.byref(layout), B, heads, Nq, Nk, _ptr(o), ldo, o_rows_per_b,
+                                            ATTN_CORE_KERNELS[kernel], _stream(self.device)))
+        return o
+
     def attn_regime_counters(self, enable):
         """(lazy_moves, reruns) counted by op_attention since the last call (gl_attn_regime_counters): the counts are reset, and
         counting is on afterwards iff `enable`. A test instrument: d = 40 only, 0 elsewhere."""
