@@ -1,6 +1,6 @@
 """ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
 include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h, include/gligen_amd_train_fusers.h, include/gligen_amd_train_prims.h,
-include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_gemm_plans.h and include/gligen_amd_attention_core.h).
+include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h and include/gligen_amd_attention_core.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -71,6 +71,20 @@ class PlmsArgs(C.Structure):
         ("noise", C.c_void_p), ("mask_B", C.c_int), ("x0_B", C.c_int), ("noise_B", C.c_int),
         ("sqrt_ac", C.POINTER(C.c_float)), ("sqrt_1mac", C.POINTER(C.c_float)),
         ("use_graph", C.c_int), ("sd_conv_w", C.c_void_p), ("sd_conv_b", C.c_void_p), ("sd_conv_step", C.c_int), ("ddim", C.c_int),
+    ]
+
+
+class SolverArgs(C.Structure):   # = gl_solver_args
+    _fields_ = [
+        ("struct_size", C.c_uint), ("B", C.c_int), ("h", C.c_int), ("w", C.c_int), ("n_steps", C.c_int),
+        ("timesteps", C.POINTER(C.c_int64)), ("a_t", C.POINTER(C.c_float)),
+        ("cx", C.POINTER(C.c_float)), ("c0", C.POINTER(C.c_float)), ("c1", C.POINTER(C.c_float)), ("c2", C.POINTER(C.c_float)),
+        ("cn", C.POINTER(C.c_float)), ("step_noise", C.c_void_p),
+        ("fuser_scale", C.POINTER(C.c_float)), ("guidance_scale", C.c_float),
+        ("x", C.c_void_p), ("inpaint_extra", C.c_void_p), ("mask", C.c_void_p), ("x0", C.c_void_p),
+        ("noise", C.c_void_p), ("mask_B", C.c_int), ("x0_B", C.c_int), ("noise_B", C.c_int),
+        ("sqrt_ac", C.POINTER(C.c_float)), ("sqrt_1mac", C.POINTER(C.c_float)),
+        ("use_graph", C.c_int), ("sd_conv_w", C.c_void_p), ("sd_conv_b", C.c_void_p), ("sd_conv_step", C.c_int),
     ]
 
 
@@ -228,6 +242,13 @@ SAMPLER_SYMBOLS = {
     "gl_set_cfg_shared_prefix": (_I, [_I]),
 }
 
+# every symbol include/gligen_amd_solver.h declares (the linear multistep solver loop and its update kernel)
+SOLVER_SYMBOLS = {
+    "gl_sample_solver": (_I, [_P, C.POINTER(SolverArgs), _P]),
+    "gl_op_solver_update": (_I, [_P, _P, _I, C.c_float, C.c_float, _P, _P, _P, _P, _P, _P] + [C.c_float] * 5 + [C.c_int64, _P]),
+}
+
+
 class GemmPlanRecord(C.Structure):   # = gl_gemm_plan_record
     _fields_ = [("kernel", C.c_char * 96)] + [(n, C.c_int) for n in ("family", "M", "N", "K", "tm", "tn", "splits", "grid", "n_items", "box", "rm", "rz",
                                                                      "units_per_split", "xcd")]
@@ -284,7 +305,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS, **TRAIN_PRIM_SYMBOLS,
-                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS}.items():
+                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -380,6 +380,30 @@ int gl_sample_plms(gl_ctx* ctx, const gl_plms_args* args, gl_stream s) {
     GL_API_END
 }
 
+int gl_sample_solver(gl_ctx* ctx, const gl_solver_args* args, gl_stream s) {
+    // the layout first: a caller built against another header is told so whatever else is wrong with the call
+    if (!args) return gl::set_error(GL_ERR_ARG, "null args");
+    if (args->struct_size != sizeof(gl_solver_args))
+        return gl::set_error(GL_ERR_ARG, "gl_sample_solver: args->struct_size is %u, this library's gl_solver_args has %zu bytes (set it to sizeof(gl_solver_args))",
+                             args->struct_size, sizeof(gl_solver_args));
+    NEED(ctx);
+    GL_API_BEGIN
+    ctx->eng->sample_solver(*args, S(s));
+    GL_API_END
+}
+
+int gl_op_solver_update(gl_ctx* ctx, const float* eps_pair, int has_uncond, float guidance, float a_t, const float* x, float* x_out,
+                        float* d0_out, const float* d1, const float* d2, const float* z, float cx, float c0, float c1, float c2, float cn,
+                        int64_t n, gl_stream s) {
+    NEED(ctx);
+    gl::SolverParams P{};
+    P.eps_pair = eps_pair; P.has_uncond = has_uncond ? 1 : 0; P.guidance = guidance;
+    P.d0_out = d0_out; P.d1 = d1; P.d2 = d2; P.z = z;
+    P.cx = cx; P.c0 = c0; P.c1 = c1; P.c2 = c2; P.cn = cn;
+    P.x = x; P.x_out = x_out; P.a_t = a_t; P.n = n;
+    return gl::solver_update_launch(P, S(s));
+}
+
 int gl_sampler_timing(gl_ctx* ctx, float* avg_unet_eval_ms, float* first_eval_ms, int* n_evals) {
     NEED(ctx);
     if (!avg_unet_eval_ms || !first_eval_ms || !n_evals) return gl::set_error(GL_ERR_ARG, "null pointer");

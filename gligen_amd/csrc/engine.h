@@ -23,6 +23,7 @@
 #include "norm.h"
 #include "train.h"
 #include "../../include/gligen_amd.h"
+#include "../../include/gligen_amd_solver.h"
 
 namespace gl {
 
@@ -132,6 +133,21 @@ bool cfg_shared_prefix();
 // the attention kernel's arguments over q / k / v^T in their head layouts, o [B][Nq][H * d]
 AttnParams attn_params(const bf16* q, const bf16* k, const bf16* vt, bf16* o, int H, int d, int Nq, int Nk, int Tq_pad, int Tk_pad, int vt_layout);
 
+// What a sampling run is apart from its update rule: the fields gl_plms_args and gl_solver_args have in common
+struct SamplerLoopArgs {
+    int B, h, w, n_steps;
+    const int64_t* timesteps;
+    const float* fuser_scale;
+    float guidance_scale;
+    float* x;
+    const float* inpaint_extra; const float* mask; const float* x0; const float* noise;
+    int mask_B, x0_B, noise_B;
+    const float* sqrt_ac; const float* sqrt_1mac;
+    int use_graph;
+    const float* sd_conv_w; const float* sd_conv_b;
+    int sd_conv_step;
+};
+
 class Engine {
    public:
     explicit Engine(int device);
@@ -180,6 +196,7 @@ class Engine {
     void clip_vision_encode(const float* pixel_values, int S, float* last_hidden, float* pooled, float* image_embeds, hipStream_t s);
     int clip_vision_tokens() const { const int g = clipv_.cfg.patch ? clipv_.cfg.image_size / clipv_.cfg.patch : 0; return g * g + 1; }
     void sample_plms(const gl_plms_args& a, hipStream_t s);
+    void sample_solver(const gl_solver_args& a, hipStream_t s);
     void sampler_timing(float* avg_ms, float* first_ms, int* n);
 
     // single-op entry points (tests / profiling)
@@ -485,6 +502,11 @@ class Engine {
     } smp_;
     void sampler_release_graph();
     void sampler_wait_idle();
+    // One sampling run around `step(i, eval, n, cfg, s)`, the update rule of step i (engine_sampler.hip, where both loops live): stream
+    // choice and the run's end event, the buffers, the time-embedding table, the evaluation (eager once, then captured and replayed), the
+    // gate-scale schedule, the SD first-conv swap and the inpainting blend. `who` is the entry point's name in error messages.
+    template <class Step>
+    void sampler_run(const SamplerLoopArgs& a, const char* who, hipStream_t caller, Step&& step);
 };
 
 }  // namespace gl

@@ -39,7 +39,8 @@ void Engine::sampler_release_graph() {
     }
 }
 
-void Engine::sample_plms(const gl_plms_args& a, hipStream_t caller) {
+template <class Step>
+void Engine::sampler_run(const SamplerLoopArgs& a, const char* who, hipStream_t caller, Step&& step) {
     if (!unet_.present || !finalized_) throw GlError(GL_ERR_STATE, "unet not finalized");
     // The loop runs on the CALLER's stream -- one stream per execution context: with a second, engine-owned stream per context the
     // lanes of a process are four streams on the chip's few hardware queues, and which lanes overlap depends on the order the streams
@@ -67,14 +68,14 @@ void Engine::sample_plms(const gl_plms_args& a, hipStream_t caller) {
         ~DoneGuard() { (void)hipEventRecord(e->smp_.ev_done, s); e->smp_.run_stream = s; e->smp_.ran = true; }
     } done_guard{this, s};
     const gl_unet_config& c = unet_.cfg;
-    if (a.n_steps < 1 || !a.timesteps || !a.a_t || !a.a_prev || !a.x) throw GlError(GL_ERR_ARG, "sample_plms: missing schedule or latent");
-    if (a.mask && (!a.x0 || !a.noise || !a.sqrt_ac || !a.sqrt_1mac)) throw GlError(GL_ERR_ARG, "sample_plms: mask needs x0, noise and q_sample coefficients");
+    if (a.n_steps < 1 || !a.timesteps || !a.x) throw GlError(GL_ERR_ARG, fmt("%s: missing schedule or latent", who));
+    if (a.mask && (!a.x0 || !a.noise || !a.sqrt_ac || !a.sqrt_1mac)) throw GlError(GL_ERR_ARG, fmt("%s: mask needs x0, noise and q_sample coefficients", who));
     const int maskB = a.mask_B ? a.mask_B : a.B, x0B = a.x0_B ? a.x0_B : a.B, noiseB = a.noise_B ? a.noise_B : a.B;
     if (a.mask && ((maskB != 1 && maskB != a.B) || (x0B != 1 && x0B != a.B) || (noiseB != 1 && noiseB != a.B)))
-        throw GlError(GL_ERR_ARG, fmt("sample_plms: mask / x0 / noise batch (%d, %d, %d) must be 1 or the latent batch %d", maskB, x0B, noiseB, a.B));
+        throw GlError(GL_ERR_ARG, fmt("%s: mask / x0 / noise batch (%d, %d, %d) must be 1 or the latent batch %d", who, maskB, x0B, noiseB, a.B));
     const bool cfg = a.guidance_scale != 1.f;
     const int Beff = cfg ? 2 * a.B : a.B;
-    if (cond_.Beff != Beff) throw GlError(GL_ERR_STATE, fmt("sample_plms: conditioning batch is %d, need %d", cond_.Beff, Beff));
+    if (cond_.Beff != Beff) throw GlError(GL_ERR_STATE, fmt("%s: conditioning batch is %d, need %d", who, cond_.Beff, Beff));
     const int Cl = c.in_channels;
     const int64_t n = (int64_t)a.B * Cl * a.h * a.w;
     if (smp_.B != a.B || smp_.h != a.h || smp_.w != a.w || smp_.extra != a.inpaint_extra || smp_.policy_epoch != ff_rows_policy_epoch()) {
@@ -144,10 +145,10 @@ void Engine::sample_plms(const gl_plms_args& a, hipStream_t caller) {
             for (int i = 0; i < a.n_steps && sd_step < 0; ++i)
                 if (a.fuser_scale[i] == 0.f) sd_step = i;
             if (a.sd_conv_step > 0 && a.sd_conv_step != sd_step)
-                throw GlError(GL_ERR_ARG, fmt("sample_plms: sd_conv_step %d is not the first step with fuser_scale 0 (%d)", a.sd_conv_step, sd_step));
+                throw GlError(GL_ERR_ARG, fmt("%s: sd_conv_step %d is not the first step with fuser_scale 0 (%d)", who, a.sd_conv_step, sd_step));
         } else {
             sd_step = a.sd_conv_step;
-            if (sd_step >= a.n_steps) throw GlError(GL_ERR_ARG, "sample_plms: sd_conv_step beyond the last step");
+            if (sd_step >= a.n_steps) throw GlError(GL_ERR_ARG, fmt("%s: sd_conv_step beyond the last step", who));
         }
     }
     bool restored = false;
@@ -160,6 +161,23 @@ void Engine::sample_plms(const gl_plms_args& a, hipStream_t caller) {
         if (a.mask)
             CK(inpaint_blend_launch(a.x, a.x0, a.noise + (size_t)i * (n / a.B) * noiseB, a.mask, a.sqrt_ac[i], a.sqrt_1mac[i], a.B, Cl, a.h * a.w,
                                     x0B, noiseB, maskB, s));
+        step(i, eval, n, cfg, s);
+    }
+    if (own) {
+        HIPCK(hipEventRecord(smp_.ev_out, s));
+        HIPCK(hipStreamWaitEvent(caller, smp_.ev_out, 0));
+    }
+}
+
+template <class A>
+static SamplerLoopArgs loop_args(const A& a) {
+    return {a.B, a.h, a.w, a.n_steps, a.timesteps, a.fuser_scale, a.guidance_scale, a.x, a.inpaint_extra, a.mask, a.x0, a.noise,
+            a.mask_B, a.x0_B, a.noise_B, a.sqrt_ac, a.sqrt_1mac, a.use_graph, a.sd_conv_w, a.sd_conv_b, a.sd_conv_step};
+}
+
+void Engine::sample_plms(const gl_plms_args& a, hipStream_t caller) {
+    if (a.n_steps < 1 || !a.timesteps || !a.a_t || !a.a_prev || !a.x) throw GlError(GL_ERR_ARG, "sample_plms: missing schedule or latent");
+    sampler_run(loop_args(a), "sample_plms", caller, [&](int i, auto& eval, int64_t n, bool cfg, hipStream_t s) {
         eval(a.x, a.timesteps[i], i);
         PlmsParams P{};
         P.eps_pair = smp_.eps_pair; P.has_uncond = cfg ? 1 : 0; P.guidance = a.guidance_scale;
@@ -187,11 +205,36 @@ void Engine::sample_plms(const gl_plms_args& a, hipStream_t caller) {
             }
             CK(plms_update_launch(P, s));
         }
+    });
+}
+
+// ---------------------------------------------------------------- linear multistep solvers (DPM-Solver++ 1 / 2M, DDIM with eta > 0)
+// One evaluation per step, then x <- cx x + c0 D0 + c1 D1 + c2 D2 + cn z with step i's host-computed coefficients; the data
+// predictions rotate through smp_.hist. What the coefficients mean is the caller's business (ldm/models/diffusion/dpm_solver.py).
+void Engine::sample_solver(const gl_solver_args& a, hipStream_t caller) {
+    if (a.n_steps < 1 || !a.timesteps || !a.a_t || !a.x) throw GlError(GL_ERR_ARG, "sample_solver: missing schedule or latent");
+    if (!a.cx || !a.c0 || !a.c1) throw GlError(GL_ERR_ARG, "sample_solver: cx, c0 and c1 are required (c2 and cn may be NULL)");
+    if ((a.cn != nullptr) != (a.step_noise != nullptr))
+        throw GlError(GL_ERR_ARG, fmt("sample_solver: cn is %s and step_noise is %s (the noise term needs both)", a.cn ? "given" : "NULL", a.step_noise ? "given" : "NULL"));
+    for (int i = 0; i < a.n_steps; ++i) {
+        if (!(a.a_t[i] > 0.f && a.a_t[i] <= 1.f)) throw GlError(GL_ERR_ARG, fmt("sample_solver: a_t[%d] = %g is outside (0, 1]", i, (double)a.a_t[i]));
+        if (i < 1 && a.c1[i] != 0.f) throw GlError(GL_ERR_ARG, fmt("sample_solver: c1[%d] = %g, but step %d has no earlier data prediction", i, (double)a.c1[i], i));
+        if (i < 2 && a.c2 && a.c2[i] != 0.f) throw GlError(GL_ERR_ARG, fmt("sample_solver: c2[%d] = %g, but step %d has no second earlier data prediction", i, (double)a.c2[i], i));
     }
-    if (own) {
-        HIPCK(hipEventRecord(smp_.ev_out, s));
-        HIPCK(hipStreamWaitEvent(caller, smp_.ev_out, 0));
-    }
+    sampler_run(loop_args(a), "sample_solver", caller, [&](int i, auto& eval, int64_t n, bool cfg, hipStream_t s) {
+        eval(a.x, a.timesteps[i], i);
+        SolverParams P{};
+        P.eps_pair = smp_.eps_pair; P.has_uncond = cfg ? 1 : 0; P.guidance = a.guidance_scale;
+        P.a_t = a.a_t[i]; P.n = n;
+        P.x = a.x; P.x_out = a.x; P.d0_out = smp_.hist[i & 3];
+        P.cx = a.cx[i]; P.c0 = a.c0[i];
+        // a zero coefficient is a term the launch does not load
+        const bool h2 = a.c2 && a.c2[i] != 0.f, h1 = h2 || a.c1[i] != 0.f;
+        if (h1) { P.d1 = smp_.hist[(i - 1) & 3]; P.c1 = a.c1[i]; }
+        if (h2) { P.d2 = smp_.hist[(i - 2) & 3]; P.c2 = a.c2[i]; }
+        if (a.cn && a.cn[i] != 0.f) { P.z = a.step_noise + (size_t)i * n; P.cn = a.cn[i]; }
+        CK(solver_update_launch(P, s));
+    });
 }
 
 }  // namespace gl

@@ -86,6 +86,22 @@ struct PlmsParams {
 };
 int plms_update_launch(const PlmsParams& p, hipStream_t stream);
 
+// e = e_c, or e_u + s (e_c - e_u) ; D0 = (x - sqrt(1-a_t) e) / sqrt(a_t) -> d0_out ;
+// x_out = cx x + c0 D0 [+ c1 d1] [+ c2 d2] [+ cn z]
+// The update every solver of the family is linear in: DPM-Solver++ of order 1 (= DDIM, eta 0) and 2M (d1 = the previous step's D0), DDIM
+// with eta > 0 (z = the step's noise). The caller computes the coefficients; a null d1 / d2 / z is a term the launch does not have.
+// x_out may be x; d0_out must not be d1 or d2.
+struct SolverParams {
+    const float* eps_pair; int has_uncond; float guidance;
+    float* d0_out;
+    const float* d1; const float* d2; const float* z;
+    float cx, c0, c1, c2, cn;
+    const float* x; float* x_out;
+    float a_t;
+    int64_t n;  // elements per batch tensor (B*4*h*w)
+};
+int solver_update_launch(const SolverParams& p, hipStream_t stream);
+
 // The four cubic-convolution weights (A = -0.75, torch's bicubic) of the taps floor(src) - 1 .. floor(src) + 2, t = src - floor(src):
 // fuser_resize_kernel / resize_f32_kernel (misc.hip); the training path's fp32 grid resize (train_fusers.hip) takes the factored form below
 __device__ __forceinline__ void cubic_taps(float t, float w[4]) {

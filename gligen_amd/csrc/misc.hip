@@ -374,6 +374,90 @@ int plms_update_launch(const PlmsParams& p, hipStream_t stream) {
     return GL_OK;
 }
 
+// ---- CFG + linear solver update (DPM-Solver++ 1 / 2M, DDIM with eta >= 0): misc.h SolverParams
+// One element's update; which terms exist is a template argument, so a launch compiles to the loads it needs and nothing else.
+template <bool UNCOND, int NH, bool NOISE>
+__device__ __forceinline__ float solver_elem(const SolverParams& p, float sa_inv, float s1a, float ec, float eu, float x, float d1, float d2, float z,
+                                             float& d0) {
+    float e = ec;
+    if (UNCOND) e = eu + p.guidance * (ec - eu);
+    d0 = (x - s1a * e) * sa_inv;
+    float r = p.cx * x + p.c0 * d0;
+    if (NH >= 1) r += p.c1 * d1;
+    if (NH >= 2) r += p.c2 * d2;
+    if (NOISE) r += p.cn * z;
+    return r;
+}
+// VEC: every pointer is 16-byte aligned; the first n / 4 quads move as 128-bit loads / stores, the n % 4 tail (and, without VEC,
+// everything) goes through the scalar grid-stride loop. x_out may be x: an element is read and written by the same thread.
+template <bool UNCOND, int NH, bool NOISE, bool VEC>
+__global__ void solver_update_kernel(SolverParams p) {
+    const float sa_inv = 1.f / sqrtf(p.a_t), s1a = sqrtf(1.f - p.a_t);
+    const int64_t tid = (int64_t)blockIdx.x * blockDim.x + threadIdx.x, nth = (int64_t)gridDim.x * blockDim.x;
+    int64_t done = 0;
+    if (VEC) {
+        const int64_t n4 = p.n >> 2;
+        const float4* ec4 = reinterpret_cast<const float4*>(p.eps_pair);
+        const float4* eu4 = reinterpret_cast<const float4*>(p.eps_pair + p.n);
+        const float4* x4 = reinterpret_cast<const float4*>(p.x);
+        const float4* d14 = reinterpret_cast<const float4*>(p.d1);
+        const float4* d24 = reinterpret_cast<const float4*>(p.d2);
+        const float4* z4 = reinterpret_cast<const float4*>(p.z);
+        float4* o4 = reinterpret_cast<float4*>(p.x_out);
+        float4* h4 = reinterpret_cast<float4*>(p.d0_out);
+        for (int64_t i = tid; i < n4; i += nth) {
+            const float4 z0 = make_float4(0.f, 0.f, 0.f, 0.f);
+            const float4 ec = ec4[i], eu = UNCOND ? eu4[i] : z0, x = x4[i];
+            const float4 d1 = NH >= 1 ? d14[i] : z0, d2 = NH >= 2 ? d24[i] : z0, z = NOISE ? z4[i] : z0;
+            float4 d0, r;
+            r.x = solver_elem<UNCOND, NH, NOISE>(p, sa_inv, s1a, ec.x, eu.x, x.x, d1.x, d2.x, z.x, d0.x);
+            r.y = solver_elem<UNCOND, NH, NOISE>(p, sa_inv, s1a, ec.y, eu.y, x.y, d1.y, d2.y, z.y, d0.y);
+            r.z = solver_elem<UNCOND, NH, NOISE>(p, sa_inv, s1a, ec.z, eu.z, x.z, d1.z, d2.z, z.z, d0.z);
+            r.w = solver_elem<UNCOND, NH, NOISE>(p, sa_inv, s1a, ec.w, eu.w, x.w, d1.w, d2.w, z.w, d0.w);
+            h4[i] = d0;
+            o4[i] = r;
+        }
+        done = n4 << 2;
+    }
+    for (int64_t i = done + tid; i < p.n; i += nth) {
+        float d0;
+        const float r = solver_elem<UNCOND, NH, NOISE>(p, sa_inv, s1a, p.eps_pair[i], UNCOND ? p.eps_pair[p.n + i] : 0.f, p.x[i], NH >= 1 ? p.d1[i] : 0.f,
+                                                       NH >= 2 ? p.d2[i] : 0.f, NOISE ? p.z[i] : 0.f, d0);
+        p.d0_out[i] = d0;
+        p.x_out[i] = r;
+    }
+}
+template <bool UNCOND, int NH, bool NOISE>
+static void solver_update_go(const SolverParams& p, bool vec, hipStream_t stream) {
+    if (vec) hipLaunchKernelGGL((solver_update_kernel<UNCOND, NH, NOISE, true>), dim3(grid_for(cdiv64(p.n, 4))), dim3(256), 0, stream, p);
+    else hipLaunchKernelGGL((solver_update_kernel<UNCOND, NH, NOISE, false>), dim3(grid_for(p.n)), dim3(256), 0, stream, p);
+}
+template <bool UNCOND, int NH>
+static void solver_update_noise(const SolverParams& p, bool vec, hipStream_t stream) {
+    if (p.z) solver_update_go<UNCOND, NH, true>(p, vec, stream);
+    else solver_update_go<UNCOND, NH, false>(p, vec, stream);
+}
+template <bool UNCOND>
+static void solver_update_hist(const SolverParams& p, bool vec, hipStream_t stream) {
+    if (p.d2) solver_update_noise<UNCOND, 2>(p, vec, stream);
+    else if (p.d1) solver_update_noise<UNCOND, 1>(p, vec, stream);
+    else solver_update_noise<UNCOND, 0>(p, vec, stream);
+}
+int solver_update_launch(const SolverParams& p, hipStream_t stream) {
+    if (!p.eps_pair || !p.x || !p.x_out || !p.d0_out || p.n < 1) return set_error(GL_ERR_ARG, "solver_update: null pointer or n = %lld", (long long)p.n);
+    if (p.d2 && !p.d1) return set_error(GL_ERR_ARG, "solver_update: d2 without d1");
+    if (p.d0_out == p.d1 || p.d0_out == p.d2 || p.d0_out == p.x || p.d0_out == p.x_out) return set_error(GL_ERR_ARG, "solver_update: d0_out aliases an input or x_out");
+    if (!(p.a_t > 0.f && p.a_t <= 1.f)) return set_error(GL_ERR_ARG, "solver_update: a_t = %g is outside (0, 1]", (double)p.a_t);
+    // 128-bit moves need every base 16-byte aligned; the uncond half starts n floats behind the cond half
+    uintptr_t bits = (uintptr_t)p.eps_pair | (uintptr_t)p.x | (uintptr_t)p.x_out | (uintptr_t)p.d0_out | (uintptr_t)p.d1 | (uintptr_t)p.d2 | (uintptr_t)p.z;
+    if (p.has_uncond) bits |= (uintptr_t)(p.eps_pair + p.n);
+    const bool vec = (bits & 15) == 0 && p.n >= 4;
+    if (p.has_uncond) solver_update_hist<true>(p, vec, stream);
+    else solver_update_hist<false>(p, vec, stream);
+    GL_LAUNCH_CHECK();
+    return GL_OK;
+}
+
 // x0 / noise / mask may carry batch 1 (broadcast over the latent batch, as the reference's tensor broadcasting does for the
 // single encoded input image of gligen_inference.run) or batch B
 __global__ void inpaint_blend_kernel(float* img, const float* x0, const float* noise, const float* mask, float sa, float s1, int B, int C, int HW,

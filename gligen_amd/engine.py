@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from ._lib import Grounding, PlmsArgs, UNetConfig, VaeConfig, check
+from ._lib import Grounding, PlmsArgs, SolverArgs, UNetConfig, VaeConfig, check
 
 GROUNDING_KINDS = {"text": 0, "text_image": 1, "keypoint": 2, "tokens": 3}
 
@@ -512,26 +512,17 @@ class Engine:
                                          _stream(self.device)))
         return out
 
-    def sample_plms(self, x: torch.Tensor, timesteps: np.ndarray, a_t: np.ndarray, a_prev: np.ndarray,
-                    fuser_scale: Optional[np.ndarray], guidance_scale: float, *, inpaint_extra=None, mask=None, x0=None,
-                    noise=None, sqrt_ac=None, sqrt_1mac=None, use_graph: bool = True, sd_first_conv=None,
-                    restore_at: int = -1, ddim: bool = False) -> torch.Tensor:
-        """In-place PLMS (or, ddim=True, eta-0 DDIM) loop on x (fp32 [B,C,h,w]); conditioning must already be set.
-        Inpainting: mask [B|1,1,h,w], x0 [B|1,C,h,w], noise [S,B|1,C,h,w] (batch 1 broadcasts over the latent batch, as
-        the reference's q_sample(x0, ts) * mask does). sd_first_conv = (weight, bias) swapped in before step restore_at."""
+    def _sampler_args(self, a, who, x, timesteps, fuser_scale, guidance_scale, inpaint_extra, mask, x0, noise, sqrt_ac, sqrt_1mac,
+                      use_graph, sd_first_conv, restore_at):
+        """The fields gl_plms_args and gl_solver_args share, written into `a`; returns what has to outlive the call."""
         dev = self.device
         assert x.is_cuda and x.dtype == torch.float32 and x.is_contiguous()
         n = len(timesteps)
         ts = np.ascontiguousarray(timesteps, dtype=np.int64)
-        at = np.ascontiguousarray(a_t, dtype=np.float32)
-        ap = np.ascontiguousarray(a_prev, dtype=np.float32)
-        a = PlmsArgs()
-        a.struct_size = C.sizeof(PlmsArgs)
+        a.struct_size = C.sizeof(type(a))
         a.B, a.h, a.w, a.n_steps = int(x.shape[0]), int(x.shape[2]), int(x.shape[3]), n
         a.timesteps = ts.ctypes.data_as(C.POINTER(C.c_int64))
-        a.a_t = at.ctypes.data_as(C.POINTER(C.c_float))
-        a.a_prev = ap.ctypes.data_as(C.POINTER(C.c_float))
-        keep = [ts, at, ap]
+        keep = [ts]
         if fuser_scale is not None:
             fs = np.ascontiguousarray(fuser_scale, dtype=np.float32)
             a.fuser_scale = fs.ctypes.data_as(C.POINTER(C.c_float))
@@ -546,7 +537,7 @@ class Engine:
             if (mask.dim() != 4 or tuple(mask.shape[1:]) != (1, h, w) or x0.dim() != 4 or tuple(x0.shape[1:]) != (Cl, h, w)
                     or noise.dim() != 5 or noise.shape[0] != n or tuple(noise.shape[2:]) != (Cl, h, w)
                     or any(int(b) not in (1, B) for b in (mask.shape[0], x0.shape[0], noise.shape[1]))):
-                raise ValueError(f"sample_plms: mask {tuple(mask.shape)}, x0 {tuple(x0.shape)}, noise {tuple(noise.shape)} do not fit "
+                raise ValueError(f"{who}: mask {tuple(mask.shape)}, x0 {tuple(x0.shape)}, noise {tuple(noise.shape)} do not fit "
                                  f"a latent {tuple(x.shape)} over {n} steps ([B|1,1,h,w], [B|1,C,h,w], [S,B|1,C,h,w])")
             sa = np.ascontiguousarray(sqrt_ac, dtype=np.float32); s1 = np.ascontiguousarray(sqrt_1mac, dtype=np.float32)
             keep += [mask, x0, noise, sa, s1]
@@ -554,17 +545,89 @@ class Engine:
             a.mask_B, a.x0_B, a.noise_B = int(mask.shape[0]), int(x0.shape[0]), int(noise.shape[1])
             a.sqrt_ac = sa.ctypes.data_as(C.POINTER(C.c_float)); a.sqrt_1mac = s1.ctypes.data_as(C.POINTER(C.c_float))
         a.use_graph = int(bool(use_graph))
-        a.ddim = int(bool(ddim))
         if sd_first_conv is not None:
             cw, cb = _f32(sd_first_conv[0], dev), _f32(sd_first_conv[1], dev)
             keep += [cw, cb]
             a.sd_conv_w, a.sd_conv_b = cw.data_ptr(), cb.data_ptr()
             if not 0 <= restore_at < n:
-                raise ValueError("sample_plms: sd_first_conv needs restore_at = the step index it is swapped in at")
+                raise ValueError(f"{who}: sd_first_conv needs restore_at = the step index it is swapped in at")
             a.sd_conv_step = int(restore_at)
+        return keep
+
+    def sample_plms(self, x: torch.Tensor, timesteps: np.ndarray, a_t: np.ndarray, a_prev: np.ndarray,
+                    fuser_scale: Optional[np.ndarray], guidance_scale: float, *, inpaint_extra=None, mask=None, x0=None,
+                    noise=None, sqrt_ac=None, sqrt_1mac=None, use_graph: bool = True, sd_first_conv=None,
+                    restore_at: int = -1, ddim: bool = False) -> torch.Tensor:
+        """In-place PLMS (or, ddim=True, eta-0 DDIM) loop on x (fp32 [B,C,h,w]); conditioning must already be set.
+        Inpainting: mask [B|1,1,h,w], x0 [B|1,C,h,w], noise [S,B|1,C,h,w] (batch 1 broadcasts over the latent batch, as
+        the reference's q_sample(x0, ts) * mask does). sd_first_conv = (weight, bias) swapped in before step restore_at."""
+        a = PlmsArgs()
+        keep = self._sampler_args(a, "sample_plms", x, timesteps, fuser_scale, guidance_scale, inpaint_extra, mask, x0, noise, sqrt_ac, sqrt_1mac,
+                                  use_graph, sd_first_conv, restore_at)
+        at = np.ascontiguousarray(a_t, dtype=np.float32)
+        ap = np.ascontiguousarray(a_prev, dtype=np.float32)
+        a.a_t = at.ctypes.data_as(C.POINTER(C.c_float))
+        a.a_prev = ap.ctypes.data_as(C.POINTER(C.c_float))
+        keep += [at, ap]
+        a.ddim = int(bool(ddim))
         check(self.lib.gl_sample_plms(self._ctx, C.byref(a), _stream(self.device)))
         self._keep_plms = keep
         return x
+
+    def sample_solver(self, x: torch.Tensor, timesteps: np.ndarray, a_t: np.ndarray, coefs: np.ndarray,
+                      fuser_scale: Optional[np.ndarray], guidance_scale: float, *, step_noise=None, inpaint_extra=None, mask=None, x0=None,
+                      noise=None, sqrt_ac=None, sqrt_1mac=None, use_graph: bool = True, sd_first_conv=None,
+                      restore_at: int = -1) -> torch.Tensor:
+        """In-place linear multistep solver loop on x (gl_sample_solver): per step one evaluation at timesteps[i], D0 = (x - sqrt(1 - a_t) e) /
+        sqrt(a_t), then x <- cx x + c0 D0 + c1 D1 [+ c2 D2] [+ cn z]. coefs: [S, 3] = (cx, c0, c1) (what dpm_solver_coefficients returns),
+        [S, 4] with cn behind them when step_noise [S, B, C, h, w] is given, or a dict with keys cx, c0, c1 and optionally c2, cn.
+        The other arguments are sample_plms'."""
+        a = SolverArgs()
+        keep = self._sampler_args(a, "sample_solver", x, timesteps, fuser_scale, guidance_scale, inpaint_extra, mask, x0, noise, sqrt_ac, sqrt_1mac,
+                                  use_graph, sd_first_conv, restore_at)
+        n = len(timesteps)
+        if isinstance(coefs, dict):
+            cols = dict(coefs)
+        else:
+            cf = np.asarray(coefs, dtype=np.float64)
+            if cf.ndim != 2 or cf.shape[0] != n or cf.shape[1] not in (3, 4):
+                raise ValueError(f"sample_solver: coefs has shape {cf.shape}, need [{n}, 3] = (cx, c0, c1) or [{n}, 4] with cn")
+            cols = dict(zip(("cx", "c0", "c1", "cn"), cf.T))
+        unknown = set(cols) - {"cx", "c0", "c1", "c2", "cn"}
+        if unknown or not {"cx", "c0", "c1"} <= set(cols):
+            raise ValueError(f"sample_solver: coefs has the columns {sorted(cols)}, need cx, c0, c1 and optionally c2, cn")
+        if ("cn" in cols) != (step_noise is not None):
+            raise ValueError("sample_solver: the noise term needs both the cn column and step_noise")
+        for name, col in list(cols.items()) + [("a_t", a_t)]:
+            arr = np.ascontiguousarray(col, dtype=np.float32)
+            if arr.shape != (n,):
+                raise ValueError(f"sample_solver: {name} has shape {arr.shape}, need ({n},)")
+            setattr(a, name, arr.ctypes.data_as(C.POINTER(C.c_float)))
+            keep.append(arr)
+        if step_noise is not None:
+            step_noise = _f32(step_noise, self.device)
+            if tuple(step_noise.shape) != (n, *x.shape):
+                raise ValueError(f"sample_solver: step_noise {tuple(step_noise.shape)} is not [S, B, C, h, w] = {(n, *x.shape)}")
+            keep.append(step_noise)
+            a.step_noise = step_noise.data_ptr()
+        check(self.lib.gl_sample_solver(self._ctx, C.byref(a), _stream(self.device)))
+        self._keep_plms = keep
+        return x
+
+    def op_solver_update(self, eps, x, a_t, cx, c0, *, guidance=None, d1=None, c1=0.0, d2=None, c2=0.0, z=None, cn=0.0, out=None):
+        """One solver_update_kernel launch (gl_op_solver_update): eps fp32 [n], or [2, n] = [cond ; uncond] with `guidance`; returns
+        (x_out, D0). out: the tensor x_out is written to (x itself for an in-place update; a new one when None)."""
+        dev = self.device
+        n = x.numel()
+        assert eps.is_cuda and eps.dtype == torch.float32 and x.dtype == torch.float32
+        assert eps.numel() == (2 * n if guidance is not None else n)
+        out = torch.empty_like(x) if out is None else out
+        d0 = torch.empty_like(x)
+        opt = lambda t: None if t is None else _ptr(t)
+        check(self.lib.gl_op_solver_update(self._ctx, _ptr(eps), int(guidance is not None), float(guidance if guidance is not None else 1.0), float(a_t),
+                                           _ptr(x), _ptr(out), _ptr(d0), opt(d1), opt(d2), opt(z), float(cx), float(c0), float(c1), float(c2), float(cn),
+                                           int(n), _stream(dev)))
+        return out, d0
 
     def sampler_timing(self):
         """(mean UNet-evaluation ms over graph replays, first eager evaluation ms, number of evaluations)."""

@@ -252,10 +252,12 @@ class Trainer:
 
     # ---- in-training inference -------------------------------------------------------------------------------------------------
     @torch.no_grad()
-    def preview(self, batch: Mapping, steps: int = 50, guidance_scale: float = 5, use_ema: bool = False, x_T: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def preview(self, batch: Mapping, steps: int = 50, guidance_scale: float = 5, use_ema: bool = False, x_T: Optional[torch.Tensor] = None,
+                sampler: str = "plms", discretize: str = "uniform") -> torch.Tensor:
         """trainer.py:419-466: the current parameters (use_ema: the EMA ones) loaded into this package's inference UNetModel,
         PLMSSampler.sample from x_T (drawn when None), decoded; returns u8 [B, H, W, 3] on the device. Needs an autoencoder; the
-        context and the unconditional context come from the text encoder, or from batch["context"] / batch["uc"] (zeros)."""
+        context and the unconditional context come from the text encoder, or from batch["context"] / batch["uc"] (zeros).
+        sampler="dpmpp_2m": DPMSolverSampler on the `discretize` grid instead (20 steps do what 50 PLMS steps do)."""
         from ldm.models.diffusion.plms import PLMSSampler
         from ldm.modules.diffusionmodules.openaimodel import UNetModel
         if self.autoencoder is None:
@@ -296,8 +298,14 @@ class Trainer:
         grounding_extra_input = self.grounding_downsampler_input.prepare(batch) if self.grounding_downsampler_input is not None else None
         inp = dict(x=None if x_T is None else x_T.to(device=dev, dtype=torch.float32), timesteps=None, context=context, inpainting_extra_input=inpainting_extra_input,
                    grounding_extra_input=grounding_extra_input, grounding_input=self.grounding_tokenizer_input.prepare(batch))
+        if sampler not in ("plms", "dpmpp_2m"):
+            raise ValueError(f"Trainer.preview: sampler {sampler!r}: 'plms' or 'dpmpp_2m'")
+        schedule_kwargs = {}
+        if sampler == "dpmpp_2m":
+            from ldm.models.diffusion.dpm_solver import DPMSolverSampler as PLMSSampler  # noqa: F811
+            schedule_kwargs = dict(ddim_discretize=discretize)
         sampler = PLMSSampler(self.diffusion, model)
-        samples = sampler.sample(S=steps, shape=(B, self.cfg["in_channels"], hw, hw), input=inp, uc=uc, guidance_scale=guidance_scale)
+        samples = sampler.sample(S=steps, shape=(B, self.cfg["in_channels"], hw, hw), input=inp, uc=uc, guidance_scale=guidance_scale, **schedule_kwargs)
         images = torch.clamp(self.autoencoder.decode(samples), min=-1, max=1)
         return self.autoencoder.engine.to_uint8(images)
 

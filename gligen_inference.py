@@ -477,15 +477,43 @@ def load_synthetic(kind="text", inpaint=False, image_size=64, seed=1234, fast=Fa
 
 
 # ---- run ---------------------------------------------------------------------------------------------
+SAMPLER_STEPS = {"plms": 50, "ddim": 250, "dpmpp_2m": 20}      # the step count each sampler runs with when none is given
+
+
+def sampler_choice(sampler=None, no_plms=False, discretize="uniform", ddim_eta=0.0):
+    """(name, default step count) of the sampler a run uses: `sampler` (plms | ddim | dpmpp_2m) when given, else the reference's choice
+    (gligen_inference.py:385-390: DDIM with 250 steps under --no_plms, else PLMS with 50). Refuses options the sampler does not have."""
+    name = sampler or ("ddim" if no_plms else "plms")
+    if name not in SAMPLER_STEPS:
+        raise ValueError(f"sampler {name!r}: one of {sorted(SAMPLER_STEPS)}")
+    if discretize not in ("uniform", "logsnr") or (discretize == "logsnr" and name != "dpmpp_2m"):
+        raise ValueError(f"discretize {discretize!r} with sampler {name!r}: 'uniform', or 'logsnr' for dpmpp_2m")
+    if ddim_eta and name != "ddim":
+        raise ValueError(f"ddim_eta = {ddim_eta} with sampler {name!r}: only ddim has a noise term")
+    return name, SAMPLER_STEPS[name]
+
+
 @torch.no_grad()
-def generate(model, autoencoder, diffusion, batch, context, uc, *, steps=50, guidance_scale=7.5, alpha_type=None,
+def generate(model, autoencoder, diffusion, batch, context, uc, *, steps=None, guidance_scale=7.5, alpha_type=None,
              starting_noise=None, inpainting_mask=None, z0=None, use_graph=True, no_plms=False, grounding_extra_input=None,
-             grounding_input=None):
-    """The sampling core of run() (reference gligen_inference.py:389-431) on already-encoded inputs."""
-    # reference gligen_inference.py:385-390: DDIM (250 steps) with --no_plms, else PLMS (50 steps)
-    sampler_cls = DDIMSampler if no_plms else PLMSSampler
+             grounding_input=None, sampler=None, discretize="uniform", ddim_eta=0.0):
+    """The sampling core of run() (reference gligen_inference.py:389-431) on already-encoded inputs. steps: None = 50, or 20 for
+    sampler="dpmpp_2m"."""
+    name, _ = sampler_choice(sampler, no_plms, discretize, ddim_eta)
+    schedule_kwargs = {}
+    if name == "dpmpp_2m":
+        from ldm.models.diffusion.dpm_solver import DPMSolverSampler as sampler_cls
+        schedule_kwargs = dict(ddim_discretize=discretize)
+    elif name == "ddim" and ddim_eta:
+        from ldm.models.diffusion.ddim import StochasticDDIMSampler as sampler_cls
+    else:
+        sampler_cls = DDIMSampler if name == "ddim" else PLMSSampler
+    if steps is None:
+        steps = 20 if name == "dpmpp_2m" else 50
     sampler = sampler_cls(diffusion, model, alpha_generator_func=partial(alpha_generator, type=alpha_type), set_alpha_scale=set_alpha_scale)
     sampler.use_graph = use_graph
+    if name == "ddim" and ddim_eta:
+        sampler.ddim_eta = float(ddim_eta)
     inpainting_extra_input = None
     if inpainting_mask is not None:
         inpainting_extra_input = torch.cat([z0 * inpainting_mask, inpainting_mask], dim=1)
@@ -495,7 +523,7 @@ def generate(model, autoencoder, diffusion, batch, context, uc, *, steps=50, gui
                  inpainting_extra_input=inpainting_extra_input, grounding_extra_input=grounding_extra_input)
     B = context.shape[0]
     shape = (B, model.in_channels, model.image_size, model.image_size)
-    latents = sampler.sample(S=steps, shape=shape, input=input, uc=uc, guidance_scale=guidance_scale, mask=inpainting_mask, x0=z0)
+    latents = sampler.sample(S=steps, shape=shape, input=input, uc=uc, guidance_scale=guidance_scale, mask=inpainting_mask, x0=z0, **schedule_kwargs)
     return autoencoder.decode(latents)
 
 
@@ -721,23 +749,26 @@ def run(meta, config, starting_noise=None, models=None):
         model.grounding_tokenizer_input.prepare(batch)   # remembers the shapes its null input needs
         grounding_input = {"tokens": batch["tokens"]}
     no_plms = bool(args.get("no_plms"))
-    steps = int(args.get("steps") or (250 if no_plms else 50))
+    # optional keys; a config without them runs what it always ran
+    skw = dict(sampler=args.get("sampler"), discretize=args.get("discretize") or "uniform", ddim_eta=float(args.get("ddim_eta") or 0.0))
+    _, default_steps = sampler_choice(no_plms=no_plms, **skw)
+    steps = int(args.get("steps") or default_steps)
     # batches of 32 and more run as two half-batches in flight (generate_lanes); below that one evaluation over the whole batch is the
     # faster schedule (measured, profiles/r6/batch_sweep.txt: 8 images 6.69 images/s as one batch against 6.24 as two halves, 16 images
     # 7.08 against 6.91, 32 images 7.11 against 7.19). Not for inpainting: its per-step q_sample noise comes from the device generator,
     # whose draws would interleave differently
     lanes = args.get("lanes")
     lanes = 2 if lanes is None else min(2, max(1, int(lanes)))      # (--lanes 0 and 1 both mean one batch at a time; one batch is split in two at most)
-    if mask is not None or (hi - lo) < SPLIT_BATCH_AT:
+    if mask is not None or skw["ddim_eta"] or (hi - lo) < SPLIT_BATCH_AT:     # (eta > 0 draws its step noise from the device generator too)
         lanes = 1
     if lanes > 1 and starting_noise is None:   # x_T as the sampler would draw it (plms.py:71), before the batch is split
         starting_noise = torch.randn((hi - lo, model.in_channels, model.image_size, model.image_size), device=device)
     repeat = max(1, int(args.get("repeat") or 1))
     n_lanes_req = 3 if args.get("lanes") is None else max(1, int(args.get("lanes")))    # whole batches in flight (--repeat): 3, as bench.py
-    if repeat > 1 and mask is None and meta.get("alpha_type") in (None, [1, 0, 0], [1.0, 0.0, 0.0]):
+    if repeat > 1 and mask is None and not skw["ddim_eta"] and meta.get("alpha_type") in (None, [1, 0, 0], [1.0, 0.0, 0.0]):
         # `repeat` batches of this prompt (seed, seed + 1, ...): whole batches in flight on the lanes, as bench.py runs them
         gkw = dict(steps=steps, guidance_scale=args["guidance_scale"], alpha_type=meta.get("alpha_type"), no_plms=no_plms,
-                   grounding_extra_input=grounding_extra_input, grounding_input=grounding_input)
+                   grounding_extra_input=grounding_extra_input, grounding_input=grounding_input, **skw)
         shape = (hi - lo, model.in_channels, model.image_size, model.image_size)
         seed0 = int(args.get("seed") or 0)
         seeded = world > 1 or args.get("seed") is not None
@@ -767,7 +798,7 @@ def run(meta, config, starting_noise=None, models=None):
         samples = generate_lanes(model, autoencoder, diffusion, batch, context, uc, lanes=lanes, steps=steps,
                                  guidance_scale=args["guidance_scale"], alpha_type=meta.get("alpha_type"), starting_noise=starting_noise,
                                  inpainting_mask=mask, z0=z0, no_plms=no_plms, grounding_extra_input=grounding_extra_input,
-                                 grounding_input=grounding_input)
+                                 grounding_input=grounding_input, **skw)
         if torch.cuda.is_available():
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
@@ -845,6 +876,11 @@ def main(argv=None):
     parser.add_argument("--folder", type=str, default="generation_samples", help="root folder for output")
     parser.add_argument("--batch_size", type=int, default=5, help="images per prompt (the GLOBAL batch under torch.distributed.run)")
     parser.add_argument("--no_plms", action="store_true", help="use DDIM instead. WARNING: I did not test the code yet")
+    parser.add_argument("--sampler", type=str, default=None, choices=sorted(SAMPLER_STEPS),
+                        help="plms (50 steps, 51 evaluations; the default), ddim (250; what --no_plms selects) or dpmpp_2m (DPM-Solver++ 2M, 20 steps = 20 evaluations)")
+    parser.add_argument("--discretize", type=str, default="uniform", choices=["uniform", "logsnr"],
+                        help="timestep grid of dpmpp_2m: the reference's uniform grid, or the integer timesteps nearest to a grid uniform in log-SNR (at most 27 steps)")
+    parser.add_argument("--ddim_eta", type=float, default=0.0, help="with ddim: the eta of the stochastic update (0 = deterministic, the reference's value)")
     parser.add_argument("--guidance_scale", type=float, default=7.5, help="")
     parser.add_argument("--negative_prompt", type=str,
                         default="longbody, lowres, bad anatomy, bad hands, missing fingers, extra digit, fewer digits, cropped, worst quality, low quality", help="")

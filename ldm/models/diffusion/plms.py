@@ -71,7 +71,11 @@ class PLMSSampler(object):
         return self._sample_generic(shape, input, uc, guidance_scale, mask, x0)
 
     # ---- device loop ---------------------------------------------------------------------
-    def _sample_native(self, shape, input, uc, guidance_scale, mask, x0):
+    def _native_setup(self, input, uc, guidance_scale, mask, x0, update_draws):
+        """What a run on the device needs apart from its update rule (shared with DDIMSampler's eta > 0 path and DPMSolverSampler):
+        conditioning, gate-scale schedule, the latent, the device-generator draws, the inpainting tensors, the SD first-conv swap and
+        the channels in front of the first conv. update_draws(i) = how many randn_like(x) draws the reference's update makes at step i.
+        Returns (img, time_range, cfg, scales, alphas, sd_conv, update_noise, engine keyword arguments)."""
         model = self.model
         time_range = np.flip(self.ddim_timesteps).copy()
         S = len(time_range)
@@ -102,14 +106,13 @@ class PLMSSampler(object):
             scales = None
 
         img = input["x"].to(device=model.engine.device, dtype=torch.float32).contiguous().clone()
-        a_t = _np(self.ddim_alphas).astype(np.float32)[::-1].copy()          # index = S - i - 1
-        a_prev = _np(self.ddim_alphas_prev).astype(np.float32)[::-1].copy()
         extra = {}
         # Device-generator draws, call for call as the reference makes them, so that equal seeds give equal noise:
         # per step one randn_like(x0) inside q_sample when inpainting (plms.py:96-99 -> ldm.py:19-22), then the
         # sigma_t * randn_like(x) of get_x_prev_and_pred_x0 (plms.py:138; sigma is 0, the draw still advances the
         # generator) -- twice on the first PLMS step (plms.py:144,159), once otherwise and for DDIM (ddim.py:131).
         noise = []
+        update_noise = []
         if mask is not None:
             assert x0 is not None
             x0 = x0.to(device=img.device, dtype=torch.float32)
@@ -117,8 +120,8 @@ class PLMSSampler(object):
         for i in range(S):
             if mask is not None:
                 noise.append(torch.randn_like(x0))
-            for _ in range(2 if (i == 0 and self.multistep) else 1):
-                torch.randn_like(img)
+            for _ in range(update_draws(i)):
+                update_noise.append(torch.randn_like(img))
         if mask is not None:
             if tuple(mask.shape[1:]) != (1, *img.shape[2:]) or tuple(x0.shape[1:]) != tuple(img.shape[1:]):
                 raise ValueError(f"inpainting: mask {tuple(mask.shape)} / x0 {tuple(x0.shape)} do not match the latent {tuple(img.shape)}")
@@ -142,9 +145,11 @@ class PLMSSampler(object):
                 raise ValueError("inpaint_mode model needs input['inpainting_extra_input']")
         else:
             first_conv_extra = model.first_conv_extra(input)
-        model.engine.sample_plms(img, time_range, a_t, a_prev, scales, guidance_scale if cfg else 1.0,
-                                 inpaint_extra=first_conv_extra, use_graph=self.use_graph,
-                                 sd_first_conv=sd_conv, restore_at=restore_at, ddim=not self.multistep, **extra)
+        kwargs = dict(inpaint_extra=first_conv_extra, use_graph=self.use_graph, sd_first_conv=sd_conv, restore_at=restore_at, **extra)
+        return img, time_range, cfg, scales, alphas, sd_conv, update_noise, kwargs
+
+    def _native_finish(self, shape, input, img, time_range, alphas, sd_conv):
+        model = self.model
         if sd_conv is not None:
             model.restore_first_conv_from_SD()  # bring the module parameters in line with the engine
         if alphas is not None and self.set_alpha_scale is not None:
@@ -152,6 +157,14 @@ class PLMSSampler(object):
         input["x"] = img
         input["timesteps"] = torch.full((shape[0],), int(time_range[-1]), device=img.device, dtype=torch.long)
         return img
+
+    def _sample_native(self, shape, input, uc, guidance_scale, mask, x0):
+        img, time_range, cfg, scales, alphas, sd_conv, _, kwargs = self._native_setup(
+            input, uc, guidance_scale, mask, x0, lambda i: 2 if (i == 0 and self.multistep) else 1)
+        a_t = _np(self.ddim_alphas).astype(np.float32)[::-1].copy()          # index = S - i - 1
+        a_prev = _np(self.ddim_alphas_prev).astype(np.float32)[::-1].copy()
+        self.model.engine.sample_plms(img, time_range, a_t, a_prev, scales, guidance_scale if cfg else 1.0, ddim=not self.multistep, **kwargs)
+        return self._native_finish(shape, input, img, time_range, alphas, sd_conv)
 
     # ---- reference-shaped host loop for arbitrary model callables -------------------------------
     def _sample_generic(self, shape, input, uc, guidance_scale, mask, x0):
