@@ -12,6 +12,7 @@
 #include "../../include/gligen_amd_sampler.h"
 #include "../../include/gligen_amd_gemm_plans.h"
 #include "../../include/gligen_amd_attention_core.h"
+#include "../../include/gligen_amd_vae.h"
 #include "gemm_plan.h"
 
 #include <cstdlib>
@@ -477,6 +478,24 @@ int gl_ff_rows_policy_report(char* buf, size_t cap) { return gl::ff_rows_policy_
 
 // ---- include/gligen_amd_sampler.h
 int gl_set_cfg_shared_prefix(int on) { return gl::cfg_shared_prefix_set(on); }
+
+// ---- include/gligen_amd_vae.h
+int gl_vae_set_attention(gl_ctx* ctx, int mode) {
+    NEED(ctx);
+    GL_API_BEGIN
+    ctx->eng->set_vae_attention(mode);
+    GL_API_END
+}
+
+int gl_op_vae_attention(gl_ctx* ctx, const void* q, const void* k, const void* v, int B, int T, int C, int mode, void* out, gl_stream s) {
+    NEED(ctx);
+    if (!q || !k || !v || !out) return gl::set_error(GL_ERR_ARG, "gl_op_vae_attention: null pointer");
+    GL_API_BEGIN
+    if (((reinterpret_cast<uintptr_t>(q) | reinterpret_cast<uintptr_t>(k) | reinterpret_cast<uintptr_t>(v) | reinterpret_cast<uintptr_t>(out)) & 15) != 0)
+        throw GlError(GL_ERR_ARG, "gl_op_vae_attention: q, k, v and out are 16-byte aligned");
+    ctx->eng->op_vae_attention((const bf16*)q, (const bf16*)k, (const bf16*)v, B, T, C, mode, (bf16*)out, S(s));
+    GL_API_END
+}
 
 // ---- include/gligen_amd_gemm_plans.h
 int gl_gemm_force_plan(int tm, int tn, int splits, int grid_cap) {

@@ -22,6 +22,7 @@
 #include "misc.h"
 #include "norm.h"
 #include "train.h"
+#include "vae_attention.h"
 #include "../../include/gligen_amd.h"
 #include "../../include/gligen_amd_solver.h"
 
@@ -186,6 +187,11 @@ class Engine {
     void vae_decode(int B, int h, int w, const float* z, float* out, hipStream_t s);
     void vae_encode(int B, int H, int W, const float* img, const float* noise, float* z, hipStream_t s);
     bool has_vae_encoder() const { return vae_.enc.present; }
+    // The form of the VAE's AttnBlock (gl_vae_set_attention): 0 = auto (the score-matrix form up to 4096 tokens, above that -- and
+    // wherever the score matrices do not fit what is left of the arena -- vae_attn_flash_kernel), 1 = score matrices, 2 = flash
+    void set_vae_attention(int mode);
+    // o = softmax(q k^T C^-0.5) v on the caller's bf16 rows [B][T][C] (gl_op_vae_attention); mode as above, for this call
+    void op_vae_attention(const bf16* q, const bf16* k, const bf16* v, int B, int T, int C, int mode, bf16* o, hipStream_t s);
     // CLIPTextModel.forward (reference ldm/modules/encoders/modules.py:144-173): ids [S][T] int32, eos_index [S] (the row HF pools)
     // -> last_hidden fp32 [S][T][width], pooled fp32 [S][width] (may be null). S is chunked to what the arena holds.
     void clip_text_encode(const int32_t* ids, const int32_t* eos_index, int S, int T, float* last_hidden, float* pooled, hipStream_t s);
@@ -442,6 +448,10 @@ class Engine {
     void build_vae_encoder();
     void build_vae_mid(VaeHalf& h, const std::string& prefix, int C);
     bf16* vae_attn(const VaeAttnW& a, const bf16* x, int B, int HW, hipStream_t s);
+    int vae_attn_mode_ = 0;
+    bool vae_attn_flash_for(int mode, int HW, int C, size_t vt_bytes) const;
+    // one image in the score-matrix form: fp32 S [HW][HW], bf16 softmax rows, o = P v (+ vbias) from v^T [C][HW]
+    void vae_attn_matrix(const bf16* q, const bf16* k, const bf16* vT, const float* vbias, bf16* o, int HW, int C, hipStream_t s);
 
     // ---- CLIP (engine_clip.hip). Text tower: pre-LN transformer: LN1 -> q,k,v -> causal attention -> out + residual -> LN2 -> fc1 quick-GELU -> fc2 + residual.
     // The layer routine takes width / heads / tokens / causal from here and from its arguments, not from constants.

@@ -77,6 +77,39 @@ void Engine::build_vae_encoder() {
 }
 
 // ---------------------------------------------------------------- VAE
+void Engine::set_vae_attention(int mode) {
+    if (mode < 0 || mode > 2) throw GlError(GL_ERR_ARG, fmt("vae attention mode %d: 0 = auto, 1 = score matrices, 2 = flash", mode));
+    vae_attn_mode_ = mode;
+}
+
+// Does this attention run on vae_attn_flash_kernel? Mode 1 is never replaced; mode 2 refuses a head dimension the kernel lacks; auto keeps
+// the score-matrix form -- its launches and its bits -- up to 4096 tokens unless its matrices no longer fit behind the vt_bytes of v^T
+bool Engine::vae_attn_flash_for(int mode, int HW, int C, size_t vt_bytes) const {
+    if (mode == 1) return false;
+    const bool have = vae_attn_flash_supports(C);
+    if (mode == 2) {
+        if (!have) throw GlError(GL_ERR_UNSUPPORTED, fmt("vae attention: flash form asked for at C=%d channels (vae_attn_flash_kernel is built for 256 and 512)", C));
+        return true;
+    }
+    if (!have) return false;
+    if (HW > 4096) return true;
+    const size_t need = vt_bytes + (size_t)HW * HW * 6 + 3 * 256, left = arena_.capacity() - arena_.mark();
+    return need > left;
+}
+
+void Engine::vae_attn_matrix(const bf16* q, const bf16* k, const bf16* vT, const float* vbias, bf16* o, int HW, int C, hipStream_t s) {
+    float* S = arena_.get<float>((size_t)HW * HW);
+    {
+        Epilogue E = e_rows(S, HW);
+        E.out_f32 = 1;
+        gemm(a_rows(q, C), k, HW, HW, C, E, s);
+    }
+    bf16* Pm = arena_.get<bf16>((size_t)HW * HW);
+    CK(softmax_rows_launch(S, Pm, HW, HW, 1.f / std::sqrt((float)C), s));
+    ++n_launches;
+    gemm(a_rows(Pm, HW), vT, HW, C, HW, e_rows(o, C, vbias), s);
+}
+
 // AttnBlock.forward (model.py:177-202): single head over HW tokens, scale C^-0.5
 bf16* Engine::vae_attn(const VaeAttnW& a, const bf16* x, int B, int HW, hipStream_t s) {
     const int C = a.gn.C, M = B * HW;
@@ -87,30 +120,52 @@ bf16* Engine::vae_attn(const VaeAttnW& a, const bf16* x, int B, int HW, hipStrea
     bf16* q = linear_rows(n, M, a.q, ACT_NONE, nullptr, nullptr, s);
     bf16* k = linear_rows(n, M, a.k, ACT_NONE, nullptr, nullptr, s);
     bf16* o = arena_.get<bf16>((size_t)M * C);
-    for (int b = 0; b < B; ++b) {
-        const size_t mb = arena_.mark();
-        // v^T [C][HW] = Wv n_b^T  (bias folded into the P v product: rows of P sum to 1)
-        bf16* vT = arena_.get<bf16>((size_t)C * HW);
-        {
-            gemm(a_rows(a.v.w, C), n + (size_t)b * HW * C, C, HW, C, e_rows(vT, HW), s);
-        }
-        float* S = arena_.get<float>((size_t)HW * HW);
-        {
-            Epilogue E = e_rows(S, HW);
-            E.out_f32 = 1;
-            gemm(a_rows(q + (size_t)b * HW * C, C), k + (size_t)b * HW * C, HW, HW, C, E, s);
-        }
-        bf16* Pm = arena_.get<bf16>((size_t)HW * HW);
-        CK(softmax_rows_launch(S, Pm, HW, HW, 1.f / std::sqrt((float)C), s));
+    // v^T [C][HW] = Wv n_b^T per image (bias folded into the P v product: rows of P sum to 1)
+    if (vae_attn_flash_for(vae_attn_mode_, HW, C, (size_t)C * HW * sizeof(bf16))) {
+        bf16* vT = arena_.get<bf16>((size_t)M * C);
+        for (int b = 0; b < B; ++b) gemm(a_rows(a.v.w, C), n + (size_t)b * HW * C, C, HW, C, e_rows(vT + (size_t)b * HW * C, HW), s);
+        ProfScope ps(this, s, "vae_attn_flash_kernel", 4.0 * B * HW * HW * C, 0.0);
+        CK(vae_attn_flash_launch(q, k, vT, a.v.b, o, B, HW, C, s));
         ++n_launches;
-        {
-            gemm(a_rows(Pm, HW), vT, HW, C, HW, e_rows(o + (size_t)b * HW * C, C, a.v.b), s);
+    } else {
+        for (int b = 0; b < B; ++b) {
+            const size_t mb = arena_.mark();
+            bf16* vT = arena_.get<bf16>((size_t)C * HW);
+            gemm(a_rows(a.v.w, C), n + (size_t)b * HW * C, C, HW, C, e_rows(vT, HW), s);
+            vae_attn_matrix(q + (size_t)b * HW * C, k + (size_t)b * HW * C, vT, a.v.b, o + (size_t)b * HW * C, HW, C, s);
+            arena_.release(mb);
         }
-        arena_.release(mb);
     }
     gemm(a_rows(o, C), a.proj.w, M, C, C, e_rows_res(out, C, a.proj.b, x), s);
     arena_.release(mk);
     return out;
+}
+
+void Engine::op_vae_attention(const bf16* q, const bf16* k, const bf16* v, int B, int T, int C, int mode, bf16* o, hipStream_t s) {
+    if (mode < 0 || mode > 2) throw GlError(GL_ERR_ARG, fmt("vae attention mode %d: 0 = auto, 1 = score matrices, 2 = flash", mode));
+    if (B <= 0 || T <= 0 || T % 64 || C <= 0 || C % 64)
+        throw GlError(GL_ERR_UNSUPPORTED, fmt("vae attention: B=%d T=%d C=%d (T and C positive multiples of 64)", B, T, C));
+    const size_t mk = arena_.mark();
+    struct Release {
+        Arena& ar;
+        size_t mk;
+        ~Release() { ar.release(mk); }   // stream-ordered reuse, as every operator's workspace
+    } release{arena_, mk};
+    const bool flash = vae_attn_flash_for(mode, T, C, (size_t)B * T * C * sizeof(bf16));
+    bf16* vT = arena_.get<bf16>((size_t)B * T * C);
+    CK(vae_attn_transpose_launch(v, vT, B, T, C, s));
+    ++n_launches;
+    if (flash) {
+        CK(vae_attn_flash_launch(q, k, vT, nullptr, o, B, T, C, s));
+        ++n_launches;
+        return;
+    }
+    const size_t img = (size_t)T * C;
+    for (int b = 0; b < B; ++b) {
+        const size_t mb = arena_.mark();
+        vae_attn_matrix(q + b * img, k + b * img, vT + b * img, nullptr, o + b * img, T, C, s);
+        arena_.release(mb);
+    }
 }
 
 // AutoencoderKL.decode (autoencoder.py:40-44) -> Decoder.forward (model.py:535-568)

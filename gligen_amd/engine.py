@@ -282,6 +282,25 @@ class Engine:
         check(self.lib.gl_op_clip_attention(self._ctx, _ptr(qkv), _ptr(out), int(S), int(T), int(heads), int(bool(causal)), _stream(self.device)))
         return out
 
+    def set_vae_attention(self, mode="auto") -> None:
+        """gl_vae_set_attention: the form of the autoencoder's AttnBlock on this context. 'auto' (default): score matrices up to 4096
+        tokens (6 T^2 bytes of arena per image), vae_attn_flash_kernel above that or where they do not fit; 'matrix'; 'flash'."""
+        from ._lib import VAE_ATTN_MODES
+        check(self.lib.gl_vae_set_attention(self._ctx, VAE_ATTN_MODES[mode] if isinstance(mode, str) else int(mode)))
+
+    def vae_attention(self, q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, mode="auto") -> torch.Tensor:
+        """softmax(q k^T C^-0.5) v on bf16 rows [B, T, C] (gl_op_vae_attention): one head whose dimension is C, T and C multiples of
+        64; mode as set_vae_attention, for this call. Returns bf16 [B, T, C]."""
+        from ._lib import VAE_ATTN_MODES
+        for name, t in (("q", q), ("k", k), ("v", v)):
+            if t.dtype != torch.bfloat16 or t.dim() != 3 or t.shape != q.shape or not t.is_contiguous() or t.device != q.device:
+                raise ValueError(f"vae_attention: {name} must be contiguous bf16 [B, T, C] like q")
+        B, T, Cn = q.shape
+        out = torch.empty_like(q)
+        check(self.lib.gl_op_vae_attention(self._ctx, _ptr(q), _ptr(k), _ptr(v), int(B), int(T), int(Cn),
+                                           VAE_ATTN_MODES[mode] if isinstance(mode, str) else int(mode), _ptr(out), _stream(self.device)))
+        return out
+
     def upload(self, namespace: str, state_dict: Mapping[str, torch.Tensor], prefix_filter: Optional[str] = None) -> int:
         """Upload fp32 parameters under '<namespace>/<reference state_dict key>'."""
         n = 0

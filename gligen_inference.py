@@ -308,12 +308,19 @@ def prepare_batch_kp(meta, batch=1, max_persons_per_image=8):
     return batch_to_device(out, device)
 
 
-def crop_and_resize(image):
-    """center crop to a square, resize to 512 x 512 (reference gligen_inference.py:189-193)."""
+def crop_and_resize(image, size=(512, 512)):
+    """center crop to the aspect of size = (width, height), resize to it; the default is the reference's square crop and 512 x 512
+    (gligen_inference.py:189-193)."""
     w, h = image.size
-    c = min(w, h)
-    left, top = int(round((w - c) / 2.0)), int(round((h - c) / 2.0))
-    return image.crop((left, top, left + c, top + c)).resize((512, 512))
+    tw, th = size
+    if tw == th:
+        cw = ch = min(w, h)
+    elif w * th > h * tw:        # wider than the target: the full height, the middle of the width
+        cw, ch = max(1, int(round(h * tw / th))), h
+    else:
+        cw, ch = w, max(1, int(round(w * th / tw)))
+    left, top = int(round((w - cw) / 2.0)), int(round((h - ch) / 2.0))
+    return image.crop((left, top, left + cw, top + ch)).resize((tw, th))
 
 
 def _pil_to_unit_tensor(image):
@@ -342,9 +349,15 @@ def _native_rgb_512(path, centre_crop):
     return _rt.scratch_engine(device).image_resample([t], [(512, 512)], None, "bicubic", _unit_lut())[0]
 
 
-def load_inpaint_image(path, native=False):
+def load_inpaint_image(path, native=False, size=None):
     """The inpainting input as run() encodes it (reference gligen_inference.py:402-404): RGB, resized to 512 x 512 without a crop,
-    in [-1, 1], float32 [1, 3, 512, 512] on the device. native=True resizes on the device (the same bits)."""
+    in [-1, 1], float32 [1, 3, 512, 512] on the device. native=True resizes on the device (the same bits). size = (width, height):
+    another target; the image is then centre-cropped to its aspect first (crop_and_resize), so nothing is stretched."""
+    if size is not None and tuple(size) != (512, 512):
+        if native:
+            raise ValueError(f"native_inputs with an image size of {size[0]} x {size[1]}: the native front end is written for 512 x 512")
+        img = torch.from_numpy(np.asarray(crop_and_resize(Image.open(path).convert("RGB"), tuple(size))).copy()).permute(2, 0, 1)
+        return (img.float().unsqueeze(0).to(device) / 255 - 0.5) / 0.5
     if native:
         return _native_rgb_512(path, centre_crop=False).unsqueeze(0)
     img = torch.from_numpy(np.asarray(Image.open(path).convert("RGB").resize((512, 512)))).permute(2, 0, 1)
@@ -426,7 +439,19 @@ _NATIVE_PREPARE = (prepare_batch_hed, prepare_batch_canny, prepare_batch_depth, 
 
 
 def draw_masks_from_boxes(boxes, size):
-    """Inpainting mask: 1 outside, 0 inside int(box*size) rectangles (reference inpaint_mask_func.py:16-41)."""
+    """Inpainting mask: 1 outside, 0 inside int(box*size) rectangles (reference inpaint_mask_func.py:16-41). size: the side of a
+    square grid, or (h, w): x coordinates scale with w, y coordinates with h."""
+    if not isinstance(size, int):
+        h, w = (int(v) for v in size)
+        scale = torch.tensor([w, h, w, h], dtype=torch.float32)
+        masks = []
+        for per_image in boxes:
+            m = torch.ones(h, w)
+            for bx in per_image:
+                x0, y0, x1, y1 = (int(v) for v in bx.float().cpu() * scale)
+                m[y0:y1, x0:x1] = 0
+            masks.append(m)
+        return torch.stack(masks).unsqueeze(1)
     masks = []
     for per_image in boxes:
         m = torch.ones(size, size)
@@ -435,6 +460,43 @@ def draw_masks_from_boxes(boxes, size):
             m[y0:y1, x0:x1] = 0
         masks.append(m)
     return torch.stack(masks).unsqueeze(1)
+
+
+def vae_factor(autoencoder):
+    """Pixels per latent cell along one axis: 2^(levels - 1) of the autoencoder (8 for the shipped KL-f8 one)."""
+    dd = getattr(autoencoder, "ddconfig", None)
+    return 2 ** (len(dd["ch_mult"]) - 1) if dd else 8
+
+
+def latent_hw(model, autoencoder=None, height=None, width=None):
+    """(h, w) of the latent grid for an image of height x width pixels; None = the checkpoint's own size (model.image_size cells).
+    Both must be multiples of the autoencoder's factor times the UNet's total stride (8 x 8 = 64 for the shipped model). A spatial-map
+    model (canny / hed / depth / normal / sem) runs at its configured size only: its GroundingDownsampler resizes the map to a fixed
+    resize_input."""
+    if height is None and width is None:
+        return int(model.image_size), int(model.image_size)
+    f = vae_factor(autoencoder)
+    stride = 2 ** (len(model.channel_mult) - 1)
+    out = []
+    for name, v in (("height", height), ("width", width)):
+        if v is None:
+            out.append(int(model.image_size))
+            continue
+        v = int(v)
+        if v <= 0 or v % (f * stride):
+            raise ValueError(f"{name} = {v}: a positive multiple of {f * stride} pixels (the autoencoder's factor {f} x the UNet's total stride {stride})")
+        out.append(v // f)
+    ds = getattr(model, "downsample_net", None)
+    if ds is not None and tuple(out) != (int(model.image_size), int(model.image_size)):
+        raise ValueError(f"a spatial-map model at {out[0] * f} x {out[1] * f} pixels: its grounding downsampler has a fixed resize_input = "
+                         f"{getattr(ds, 'resize_input', '?')}, so it runs at {model.image_size * f} x {model.image_size * f} only")
+    return out[0], out[1]
+
+
+def _check_starting_noise(starting_noise, shape, asked=True):
+    """asked: height or width was given. Without them a starting_noise keeps deciding the latent's size, as it always did."""
+    if asked and starting_noise is not None and tuple(starting_noise.shape[1:]) != tuple(shape[1:]):
+        raise ValueError(f"starting_noise has shape {tuple(starting_noise.shape)}, height / width ask for a latent of {tuple(shape)}")
 
 
 # ---- synthetic models (no checkpoints offline) ---------------------------------------------------------
@@ -496,10 +558,13 @@ def sampler_choice(sampler=None, no_plms=False, discretize="uniform", ddim_eta=0
 @torch.no_grad()
 def generate(model, autoencoder, diffusion, batch, context, uc, *, steps=None, guidance_scale=7.5, alpha_type=None,
              starting_noise=None, inpainting_mask=None, z0=None, use_graph=True, no_plms=False, grounding_extra_input=None,
-             grounding_input=None, sampler=None, discretize="uniform", ddim_eta=0.0):
+             grounding_input=None, sampler=None, discretize="uniform", ddim_eta=0.0, height=None, width=None):
     """The sampling core of run() (reference gligen_inference.py:389-431) on already-encoded inputs. steps: None = 50, or 20 for
-    sampler="dpmpp_2m"."""
+    sampler="dpmpp_2m". height, width: the image size in pixels (None: the checkpoint's, 8 * model.image_size); see latent_hw."""
     name, _ = sampler_choice(sampler, no_plms, discretize, ddim_eta)
+    h, w = latent_hw(model, autoencoder, height, width)
+    shape = (context.shape[0], model.in_channels, h, w)
+    _check_starting_noise(starting_noise, shape, height is not None or width is not None)
     schedule_kwargs = {}
     if name == "dpmpp_2m":
         from ldm.models.diffusion.dpm_solver import DPMSolverSampler as sampler_cls
@@ -521,8 +586,6 @@ def generate(model, autoencoder, diffusion, batch, context, uc, *, steps=None, g
         grounding_input = model.grounding_tokenizer_input.prepare(batch)
     input = dict(x=starting_noise, timesteps=None, context=context, grounding_input=grounding_input,
                  inpainting_extra_input=inpainting_extra_input, grounding_extra_input=grounding_extra_input)
-    B = context.shape[0]
-    shape = (B, model.in_channels, model.image_size, model.image_size)
     latents = sampler.sample(S=steps, shape=shape, input=input, uc=uc, guidance_scale=guidance_scale, mask=inpainting_mask, x0=z0, **schedule_kwargs)
     return autoencoder.decode(latents)
 
@@ -566,7 +629,7 @@ def _lanes_of(model, autoencoder, lanes, device):
 
 @torch.no_grad()
 def generate_lanes(model, autoencoder, diffusion, batch, context, uc, *, lanes=2, starting_noise=None, grounding_extra_input=None,
-                   grounding_input=None, **kw):
+                   grounding_input=None, height=None, width=None, **kw):
     """generate() with the batch split over `lanes` execution contexts that run concurrently on their own HIP streams, so that
     one half's kernel tails, launch gaps and memory-bound kernels overlap the other half's matrix work (what bench.py's
     --lanes measures: +15 % images/s at 2). Every sample's trajectory is independent, so the images are generate()'s up to the
@@ -576,6 +639,8 @@ def generate_lanes(model, autoencoder, diffusion, batch, context, uc, *, lanes=2
     (alpha_type [0.3, 0, 0.7]) changes its own engine and the shared nn.Module, never another lane's packed weights."""
     import copy
     n = context.shape[0]
+    _check_starting_noise(starting_noise, (n, model.in_channels) + latent_hw(model, autoencoder, height, width), height is not None or width is not None)   # (before anything is split)
+    kw = dict(kw, height=height, width=width)
     if lanes < 2 or n < 2 * lanes:
         return generate(model, autoencoder, diffusion, batch, context, uc, starting_noise=starting_noise,
                         grounding_extra_input=grounding_extra_input, grounding_input=grounding_input, **kw)
@@ -618,7 +683,7 @@ def generate_lanes(model, autoencoder, diffusion, batch, context, uc, *, lanes=2
 
 
 @torch.no_grad()
-def generate_stream(model, autoencoder, diffusion, batch, context, uc, noises, *, lanes=2, first_lane=0, **kw):
+def generate_stream(model, autoencoder, diffusion, batch, context, uc, noises, *, lanes=2, first_lane=0, height=None, width=None, **kw):
     """Several WHOLE batches of the same prompt (one starting noise each), issued round-robin to `lanes` execution contexts -- what
     bench.py times: while one batch's evaluation is in its kernel tails and memory-bound kernels, the other's matrix work fills the
     chip. Each batch keeps the benchmark's shape (the tile table, the captured graph and the timed row-local / two-GEMM choice are
@@ -626,6 +691,11 @@ def generate_stream(model, autoencoder, diffusion, batch, context, uc, noises, *
     Batch i goes to lane (first_lane + i) % lanes."""
     import copy
     lanes = max(1, int(lanes))
+    shape = (context.shape[0], model.in_channels) + latent_hw(model, autoencoder, height, width)
+    noises = list(noises)
+    for x_T in noises:
+        _check_starting_noise(x_T, shape, height is not None or width is not None)
+    kw = dict(kw, height=height, width=width)
     model.engine, autoencoder.engine
     dev = context.device
     main = torch.cuda.current_stream(dev)
@@ -688,6 +758,14 @@ def run(meta, config, starting_noise=None, models=None):
     if "grounding_downsampler_input" in ckpt_config:
         grounding_downsampler_input = instantiate_from_config(ckpt_config["grounding_downsampler_input"])
     B = args["batch_size"]
+    # optional keys height / width (pixels): None = the checkpoint's size
+    height, width = args.get("height"), args.get("width")
+    lat_h, lat_w = latent_hw(model, autoencoder, height, width)
+    f = vae_factor(autoencoder)
+    default_size = (lat_h, lat_w) == (model.image_size, model.image_size)
+    if args.get("native_inputs") and not default_size:
+        raise ValueError(f"native_inputs with height / width = {lat_h * f} x {lat_w * f}: the native input front end is written for "
+                         f"{model.image_size * f} x {model.image_size * f}")
     rank, _, world = gdist.env_world()
     lo, hi = gdist.shard_range(B, rank, world)
     folder = os.path.join(args["folder"], meta["save_folder_name"])
@@ -697,7 +775,7 @@ def run(meta, config, starting_noise=None, models=None):
         os.makedirs(folder, exist_ok=True)
         gdist.barrier()
         gdist.barrier()
-        return torch.empty((0, 3, 8 * model.image_size, 8 * model.image_size))
+        return torch.empty((0, 3, 8 * model.image_size, 8 * model.image_size) if default_size else (0, 3, f * lat_h, f * lat_w))
     prepare = next((fn for key, fn in _PREPARE_BY_NAME if key in meta["ckpt"]), prepare_batch)
     native_clip = bool(args.get("native_clip"))
     native_inputs = bool(args.get("native_inputs"))   # conditioning maps and the inpainting image: crop / resize / scale on the device
@@ -730,17 +808,17 @@ def run(meta, config, starting_noise=None, models=None):
             torch.cuda.manual_seed(int(args.get("seed") or 0))
         if starting_noise is None:
             gen = torch.Generator().manual_seed(int(args.get("seed") or 0))
-            starting_noise = torch.randn((B, model.in_channels, model.image_size, model.image_size), generator=gen)
+            starting_noise = torch.randn((B, model.in_channels, lat_h, lat_w), generator=gen)
     if starting_noise is not None:
         starting_noise = starting_noise.to(device)[lo:hi] if starting_noise.shape[0] == B else starting_noise.to(device)
     mask = z0 = None
     if "input_image" in meta:
         assert ckpt_config.get("inpaint_mode"), "input_image is given, the ckpt must be the inpaint model, are you using the correct ckpt?"
-        mask = draw_masks_from_boxes(batch["boxes"], model.image_size).to(device)
+        mask = draw_masks_from_boxes(batch["boxes"], model.image_size if default_size else (lat_h, lat_w)).to(device)
         if "z0" in meta:
             z0 = meta["z0"].to(device)
         else:
-            z0 = autoencoder.encode(load_inpaint_image(meta["input_image"], native=native_inputs))
+            z0 = autoencoder.encode(load_inpaint_image(meta["input_image"], native=native_inputs, size=None if default_size else (f * lat_w, f * lat_h)))
     grounding_extra_input = None
     if grounding_downsampler_input is not None:
         grounding_extra_input = grounding_downsampler_input.prepare(batch)
@@ -762,14 +840,14 @@ def run(meta, config, starting_noise=None, models=None):
     if mask is not None or skw["ddim_eta"] or (hi - lo) < SPLIT_BATCH_AT:     # (eta > 0 draws its step noise from the device generator too)
         lanes = 1
     if lanes > 1 and starting_noise is None:   # x_T as the sampler would draw it (plms.py:71), before the batch is split
-        starting_noise = torch.randn((hi - lo, model.in_channels, model.image_size, model.image_size), device=device)
+        starting_noise = torch.randn((hi - lo, model.in_channels, lat_h, lat_w), device=device)
     repeat = max(1, int(args.get("repeat") or 1))
     n_lanes_req = 3 if args.get("lanes") is None else max(1, int(args.get("lanes")))    # whole batches in flight (--repeat): 3, as bench.py
     if repeat > 1 and mask is None and not skw["ddim_eta"] and meta.get("alpha_type") in (None, [1, 0, 0], [1.0, 0.0, 0.0]):
         # `repeat` batches of this prompt (seed, seed + 1, ...): whole batches in flight on the lanes, as bench.py runs them
         gkw = dict(steps=steps, guidance_scale=args["guidance_scale"], alpha_type=meta.get("alpha_type"), no_plms=no_plms,
-                   grounding_extra_input=grounding_extra_input, grounding_input=grounding_input, **skw)
-        shape = (hi - lo, model.in_channels, model.image_size, model.image_size)
+                   grounding_extra_input=grounding_extra_input, grounding_input=grounding_input, height=height, width=width, **skw)
+        shape = (hi - lo, model.in_channels, lat_h, lat_w)
         seed0 = int(args.get("seed") or 0)
         seeded = world > 1 or args.get("seed") is not None
         def noise(r):
@@ -798,7 +876,7 @@ def run(meta, config, starting_noise=None, models=None):
         samples = generate_lanes(model, autoencoder, diffusion, batch, context, uc, lanes=lanes, steps=steps,
                                  guidance_scale=args["guidance_scale"], alpha_type=meta.get("alpha_type"), starting_noise=starting_noise,
                                  inpainting_mask=mask, z0=z0, no_plms=no_plms, grounding_extra_input=grounding_extra_input,
-                                 grounding_input=grounding_input, **skw)
+                                 grounding_input=grounding_input, height=height, width=width, **skw)
         if torch.cuda.is_available():
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
@@ -889,6 +967,8 @@ def main(argv=None):
     parser.add_argument("--inpaint", action="store_true", help="with --synthetic text: the inpainting model (9-channel first conv, encode + blend)")
     parser.add_argument("--native_clip", action="store_true", help="run CLIP in the native HIP engine instead of transformers: the checkpoint's text tower (prompt, negative prompt, phrases) and, for image-grounded phrases, the ViT-L/14 vision tower")
     parser.add_argument("--native_inputs", action="store_true", help="prepare the conditioning inputs on the device: crop, resize and scaling of the spatial maps and of the inpainting image in HIP (the same bits as Pillow), and semantic maps as uint8 class indices in place of 152 one-hot planes; only file decoding stays on the host")
+    parser.add_argument("--height", type=int, default=None, help="image height in pixels (default: the checkpoint's, 512); a multiple of 64. Above 512 x 512 the autoencoder's attention runs as a flash kernel")
+    parser.add_argument("--width", type=int, default=None, help="image width in pixels (default: the checkpoint's, 512); a multiple of 64")
     parser.add_argument("--ckpt", type=str, default=None, help="run only the meta_list entries whose checkpoint path contains this string")
     parser.add_argument("--seed", type=int, default=None, help="seed of x_T (one draw for the whole batch, sliced across ranks)")
     parser.add_argument("--lanes", type=int, default=None, help="with --repeat: whole batches in flight (default 3, the bench's schedule); without: per-GPU batches of 32 and more run as two half-batches in flight unless this is 1")
@@ -911,7 +991,7 @@ def main(argv=None):
         meta = _synthetic_meta(args.synthetic, args.batch_size)
         if args.inpaint:
             from gligen_amd import synthetic as syn
-            meta.update(input_image="synthetic", z0=autoencoder.encode(torch.rand(1, 3, 512, 512, generator=torch.Generator().manual_seed(8)).to(device) * 2 - 1))
+            meta.update(input_image="synthetic", z0=autoencoder.encode(torch.rand(1, 3, args.height or 512, args.width or 512, generator=torch.Generator().manual_seed(8)).to(device) * 2 - 1))
         run(meta, args, models=(model, autoencoder, None, diffusion, cfg))
     else:
         for meta in meta_list:   # the reference runs every entry (gligen_inference.py:640-642)
