@@ -2,6 +2,7 @@
 #include "classmap.h"
 #include "engine_impl.h"
 #include "image.h"
+#include "latent.h"
 #include "train.h"
 #include "train_fusers.h"
 #include "../../include/gligen_amd_train_maps.h"
@@ -13,6 +14,7 @@
 #include "../../include/gligen_amd_gemm_plans.h"
 #include "../../include/gligen_amd_attention_core.h"
 #include "../../include/gligen_amd_vae.h"
+#include "../../include/gligen_amd_latent.h"
 #include "gemm_plan.h"
 
 #include <cstdlib>
@@ -865,6 +867,22 @@ int gl_op_grid_resize_backward(gl_ctx* ctx, const float* g, int B, int sg, int s
     GL_TRY(gl::grid_resize_bwd_launch(g, B, sg, sv, C, dsrc, S(s)));
     ++ctx->eng->n_launches;
     GL_API_END
+}
+
+// ---- include/gligen_amd_latent.h: resize + q_sample in one launch, and the host table of its taps
+int gl_op_latent_renoise(gl_ctx* ctx, const float* src, int B, int C, int h, int w, float* dst, int h2, int w2, int mode, float sa, float s1,
+                         const float* noise, int noise_B, gl_stream s) {
+    NEED(ctx);
+    GL_API_BEGIN
+    GL_TRY(gl::latent_renoise_launch(src, B, C, h, w, dst, h2, w2, mode, sa, s1, noise, noise_B, S(s)));
+    ++ctx->eng->n_launches;
+    GL_API_END
+}
+
+int gl_latent_resize_taps(int in_size, int out_size, int mode, int* first_index, float* weights) {
+    int n_taps = 0;
+    if (gl::latent_resize_taps(in_size, out_size, mode, first_index, weights, &n_taps) != GL_OK) return -1;
+    return n_taps;
 }
 
 // ---- include/gligen_amd_train_prims.h: the training path's primitives one by one, over the arena and workspace the slices above use

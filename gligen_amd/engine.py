@@ -648,6 +648,33 @@ class Engine:
                                            int(n), _stream(dev)))
         return out, d0
 
+    def latent_renoise(self, src: torch.Tensor, size, mode: str = "bicubic", sa: float = 1.0, s1: float = 0.0,
+                       noise: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """gl_op_latent_renoise: sa * resize(src [B,C,h,w]) + s1 * noise [B|1,C,h2,w2] in one launch, size = (h2, w2); the start point of
+        a partial sampling (image-to-image, the second pass of a two-pass generation). mode: nearest-exact, bilinear or bicubic with
+        torch's F.interpolate semantics (align_corners=False, no antialias). noise=None: the plain resize times sa. At equal sizes the
+        result is diffusion.q_sample's, bit for bit. out: a contiguous fp32 tensor of the output's shape on this device to write into."""
+        if mode not in _lib.LATENT_RESIZE_MODES:
+            raise ValueError(f"latent_renoise: mode {mode!r}: one of {sorted(_lib.LATENT_RESIZE_MODES)}")
+        dev = self.device
+        src = _f32(src, dev)
+        if src.dim() != 4:
+            raise ValueError(f"latent_renoise: src has shape {tuple(src.shape)}, need [B, C, h, w]")
+        B, Cc, h, w = (int(v) for v in src.shape)
+        h2, w2 = (int(v) for v in size)
+        if noise is not None:
+            noise = _f32(noise, dev)
+            if noise.dim() != 4 or tuple(noise.shape[1:]) != (Cc, h2, w2) or int(noise.shape[0]) not in (1, B):
+                raise ValueError(f"latent_renoise: noise {tuple(noise.shape)} is not [{B} or 1, {Cc}, {h2}, {w2}]")
+        if out is None:
+            out = torch.empty((B, Cc, h2, w2), device=dev, dtype=torch.float32)
+        elif (not out.is_cuda or out.device != dev or out.dtype != torch.float32 or not out.is_contiguous()
+              or tuple(out.shape) != (B, Cc, h2, w2)):
+            raise ValueError(f"latent_renoise: out must be a contiguous fp32 tensor of shape {(B, Cc, h2, w2)} on {dev}")
+        check(self.lib.gl_op_latent_renoise(self._ctx, _ptr(src), B, Cc, h, w, _ptr(out), h2, w2, _lib.LATENT_RESIZE_MODES[mode], float(sa), float(s1),
+                                            _ptr(noise), 0 if noise is None else int(noise.shape[0]), _stream(dev)))
+        return out
+
     def sampler_timing(self):
         """(mean UNet-evaluation ms over graph replays, first eager evaluation ms, number of evaluations)."""
         a, f, n = C.c_float(), C.c_float(), C.c_int()

@@ -555,16 +555,75 @@ def sampler_choice(sampler=None, no_plms=False, discretize="uniform", ddim_eta=0
     return name, SAMPLER_STEPS[name]
 
 
+# hires_upscaler -> how the first pass's result reaches the second pass's size: the latent resized by Engine.latent_renoise in that mode
+# (fused with the noising), or the decoded image resized by the same kernel (bicubic, C = 3) and encoded again
+HIRES_UPSCALERS = {"latent-nearest": "nearest-exact", "latent-bilinear": "bilinear", "latent-bicubic": "bicubic", "pixel-bicubic": None}
+
+
+def _hires_context(model, shape):
+    """The execution context the second pass of a two-pass generation runs on: a fork of the model's engine (_lane_clone) kept per
+    model, per first-conv state and per (B, h2, w2). The model's own engine then only ever sees the first pass's shape and the fork only
+    the second's, so neither recaptures its graphs or allocates sampler buffers after its first call. A fork carries the first conv of
+    the moment it was made: one made in another state than the model is in now (GLIGEN vs restored SD conv) is stale, as in
+    _lanes_of, and so is one whose parent engine was rebuilt."""
+    model.engine           # (built before the fork)
+    state = (model.first_conv_type, bool(model.__dict__.get("_first_conv_restored")))
+    ctxs = model.__dict__.get("_hires")
+    if ctxs is None:
+        ctxs = model.__dict__["_hires"] = {}
+    key = tuple(int(v) for v in shape)
+    for k in [k for k, (m, st) in ctxs.items() if st != state or m.__dict__.get("_engine") is None
+              or m.__dict__.get("_fork_of") is not model.__dict__.get("_engine")]:
+        m = ctxs.pop(k)[0]
+        if m.__dict__.get("_engine") is not None:
+            m.__dict__["_engine"].close()
+            m.__dict__["_engine"] = None
+    if key not in ctxs:
+        ctxs[key] = (_lane_clone(model), state)
+    m = ctxs[key][0]
+    m.grounding_tokenizer_input = model.grounding_tokenizer_input
+    m.first_conv_type = model.first_conv_type
+    return m
+
+
 @torch.no_grad()
 def generate(model, autoencoder, diffusion, batch, context, uc, *, steps=None, guidance_scale=7.5, alpha_type=None,
              starting_noise=None, inpainting_mask=None, z0=None, use_graph=True, no_plms=False, grounding_extra_input=None,
-             grounding_input=None, sampler=None, discretize="uniform", ddim_eta=0.0, height=None, width=None):
+             grounding_input=None, sampler=None, discretize="uniform", ddim_eta=0.0, height=None, width=None,
+             init_latent=None, init_image=None, strength=None, hires=None, hires_strength=0.6, hires_steps=None, hires_upscaler="latent-bicubic"):
     """The sampling core of run() (reference gligen_inference.py:389-431) on already-encoded inputs. steps: None = 50, or 20 for
-    sampler="dpmpp_2m". height, width: the image size in pixels (None: the checkpoint's, 8 * model.image_size); see latent_hw."""
+    sampler="dpmpp_2m". height, width: the image size in pixels (None: the checkpoint's, 8 * model.image_size); see latent_hw.
+    Image-to-image: init_latent (fp32 [B|1, C, h', w'], any spatial size) or init_image (fp32 [B|1, 3, H', W'] in [-1, 1], encoded to
+    one) with strength in (0, 1]: the last int(strength * steps) steps run from it, resized to the latent's size and noised to the
+    first of them (starting_noise, when given, is that noise).
+    hires = (H2, W2): two passes -- this very call at height x width, then a second sampling of int(hires_strength * hires_steps) steps
+    (hires_steps: None = steps) at H2 x W2 from the first pass's result, enlarged as hires_upscaler says (HIRES_UPSCALERS), and the
+    decode at H2 x W2. The second pass runs on a forked context (_hires_context)."""
     name, _ = sampler_choice(sampler, no_plms, discretize, ddim_eta)
     h, w = latent_hw(model, autoencoder, height, width)
     shape = (context.shape[0], model.in_channels, h, w)
     _check_starting_noise(starting_noise, shape, height is not None or width is not None)
+    if init_latent is not None and init_image is not None:
+        raise ValueError("init_latent and init_image: give one of them (init_image is encoded to the other)")
+    img2img = init_latent is not None or init_image is not None
+    if img2img and strength is None:
+        raise ValueError(f"{'init_image' if init_image is not None else 'init_latent'} needs strength (the fraction of the schedule that runs, in (0, 1])")
+    if strength is not None and not img2img:
+        raise ValueError(f"strength = {strength} needs init_image or init_latent")
+    if inpainting_mask is not None and (img2img or hires is not None):
+        raise ValueError(f"{'hires' if hires is not None else 'init_image / init_latent'} with inpainting_mask: an inpainting run starts from noise, at one size")
+    if hires is not None:
+        if hires_upscaler not in HIRES_UPSCALERS:
+            raise ValueError(f"hires_upscaler {hires_upscaler!r}: one of {sorted(HIRES_UPSCALERS)}")
+        H2, W2 = (int(v) for v in hires)
+        f = vae_factor(autoencoder)
+        if H2 < f * h or W2 < f * w:
+            raise ValueError(f"hires = {H2} x {W2} is smaller than the first pass's {f * h} x {f * w}: the second pass runs at the same or a larger size")
+        h2, w2 = latent_hw(model, autoencoder, H2, W2)
+    if init_image is not None:
+        if init_image.dim() != 4 or int(init_image.shape[1]) != 3 or int(init_image.shape[0]) not in (1, shape[0]):
+            raise ValueError(f"init_image {tuple(init_image.shape)} is not [{shape[0]} or 1, 3, H, W]")
+        init_latent = autoencoder.encode(init_image.to(device=context.device, dtype=torch.float32))
     schedule_kwargs = {}
     if name == "dpmpp_2m":
         from ldm.models.diffusion.dpm_solver import DPMSolverSampler as sampler_cls
@@ -575,18 +634,40 @@ def generate(model, autoencoder, diffusion, batch, context, uc, *, steps=None, g
         sampler_cls = DDIMSampler if name == "ddim" else PLMSSampler
     if steps is None:
         steps = 20 if name == "dpmpp_2m" else 50
-    sampler = sampler_cls(diffusion, model, alpha_generator_func=partial(alpha_generator, type=alpha_type), set_alpha_scale=set_alpha_scale)
-    sampler.use_graph = use_graph
-    if name == "ddim" and ddim_eta:
-        sampler.ddim_eta = float(ddim_eta)
     inpainting_extra_input = None
     if inpainting_mask is not None:
         inpainting_extra_input = torch.cat([z0 * inpainting_mask, inpainting_mask], dim=1)
     if grounding_input is None:
         grounding_input = model.grounding_tokenizer_input.prepare(batch)
-    input = dict(x=starting_noise, timesteps=None, context=context, grounding_input=grounding_input,
-                 inpainting_extra_input=inpainting_extra_input, grounding_extra_input=grounding_extra_input)
-    latents = sampler.sample(S=steps, shape=shape, input=input, uc=uc, guidance_scale=guidance_scale, mask=inpainting_mask, x0=z0, **schedule_kwargs)
+
+    def sample_pass(m, S, shp, x_T, **start):
+        sampler = sampler_cls(diffusion, m, alpha_generator_func=partial(alpha_generator, type=alpha_type), set_alpha_scale=set_alpha_scale)
+        sampler.use_graph = use_graph
+        if name == "ddim" and ddim_eta:
+            sampler.ddim_eta = float(ddim_eta)
+        input = dict(x=x_T, timesteps=None, context=context, grounding_input=grounding_input,
+                     inpainting_extra_input=inpainting_extra_input, grounding_extra_input=grounding_extra_input)
+        return sampler.sample(S=S, shape=shp, input=input, uc=uc, guidance_scale=guidance_scale, mask=inpainting_mask, x0=z0, **start, **schedule_kwargs)
+
+    start = dict(x_init=init_latent, strength=strength) if img2img else {}
+    latents = sample_pass(model, steps, shape, starting_noise, **start)
+    if hires is None:
+        return autoencoder.decode(latents)
+    mode = HIRES_UPSCALERS[hires_upscaler]
+    if mode is None:       # pixel-bicubic: through the image, enlarged by the same kernel (C = 3, no noise), and back to a latent
+        image = torch.clamp(autoencoder.decode(latents), -1.0, 1.0)
+        latents = autoencoder.encode(model.engine.latent_renoise(image, (H2, W2), "bicubic"))
+        mode = "bicubic"   # (equal sizes from here: the identity taps)
+    # the second pass's context is looked up after the first pass: it carries the first conv the first pass left the model with
+    m2 = _hires_context(model, (shape[0], h2, w2))
+    latents = sample_pass(m2, steps if hires_steps is None else int(hires_steps), (shape[0], shape[1], h2, w2), None,
+                          x_init=latents, strength=hires_strength, resize_mode=mode)
+    if m2.__dict__.get("_first_conv_restored") and not model.__dict__.get("_first_conv_restored"):
+        # the second pass reached a gated-off step the first did not have (another step count): the swap was made in the fork's
+        # engine and in the shared module; the model's own engine follows, and the fork now carries the model's state
+        model.restore_first_conv_from_SD()
+        key = (shape[0], h2, w2)
+        model.__dict__["_hires"][key] = (m2, (model.first_conv_type, True))
     return autoencoder.decode(latents)
 
 
@@ -599,7 +680,7 @@ def _lane_clone(module):
     parent_engine = module.engine
     m = copy.copy(module)
     m.__dict__ = dict(module.__dict__)
-    for key in ("_cond_key", "_cond_held", "_ds_cache", "_lanes"):
+    for key in ("_cond_key", "_cond_held", "_ds_cache", "_lanes", "_hires"):
         if key in m.__dict__:
             m.__dict__[key] = None
     m.__dict__["_engine"] = parent_engine.fork()
@@ -639,6 +720,8 @@ def generate_lanes(model, autoencoder, diffusion, batch, context, uc, *, lanes=2
     (alpha_type [0.3, 0, 0.7]) changes its own engine and the shared nn.Module, never another lane's packed weights."""
     import copy
     n = context.shape[0]
+    if kw.get("hires") is not None:
+        raise ValueError("hires through generate_lanes: a two-pass generation runs one batch on the model's context and its second-pass fork; call generate()")
     _check_starting_noise(starting_noise, (n, model.in_channels) + latent_hw(model, autoencoder, height, width), height is not None or width is not None)   # (before anything is split)
     kw = dict(kw, height=height, width=width)
     if lanes < 2 or n < 2 * lanes:
@@ -663,9 +746,10 @@ def generate_lanes(model, autoencoder, diffusion, batch, context, uc, *, lanes=2
             if i:
                 m.first_conv_type = model.first_conv_type
                 stream.wait_stream(main)          # the inputs were produced on the caller's stream
+            lane_kw = {k: (cut(v, i) if k in ("init_latent", "init_image") else v) for k, v in kw.items()}    # (a batch-1 start serves every lane)
             with torch.cuda.stream(stream):
                 outs.append(generate(m, ae, diffusion, sub, cut(context, i), cut(uc, i), starting_noise=cut(starting_noise, i),
-                                     grounding_extra_input=cut(grounding_extra_input, i), grounding_input=gi, **kw))
+                                     grounding_extra_input=cut(grounding_extra_input, i), grounding_input=gi, **lane_kw))
     finally:
         model.grounding_tokenizer_input = tokenizer
     for c in ctxs[:lanes - 1]:
@@ -690,6 +774,8 @@ def generate_stream(model, autoencoder, diffusion, batch, context, uc, noises, *
     per shape), unlike generate_lanes, which splits ONE batch into halves. Returns the list of decoded batches in issue order.
     Batch i goes to lane (first_lane + i) % lanes."""
     import copy
+    if kw.get("hires") is not None:
+        raise ValueError("hires through generate_stream: a two-pass generation runs one batch on the model's context and its second-pass fork; call generate()")
     lanes = max(1, int(lanes))
     shape = (context.shape[0], model.in_channels) + latent_hw(model, autoencoder, height, width)
     noises = list(noises)
@@ -766,6 +852,20 @@ def run(meta, config, starting_noise=None, models=None):
     if args.get("native_inputs") and not default_size:
         raise ValueError(f"native_inputs with height / width = {lat_h * f} x {lat_w * f}: the native input front end is written for "
                          f"{model.image_size * f} x {model.image_size * f}")
+    # optional keys init_image (a file) + strength: image-to-image; hires_height / hires_width (pixels; one alone keeps the other
+    # side), hires_strength, hires_steps, hires_upscaler: the second pass of a two-pass generation (generate())
+    hires = None
+    if args.get("hires_height") is not None or args.get("hires_width") is not None:
+        hires = (int(args.get("hires_height") or f * lat_h), int(args.get("hires_width") or f * lat_w))
+        if hires[0] < f * lat_h or hires[1] < f * lat_w:
+            raise ValueError(f"hires_height x hires_width = {hires[0]} x {hires[1]} is smaller than the first pass's {f * lat_h} x {f * lat_w}")
+        latent_hw(model, autoencoder, *hires)
+        if max(1, int(args.get("repeat") or 1)) > 1:
+            raise ValueError("hires with --repeat: whole batches in flight share the model's contexts; a two-pass generation runs one batch at a time")
+    if (args.get("init_image") is None) != (args.get("strength") is None):
+        raise ValueError("init_image and strength go together: the image to start from and the fraction of the schedule that runs from it")
+    if "input_image" in meta and (hires is not None or args.get("init_image") is not None):
+        raise ValueError(f"{'hires' if hires is not None else 'init_image'} with an inpainting entry (input_image): an inpainting run starts from noise, at one size")
     rank, _, world = gdist.env_world()
     lo, hi = gdist.shard_range(B, rank, world)
     folder = os.path.join(args["folder"], meta["save_folder_name"])
@@ -775,6 +875,8 @@ def run(meta, config, starting_noise=None, models=None):
         os.makedirs(folder, exist_ok=True)
         gdist.barrier()
         gdist.barrier()
+        if hires is not None:
+            return torch.empty((0, 3) + hires)
         return torch.empty((0, 3, 8 * model.image_size, 8 * model.image_size) if default_size else (0, 3, f * lat_h, f * lat_w))
     prepare = next((fn for key, fn in _PREPARE_BY_NAME if key in meta["ckpt"]), prepare_batch)
     native_clip = bool(args.get("native_clip"))
@@ -819,6 +921,14 @@ def run(meta, config, starting_noise=None, models=None):
             z0 = meta["z0"].to(device)
         else:
             z0 = autoencoder.encode(load_inpaint_image(meta["input_image"], native=native_inputs, size=None if default_size else (f * lat_w, f * lat_h)))
+    start = {}
+    if args.get("init_image") is not None:     # read as the inpainting image is: RGB in [-1, 1] at the run's size, batch 1 for every sample
+        start = dict(init_image=load_inpaint_image(args["init_image"], native=native_inputs, size=None if native_inputs else (f * lat_w, f * lat_h)),
+                     strength=float(args["strength"]))
+    if hires is not None:
+        start.update(hires=hires, hires_strength=float(0.6 if args.get("hires_strength") is None else args["hires_strength"]),
+                     hires_steps=None if args.get("hires_steps") is None else int(args["hires_steps"]),
+                     hires_upscaler=args.get("hires_upscaler") or "latent-bicubic")
     grounding_extra_input = None
     if grounding_downsampler_input is not None:
         grounding_extra_input = grounding_downsampler_input.prepare(batch)
@@ -839,6 +949,8 @@ def run(meta, config, starting_noise=None, models=None):
     lanes = 2 if lanes is None else min(2, max(1, int(lanes)))      # (--lanes 0 and 1 both mean one batch at a time; one batch is split in two at most)
     if mask is not None or skw["ddim_eta"] or (hi - lo) < SPLIT_BATCH_AT:     # (eta > 0 draws its step noise from the device generator too)
         lanes = 1
+    if start:       # the encoder's posterior draw and the second pass's noise are per batch as well
+        lanes = 1
     if lanes > 1 and starting_noise is None:   # x_T as the sampler would draw it (plms.py:71), before the batch is split
         starting_noise = torch.randn((hi - lo, model.in_channels, lat_h, lat_w), device=device)
     repeat = max(1, int(args.get("repeat") or 1))
@@ -846,7 +958,7 @@ def run(meta, config, starting_noise=None, models=None):
     if repeat > 1 and mask is None and not skw["ddim_eta"] and meta.get("alpha_type") in (None, [1, 0, 0], [1.0, 0.0, 0.0]):
         # `repeat` batches of this prompt (seed, seed + 1, ...): whole batches in flight on the lanes, as bench.py runs them
         gkw = dict(steps=steps, guidance_scale=args["guidance_scale"], alpha_type=meta.get("alpha_type"), no_plms=no_plms,
-                   grounding_extra_input=grounding_extra_input, grounding_input=grounding_input, height=height, width=width, **skw)
+                   grounding_extra_input=grounding_extra_input, grounding_input=grounding_input, height=height, width=width, **skw, **start)
         shape = (hi - lo, model.in_channels, lat_h, lat_w)
         seed0 = int(args.get("seed") or 0)
         seeded = world > 1 or args.get("seed") is not None
@@ -873,10 +985,11 @@ def run(meta, config, starting_noise=None, models=None):
     else:
         torch.cuda.synchronize() if torch.cuda.is_available() else None
         t0 = time.perf_counter()
-        samples = generate_lanes(model, autoencoder, diffusion, batch, context, uc, lanes=lanes, steps=steps,
-                                 guidance_scale=args["guidance_scale"], alpha_type=meta.get("alpha_type"), starting_noise=starting_noise,
-                                 inpainting_mask=mask, z0=z0, no_plms=no_plms, grounding_extra_input=grounding_extra_input,
-                                 grounding_input=grounding_input, height=height, width=width, **skw)
+        one_batch = generate if hires is not None else partial(generate_lanes, lanes=lanes)     # (a two-pass generation is never split)
+        samples = one_batch(model, autoencoder, diffusion, batch, context, uc, steps=steps,
+                            guidance_scale=args["guidance_scale"], alpha_type=meta.get("alpha_type"), starting_noise=starting_noise,
+                            inpainting_mask=mask, z0=z0, no_plms=no_plms, grounding_extra_input=grounding_extra_input,
+                            grounding_input=grounding_input, height=height, width=width, **skw, **start)
         if torch.cuda.is_available():
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
@@ -969,6 +1082,14 @@ def main(argv=None):
     parser.add_argument("--native_inputs", action="store_true", help="prepare the conditioning inputs on the device: crop, resize and scaling of the spatial maps and of the inpainting image in HIP (the same bits as Pillow), and semantic maps as uint8 class indices in place of 152 one-hot planes; only file decoding stays on the host")
     parser.add_argument("--height", type=int, default=None, help="image height in pixels (default: the checkpoint's, 512); a multiple of 64. Above 512 x 512 the autoencoder's attention runs as a flash kernel")
     parser.add_argument("--width", type=int, default=None, help="image width in pixels (default: the checkpoint's, 512); a multiple of 64")
+    parser.add_argument("--init_image", type=str, default=None, help="image-to-image: start from this image (centre-cropped and resized to the run's size) instead of pure noise; needs --strength")
+    parser.add_argument("--strength", type=float, default=None, help="with --init_image: the fraction of the schedule that runs from the noised image, in (0, 1]; int(strength * steps) steps")
+    parser.add_argument("--hires_height", type=int, default=None, help="two-pass generation: sample at --height x --width, enlarge, and finish with a partial second sampling at this height (a multiple of 64, not below --height)")
+    parser.add_argument("--hires_width", type=int, default=None, help="the second pass's width (a multiple of 64, not below --width)")
+    parser.add_argument("--hires_strength", type=float, default=0.6, help="fraction of the second pass's schedule that runs (default 0.6)")
+    parser.add_argument("--hires_steps", type=int, default=None, help="length of the second pass's schedule (default: the first pass's step count)")
+    parser.add_argument("--hires_upscaler", type=str, default="latent-bicubic", choices=sorted(HIRES_UPSCALERS),
+                        help="how the first pass's result is enlarged: the latent (nearest / bilinear / bicubic, fused with the noising), or the decoded image (bicubic) encoded again")
     parser.add_argument("--ckpt", type=str, default=None, help="run only the meta_list entries whose checkpoint path contains this string")
     parser.add_argument("--seed", type=int, default=None, help="seed of x_T (one draw for the whole batch, sliced across ranks)")
     parser.add_argument("--lanes", type=int, default=None, help="with --repeat: whole batches in flight (default 3, the bench's schedule); without: per-GPU batches of 32 and more run as two half-batches in flight unless this is 1")

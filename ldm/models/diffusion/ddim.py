@@ -77,7 +77,7 @@ class StochasticDDIMSampler(DDIMSampler):
         img = input["x"]
         time_range = np.flip(self.ddim_timesteps)
         S = len(time_range)
-        alphas = self.alpha_generator_func(S) if self.alpha_generator_func is not None else None
+        alphas = self._gate_schedule(S) if self.alpha_generator_func is not None else None
         for i, step in enumerate(time_range):
             if alphas is not None:
                 self.set_alpha_scale(self.model, alphas[i])

@@ -101,14 +101,25 @@ class DPMSolverSampler(PLMSSampler):
         else:
             super().make_schedule(ddim_num_steps, ddim_discretize=ddim_discretize, ddim_eta=0.0, verbose=verbose)
         self.solver_order, self.lower_order_final = order, lower_order_final
+        self._solver_arrays()
+
+    def _solver_arrays(self):
         # sampling order (time descending)
         self.solver_a_t = _np(self.ddim_alphas).astype(np.float64)[::-1].copy()
         self.solver_a_prev = _np(self.ddim_alphas_prev).astype(np.float64)[::-1].copy()
-        self.solver_coefs = dpm_solver_coefficients(self.solver_a_t, self.solver_a_prev, order=order, lower_order_final=lower_order_final)
+        self.solver_coefs = dpm_solver_coefficients(self.solver_a_t, self.solver_a_prev, order=self.solver_order, lower_order_final=self.lower_order_final)
+
+    def _cut_schedule(self, k):
+        # the coefficients of the k steps that run, recomputed on them: the tail's first step has no previous data prediction and is
+        # order 1, and lower_order_final is judged on k
+        super()._cut_schedule(k)
+        self._solver_arrays()
 
     @torch.no_grad()
-    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, **schedule_kwargs):
+    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, *, x_init=None, strength=None, resize_mode="bicubic",
+               **schedule_kwargs):
         self.make_schedule(ddim_num_steps=S, **schedule_kwargs)
+        self._start_tail(shape, input, x_init, strength, resize_mode)
         return self.plms_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
 
     # ---- device loop ---------------------------------------------------------------------
@@ -124,7 +135,7 @@ class DPMSolverSampler(PLMSSampler):
         img = input["x"]
         time_range = np.flip(self.ddim_timesteps)
         S = len(time_range)
-        alphas = self.alpha_generator_func(S) if self.alpha_generator_func is not None else None
+        alphas = self._gate_schedule(S) if self.alpha_generator_func is not None else None
         d_prev = None
         for i, step in enumerate(time_range):
             if alphas is not None:

@@ -40,6 +40,7 @@ class PLMSSampler(object):
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0.0, verbose=False):
         if ddim_eta != 0:
             raise ValueError("ddim_eta must be 0 for PLMS")
+        self._tail = None   # a fresh schedule runs whole; sample(strength=...) cuts it (_cut_schedule)
         self.ddim_timesteps = make_ddim_timesteps(ddim_discr_method=ddim_discretize, num_ddim_timesteps=ddim_num_steps,
                                                   num_ddpm_timesteps=self.ddpm_num_timesteps, verbose=verbose)
         ac = self.diffusion.alphas_cumprod
@@ -58,9 +59,77 @@ class PLMSSampler(object):
         self.register_buffer("ddim_sqrt_one_minus_alphas", np.sqrt(1.0 - alphas))
 
     @torch.no_grad()
-    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
+    def sample(self, S, shape, input, uc=None, guidance_scale=1, mask=None, x0=None, *, x_init=None, strength=None, resize_mode="bicubic"):
+        """x_init, strength: start from a given latent instead of pure noise (image-to-image, the second pass of a two-pass
+        generation): the schedule is built as always, the last int(strength * n) of its n steps run (n = len(ddim_timesteps): the uniform
+        grid of S = 6 has 7), from x_init resized to `shape` (resize_mode: nearest-exact, bilinear or bicubic) and noised to the first of
+        them. strength=None: nothing changes."""
         self.make_schedule(ddim_num_steps=S)
+        self._start_tail(shape, input, x_init, strength, resize_mode)
         return self.plms_sampling(shape, input, uc, guidance_scale, mask=mask, x0=x0)
+
+    # ---- partial sampling: the tail of the schedule from a given latent ---------------------------
+    def _cut_schedule(self, k):
+        """Keep the last k sampling steps of the schedule make_schedule built. Every per-step array is in ascending-timestep order
+        (index = S - i - 1 for sampling step i), so the tail is its first k entries; what the loops derive from them (time_range, a_t,
+        a_prev, sigmas, the inpainting sqrt tables, solver coefficients) follows. The gate schedule is cut from the full-length one
+        (_gate_schedule), so gating follows the noise level, not the position in the shorter run."""
+        S = len(self.ddim_timesteps)
+        self._tail = (S, k)
+        self.ddim_timesteps = self.ddim_timesteps[:k]
+        for name in ("ddim_sigmas", "ddim_alphas", "ddim_alphas_prev", "ddim_sqrt_one_minus_alphas"):
+            setattr(self, name, getattr(self, name)[:k])
+
+    def _gate_schedule(self, S):
+        """alpha_generator_func over the S steps about to run: of a tail, the last S values of the full schedule's."""
+        tail = self.__dict__.get("_tail")
+        if tail is None:
+            return self.alpha_generator_func(S)
+        full, k = tail
+        assert k == S, "the schedule was cut to another length than the loop runs"
+        return list(self.alpha_generator_func(full))[full - k:]
+
+    def _start_tail(self, shape, input, x_init, strength, resize_mode):
+        if x_init is None and strength is None:
+            return
+        who = type(self).__name__
+        if strength is None:
+            raise ValueError(f"{who}: x_init needs strength (the fraction of the schedule that runs from it, in (0, 1])")
+        if x_init is None:
+            raise ValueError(f"{who}: strength = {strength} needs x_init (the latent the tail of the schedule starts from)")
+        strength = float(strength)
+        if not 0.0 < strength <= 1.0:
+            raise ValueError(f"{who}: strength = {strength} is not in (0, 1]")
+        S = len(self.ddim_timesteps)
+        k = int(strength * S)
+        if k == 0:
+            raise ValueError(f"{who}: strength = {strength} of {S} steps leaves no step to run (int(strength * S) = 0)")
+        if resize_mode not in ("nearest-exact", "bilinear", "bicubic"):
+            raise ValueError(f"{who}: resize_mode {resize_mode!r}: nearest-exact, bilinear or bicubic")
+        shape = tuple(int(v) for v in shape)
+        if x_init.dim() != 4 or int(x_init.shape[1]) != shape[1] or int(x_init.shape[0]) not in (1, shape[0]):
+            raise ValueError(f"{who}: x_init {tuple(x_init.shape)} is not [{shape[0]} or 1, {shape[1]}, h, w]")
+        self._cut_schedule(k)
+        t0 = int(self.ddim_timesteps[-1])          # the tail's first (largest) timestep
+        # the noise: input["x"] when given (the role starting_noise has in a whole run), else one draw, before every other of the run
+        noise = input["x"] if input["x"] is not None else torch.randn(shape, device=self.device)
+        if tuple(noise.shape[1:]) != shape[1:] or int(noise.shape[0]) not in (1, shape[0]):
+            raise ValueError(f"{who}: the starting noise {tuple(noise.shape)} does not fit a latent of {shape}")
+        if int(x_init.shape[0]) != shape[0]:
+            x_init = x_init.expand(shape[0], *x_init.shape[1:])
+        if hasattr(self.model, "engine") and hasattr(self.model, "set_conditioning"):
+            sa = float(self.diffusion.sqrt_alphas_cumprod[t0])
+            s1 = float(self.diffusion.sqrt_one_minus_alphas_cumprod[t0])
+            input["x"] = self.model.engine.latent_renoise(x_init, shape[2:], resize_mode, sa, s1, noise)
+        else:
+            # the same on the host, for arbitrary model callables: F.interpolate + q_sample, in the wider of the two dtypes
+            import torch.nn.functional as F
+            dtype = torch.promote_types(x_init.dtype, noise.dtype)
+            x, noise = x_init.to(device=noise.device, dtype=dtype), noise.to(dtype)
+            if tuple(x.shape[2:]) != shape[2:]:
+                x = F.interpolate(x, size=shape[2:], mode=resize_mode, **({} if resize_mode == "nearest-exact" else dict(align_corners=False)))
+            ts = torch.full((shape[0],), t0, device=noise.device, dtype=torch.long)
+            input["x"] = self.diffusion.q_sample(x, ts, noise.expand(shape) if int(noise.shape[0]) != shape[0] else noise)
 
     @torch.no_grad()
     def plms_sampling(self, shape, input, uc=None, guidance_scale=1, mask=None, x0=None):
@@ -81,7 +150,7 @@ class PLMSSampler(object):
         S = len(time_range)
         alphas = None
         if self.alpha_generator_func is not None:
-            alphas = np.asarray(self.alpha_generator_func(S), dtype=np.float32)
+            alphas = np.asarray(self._gate_schedule(S), dtype=np.float32)
         cfg = uc is not None and guidance_scale != 1
         context = input["context"]
         g = input.get("grounding_input")
@@ -172,7 +241,7 @@ class PLMSSampler(object):
         img = input["x"]
         time_range = np.flip(self.ddim_timesteps)
         S = len(time_range)
-        alphas = self.alpha_generator_func(S) if self.alpha_generator_func is not None else None
+        alphas = self._gate_schedule(S) if self.alpha_generator_func is not None else None
         history = []
 
         def denoiser(inp):

@@ -156,6 +156,11 @@ class UNetModel(nn.Module):
                 if m.__dict__.get("_engine") is not None:
                     m.__dict__["_engine"].close()
                     m.__dict__["_engine"] = None
+        # and the second-pass contexts of two-pass generation (gligen_inference._hires_context)
+        for m, _ in (self.__dict__.pop("_hires", None) or {}).values():
+            if m.__dict__.get("_engine") is not None:
+                m.__dict__["_engine"].close()
+                m.__dict__["_engine"] = None
         eng = self.__dict__.get("_engine")
         if eng is not None:
             eng.close()
