@@ -3,6 +3,7 @@
 #include "engine_impl.h"
 #include "image.h"
 #include "latent.h"
+#include "lora.h"
 #include "train.h"
 #include "train_fusers.h"
 #include "../../include/gligen_amd_train_maps.h"
@@ -15,6 +16,7 @@
 #include "../../include/gligen_amd_attention_core.h"
 #include "../../include/gligen_amd_vae.h"
 #include "../../include/gligen_amd_latent.h"
+#include "../../include/gligen_amd_lora.h"
 #include "gemm_plan.h"
 
 #include <cstdlib>
@@ -883,6 +885,16 @@ int gl_latent_resize_taps(int in_size, int out_size, int mode, int* first_index,
     int n_taps = 0;
     if (gl::latent_resize_taps(in_size, out_size, mode, first_index, weights, &n_taps) != GL_OK) return -1;
     return n_taps;
+}
+
+// ---- include/gligen_amd_lora.h: a LoRA adapter merged into fp32 parameters in place
+int gl_op_lora_merge(gl_ctx* ctx, float* W, const float* up, const float* down, int N, int K, int r, float scale, gl_stream s) {
+    NEED(ctx);
+    GL_API_BEGIN
+    int launched = 0;
+    GL_TRY(gl::lora_merge_launch(W, up, down, N, K, r, scale, S(s), &launched));
+    ctx->eng->n_launches += launched;
+    GL_API_END
 }
 
 // ---- include/gligen_amd_train_prims.h: the training path's primitives one by one, over the arena and workspace the slices above use

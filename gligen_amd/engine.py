@@ -675,6 +675,24 @@ class Engine:
                                             _ptr(noise), 0 if noise is None else int(noise.shape[0]), _stream(dev)))
         return out
 
+    def op_lora_merge(self, W: torch.Tensor, up: torch.Tensor, down: torch.Tensor, scale: float) -> torch.Tensor:
+        """gl_op_lora_merge: W [N, K...] += scale * up [N, r...] @ down [r, K...] in place, on the current stream. W, up and down are
+        contiguous fp32 tensors on this engine's device (anything else raises: the update is in place, so nothing is converted or
+        copied); the dimensions behind the first are flattened, which makes a conv pair (down [r, Cin, kh, kw], up [Cout, r, 1, 1])
+        the same call. Returns W."""
+        for name, t in (("W", W), ("up", up), ("down", down)):
+            if not torch.is_tensor(t) or t.dtype != torch.float32 or not t.is_contiguous() or not t.is_cuda or t.device != self.device:
+                what = f"{t.dtype}, {'contiguous' if t.is_contiguous() else 'not contiguous'}, on {t.device}" if torch.is_tensor(t) else type(t).__name__
+                raise ValueError(f"op_lora_merge: {name} must be a contiguous fp32 tensor on {self.device} (it is {what})")
+            if t.dim() < 2:
+                raise ValueError(f"op_lora_merge: {name} has shape {tuple(t.shape)}, need at least two dimensions")
+        N, r = int(W.shape[0]), int(down.shape[0])
+        K = int(np.prod(W.shape[1:]))
+        if int(up.shape[0]) != N or up.numel() != N * r or down.numel() != r * K:
+            raise ValueError(f"op_lora_merge: up {tuple(up.shape)} @ down {tuple(down.shape)} does not give W {tuple(W.shape)}")
+        check(self.lib.gl_op_lora_merge(self._ctx, _ptr(W), _ptr(up), _ptr(down), N, K, r, float(scale), _stream(self.device)))
+        return W
+
     def sampler_timing(self):
         """(mean UNet-evaluation ms over graph replays, first eager evaluation ms, number of evaluations)."""
         a, f, n = C.c_float(), C.c_float(), C.c_int()

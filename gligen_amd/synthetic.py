@@ -92,6 +92,61 @@ def fill_module_(module: torch.nn.Module, seed: int = 1234) -> torch.nn.Module:
     return module
 
 
+# ---- a synthetic LoRA adapter (no real adapter exists offline) ------------------------------------------------------
+# module families of an adapter: which paths of the UNet (or of the text tower, "te") each one covers
+LORA_FAMILIES = {
+    "attn": lambda p: ".transformer_blocks." in p and ".fuser." not in p and p.endswith((".to_q", ".to_k", ".to_v", ".to_out.0")),
+    "ff": lambda p: ".transformer_blocks." in p and ".fuser." not in p and p.endswith((".ff.net.0.proj", ".ff.net.2")),
+    "proj": lambda p: p.endswith(".proj_in") or p.endswith(".proj_out"),
+    "conv": lambda p: p.endswith(".in_layers.2") or p.endswith(".out_layers.3") or p.endswith(".skip_connection"),
+    "emb": lambda p: p.endswith(".emb_layers.1"),
+    "sample": lambda p: p.endswith(".op") or p.endswith(".conv"),
+    "time": lambda p: p.startswith("time_embed."),
+    "fuser": lambda p: ".fuser." in p,
+    "first_conv": lambda p: p == "input_blocks.0.0",
+}
+
+
+def synthetic_lora(model, text_encoder=None, rank: int = 4, families=("attn", "ff"), dtype=torch.float32, seed: int = 7,
+                   alpha=None, limit=None) -> Dict[str, torch.Tensor]:
+    """A seeded adapter in kohya's format for `model` (a UNetModel) and, with the family "te", for `text_encoder`: one
+    lora_down / lora_up / alpha group per nn.Linear / nn.Conv2d of the chosen families, under the diffusers-style name where kohya
+    writes one and the module-path name elsewhere (fusers). up @ down has about 0.3 of the standard deviation of a seeded weight;
+    alpha defaults to rank / 2. limit: at most this many modules per family (the first ones in module order)."""
+    from . import lora
+    names: Dict[str, str] = {}
+    for name, path in lora.unet_name_table(model).items():
+        plain = lora.UNET_PREFIX + path.replace(".", "_")
+        if path not in names or (names[path] == plain and ".fuser." not in path):      # the diffusers alias wins, but GLIGEN's fusers have no diffusers name
+            names[path] = name
+    params = dict(model.named_parameters())
+    chosen = []
+    for fam in families:
+        if fam == "te":
+            if text_encoder is None:
+                raise ValueError("family 'te' needs the text encoder")
+            te_params = dict(text_encoder.named_parameters())
+            picks = [(n, te_params[p + ".weight"]) for n, p in lora.te_name_table(text_encoder).items()]
+        elif fam in LORA_FAMILIES:
+            picks = [(names[p], params[p + ".weight"]) for p in names if LORA_FAMILIES[fam](p)]      # (module order)
+        else:
+            raise ValueError(f"family {fam!r}: one of {sorted(LORA_FAMILIES) + ['te']}")
+        chosen += picks[:limit] if limit else picks
+    alpha = rank / 2 if alpha is None else alpha
+    out = {}
+    for name, w in chosen:
+        N, tail = int(w.shape[0]), tuple(int(s) for s in w.shape[1:])
+        K = 1
+        for s in tail:
+            K *= s
+        down = torch.randn((rank,) + tail, generator=_gen(name + ".down", seed)) * K ** -0.5
+        up = torch.randn((N, rank) + (1,) * (len(tail) - 1), generator=_gen(name + ".up", seed)) * (0.3 * rank ** -0.5 * (rank / alpha if alpha else 1.0))
+        out[name + ".lora_down.weight"] = down.to(dtype)
+        out[name + ".lora_up.weight"] = up.to(dtype)
+        out[name + ".alpha"] = torch.tensor(float(alpha), dtype=dtype)
+    return out
+
+
 # ---- synthetic inputs (SURVEY.md §8d) ------------------------------------------------------
 def make_boxes(B: int, n_valid: int, max_objs: int = 30, seed: int = 0):
     g = torch.Generator().manual_seed(1000 + seed)

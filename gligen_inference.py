@@ -104,7 +104,9 @@ def read_ckpt(ckpt_path):
         return torch.load(ckpt_path, map_location="cpu", weights_only=False, pickle_module=_ShimPickle)
 
 
-def load_ckpt(ckpt_path):
+def load_ckpt(ckpt_path, loras=None):
+    """loras: LoRA adapters merged into the UNet and the text tower once the checkpoint is in place -- a list of
+    (source, scale) / (source, unet_scale, te_scale) or `PATH[:SCALE[:TE_SCALE]]` strings (gligen_amd.lora.apply_loras)."""
     saved_ckpt = read_ckpt(ckpt_path)
     config = _plain(saved_ckpt["config_dict"]["_content"])
     model = instantiate_from_config(config["model"]).to(device).eval()
@@ -115,7 +117,20 @@ def load_ckpt(ckpt_path):
     autoencoder.load_state_dict(saved_ckpt["autoencoder"])
     text_encoder.load_state_dict(saved_ckpt["text_encoder"])
     diffusion.load_state_dict(saved_ckpt["diffusion"])
+    use_loras(model, text_encoder, loras)
     return model, autoencoder, text_encoder, diffusion, config
+
+
+def use_loras(model, text_encoder, loras):
+    """Merge `loras` (see load_ckpt) unless the model carries exactly this list already; None or an empty list leaves the model as it
+    is. The packed engines are rebuilt from the merged parameters on the next call."""
+    if not loras:
+        return None
+    from gligen_amd import lora
+    report = lora.ensure_loras(model, text_encoder, [lora.parse_lora_spec(s) for s in loras])
+    if report is not None:
+        print(lora.describe(report), flush=True)
+    return report
 
 
 # ---- batch preparation ---------------------------------------------------------------------------
@@ -835,10 +850,12 @@ def run(meta, config, starting_noise=None, models=None):
     contiguous slice (gligen_amd.dist.shard_range) with replicated weights and writes its own images."""
     from gligen_amd import dist as gdist
     args = dict(config) if isinstance(config, dict) else vars(config)
+    # optional key loras: LoRA adapters (load_ckpt), merged once per model load -- a model handed in that carries them already is left alone
     if models is None:
-        model, autoencoder, text_encoder, diffusion, ckpt_config = load_ckpt(meta["ckpt"])
+        model, autoencoder, text_encoder, diffusion, ckpt_config = load_ckpt(meta["ckpt"], loras=args.get("loras"))
     else:
         model, autoencoder, text_encoder, diffusion, ckpt_config = models
+        use_loras(model, text_encoder, args.get("loras"))
     model.grounding_tokenizer_input = instantiate_from_config(ckpt_config["grounding_tokenizer_input"])
     grounding_downsampler_input = None
     if "grounding_downsampler_input" in ckpt_config:
@@ -1090,6 +1107,8 @@ def main(argv=None):
     parser.add_argument("--hires_steps", type=int, default=None, help="length of the second pass's schedule (default: the first pass's step count)")
     parser.add_argument("--hires_upscaler", type=str, default="latent-bicubic", choices=sorted(HIRES_UPSCALERS),
                         help="how the first pass's result is enlarged: the latent (nearest / bilinear / bicubic, fused with the noising), or the decoded image (bicubic) encoded again")
+    parser.add_argument("--lora", dest="loras", action="append", default=None, metavar="PATH[:SCALE[:TE_SCALE]]",
+                        help="merge a LoRA adapter (kohya format: safetensors or torch file) into the UNet and the text tower before sampling; repeatable, merged in the order given. SCALE multiplies alpha / rank (default 1), TE_SCALE is the text tower's (default SCALE; 0 leaves the text tower alone)")
     parser.add_argument("--ckpt", type=str, default=None, help="run only the meta_list entries whose checkpoint path contains this string")
     parser.add_argument("--seed", type=int, default=None, help="seed of x_T (one draw for the whole batch, sliced across ranks)")
     parser.add_argument("--lanes", type=int, default=None, help="with --repeat: whole batches in flight (default 3, the bench's schedule); without: per-GPU batches of 32 and more run as two half-batches in flight unless this is 1")
@@ -1113,11 +1132,18 @@ def main(argv=None):
         if args.inpaint:
             from gligen_amd import synthetic as syn
             meta.update(input_image="synthetic", z0=autoencoder.encode(torch.rand(1, 3, args.height or 512, args.width or 512, generator=torch.Generator().manual_seed(8)).to(device) * 2 - 1))
-        run(meta, args, models=(model, autoencoder, None, diffusion, cfg))
+        run_checked = partial(run, meta, args, models=(model, autoencoder, None, diffusion, cfg))
     else:
-        for meta in meta_list:   # the reference runs every entry (gligen_inference.py:640-642)
-            if args.ckpt is None or args.ckpt in meta["ckpt"]:
-                run(meta, args)
+        def run_checked():
+            for meta in meta_list:   # the reference runs every entry (gligen_inference.py:640-642)
+                if args.ckpt is None or args.ckpt in meta["ckpt"]:
+                    run(meta, args)
+    from gligen_amd.lora import LoraError
+    try:
+        run_checked()
+    except LoraError as e:       # a refused adapter: nothing was merged, nothing was sampled
+        gdist.shutdown()
+        raise SystemExit(f"gligen_inference: --lora refused: {e}") from None
     gdist.shutdown()
 
 

@@ -9,6 +9,7 @@ MI355X engine (gligen_amd/csrc/engine_unet.hip: Engine::unet_forward) — no tor
 import torch
 import torch.nn as nn
 
+from gligen_amd import lora as _lora
 from gligen_amd import runtime as _rt
 from ldm.modules.attention import SpatialTransformer, _EngineOnly, _slots, zero_module
 from ldm.modules.diffusionmodules.util import conv_nd, linear, normalization
@@ -147,6 +148,7 @@ class UNetModel(nn.Module):
 
     def load_state_dict(self, *a, **k):
         self._drop_engine()
+        _lora.forget_loras(self)  # new weights: the originals stashed under merged adapters are not this model's any more
         return super().load_state_dict(*a, **k)
 
     def _drop_engine(self):

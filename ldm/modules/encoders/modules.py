@@ -6,6 +6,7 @@ the parameters."""
 import torch
 import torch.nn as nn
 
+from gligen_amd import lora as _lora
 from gligen_amd import runtime as _rt
 
 
@@ -66,6 +67,7 @@ class FrozenCLIPEmbedder(AbstractEncoder):
         (keys `transformer.text_model.embeddings...`); transformers 5.x dropped that level (`transformer.embeddings...`). Keys are
         renamed to whatever the installed class uses, so an existing checkpoint loads unchanged under either version."""
         self._drop_engine()
+        _lora.forget_loras(self)                  # new weights: the originals stashed under merged adapters are not this tower's any more
         own = self.state_dict().keys()
         wrapped_here = any(k.startswith("transformer.text_model.") for k in own)
         out = {}
