@@ -5,7 +5,7 @@
 //   CrossAttention.forward  ldm/modules/attention.py:127-149   (attn2, 77 CLIP tokens)
 // sim = (q k^T) * d^-0.5 ; softmax over keys ; out = attn v.   No mask, no dropout.
 //
-// Layouts (written by the projection GEMM epilogues, gemm.hip EPI_QK_HEADS / EPI_VT_HEADS):
+// Layouts (written by the projection GEMM epilogues, gemm_u.hip / gemm_impl.h EPI_QK_HEADS / EPI_VT_HEADS):
 //   q  [B*H][Tq_pad][DP]   head dim zero-padded to DP (48 / 80 / 160)
 //   k  [B*H][Tk_pad/64][DP/8][64][8]   key-tile layout (gemm.h ktile_off): a 64-key tile is one contiguous block, 16-byte
 //                          chunks chunk-major; for d = 40 column 40 holds 1.0 (attn_k_init_launch), see BIAS below
@@ -321,7 +321,7 @@ __global__ void __launch_bounds__(256, DP == 48 ? 3 : 1) attn_kernel(AttnParams 
 // The rare stabiliser move (a tile's scores exceed the running one by > 2^6) sits at the end of the iteration, after PV(j-1):
 // O^T -- then consistently at the old stabiliser -- and S(j) are rescaled there.
 // Stage j of the two-slot ring holds {K(j), V^T(j-1)} and is fetched during iteration j-1. Fragment reads are inline asm (hipcc
-// would drain the DMA in front of a visible LDS load, see gemm.hip) with counted lgkmcnt waits.
+// would drain the DMA in front of a visible LDS load, see lds_rd16 in gemm_impl.h) with counted lgkmcnt waits.
 //   K tile   [DP/8 chunks][64 keys][16 B]: ds_read_b128 of chunk c for keys lrow is conflict free as it stands
 //   V^T tile [DPV rows][128 B], 16-byte chunk c of row r at slot c ^ ((r >> 1) & 7) (source-side swizzle of the DMA)
 typedef __attribute__((address_space(3))) unsigned char* lds_ptr;

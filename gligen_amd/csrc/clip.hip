@@ -1,5 +1,5 @@
 // CLIP tower kernels for gfx950 (see clip.h). Work per text call is small (S <= ~32 sequences of <= 77 tokens, 13 GFLOP each at
-// ViT-L/14 size): the aim is few, exact, spill-free launches. The projections run on the bf16 MFMA GEMM (gemm.hip).
+// ViT-L/14 size): the aim is few, exact, spill-free launches. The projections run on the bf16 MFMA GEMM (gemm.h; kernel: gemm_u.hip).
 #include "clip.h"
 
 #include <math.h>

@@ -1,7 +1,7 @@
 // Kernels of the spatial-map grounding tokenizers (reference ldm/modules/diffusionmodules/convnext.py,
 // canny/hed/depth/normal/sem_grounding_net.py): ConvNeXt-tiny over the conditioning map, once per prompt.
 // Activations are NHWC bf16 with a row stride `ld` >= C (the 96-channel stage is padded to 128 so its rows are legal GEMM K
-// operands); the pointwise / patchify convolutions run on the bf16 MFMA GEMM (gemm.hip), these are the pieces around it.
+// operands); the pointwise / patchify convolutions run on the bf16 MFMA GEMM (gemm.h; kernels: gemm_u.hip, gemm_basic.hip), these are the pieces around it.
 #pragma once
 #include "common.h"
 

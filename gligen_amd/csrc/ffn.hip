@@ -760,7 +760,7 @@ __global__ void __launch_bounds__(256, 1) ff_rows_kernel(FFRowsParams p) {
 //         row-major q layout and of the key-tile k layout (gemm.h ktile_off);
 //   v^T : the SAME fragments with the operand roles exchanged (rows in the A slot, weights in the B slot -- both layouts are
 //         lane = row / column, 8 k-slots per half), so a lane holds 16 TOKENS of one feature, contiguous under the 32-token
-//         permutation of attn3_kernel (gemm.hip perm_tok4): two 16-byte stores per feature block.
+//         permutation of attn3_kernel (gemm_impl.h perm_tok4): two 16-byte stores per feature block.
 // Weights: one stream of projection segments (5 stages x 40 blocks of 1 KiB each, k-step major), the main loop is proj_phase's
 // fixed instruction order; the epilogues between the segments are hipcc's. A segment's first stage is fetched under the last
 // stage of the segment before it and waited for BEFORE the epilogue's stores join the vmcnt counter, so the stores drain under

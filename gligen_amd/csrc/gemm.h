@@ -1,4 +1,4 @@
-// Host-visible descriptors for the bf16 MFMA GEMM / implicit-GEMM conv kernel (gemm.hip).
+// Host-visible descriptors for the bf16 MFMA GEMM / implicit-GEMM conv kernels (gemm.hip: gemm_launch; the kernels: gemm_u.hip, gemm_halo.hip, gemm_wide.hip, gemm_basic.hip).
 #pragma once
 #include "common.h"
 

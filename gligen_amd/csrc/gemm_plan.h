@@ -1,5 +1,6 @@
 // Which kernel runs a GEMM / conv, with which tile, K split, resident grid and item order: pure functions of the problem descriptor
-// (gemm_plan.hip: no kernel, no HIP call; tests/test_gemm_plan_cpu.py). gemm.hip executes a GemmPlan and times the tuner's candidates.
+// (gemm_plan.hip: no kernel, no HIP call; tests/test_gemm_plan_cpu.py). gemm.hip executes a GemmPlan (through the
+// entry function of the kernel unit that holds the plan's family, gemm_impl.h) and times the tuner's candidates.
 #pragma once
 #include <functional>
 #include <vector>
@@ -8,7 +9,8 @@
 
 namespace gl {
 
-// ---- kernel descriptors (the planner fills them, the kernels of gemm.hip read them)
+// ---- kernel descriptors (the planner fills them, the kernels read them: WorkDesc gemm_u.hip / gemm_basic.hip, HaloDesc gemm_halo.hip,
+// WideDesc gemm_wide.hip)
 struct WorkDesc {
     int tiles_n;
     int splits;

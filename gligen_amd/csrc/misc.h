@@ -60,7 +60,7 @@ int bf16_rows_to_f32_launch(const bf16* src, float* dst, int B, int rows, int sr
 // (torch bicubic align_corners=False, or legacy nearest), Conv2d(k 4, s 2, p 1) in fp32 NCHW with optional SiLU
 int resize_f32_launch(const float* img, float* out, int B, int Cimg, int n, int H, int W, int R, int nearest, hipStream_t stream);
 int conv4x4s2_f32_launch(const float* x, const float* w, const float* bias, float* y, int B, int Cin, int Cout, int Hin, int Win, int silu, hipStream_t stream);
-// GEGLU projection [8C][K] fp32 (+bias [8C]) -> row-interleaved bf16 / fp32 (see gemm.hip epi_geglu4)
+// GEGLU projection [8C][K] fp32 (+bias [8C]) -> row-interleaved bf16 / fp32 (see gemm_impl.h epi_geglu4)
 // layout: gemm_geglu_layout() of the GEMM variant that will consume the packed rows
 int pack_geglu_launch(const float* w, const float* b, bf16* wp, float* bp, int C4, int K, int layout, hipStream_t stream);
 

@@ -271,9 +271,9 @@ __global__ void pack_geglu_kernel(const float* __restrict__ w, const float* __re
         const int p = (int)(idx / K);
         const int tile = p >> 5, i = p & 31;
         int orig;
-        if (layout == 1) {  // 16 value rows then the 16 matching gate rows (gemm.hip epi_geglu4_t16)
+        if (layout == 1) {  // 16 value rows then the 16 matching gate rows (gemm_impl.h epi_geglu4_t16)
             orig = (i >> 4) * C4 + tile * 16 + (i & 15);
-        } else {            // 32x32-tile interleave (gemm.hip epi_geglu4)
+        } else {            // 32x32-tile interleave (gemm_impl.h epi_geglu4)
             const int q = i >> 3, g = (i >> 2) & 1, e = i & 3;
             const int j = tile * 16 + e + 4 * g + 8 * (q >> 1);
             orig = (q & 1) * C4 + j;

@@ -229,7 +229,7 @@ __global__ void __launch_bounds__(NT) gn_small_kernel(GNParams P, int cpg) {
 }
 
 // ---- GroupNorm as the consumer's prologue (round 6): the statistics pass stays, the apply pass does not. The conv that follows
-// (conv_halo_kernel, gemm.hip) normalises + SiLUs its input tile while staging it, from per-(sample, channel) coefficients
+// (conv_halo_kernel, gemm_halo.hip) normalises + SiLUs its input tile while staging it, from per-(sample, channel) coefficients
 //     y = silu(x * a + c),  a = rstd * gamma,  c = beta - mean * a          (reference openaimodel.py:212-232: GroupNorm32 -> SiLU -> conv)
 // written here as coef[b][C / 8][16]: a of 8 consecutive channels, then their c -- 64 bytes per 16-byte activation chunk, so a
 // 64-channel chunk of the conv's K loop is one contiguous 512-byte block that the conv fetches by LDS-DMA beside its halo.

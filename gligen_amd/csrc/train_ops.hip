@@ -527,7 +527,7 @@ void Ctx::lin_wgrad(const float* dy, const float* x, int M, int N, int K, float*
 }
 
 float* Ctx::conv_dgrad_weight(const float* w_oihw, int O, int I) const { return ew_new(conv_dgrad_weight_kernel, (size_t)I * O * 9, (size_t)I * O * 9, w_oihw, O, I); }
-// The activations are cast to bf16 for the implicit-GEMM kernel of gemm.hip. One launch over 3 Ci input channels where the loader's
+// The activations are cast to bf16 for the implicit-GEMM kernel of gemm_u.hip. One launch over 3 Ci input channels where the loader's
 // 64-channel step allows it -- activations (hi | lo | hi) as a two-source concat of the (hi | lo) buffer with its own first half,
 // weights (hi | hi | lo) along I (cached for frozen convs: flip / transpose for dgrad, split, pack -- once) --, else three launches
 float* Ctx::conv3(const float* a, int B, int H, int W, const float* w_oihw, const float* bias, int Cin, int Cout, bool dgrad, int stride, int ups) const {

@@ -469,7 +469,7 @@ def test_lib_load_imports_torch_first():
 
 
 def _halo_geometry_ok(H, W, B):
-    """Python restatement of conv_halo_kernel's index math (gligen_amd/csrc/gemm.hip): the DMA side maps halo row h of a 256-pixel tile
+    """Python restatement of conv_halo_kernel's index math (gligen_amd/csrc/gemm_halo.hip): the DMA side maps halo row h of a 256-pixel tile
     to a source pixel or to zero padding; the fragment side reads, for output pixel p and tap (ky, kx), halo row hr. Every such read
     must find pixel (y + ky - 1, x + kx - 1) of p's own image, or padding outside it."""
     lgW, lgH = W.bit_length() - 1, H.bit_length() - 1
@@ -607,7 +607,7 @@ def _fragment_read_conflicts(swizzle, first_row, kstep):
 
 
 def test_lds_swizzles_are_conflict_free_where_they_are_used():
-    """gemm.hip stages 128-byte rows with the 16-byte chunk index XOR-swizzled by the row. The aligned tiles (every fragment starts
+    """The GEMM kernels (gemm_u.hip, gemm_halo.hip, ...) stage 128-byte rows with the 16-byte chunk index XOR-swizzled by the row. The aligned tiles (every fragment starts
     at a multiple of 16 rows) use (row >> 1) & 7; conv_halo_kernel reads its halo buffer at nine row shifts and uses row & 6, which
     stays conflict free under ANY shift (the (row >> 1) & 7 form does not: PMC counted 23 % of the halo kernel's LDS cycles as
     bank conflicts before the change, 0 after; profiles/r3/halo_swizzle_lds_counters.txt)."""
@@ -619,7 +619,7 @@ def test_lds_swizzles_are_conflict_free_where_they_are_used():
         for first in range(64):
             assert _fragment_read_conflicts(shifted, first, k) == 0
         assert _fragment_read_conflicts(aligned, 1, k) > 0 and _fragment_read_conflicts(aligned, 2, k) > 0   # why the halo buffer needed its own
-    src = open(os.path.join(str(ROOT), "gligen_amd", "csrc", "gemm.hip")).read()
+    src = open(os.path.join(str(ROOT), "gligen_amd", "csrc", "gemm_halo.hip")).read()
     assert "(((unsigned)q ^ (hr & 6u)) << 4)" in src and "((t & 7) ^ (r0 & 6)) * 16" in src   # read side and DMA side agree
 
 
@@ -729,7 +729,7 @@ def test_train_step_bookkeeping_on_flat_buckets():
 def test_attn3_operand_handover_model():
     """The index arithmetic of attn3_kernel (attention.hip, round 5), modelled lane by lane: 32x32x16 S^T accumulators -> packed exps ->
     v_permlane16_swap (odd 16-lane rows of the first operand <-> even rows of the second) -> B operands of two 16-query halves of
-    v_mfma_f32_16x16x32; V^T stored by the projection epilogue with tokens permuted in groups of 32 (gemm.hip perm_tok4, p32), copied to
+    v_mfma_f32_16x16x32; V^T stored by the projection epilogue with tokens permuted in groups of 32 (gemm_impl.h perm_tok4, p32), copied to
     LDS by the source-swizzled DMA, read back as A fragments (row 16 i + (lane & 15), chunk 4 u + (lane >> 4)): the product must be
     V^T P^T, and every 16-lane group of a ds_read_b128 must touch 16 distinct 16-byte slots (no bank conflict)."""
     import numpy as np

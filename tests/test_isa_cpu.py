@@ -3,8 +3,9 @@
 The v5 GEMM prefetches K tiles by LDS-DMA and relies on NOTHING draining that DMA between its issue and the MFMAs
 of the tile being multiplied. hipcc re-inserts `s_waitcnt vmcnt(0)` there at the slightest provocation (a
 compiler-visible LDS load, an inline asm with a "memory" clobber, a conditional drain at the loop top), which is
-invisible to every numerical test and costs 10-25 % of GEMM throughput. This test compiles gemm.hip to gfx950
-assembly and asserts, for every gemm_u_kernel instantiation, that between the main loop's s_barrier and its last
+invisible to every numerical test and costs 10-25 % of GEMM throughput. This test compiles the GEMM's units
+(gemm_u.hip, gemm_halo.hip, gemm_wide.hip, gemm_basic.hip, gemm.hip) to gfx950 assembly and asserts, for every
+gemm_u_kernel instantiation, that between the main loop's s_barrier and its last
 MFMA the only vmcnt wait is the intended one directly in front of the barrier, that the DMA is not wrapped in
 waterfall loops, and that nothing spills."""
 import re
@@ -20,13 +21,22 @@ ROOT = Path(__file__).resolve().parent.parent
 
 @pytest.fixture(scope="module")
 def gemm_asm(tmp_path_factory):
+    """The assembly of the GEMM's translation units (gemm_impl.h: one per kernel family + the host unit with the split-K reduce),
+    compiled side by side and concatenated: a kernel is defined in exactly one of them."""
+    from gligen_amd.build import GEMM_UNITS
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
-    out = tmp_path_factory.mktemp("isa") / "gemm.s"
-    cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", str(ROOT / "include"), "--offload-device-only", "-S",
-           str(ROOT / "gligen_amd" / "csrc" / "gemm.hip"), "-o", str(out)]
-    r = subprocess.run(cmd, capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr[-3000:]
-    return out.read_text()
+    tmp = tmp_path_factory.mktemp("isa")
+
+    def listing(unit):
+        out = tmp / (unit + ".s")
+        cmd = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", str(ROOT / "include"), "--offload-device-only", "-S",
+               str(ROOT / "gligen_amd" / "csrc" / unit), "-o", str(out)]
+        r = subprocess.run(cmd, capture_output=True, text=True)
+        assert r.returncode == 0, r.stderr[-3000:]
+        return out.read_text()
+
+    with ThreadPoolExecutor(max_workers=min(len(GEMM_UNITS), 8)) as ex:
+        return "\n".join(ex.map(listing, GEMM_UNITS))
 
 
 def _kernels(asm):
@@ -65,7 +75,7 @@ def test_gemm_main_loop_has_no_dma_drain(gemm_asm):
 
 
 def test_gemm_kernels_do_not_spill(gemm_asm):
-    """No kernel of gemm.hip spills -- with one bounded exception: conv_halo_kernel<5, 8, GN = true> (256 registers, the GroupNorm
+    """No kernel of the GEMM's units spills -- with one bounded exception: conv_halo_kernel<5, 8, GN = true> (256 registers, the GroupNorm
     prologue's operands on top of 80 accumulators + 72 fragment registers) parks a handful of lane constants (<= 6 dwords) of its EPILOGUE in
     scratch, once per work item; test_halo_kernel_gn_prologue_rides_under_the_deferred_mfmas pins that its tap loop has none."""
     meta = gemm_asm[gemm_asm.index("amdhsa.kernels:"):]

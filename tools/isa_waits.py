@@ -6,7 +6,7 @@
     block (the remedy is an unconditional load from a clamped address and a select on the unpacked value);
   * a `vmcnt(0)` wait behind a global store with no load in between ("wait after store"): vmcnt counts stores, so the wave
     waits for the store's acknowledgement before it may issue the next one -- typically a coefficient load between stores or a
-    wait hipcc re-inserts in every guarded block (the remedy is to issue all loads first and force ONE wait, epi_ready in gemm.hip).
+    wait hipcc re-inserts in every guarded block (the remedy is to issue all loads first and force ONE wait, epi_ready in gemm_impl.h).
 
 usage: isa_waits.py FILE.s [substring-of-kernel-name ...]     (FILE.s from `hipcc --offload-device-only -S`)
 The scan is linear over the listing (it does not follow branches): counts are upper bounds per kernel, good for before / after."""
