@@ -1,6 +1,6 @@
 """ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
 include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h, include/gligen_amd_train_fusers.h, include/gligen_amd_train_prims.h,
-include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h and include/gligen_amd_lora.h).
+include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h, include/gligen_amd_lora.h and include/gligen_amd_tiling.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -294,6 +294,21 @@ LORA_SYMBOLS = {
     "gl_op_lora_merge": (_I, [_P, _P, _P, _P, _I, _I, _I, _F, _P]),
 }
 
+
+
+class TilePlan(C.Structure):   # = gl_tile_plan
+    _fields_ = [("struct_size", C.c_uint)] + [(n, C.c_int) for n in ("ny", "nx", "th_in", "tw_in", "th_out", "tw_out")] + \
+               [(n, C.c_void_p) for n in ("windows", "oy", "ox", "wy", "wx")]
+
+
+# every symbol include/gligen_amd_tiling.h declares (the autoencoder over overlapping tiles; the gather and the blend by themselves)
+TILING_SYMBOLS = {
+    "gl_vae_decode_tiled": (_I, [_P, _I, _I, _I, _P, _P, C.POINTER(TilePlan), _I, _P]),
+    "gl_vae_encode_tiled": (_I, [_P, _I, _I, _I, _P, _P, _P, _P, C.POINTER(TilePlan), _I, _P]),
+    "gl_op_tile_gather": (_I, [_P, _P, _I, _I, _I, _I, _P, _I, _P, _I, _I, _P]),
+    "gl_op_tile_blend": (_I, [_P, _P, _I, _I, C.POINTER(TilePlan), _P, _I, _I, _I, _I, _P]),
+}
+
 # gl_unet_config.fuser_kind / the fuser_kind of gl_op_block_train_fuser, by the reference's fuser_type
 FUSER_KINDS = {"gatedSA": 0, "gatedSA2": 1, "gatedCA": 2}
 
@@ -324,7 +339,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS, **TRAIN_PRIM_SYMBOLS,
-                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS}.items():
+                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS, **TILING_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

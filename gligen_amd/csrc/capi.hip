@@ -4,6 +4,7 @@
 #include "image.h"
 #include "latent.h"
 #include "lora.h"
+#include "tile.h"
 #include "train.h"
 #include "train_fusers.h"
 #include "../../include/gligen_amd_train_maps.h"
@@ -17,6 +18,7 @@
 #include "../../include/gligen_amd_vae.h"
 #include "../../include/gligen_amd_latent.h"
 #include "../../include/gligen_amd_lora.h"
+#include "../../include/gligen_amd_tiling.h"
 #include "gemm_plan.h"
 
 #include <cstdlib>
@@ -499,6 +501,40 @@ int gl_op_vae_attention(gl_ctx* ctx, const void* q, const void* k, const void* v
         throw GlError(GL_ERR_ARG, "gl_op_vae_attention: q, k, v and out are 16-byte aligned");
     ctx->eng->op_vae_attention((const bf16*)q, (const bf16*)k, (const bf16*)v, B, T, C, mode, (bf16*)out, S(s));
     GL_API_END
+}
+
+// ---- include/gligen_amd_tiling.h
+int gl_vae_decode_tiled(gl_ctx* ctx, int B, int h, int w, const float* z, float* img, const gl_tile_plan* plan, int tiles_per_pass, gl_stream s) {
+    NEED(ctx);
+    if (!z || !img || !plan || B <= 0 || h <= 0 || w <= 0) return gl::set_error(GL_ERR_ARG, "bad vae_decode_tiled arguments");
+    GL_API_BEGIN
+    ctx->eng->vae_decode_tiled(B, h, w, z, img, *plan, tiles_per_pass, S(s));
+    GL_API_END
+}
+
+int gl_vae_encode_tiled(gl_ctx* ctx, int B, int H, int W, const float* img, const float* noise, float* z, float* moments_out,
+                        const gl_tile_plan* plan, int tiles_per_pass, gl_stream s) {
+    NEED(ctx);
+    if (!img || !noise || !z || !plan || B <= 0 || H <= 0 || W <= 0) return gl::set_error(GL_ERR_ARG, "bad vae_encode_tiled arguments");
+    GL_API_BEGIN
+    ctx->eng->vae_encode_tiled(B, H, W, img, noise, z, moments_out, *plan, tiles_per_pass, S(s));
+    GL_API_END
+}
+
+int gl_op_tile_gather(gl_ctx* ctx, const float* src, int B, int C, int H, int W, const int* windows, int n, float* dst, int TH, int TW, gl_stream s) {
+    NEED(ctx);
+    return gl::tile_gather_launch(src, B, C, H, W, windows, n, dst, TH, TW, S(s));
+}
+
+int gl_op_tile_blend(gl_ctx* ctx, const float* tiles, int first_tile, int n, const gl_tile_plan* plan, float* out, int B, int C, int H, int W,
+                     gl_stream s) {
+    NEED(ctx);
+    if (!plan) return gl::set_error(GL_ERR_ARG, "gl_op_tile_blend: null plan");
+    if (plan->struct_size != sizeof(gl_tile_plan))
+        return gl::set_error(GL_ERR_ARG, "gl_op_tile_blend: plan->struct_size is %u, this library's gl_tile_plan has %zu bytes", plan->struct_size,
+                             sizeof(gl_tile_plan));
+    const gl::TileBlendPlan bp{plan->ny, plan->nx, plan->th_out, plan->tw_out, plan->oy, plan->ox, plan->wy, plan->wx};
+    return gl::tile_blend_launch(tiles, first_tile, n, bp, out, B, C, H, W, S(s));
 }
 
 // ---- include/gligen_amd_gemm_plans.h

@@ -25,6 +25,7 @@
 #include "vae_attention.h"
 #include "../../include/gligen_amd.h"
 #include "../../include/gligen_amd_solver.h"
+#include "../../include/gligen_amd_tiling.h"
 
 namespace gl {
 
@@ -186,6 +187,12 @@ class Engine {
                       int extraB, float* eps, hipStream_t s, const float* emb_row = nullptr);
     void vae_decode(int B, int h, int w, const float* z, float* out, hipStream_t s);
     void vae_encode(int B, int H, int W, const float* img, const float* noise, float* z, hipStream_t s);
+    // The same over the tiles of a plan (gl_vae_decode_tiled / gl_vae_encode_tiled): per pass up to tiles_per_pass tiles are gathered
+    // (tile_gather_kernel), run through the pass above as one batch and blended into the result (tile_blend_kernel). One tile per axis
+    // is the untiled call itself. moments_out (may be null): the blended raw moments [B][2 zc][H/f][W/f]
+    void vae_decode_tiled(int B, int h, int w, const float* z, float* out, const gl_tile_plan& plan, int tiles_per_pass, hipStream_t s);
+    void vae_encode_tiled(int B, int H, int W, const float* img, const float* noise, float* z, float* moments_out, const gl_tile_plan& plan,
+                          int tiles_per_pass, hipStream_t s);
     bool has_vae_encoder() const { return vae_.enc.present; }
     // The form of the VAE's AttnBlock (gl_vae_set_attention): 0 = auto (the score-matrix form up to 4096 tokens, above that -- and
     // wherever the score matrices do not fit what is left of the arena -- vae_attn_flash_kernel), 1 = score matrices, 2 = flash
@@ -447,6 +454,13 @@ class Engine {
     void build_vae();
     void build_vae_encoder();
     void build_vae_mid(VaeHalf& h, const std::string& prefix, int C);
+    // one pass of either half on what the arena holds (no reset): the bodies of vae_decode / vae_encode and of every tiled pass.
+    // moments null: allocated from the arena where vae_encode always did; returns where they are
+    void vae_decode_pass(int B, int h, int w, const float* z, float* out, hipStream_t s);
+    float* vae_encode_pass(int B, int H, int W, const float* img, float* moments, hipStream_t s);
+    void vae_posterior(const float* moments, const float* noise, float* z, int B, int HW, hipStream_t s);
+    // h_in x w_in: the input grid; f: the autoencoder's factor; decode: out = f in, else in = f out
+    void vae_tile_plan_check(const gl_tile_plan& p, int h_in, int w_in, int f, bool decode, int tiles_per_pass, const char* who) const;
     bf16* vae_attn(const VaeAttnW& a, const bf16* x, int B, int HW, hipStream_t s);
     int vae_attn_mode_ = 0;
     bool vae_attn_flash_for(int mode, int HW, int C, size_t vt_bytes) const;

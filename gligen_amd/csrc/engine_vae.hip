@@ -1,5 +1,7 @@
 // gligen_amd engine -- AutoencoderKL: decoder and encoder
 #include "engine_impl.h"
+#include "tile.h"
+#include <algorithm>
 #include <cmath>
 
 namespace gl {
@@ -171,8 +173,12 @@ void Engine::op_vae_attention(const bf16* q, const bf16* k, const bf16* v, int B
 // AutoencoderKL.decode (autoencoder.py:40-44) -> Decoder.forward (model.py:535-568)
 void Engine::vae_decode(int B, int h, int w, const float* z, float* out, hipStream_t s) {
     if (!vae_.dec.present || !finalized_) throw GlError(GL_ERR_STATE, "vae not finalized");
-    const gl_vae_config& c = vae_.cfg;
     arena_.reset();
+    vae_decode_pass(B, h, w, z, out, s);
+}
+
+void Engine::vae_decode_pass(int B, int h, int w, const float* z, float* out, hipStream_t s) {
+    const gl_vae_config& c = vae_.cfg;
     int H = h, W = w;
     int C = vae_.dec.in_small.Cout;
     Im2colParams P{};
@@ -204,6 +210,18 @@ void Engine::vae_encode(int B, int H, int W, const float* img, const float* nois
     const int total_stride = 1 << (c.n_mult - 1);
     if (H % total_stride || W % total_stride) throw GlError(GL_ERR_ARG, "vae_encode: image size must be divisible by the encoder stride");
     arena_.reset();
+    const float* moments = vae_encode_pass(B, H, W, img, nullptr, s);
+    vae_posterior(moments, noise, z, B, (H / total_stride) * (W / total_stride), s);
+}
+
+void Engine::vae_posterior(const float* moments, const float* noise, float* z, int B, int HW, hipStream_t s) {
+    const gl_vae_config& c = vae_.cfg;
+    CK(vae_posterior_launch(moments, vae_.enc.quant_w, vae_.enc.quant_b, noise, z, B, c.z_channels, HW, c.scale_factor, s));
+    ++n_launches;
+}
+
+float* Engine::vae_encode_pass(int B, int H, int W, const float* img, float* moments, hipStream_t s) {
+    const gl_vae_config& c = vae_.cfg;
     int C = vae_.enc.in_small.Cout;
     Im2colParams P{};
     P.x0 = img; P.C0 = vae_.enc.in_small.Cin; P.B = B; P.H = H; P.W = W;
@@ -225,11 +243,80 @@ void Engine::vae_encode(int B, int H, int W, const float* img, const float* nois
     cur = resblock(vae_.enc.mid1, TRef{cur, C, nullptr, 0}, B, H, W, nullptr, 0, eps, s);
     cur = vae_attn(vae_.enc.attn, cur, B, H * W, s);
     cur = resblock(vae_.enc.mid2, TRef{cur, C, nullptr, 0}, B, H, W, nullptr, 0, eps, s);
-    const int HW = H * W;
-    float* moments = arena_.get<float>((size_t)B * 2 * c.z_channels * HW);
+    if (!moments) moments = arena_.get<float>((size_t)B * 2 * c.z_channels * H * W);
     gn_silu_conv3x3_nchw(cur, C, B, H, W, vae_.enc.norm_out, eps, vae_.enc.conv_out, 2 * c.z_channels, moments, s);
-    CK(vae_posterior_launch(moments, vae_.enc.quant_w, vae_.enc.quant_b, noise, z, B, c.z_channels, HW, c.scale_factor, s));
-    ++n_launches;
+    return moments;
+}
+
+// ---------------------------------------------------------------- tiled passes (include/gligen_amd_tiling.h)
+void Engine::vae_tile_plan_check(const gl_tile_plan& p, int h_in, int w_in, int f, bool decode, int tiles_per_pass, const char* who) const {
+    if (p.struct_size != sizeof(gl_tile_plan))
+        throw GlError(GL_ERR_ARG, fmt("%s: plan->struct_size is %u, this library's gl_tile_plan has %zu bytes", who, p.struct_size, sizeof(gl_tile_plan)));
+    if (tiles_per_pass < 1) throw GlError(GL_ERR_ARG, fmt("%s: tiles_per_pass = %d (at least 1)", who, tiles_per_pass));
+    if (p.ny < 1 || p.nx < 1 || p.th_in < 1 || p.tw_in < 1 || p.th_in > h_in || p.tw_in > w_in)
+        throw GlError(GL_ERR_ARG, fmt("%s: %d x %d tiles of %d x %d on a %d x %d input", who, p.ny, p.nx, p.th_in, p.tw_in, h_in, w_in));
+    const bool scaled = decode ? (p.th_out == p.th_in * f && p.tw_out == p.tw_in * f) : (p.th_in == p.th_out * f && p.tw_in == p.tw_out * f);
+    if (!scaled)
+        throw GlError(GL_ERR_ARG, fmt("%s: tile %d x %d -> %d x %d does not match the autoencoder's factor %d", who, p.th_in, p.tw_in, p.th_out, p.tw_out, f));
+    if (p.ny == 1 && p.nx == 1) {
+        if (p.th_in != h_in || p.tw_in != w_in) throw GlError(GL_ERR_ARG, fmt("%s: a single tile must be the whole %d x %d input", who, h_in, w_in));
+        return;
+    }
+    const int th_lat = decode ? p.th_in : p.th_out, tw_lat = decode ? p.tw_in : p.tw_out;
+    if ((th_lat * tw_lat) % 64) throw GlError(GL_ERR_UNSUPPORTED, fmt("%s: tile of %d x %d latent pixels: VAE attention needs th * tw to be a multiple of 64", who, th_lat, tw_lat));
+    if (!p.windows || !p.oy || !p.ox || !p.wy || !p.wx) throw GlError(GL_ERR_ARG, fmt("%s: null plan table", who));
+}
+
+void Engine::vae_decode_tiled(int B, int h, int w, const float* z, float* out, const gl_tile_plan& p, int tiles_per_pass, hipStream_t s) {
+    if (!vae_.dec.present || !finalized_) throw GlError(GL_ERR_STATE, "vae not finalized");
+    const gl_vae_config& c = vae_.cfg;
+    const int f = 1 << (c.n_mult - 1);
+    vae_tile_plan_check(p, h, w, f, true, tiles_per_pass, "vae_decode_tiled");
+    if (p.ny == 1 && p.nx == 1) return vae_decode(B, h, w, z, out, s);
+    const int total = B * p.ny * p.nx;
+    const TileBlendPlan bp{p.ny, p.nx, p.th_out, p.tw_out, p.oy, p.ox, p.wy, p.wx};
+    for (int t0 = 0; t0 < total; t0 += tiles_per_pass) {
+        const int n = std::min(tiles_per_pass, total - t0);
+        arena_.reset();
+        float* zt = arena_.get<float>((size_t)n * c.z_channels * p.th_in * p.tw_in);
+        float* it = arena_.get<float>((size_t)n * c.out_ch * p.th_out * p.tw_out);
+        CK(tile_gather_launch(z, B, c.z_channels, h, w, p.windows + 3 * (size_t)t0, n, zt, p.th_in, p.tw_in, s));
+        ++n_launches;
+        vae_decode_pass(n, p.th_in, p.tw_in, zt, it, s);
+        CK(tile_blend_launch(it, t0, n, bp, out, B, c.out_ch, h * f, w * f, s));
+        ++n_launches;
+    }
+}
+
+void Engine::vae_encode_tiled(int B, int H, int W, const float* img, const float* noise, float* z, float* moments_out, const gl_tile_plan& p,
+                              int tiles_per_pass, hipStream_t s) {
+    if (!vae_.enc.present || !finalized_) throw GlError(GL_ERR_STATE, "vae encoder weights were not uploaded / not finalized");
+    const gl_vae_config& c = vae_.cfg;
+    const int f = 1 << (c.n_mult - 1);
+    if (H % f || W % f) throw GlError(GL_ERR_ARG, "vae_encode: image size must be divisible by the encoder stride");
+    vae_tile_plan_check(p, H, W, f, false, tiles_per_pass, "vae_encode_tiled");
+    const int h = H / f, w = W / f, Cin = vae_.enc.in_small.Cin, Cm = 2 * c.z_channels;
+    arena_.reset();
+    if (p.ny == 1 && p.nx == 1) {                                 // the untiled call; its moments land where the caller wants them
+        const float* m = vae_encode_pass(B, H, W, img, moments_out, s);
+        return vae_posterior(m, noise, z, B, h * w, s);
+    }
+    float* moments = moments_out ? moments_out : arena_.get<float>((size_t)B * Cm * h * w);
+    const size_t base = arena_.mark();                            // the passes' reset: everything above the blended moments
+    const int total = B * p.ny * p.nx;
+    const TileBlendPlan bp{p.ny, p.nx, p.th_out, p.tw_out, p.oy, p.ox, p.wy, p.wx};
+    for (int t0 = 0; t0 < total; t0 += tiles_per_pass) {
+        const int n = std::min(tiles_per_pass, total - t0);
+        arena_.release(base);
+        float* it = arena_.get<float>((size_t)n * Cin * p.th_in * p.tw_in);
+        float* mt = arena_.get<float>((size_t)n * Cm * p.th_out * p.tw_out);
+        CK(tile_gather_launch(img, B, Cin, H, W, p.windows + 3 * (size_t)t0, n, it, p.th_in, p.tw_in, s));
+        ++n_launches;
+        vae_encode_pass(n, p.th_in, p.tw_in, it, mt, s);
+        CK(tile_blend_launch(mt, t0, n, bp, moments, B, Cm, h, w, s));
+        ++n_launches;
+    }
+    vae_posterior(moments, noise, z, B, h * w, s);
 }
 
 }  // namespace gl

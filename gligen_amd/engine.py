@@ -11,7 +11,7 @@ from typing import Dict, Mapping, Optional, Sequence
 import numpy as np
 import torch
 
-from . import _lib
+from . import _lib, vae_tiling
 from ._lib import Grounding, PlmsArgs, SolverArgs, UNetConfig, VaeConfig, check
 
 GROUNDING_KINDS = {"text": 0, "text_image": 1, "keypoint": 2, "tokens": 3}
@@ -100,6 +100,9 @@ class Engine:
         self.clip_cfg: Optional[dict] = None
         self.clip_vision_cfg: Optional[dict] = None
         self._keep: list = []
+        self._vae_tiling = ("off", vae_tiling.DEFAULT_TILE, vae_tiling.DEFAULT_OVERLAP)
+        self._vae_tiled_shapes: set = set()
+        self._vae_plans: dict = {}
 
     def fork(self, arena_gb: Optional[float] = None) -> "Engine":
         """A second execution context on the same packed weights (gl_ctx_fork): its own arena, conditioning, gates, captured
@@ -109,6 +112,7 @@ class Engine:
         e._ctx = C.c_void_p()
         e.unet_cfg, e.vae_cfg = self.unet_cfg, self.vae_cfg
         e._keep = []
+        e._vae_tiling, e._vae_tiled_shapes, e._vae_plans = self._vae_tiling, set(), {}
         nbytes = 0 if arena_gb is None else int(arena_gb * (1 << 30))
         check(self.lib.gl_ctx_fork(self._ctx, C.c_size_t(nbytes), C.byref(e._ctx)))
         return e
@@ -504,12 +508,104 @@ class Engine:
         return [dict(name=recs[i].name.decode(), calls=recs[i].calls, ms=recs[i].ms, flops=recs[i].flops, bytes=recs[i].bytes)
                 for i in range(n.value)]
 
-    def vae_decode(self, z: torch.Tensor) -> torch.Tensor:
+    def set_vae_tiling(self, mode="off", tile=vae_tiling.DEFAULT_TILE, overlap=vae_tiling.DEFAULT_OVERLAP) -> None:
+        """The default of vae_decode / vae_encode on this context (a fork starts with its parent's): mode 'off' (the untiled pass),
+        'on' (overlapping tiles blended by tile_blend_kernel; one tile per axis is the untiled pass itself) or 'auto' (untiled where
+        it fits the arena, tiles where it does not); tile and overlap in latent pixels, an integer or (y, x). Tiles have their own
+        GroupNorm statistics and attention: 'on' is not the untiled result."""
+        vae_tiling.check_tiling(tile, overlap)
+        self._vae_tiling = (vae_tiling.check_mode(mode), tile, overlap)
+
+    def _vae_tiling_args(self, tiling, tile, overlap):
+        mode, t0, o0 = self._vae_tiling
+        mode = mode if tiling is None else vae_tiling.check_mode(tiling)
+        tile, overlap = (t0 if tile is None else tile), (o0 if overlap is None else overlap)
+        if mode != "off":
+            vae_tiling.check_tiling(tile, overlap)
+        return mode, tile, overlap
+
+    def _vae_plan(self, kind: str, B: int, h: int, w: int, tile, overlap):
+        """(Plan2D, gl_tile_plan with its device tables) of a decode ('dec') or encode ('enc') of B latents of h x w; kept per shape."""
+        (th, tw), (ovy, ovx) = vae_tiling.check_tiling(tile, overlap)
+        key = (kind, B, h, w, th, tw, ovy, ovx)
+        hit = self._vae_plans.get(key)
+        if hit is not None:
+            return hit
+        f = 2 ** self.vae_cfg["n_up"]
+        p = vae_tiling.Plan2D(h, w, (th, tw), (ovy, ovx))
+        s_in, s_out = (1, f) if kind == "dec" else (f, 1)
+        wy, wx = p.tables(s_out)
+        dev = self.device
+        win = np.array([(b, oy * s_in, ox * s_in) for b in range(B) for oy in p.oy for ox in p.ox], dtype=np.int32)
+        t = dict(windows=torch.from_numpy(win).to(dev), oy=torch.tensor([o * s_out for o in p.oy], dtype=torch.int32, device=dev),
+                 ox=torch.tensor([o * s_out for o in p.ox], dtype=torch.int32, device=dev),
+                 wy=torch.from_numpy(wy).contiguous().to(dev), wx=torch.from_numpy(wx).contiguous().to(dev))
+        c = _lib.TilePlan(struct_size=C.sizeof(_lib.TilePlan), ny=p.ny, nx=p.nx, th_in=p.th * s_in, tw_in=p.tw * s_in, th_out=p.th * s_out,
+                          tw_out=p.tw * s_out, **{k: v.data_ptr() for k, v in t.items()})
+        if len(self._vae_plans) >= 16:
+            self._vae_plans.pop(next(iter(self._vae_plans)))
+        self._vae_plans[key] = (p, c, t)
+        return self._vae_plans[key]
+
+    def tile_gather(self, src: torch.Tensor, windows, th: int, tw: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """gl_op_tile_gather: the windows (b, oy, ox) of size th x tw of src fp32 [B, C, H, W] as tiles [n, C, th, tw], an exact copy."""
+        assert src.is_cuda and src.dtype == torch.float32 and src.is_contiguous()
+        B, Cn, H, W = src.shape
+        win = torch.as_tensor(np.asarray(windows, dtype=np.int32).reshape(-1, 3)).to(self.device)
+        if out is None:
+            out = torch.empty((win.shape[0], Cn, th, tw), device=self.device, dtype=torch.float32)
+        assert out.is_contiguous() and tuple(out.shape) == (win.shape[0], Cn, th, tw)
+        check(self.lib.gl_op_tile_gather(self._ctx, _ptr(src), int(B), int(Cn), int(H), int(W), _ptr(win), int(win.shape[0]), _ptr(out), int(th), int(tw),
+                                         _stream(self.device)))
+        return out
+
+    def tile_blend(self, tiles: torch.Tensor, out: torch.Tensor, oy, ox, wy, wx, first_tile: int = 0) -> torch.Tensor:
+        """gl_op_tile_blend: tiles fp32 [n, C, TH, TW] = the tiles first_tile .. first_tile + n - 1 (index (b ny + ty) nx + tx) of the plan
+        with output-grid origins oy / ox and fp32 weight tables wy [ny, TH], wx [nx, TW], blended into out fp32 [B, C, H, W] in place."""
+        assert tiles.is_cuda and tiles.dtype == torch.float32 and tiles.is_contiguous() and out.is_contiguous() and out.dtype == torch.float32
+        dev = self.device
+        t = dict(oy=torch.as_tensor(np.asarray(oy, dtype=np.int32)).to(dev), ox=torch.as_tensor(np.asarray(ox, dtype=np.int32)).to(dev),
+                 wy=torch.as_tensor(np.ascontiguousarray(wy, dtype=np.float32)).to(dev), wx=torch.as_tensor(np.ascontiguousarray(wx, dtype=np.float32)).to(dev))
+        n, Cn, TH, TW = tiles.shape
+        assert tuple(t["wy"].shape) == (len(oy), TH) and tuple(t["wx"].shape) == (len(ox), TW) and out.shape[1] == Cn
+        c = _lib.TilePlan(struct_size=C.sizeof(_lib.TilePlan), ny=len(oy), nx=len(ox), th_in=TH, tw_in=TW, th_out=TH, tw_out=TW,
+                          **{k: v.data_ptr() for k, v in t.items()})
+        B, _, H, W = out.shape
+        check(self.lib.gl_op_tile_blend(self._ctx, _ptr(tiles), int(first_tile), int(n), C.byref(c), _ptr(out), int(B), int(Cn), int(H), int(W),
+                                        _stream(self.device)))
+        torch.cuda.current_stream(dev).synchronize()          # the tables above are this call's own: they must outlive the launch
+        return out
+
+    def _vae_auto(self, key, untiled, tiled):
+        """'auto': the untiled call where it fits the arena; where the arena refuses it, the tiled one -- and straight away from then on
+        for that shape on this context. An exhausted arena leaves nothing behind: every pass starts by resetting it."""
+        if key not in self._vae_tiled_shapes:
+            try:
+                return untiled()
+            except _lib.GligenAmdError as e:
+                if "workspace arena exhausted" not in str(e):
+                    raise
+            self._vae_tiled_shapes.add(key)
+        return tiled()
+
+    def vae_decode(self, z: torch.Tensor, tiling=None, tile=None, overlap=None, tiles_per_pass: Optional[int] = None) -> torch.Tensor:
+        """AutoencoderKL.decode. tiling: None (this context's set_vae_tiling default), 'off', 'on' or 'auto'; tile / overlap in latent
+        pixels; tiles_per_pass: how many tiles one pass decodes as a batch (default: eight 64 x 64 tiles' worth)."""
         dev = self.device
         z = _f32(z, dev)
         B, _, h, w = z.shape
+        mode, tile, overlap = self._vae_tiling_args(tiling, tile, overlap)
+        if mode == "auto":
+            return self._vae_auto(("dec", B, h, w), lambda: self.vae_decode(z, "off"),
+                                  lambda: self.vae_decode(z, "on", tile, overlap, tiles_per_pass))
         f = 2 ** self.vae_cfg["n_up"]
         out = torch.empty((B, self.vae_cfg["out_ch"], h * f, w * f), device=dev, dtype=torch.float32)
+        if mode == "on":
+            p, c, _ = self._vae_plan("dec", B, h, w, tile, overlap)
+            if not p.single:
+                n = int(tiles_per_pass) if tiles_per_pass is not None else max(1, (8 * 64 * 64) // (p.th * p.tw))
+                check(self.lib.gl_vae_decode_tiled(self._ctx, int(B), int(h), int(w), _ptr(z), _ptr(out), C.byref(c), n, _stream(self.device)))
+                return out
         # samples are independent: batches beyond 8 images at 64 x 64 go through in slices, so the arena (sized for the benchmark's
         # batch) bounds the activations whatever the caller's batch is
         n = max(1, (8 * 64 * 64) // (h * w))
@@ -518,18 +614,56 @@ class Engine:
             check(self.lib.gl_vae_decode(self._ctx, int(m), int(h), int(w), _ptr(z[i:i + m]), _ptr(out[i:i + m]), _stream(self.device)))
         return out
 
-    def vae_encode(self, img: torch.Tensor, noise: torch.Tensor) -> torch.Tensor:
-        """AutoencoderKL.encode: img [B,3,H,W] in [-1,1], noise [B,zc,H/8,W/8] (the posterior's randn draw) -> latent."""
+    def vae_encode(self, img: torch.Tensor, noise: torch.Tensor, tiling=None, return_moments: bool = False, tile=None, overlap=None,
+                   tiles_per_pass: Optional[int] = None):
+        """AutoencoderKL.encode: img [B,3,H,W] in [-1,1], noise [B,zc,H/8,W/8] (the posterior's randn draw) -> latent. tiling, tile,
+        overlap (latent pixels) and tiles_per_pass as in vae_decode; return_moments (tiled form only): (latent, the blended raw
+        moments [B, 2 zc, H/f, W/f] the posterior was drawn from)."""
         dev = self.device
         img, noise = _f32(img, dev), _f32(noise, dev)
         B, _, H, W = img.shape
+        mode, tile, overlap = self._vae_tiling_args(tiling, tile, overlap)
+        if return_moments and mode == "off":
+            raise ValueError("vae_encode: return_moments needs vae_tiling 'on' or 'auto' (only the tiled form hands out the moments)")
+        f = 2 ** self.vae_cfg["n_up"]
+        if mode == "auto":
+            return self._vae_auto(("enc", B, H, W), lambda: self._vae_encode_untiled(img, noise, return_moments),
+                                  lambda: self.vae_encode(img, noise, "on", return_moments, tile, overlap, tiles_per_pass))
+        if mode == "on":
+            if H % f or W % f:
+                raise ValueError(f"vae_encode: image size {H} x {W} must be divisible by the encoder stride {f}")
+            h, w = H // f, W // f
+            p, c, _ = self._vae_plan("enc", B, h, w, tile, overlap)
+            if not p.single:
+                out = torch.empty_like(noise)
+                moments = torch.empty((B, 2 * self.vae_cfg["z_channels"], h, w), device=dev, dtype=torch.float32) if return_moments else None
+                # the analogue of vae_decode's rule, in image pixels: eight 512 x 512 tiles' worth per pass
+                k = int(tiles_per_pass) if tiles_per_pass is not None else max(1, (8 * 512 * 512) // (p.th * p.tw * f * f))
+                check(self.lib.gl_vae_encode_tiled(self._ctx, int(B), int(H), int(W), _ptr(img), _ptr(noise), _ptr(out), _ptr(moments),
+                                                   C.byref(c), k, _stream(self.device)))
+                return (out, moments) if return_moments else out
+        return self._vae_encode_untiled(img, noise, return_moments)       # one tile per axis is the untiled pass itself
+
+    def _vae_encode_untiled(self, img, noise, with_moments: bool):
+        """The untiled encode in slices of the batch; with_moments: through gl_vae_encode_tiled's single-tile form, which is the same
+        launches writing the moments where the caller can read them."""
+        B, _, H, W = img.shape
         out = torch.empty_like(noise)
         n = max(1, (8 * 512 * 512) // (H * W))       # (slices of the batch, as in vae_decode)
+        if not with_moments:
+            for i in range(0, B, n):
+                m = min(n, B - i)
+                check(self.lib.gl_vae_encode(self._ctx, int(m), int(H), int(W), _ptr(img[i:i + m]), _ptr(noise[i:i + m]), _ptr(out[i:i + m]),
+                                             _stream(self.device)))
+            return out
+        f = 2 ** self.vae_cfg["n_up"]
+        moments = torch.empty((B, 2 * self.vae_cfg["z_channels"], H // f, W // f), device=self.device, dtype=torch.float32)
+        one = _lib.TilePlan(struct_size=C.sizeof(_lib.TilePlan), ny=1, nx=1, th_in=H, tw_in=W, th_out=H // f, tw_out=W // f)
         for i in range(0, B, n):
             m = min(n, B - i)
-            check(self.lib.gl_vae_encode(self._ctx, int(m), int(H), int(W), _ptr(img[i:i + m]), _ptr(noise[i:i + m]), _ptr(out[i:i + m]),
-                                         _stream(self.device)))
-        return out
+            check(self.lib.gl_vae_encode_tiled(self._ctx, int(m), int(H), int(W), _ptr(img[i:i + m]), _ptr(noise[i:i + m]), _ptr(out[i:i + m]),
+                                               _ptr(moments[i:i + m]), C.byref(one), 1, _stream(self.device)))
+        return out, moments
 
     def _sampler_args(self, a, who, x, timesteps, fuser_scale, guidance_scale, inpaint_extra, mask, x0, noise, sqrt_ac, sqrt_1mac,
                       use_graph, sd_first_conv, restore_at):

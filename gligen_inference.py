@@ -601,11 +601,21 @@ def _hires_context(model, shape):
     return m
 
 
+def vae_tiling_kwargs(vae_tiling="off", vae_tile=64, vae_tile_overlap=16) -> dict:
+    """What generate() hands AutoencoderKL.decode / encode: nothing for "off" (None is "off"), the checked setting otherwise."""
+    from gligen_amd.vae_tiling import check_mode, check_tiling
+    if check_mode(vae_tiling) == "off":
+        return {}
+    check_tiling(vae_tile, vae_tile_overlap)
+    return dict(tiling=vae_tiling, tile=vae_tile, overlap=vae_tile_overlap)
+
+
 @torch.no_grad()
 def generate(model, autoencoder, diffusion, batch, context, uc, *, steps=None, guidance_scale=7.5, alpha_type=None,
              starting_noise=None, inpainting_mask=None, z0=None, use_graph=True, no_plms=False, grounding_extra_input=None,
              grounding_input=None, sampler=None, discretize="uniform", ddim_eta=0.0, height=None, width=None,
-             init_latent=None, init_image=None, strength=None, hires=None, hires_strength=0.6, hires_steps=None, hires_upscaler="latent-bicubic"):
+             init_latent=None, init_image=None, strength=None, hires=None, hires_strength=0.6, hires_steps=None, hires_upscaler="latent-bicubic",
+             vae_tiling="off", vae_tile=64, vae_tile_overlap=16):
     """The sampling core of run() (reference gligen_inference.py:389-431) on already-encoded inputs. steps: None = 50, or 20 for
     sampler="dpmpp_2m". height, width: the image size in pixels (None: the checkpoint's, 8 * model.image_size); see latent_hw.
     Image-to-image: init_latent (fp32 [B|1, C, h', w'], any spatial size) or init_image (fp32 [B|1, 3, H', W'] in [-1, 1], encoded to
@@ -613,7 +623,12 @@ def generate(model, autoencoder, diffusion, batch, context, uc, *, steps=None, g
     first of them (starting_noise, when given, is that noise).
     hires = (H2, W2): two passes -- this very call at height x width, then a second sampling of int(hires_strength * hires_steps) steps
     (hires_steps: None = steps) at H2 x W2 from the first pass's result, enlarged as hires_upscaler says (HIRES_UPSCALERS), and the
-    decode at H2 x W2. The second pass runs on a forked context (_hires_context)."""
+    decode at H2 x W2. The second pass runs on a forked context (_hires_context).
+    vae_tiling = "on" / "auto": every decode and encode of this call (the final decode, init_image, the pixel-bicubic round trip) runs
+    as overlapping tiles of vae_tile latent pixels (an integer or (y, x)) overlapping by vae_tile_overlap, blended on the device
+    (Engine.vae_decode / vae_encode; "auto": only where the untiled pass does not fit the arena). Tiles have their own GroupNorm
+    statistics and attention, so "on" is close to, not equal to, the untiled image. "off" (default): the calls are what they were."""
+    vkw = vae_tiling_kwargs(vae_tiling, vae_tile, vae_tile_overlap)
     name, _ = sampler_choice(sampler, no_plms, discretize, ddim_eta)
     h, w = latent_hw(model, autoencoder, height, width)
     shape = (context.shape[0], model.in_channels, h, w)
@@ -638,7 +653,7 @@ def generate(model, autoencoder, diffusion, batch, context, uc, *, steps=None, g
     if init_image is not None:
         if init_image.dim() != 4 or int(init_image.shape[1]) != 3 or int(init_image.shape[0]) not in (1, shape[0]):
             raise ValueError(f"init_image {tuple(init_image.shape)} is not [{shape[0]} or 1, 3, H, W]")
-        init_latent = autoencoder.encode(init_image.to(device=context.device, dtype=torch.float32))
+        init_latent = autoencoder.encode(init_image.to(device=context.device, dtype=torch.float32), **vkw)
     schedule_kwargs = {}
     if name == "dpmpp_2m":
         from ldm.models.diffusion.dpm_solver import DPMSolverSampler as sampler_cls
@@ -667,11 +682,11 @@ def generate(model, autoencoder, diffusion, batch, context, uc, *, steps=None, g
     start = dict(x_init=init_latent, strength=strength) if img2img else {}
     latents = sample_pass(model, steps, shape, starting_noise, **start)
     if hires is None:
-        return autoencoder.decode(latents)
+        return autoencoder.decode(latents, **vkw)
     mode = HIRES_UPSCALERS[hires_upscaler]
     if mode is None:       # pixel-bicubic: through the image, enlarged by the same kernel (C = 3, no noise), and back to a latent
-        image = torch.clamp(autoencoder.decode(latents), -1.0, 1.0)
-        latents = autoencoder.encode(model.engine.latent_renoise(image, (H2, W2), "bicubic"))
+        image = torch.clamp(autoencoder.decode(latents, **vkw), -1.0, 1.0)
+        latents = autoencoder.encode(model.engine.latent_renoise(image, (H2, W2), "bicubic"), **vkw)
         mode = "bicubic"   # (equal sizes from here: the identity taps)
     # the second pass's context is looked up after the first pass: it carries the first conv the first pass left the model with
     m2 = _hires_context(model, (shape[0], h2, w2))
@@ -683,7 +698,7 @@ def generate(model, autoencoder, diffusion, batch, context, uc, *, steps=None, g
         model.restore_first_conv_from_SD()
         key = (shape[0], h2, w2)
         model.__dict__["_hires"][key] = (m2, (model.first_conv_type, True))
-    return autoencoder.decode(latents)
+    return autoencoder.decode(latents, **vkw)
 
 
 def _lane_clone(module):
@@ -850,6 +865,9 @@ def run(meta, config, starting_noise=None, models=None):
     contiguous slice (gligen_amd.dist.shard_range) with replicated weights and writes its own images."""
     from gligen_amd import dist as gdist
     args = dict(config) if isinstance(config, dict) else vars(config)
+    # optional keys vae_tiling ("off" | "on" | "auto"), vae_tile, vae_tile_overlap (latent pixels): the autoencoder over blended tiles
+    tiling = {k: args[k] for k in ("vae_tiling", "vae_tile", "vae_tile_overlap") if args.get(k) is not None}
+    vae_kw = vae_tiling_kwargs(**tiling)
     # optional key loras: LoRA adapters (load_ckpt), merged once per model load -- a model handed in that carries them already is left alone
     if models is None:
         model, autoencoder, text_encoder, diffusion, ckpt_config = load_ckpt(meta["ckpt"], loras=args.get("loras"))
@@ -937,7 +955,7 @@ def run(meta, config, starting_noise=None, models=None):
         if "z0" in meta:
             z0 = meta["z0"].to(device)
         else:
-            z0 = autoencoder.encode(load_inpaint_image(meta["input_image"], native=native_inputs, size=None if default_size else (f * lat_w, f * lat_h)))
+            z0 = autoencoder.encode(load_inpaint_image(meta["input_image"], native=native_inputs, size=None if default_size else (f * lat_w, f * lat_h)), **vae_kw)
     start = {}
     if args.get("init_image") is not None:     # read as the inpainting image is: RGB in [-1, 1] at the run's size, batch 1 for every sample
         start = dict(init_image=load_inpaint_image(args["init_image"], native=native_inputs, size=None if native_inputs else (f * lat_w, f * lat_h)),
@@ -975,7 +993,7 @@ def run(meta, config, starting_noise=None, models=None):
     if repeat > 1 and mask is None and not skw["ddim_eta"] and meta.get("alpha_type") in (None, [1, 0, 0], [1.0, 0.0, 0.0]):
         # `repeat` batches of this prompt (seed, seed + 1, ...): whole batches in flight on the lanes, as bench.py runs them
         gkw = dict(steps=steps, guidance_scale=args["guidance_scale"], alpha_type=meta.get("alpha_type"), no_plms=no_plms,
-                   grounding_extra_input=grounding_extra_input, grounding_input=grounding_input, height=height, width=width, **skw, **start)
+                   grounding_extra_input=grounding_extra_input, grounding_input=grounding_input, height=height, width=width, **skw, **start, **tiling)
         shape = (hi - lo, model.in_channels, lat_h, lat_w)
         seed0 = int(args.get("seed") or 0)
         seeded = world > 1 or args.get("seed") is not None
@@ -1006,7 +1024,7 @@ def run(meta, config, starting_noise=None, models=None):
         samples = one_batch(model, autoencoder, diffusion, batch, context, uc, steps=steps,
                             guidance_scale=args["guidance_scale"], alpha_type=meta.get("alpha_type"), starting_noise=starting_noise,
                             inpainting_mask=mask, z0=z0, no_plms=no_plms, grounding_extra_input=grounding_extra_input,
-                            grounding_input=grounding_input, height=height, width=width, **skw, **start)
+                            grounding_input=grounding_input, height=height, width=width, **skw, **start, **tiling)
         if torch.cuda.is_available():
             torch.cuda.synchronize()
             dt = time.perf_counter() - t0
@@ -1105,6 +1123,11 @@ def main(argv=None):
     parser.add_argument("--hires_width", type=int, default=None, help="the second pass's width (a multiple of 64, not below --width)")
     parser.add_argument("--hires_strength", type=float, default=0.6, help="fraction of the second pass's schedule that runs (default 0.6)")
     parser.add_argument("--hires_steps", type=int, default=None, help="length of the second pass's schedule (default: the first pass's step count)")
+    parser.add_argument("--vae_tiling", type=str, default="off", choices=["off", "on", "auto"],
+                        help="decode / encode the image as overlapping tiles blended on the device: on, or auto = only where the untiled pass does not fit the arena "
+                             "(tiles have their own GroupNorm statistics and attention: close to, not equal to, the untiled image)")
+    parser.add_argument("--vae_tile", type=int, default=64, help="tile side in latent pixels, a multiple of 8 (default 64: 512 x 512 image tiles)")
+    parser.add_argument("--vae_tile_overlap", type=int, default=16, help="overlap of neighbouring tiles in latent pixels, 1 .. vae_tile // 2 (default 16)")
     parser.add_argument("--hires_upscaler", type=str, default="latent-bicubic", choices=sorted(HIRES_UPSCALERS),
                         help="how the first pass's result is enlarged: the latent (nearest / bilinear / bicubic, fused with the noising), or the decoded image (bicubic) encoded again")
     parser.add_argument("--lora", dest="loras", action="append", default=None, metavar="PATH[:SCALE[:TE_SCALE]]",

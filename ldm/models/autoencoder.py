@@ -45,13 +45,15 @@ class AutoencoderKL(nn.Module):
         return self._engine
 
     @torch.no_grad()
-    def encode(self, x):
+    def encode(self, x, tiling=None, tile=None, overlap=None):
         """posterior.sample() * scale_factor (autoencoder.py:34-38). The reference draws the posterior noise with the CPU
-        generator (distributions.py:35: torch.randn(mean.shape).to(device)); so does this, for seed-for-seed parity."""
+        generator (distributions.py:35: torch.randn(mean.shape).to(device)); so does this, for seed-for-seed parity.
+        tiling / tile / overlap: Engine.vae_encode's (None: the engine's set_vae_tiling default, "off" unless set)."""
         f = 2 ** (len(self.ddconfig["ch_mult"]) - 1)
         noise = torch.randn((x.shape[0], self.ddconfig["z_channels"], x.shape[2] // f, x.shape[3] // f))
-        return self.engine.vae_encode(x, noise).to(x.dtype)
+        return self.engine.vae_encode(x, noise, tiling=tiling, tile=tile, overlap=overlap).to(x.dtype)
 
     @torch.no_grad()
-    def decode(self, z):
-        return self.engine.vae_decode(z).to(z.dtype)
+    def decode(self, z, tiling=None, tile=None, overlap=None):
+        """tiling / tile / overlap: Engine.vae_decode's (None: the engine's set_vae_tiling default, "off" unless set)."""
+        return self.engine.vae_decode(z, tiling=tiling, tile=tile, overlap=overlap).to(z.dtype)
