@@ -1,6 +1,6 @@
 """ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
 include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h, include/gligen_amd_train_fusers.h, include/gligen_amd_train_prims.h,
-include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h, include/gligen_amd_lora.h and include/gligen_amd_tiling.h).
+include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_ffn_rows.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h, include/gligen_amd_lora.h and include/gligen_amd_tiling.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -275,6 +275,28 @@ ATTENTION_CORE_SYMBOLS = {
 ATTN_CORE_KERNELS = {"auto": 0, "attn_kernel": 1, "attn2_kernel_w4": 2, "attn2_kernel_w8": 3, "attn3_kernel": 4}   # = GL_ATTN_CORE_*
 GL_ERR_UNSUPPORTED = 5
 
+
+class FFRowsArgs(C.Structure):   # = gl_ff_rows_args
+    _fields_ = [("struct_size", C.c_uint), ("M", _I), ("C", _I), ("x", _P), ("ldx", _I), ("normalize", _I), ("eps", C.c_float), ("gamma", _P), ("beta", _P),
+                ("w1", _P), ("b1", _P), ("w2", _P), ("b2", _P), ("res", _P), ("ldres", _I), ("gate", _P), ("out", _P), ("ldo", _I), ("stats_out", _P),
+                ("stats_ld", _I), ("pre", _I), ("post", _I), ("pre_w", _P), ("pre_b", _P), ("pre_res", _P), ("ld_pre_res", _I), ("pre_gate", _P),
+                ("mid_out", _P), ("ld_mid", _I), ("post_w", _P), ("post_b", _P), ("post_res", _P), ("ld_post_res", _I), ("gamma_q", _P), ("beta_q", _P),
+                ("q", _P), ("qDP", _I), ("qT", _I), ("qTpad", _I)]
+
+
+class QkvRowsArgs(C.Structure):   # = gl_qkv_rows_args
+    _fields_ = [("struct_size", C.c_uint), ("M", _I), ("C", _I), ("H", _I), ("x", _P), ("ldx", _I), ("normalize", _I), ("eps", C.c_float), ("pre", _I),
+                ("pre_w", _P), ("pre_b", _P), ("pre_res", _P), ("ld_pre_res", _I), ("mid_out", _P), ("ld_mid", _I), ("stats_out", _P), ("gamma", _P),
+                ("beta", _P), ("np", _I), ("w", _P), ("bias", _P), ("q", _P), ("k", _P), ("vt", _P), ("DP", _I), ("DPV", _I), ("T", _I), ("Tpad_q", _I),
+                ("Tpad_k", _I), ("in_period", _I)]
+
+
+# every symbol include/gligen_amd_ffn_rows.h declares (the row-local feed-forward and q,k,v^T kernels on the caller's buffers)
+FFN_ROWS_SYMBOLS = {
+    "gl_op_ff_rows": (_I, [_P, C.POINTER(FFRowsArgs), _P]),
+    "gl_op_qkv_rows": (_I, [_P, C.POINTER(QkvRowsArgs), _P]),
+}
+
 # every symbol include/gligen_amd_vae.h declares (the form of the autoencoder's attention, and the operator by itself)
 VAE_SYMBOLS = {
     "gl_vae_set_attention": (_I, [_P, _I]),
@@ -339,7 +361,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS, **TRAIN_PRIM_SYMBOLS,
-                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS, **TILING_SYMBOLS}.items():
+                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **FFN_ROWS_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS, **TILING_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

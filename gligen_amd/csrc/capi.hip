@@ -15,6 +15,7 @@
 #include "../../include/gligen_amd_sampler.h"
 #include "../../include/gligen_amd_gemm_plans.h"
 #include "../../include/gligen_amd_attention_core.h"
+#include "../../include/gligen_amd_ffn_rows.h"
 #include "../../include/gligen_amd_vae.h"
 #include "../../include/gligen_amd_latent.h"
 #include "../../include/gligen_amd_lora.h"
@@ -1486,6 +1487,129 @@ int gl_op_proj_attention(gl_ctx* ctx, const void* x, int B, int N, int C, int H,
         ck(gemm_launch(a_rows(xn, C), wqkv, M, 3 * C, C, E, nullptr, 0, S(s)));
     }
     ck(attn_launch(attn_params(bufs.q, bufs.k, bufs.vt, (bf16*)o, H, d, N, N, bufs.Tq_pad, bufs.Tk_pad, vt_layout), B, S(s)));
+    GL_API_END
+}
+
+// include/gligen_amd_ffn_rows.h: the row-local kernels on the caller's buffers, every field of their parameter blocks the caller's.
+// Folding and packing as gl_op_feedforward / gl_op_ff_chain / gl_op_ff_chain_q / gl_op_proj_attention do them; no other kernel
+// stands in where the row-local one refuses.
+static bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+int gl_op_ff_rows(gl_ctx* ctx, const gl_ff_rows_args* a, gl_stream s) {
+    NEED(ctx);
+    if (!a) return gl::set_error(GL_ERR_ARG, "gl_op_ff_rows: null args");
+    if (a->struct_size != sizeof(gl_ff_rows_args))
+        return gl::set_error(GL_ERR_ARG, "gl_op_ff_rows: args->struct_size is %u, this library's gl_ff_rows_args has %zu bytes", a->struct_size,
+                             sizeof(gl_ff_rows_args));
+    if (!a->x || !a->w1 || !a->b1 || !a->w2 || !a->b2 || !a->out) return gl::set_error(GL_ERR_ARG, "gl_op_ff_rows: null pointer");
+    if ((a->gamma == nullptr) != (a->beta == nullptr)) return gl::set_error(GL_ERR_ARG, "gl_op_ff_rows: gamma and beta come together");
+    GL_API_BEGIN
+    Arena& ar = ctx->eng->arena();
+    ar.reset();
+    auto ck = [&](int rc) { if (rc != GL_OK) throw GlError(rc, gl::last_error()); };
+    const int M = a->M, C = a->C;
+    if (!ff_rows_supported(M, C)) throw GlError(GL_ERR_UNSUPPORTED, "gl_op_ff_rows: no row-local kernel for this shape (C = 320, M % 128 == 0)");
+    if (a->pre != 0 && a->pre != 1) throw GlError(GL_ERR_ARG, "gl_op_ff_rows: pre is 0 or 1");
+    if (a->post < 0 || a->post > 2) throw GlError(GL_ERR_ARG, "gl_op_ff_rows: post is 0, 1 or 2");
+    if (a->post && !a->pre) throw GlError(GL_ERR_UNSUPPORTED, "gl_op_ff_rows: a trailing projection is built only together with a leading one");
+    if (a->gamma && !a->normalize) throw GlError(GL_ERR_ARG, "gl_op_ff_rows: a LayerNorm affine needs normalize = 1");
+    if (a->ldx < C || a->ldo < C || !aligned_to(a->x, 16) || !aligned_to(a->out, 8))
+        throw GlError(GL_ERR_ARG, "gl_op_ff_rows: ldx, ldo >= C; x 16-byte, out 8-byte aligned");
+    if (!a->pre && a->res && (a->ldres < C || !aligned_to(a->res, 8))) throw GlError(GL_ERR_ARG, "gl_op_ff_rows: ldres >= C, res 8-byte aligned");
+    if (a->stats_out && (a->stats_ld < 1 || !aligned_to(a->stats_out, 8))) throw GlError(GL_ERR_ARG, "gl_op_ff_rows: stats_ld >= 1, stats_out 8-byte aligned");
+    if (a->pre && (!a->pre_w || !a->pre_b || !a->pre_res || !a->mid_out || a->ld_pre_res < C || a->ld_mid < C || !aligned_to(a->pre_res, 8) ||
+                   !aligned_to(a->mid_out, 8)))
+        throw GlError(GL_ERR_ARG, "gl_op_ff_rows: the leading projection needs its weights, bias, residual and mid_out (strides >= C, 8-byte aligned)");
+    if (a->post == 1 && (!a->post_w || !a->post_b || !a->post_res || a->ld_post_res < C || !aligned_to(a->post_res, 8)))
+        throw GlError(GL_ERR_ARG, "gl_op_ff_rows: the trailing projection needs its weights, bias and residual (stride >= C, 8-byte aligned)");
+    if (a->post == 2 && (!a->post_w || !a->gamma_q || !a->beta_q || !a->q || a->qT <= 0 || M % a->qT || a->qT % 32 || a->qTpad < a->qT || a->qDP < 40 ||
+                         a->qDP % 4 || !aligned_to(a->q, 8)))
+        throw GlError(GL_ERR_ARG, "gl_op_ff_rows: the trailing to_q projection needs Wq, its LayerNorm affine, q and qT % 32 == 0 | M, qTpad >= qT, qDP >= 40, qDP % 4 == 0");
+    const float* w1e = a->w1;
+    const float* b1e = a->b1;
+    if (a->gamma) {
+        float* wf = ar.get<float>((size_t)8 * C * C);
+        float* bf = ar.get<float>((size_t)8 * C);
+        ck(ln_fold_launch(a->w1, a->b1, a->gamma, a->beta, wf, bf, 8 * C, C, S(s)));
+        w1e = wf; b1e = bf;
+    }
+    const float* post_w = a->post ? a->post_w : nullptr;
+    const float* post_b = a->post_b;
+    if (a->post == 2) {
+        float* wqf = ar.get<float>((size_t)C * C);
+        float* bqf = ar.get<float>((size_t)C);
+        ck(ln_fold_launch(a->post_w, nullptr, a->gamma_q, a->beta_q, wqf, bqf, C, C, S(s)));
+        post_w = wqf; post_b = bqf;
+    }
+    void* st = ar.alloc(ff_chain_stream_bytes(C, a->pre != 0, a->post != 0));
+    ck(ff_chain_pack_launch(w1e, b1e, a->w2, a->pre ? a->pre_w : nullptr, post_w, st, C, S(s)));
+    FFRowsParams P{};
+    P.x = (const bf16*)a->x; P.ldx = a->ldx; P.normalize = a->normalize ? 1 : 0; P.eps = a->eps; P.stream = st; P.b2 = a->b2;
+    P.res = a->pre ? nullptr : (const bf16*)a->res; P.ldres = a->ldres; P.gate = a->gate; P.out = (bf16*)a->out; P.ldo = a->ldo; P.M = M;
+    P.stats_out = (float2*)a->stats_out; P.stats_ld = a->stats_ld;
+    P.pre = a->pre; P.post = a->post;
+    if (a->pre) {
+        P.pre_b = a->pre_b; P.pre_res = (const bf16*)a->pre_res; P.ld_pre_res = a->ld_pre_res; P.pre_gate = a->pre_gate;
+        P.mid_out = (bf16*)a->mid_out; P.ld_mid = a->ld_mid;
+    }
+    if (a->post) P.post_b = post_b;
+    if (a->post == 1) { P.post_res = (const bf16*)a->post_res; P.ld_post_res = a->ld_post_res; }
+    if (a->post == 2) { P.q = (bf16*)a->q; P.qDP = a->qDP; P.qT = a->qT; P.qTpad = a->qTpad; }
+    ck(ff_rows_launch(P, C, S(s)));
+    GL_API_END
+}
+
+int gl_op_qkv_rows(gl_ctx* ctx, const gl_qkv_rows_args* a, gl_stream s) {
+    NEED(ctx);
+    if (!a) return gl::set_error(GL_ERR_ARG, "gl_op_qkv_rows: null args");
+    if (a->struct_size != sizeof(gl_qkv_rows_args))
+        return gl::set_error(GL_ERR_ARG, "gl_op_qkv_rows: args->struct_size is %u, this library's gl_qkv_rows_args has %zu bytes", a->struct_size,
+                             sizeof(gl_qkv_rows_args));
+    if (!a->x || !a->w || !a->q) return gl::set_error(GL_ERR_ARG, "gl_op_qkv_rows: null pointer");
+    if ((a->gamma == nullptr) != (a->beta == nullptr)) return gl::set_error(GL_ERR_ARG, "gl_op_qkv_rows: gamma and beta come together");
+    GL_API_BEGIN
+    Arena& ar = ctx->eng->arena();
+    ar.reset();
+    auto ck = [&](int rc) { if (rc != GL_OK) throw GlError(rc, gl::last_error()); };
+    const int M = a->M, C = a->C, H = a->H, np = a->np;
+    if (H <= 0 || C % H) throw GlError(GL_ERR_ARG, "gl_op_qkv_rows: C % H == 0");
+    const int d = C / H;
+    if (!qkv_rows_supported(M, C, d, a->T)) throw GlError(GL_ERR_UNSUPPORTED, "gl_op_qkv_rows: no row-local kernel for this shape (C = 320, d = 40, T % 128 == 0 divides M)");
+    if (np != 1 && np != 3) throw GlError(GL_ERR_ARG, "gl_op_qkv_rows: np must be 1 (q) or 3 (q, k, v^T)");
+    if (a->pre != 0 && a->pre != 1) throw GlError(GL_ERR_ARG, "gl_op_qkv_rows: pre is 0 or 1");
+    if (a->ldx < C || !aligned_to(a->x, 16) || !aligned_to(a->q, 8) || a->Tpad_q < a->T || a->DP < d || a->DP % 8)
+        throw GlError(GL_ERR_ARG, "gl_op_qkv_rows: ldx >= C, x 16-byte and q 8-byte aligned, Tpad_q >= T, DP >= d, DP % 8 == 0");
+    if (np == 3 && (!a->k || !a->vt || !aligned_to(a->k, 16) || !aligned_to(a->vt, 16) || a->Tpad_k < a->T || a->Tpad_k % 64 || a->DPV < d))
+        throw GlError(GL_ERR_ARG, "gl_op_qkv_rows: k and vt 16-byte aligned, Tpad_k >= T, Tpad_k % 64 == 0, DPV >= d");
+    if (a->pre && (!a->pre_w || !a->pre_b || !a->mid_out || a->ld_mid < C || !aligned_to(a->mid_out, 8) ||
+                   (a->pre_res && (a->ld_pre_res < C || !aligned_to(a->pre_res, 8))) || (a->stats_out && !aligned_to(a->stats_out, 8))))
+        throw GlError(GL_ERR_ARG, "gl_op_qkv_rows: the leading projection needs its weights, bias and mid_out (strides >= C, 8-byte aligned)");
+    if (a->in_period < 0 || (a->in_period && (a->in_period % a->T || M % a->in_period)))
+        throw GlError(GL_ERR_ARG, "gl_op_qkv_rows: the input period must be whole samples and divide M");
+    const int N = np * C;
+    bf16* wb = ar.get<bf16>((size_t)N * C);
+    float* bias = ar.get<float>((size_t)N);
+    if (a->gamma) {
+        float* wf = ar.get<float>((size_t)N * C);
+        ck(ln_fold_launch(a->w, a->bias, a->gamma, a->beta, wf, bias, N, C, S(s)));
+        ck(cast_f32_bf16_launch(wf, wb, (int64_t)N * C, S(s)));
+    } else {
+        ck(cast_f32_bf16_launch(a->w, wb, (int64_t)N * C, S(s)));
+        if (a->bias) HIPCK_API(hipMemcpyAsync(bias, a->bias, (size_t)N * sizeof(float), hipMemcpyDeviceToDevice, S(s)));
+        else ck(fill_f32_launch(bias, 0.f, N, S(s)));
+    }
+    void* st = ar.alloc(qkv_rows_stream_bytes(C, a->pre != 0, np));
+    ck(qkv_rows_pack_launch(a->pre ? a->pre_w : nullptr, wb, np, st, C, S(s)));
+    QkvRowsParams P{};
+    P.x = (const bf16*)a->x; P.ldx = a->ldx; P.normalize = a->normalize ? 1 : 0; P.eps = a->eps; P.stream = st; P.M = M;
+    P.pre = a->pre;
+    if (a->pre) {
+        P.pre_b = a->pre_b; P.pre_res = (const bf16*)a->pre_res; P.ld_pre_res = a->ld_pre_res; P.mid_out = (bf16*)a->mid_out; P.ld_mid = a->ld_mid;
+        P.stats_out = (float2*)a->stats_out;
+    }
+    P.np = np; P.bias = bias; P.q = (bf16*)a->q; P.k = (bf16*)a->k; P.vt = (bf16*)a->vt;
+    P.H = H; P.d = d; P.DP = a->DP; P.DPV = a->DPV; P.T = a->T; P.Tpad_q = a->Tpad_q; P.Tpad_k = a->Tpad_k; P.vt_perm32 = 1; P.in_period = a->in_period;
+    ck(qkv_rows_launch(P, C, S(s)));
     GL_API_END
 }
 

@@ -1520,6 +1520,28 @@ class Engine:
                                             ATTN_CORE_KERNELS[kernel], _stream(self.device)))
         return o
 
+    def op_ff_rows(self, **fields):
+        """ff_rows_kernel on the caller's buffers (gl_op_ff_rows; include/gligen_amd_ffn_rows.h). fields: the members of gl_ff_rows_args
+        by name -- tensors (or None) for the pointers, ints / floats for the rest; whatever is left out is 0 / null, eps 1e-5."""
+        from ._lib import FFRowsArgs
+        self._rows_call(self.lib.gl_op_ff_rows, FFRowsArgs, fields)
+
+    def op_qkv_rows(self, **fields):
+        """qkv_rows_kernel on the caller's buffers (gl_op_qkv_rows; include/gligen_amd_ffn_rows.h), fields as in op_ff_rows."""
+        from ._lib import QkvRowsArgs
+        self._rows_call(self.lib.gl_op_qkv_rows, QkvRowsArgs, fields)
+
+    def _rows_call(self, fn, struct, fields):
+        names = {n for n, _ in struct._fields_}
+        unknown = set(fields) - names
+        if unknown or "struct_size" in fields:
+            raise TypeError(f"{struct.__name__} has no field(s) {sorted(unknown | ({'struct_size'} & set(fields)))}")
+        args = struct(struct_size=C.sizeof(struct), eps=1e-5)
+        for name, ctype in struct._fields_:
+            if name in fields and fields[name] is not None:
+                setattr(args, name, fields[name].data_ptr() if ctype is C.c_void_p else fields[name])
+        check(fn(self._ctx, C.byref(args), _stream(self.device)))
+
     def attn_regime_counters(self, enable):
         """(lazy_moves, reruns) counted by op_attention since the last call (gl_attn_regime_counters): the counts are reset, and
         counting is on afterwards iff `enable`. A test instrument: d = 40 only, 0 elsewhere."""

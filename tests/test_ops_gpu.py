@@ -413,6 +413,15 @@ def test_feedforward_rows_large_gate_inputs(engine):
     assert used == 1 and bool(torch.isfinite(y.float()).all())
     ref = (F.gelu(b1[4 * C:]).view(4, C).sum(0) / 4.0).expand(M, C)
     assert rel_err(y, ref) < TOL
+    # per hidden feature (an average of 4 and a max-over-max tolerance hide one feature's error): FF-out selects one hidden feature per
+    # output, the gate pre-activations cover [-12, 12] and the tails, each element against float64 erfc and the derived bound
+    import ffn_rows_ref as R
+    for c in (c for c in R.FF_CASES if c.special and c.special[0] == "sweep"):
+        ins = R.make_inputs(c, x.device)
+        ys, _, used = engine.op_feedforward(ins["x"], ins["w1"], ins["b1"], ins["w2"], ins["b2"])
+        assert used == 1 and bool(torch.isfinite(ys.float()).all())
+        got, want, bound = R.expect(c, ins, {"out": ys})["out"]
+        assert bool(((got - want).abs() <= bound).all()), (c.name, float(((got - want).abs() / bound).max()))
 
 
 # ---- training slice (second half): forward + backward of one BasicTransformerBlock (gatedSA fuser) under
