@@ -1,6 +1,6 @@
 """ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
 include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h, include/gligen_amd_train_fusers.h, include/gligen_amd_train_prims.h,
-include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_ffn_rows.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h, include/gligen_amd_lora.h and include/gligen_amd_tiling.h).
+include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_ffn_rows.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h, include/gligen_amd_lora.h, include/gligen_amd_tiling.h and include/gligen_amd_train_lora.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -232,6 +232,19 @@ TRAIN_PRIM_SYMBOLS = {
     "gl_op_train_dot": (_I, [_P, C.c_int64, _P, _P, _P, _F, _I, _P, _P]),
 }
 
+class LoraAdapter(C.Structure):   # = gl_lora_adapter
+    _fields_ = [("name", C.c_char_p), ("down", C.c_void_p), ("up", C.c_void_p), ("g_down", C.c_void_p), ("g_up", C.c_void_p), ("rank", C.c_int),
+                ("scale", C.c_float)]
+
+
+# every symbol include/gligen_amd_train_lora.h declares (the training iteration with LoRA adapters; one adapted Linear's low-rank part)
+TRAIN_LORA_SYMBOLS = {
+    "gl_unet_train_step_lora": (_I, [_P, C.POINTER(UNetConfig), C.POINTER(TrainUNetIn), _I, C.POINTER(C.c_char_p), C.POINTER(_P), C.POINTER(_P),
+                                     C.POINTER(LoraAdapter), _I, _P, _P, _P]),
+    "gl_op_lora_linear": (_I, [_P, _I, _I, _I, _I, _F, _I, _I] + [_P] * 10 + [_P]),
+    "gl_lora_wgrad_chunk_rows": (_I, [_I]),
+}
+
 # every symbol include/gligen_amd_trainer.h declares (the optimizer unit of a training run: AdamW + EMA in one pass)
 TRAINER_SYMBOLS = {
     "gl_op_adamw_ema_step": (_I, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _I, _P]),
@@ -361,7 +374,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS, **TRAIN_PRIM_SYMBOLS,
-                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **FFN_ROWS_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS, **TILING_SYMBOLS}.items():
+                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **FFN_ROWS_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS, **TILING_SYMBOLS, **TRAIN_LORA_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -11,6 +11,7 @@
 #include "../../include/gligen_amd_train_inputs.h"
 #include "../../include/gligen_amd_train_fusers.h"
 #include "../../include/gligen_amd_train_prims.h"
+#include "../../include/gligen_amd_train_lora.h"
 #include "../../include/gligen_amd_trainer.h"
 #include "../../include/gligen_amd_sampler.h"
 #include "../../include/gligen_amd_gemm_plans.h"
@@ -1061,8 +1062,10 @@ int gl_op_resample_train(gl_ctx* ctx, int mode, int B, int H, int W, int C, cons
     GL_API_END
 }
 
-int gl_unet_train_step(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, int n_params, const char* const* names,
-                       const float* const* params, float* const* grads, float* eps_out, float* loss, gl_stream s) {
+// gl_unet_train_step and gl_unet_train_step_lora (include/gligen_amd_train_lora.h): the same iteration, with or without adapters
+static int train_step_discrete(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, int n_params, const char* const* names,
+                               const float* const* params, float* const* grads, const gl::TrainLoraAdapter* adapters, int n_adapters, float* eps_out,
+                               float* loss, gl_stream s) {
     NEED(ctx);
     if (!cfg || !in || !names || !params || !grads || !loss || n_params <= 0) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step: null pointer");
     if (cfg->grounding_kind < 0 || cfg->grounding_kind > 2 || cfg->fuser_kind < 0 || cfg->fuser_kind > 2 || cfg->extra_channels)
@@ -1086,11 +1089,44 @@ int gl_unet_train_step(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_un
     gl::TrainUNetIn u{in->B, in->H, in->W, in->ctx_T, cfg->grounding_kind == 1 ? 2 * in->Ng : in->Ng, in->Ng, in->x, in->timesteps, in->context, in->boxes,
                       in->masks, in->positive_embeddings, in->text_masks, in->image_masks, in->image_embeddings, in->target, in->fuser_scale, in->checkpoint};
     int rc = gl::unet_train_step(eng.arena(), eng.splitk_ws(), eng.splitk_ws_bytes(), c, u, n_params, names, params, grads, k_train_block_names, eps_out, loss, S(s),
-                                 eng.train_events(), Engine::kTrainEvents, in->use_weight_cache ? eng.train_cache : nullptr);
+                                 eng.train_events(), Engine::kTrainEvents, in->use_weight_cache ? eng.train_cache : nullptr, nullptr, adapters, n_adapters);
     if (rc != GL_OK) throw GlError(rc, gl::last_error());
     eng.train_events_recorded = true;
     GL_API_END
 }
+
+int gl_unet_train_step(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, int n_params, const char* const* names,
+                       const float* const* params, float* const* grads, float* eps_out, float* loss, gl_stream s) {
+    return train_step_discrete(ctx, cfg, in, n_params, names, params, grads, nullptr, 0, eps_out, loss, s);
+}
+
+// ---- include/gligen_amd_train_lora.h: the iteration with adapters, and the low-rank part of one adapted Linear by itself
+int gl_unet_train_step_lora(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, int n_params, const char* const* names,
+                            const float* const* params, float* const* grads, const gl_lora_adapter* adapters, int n_adapters, float* eps_out,
+                            float* loss, gl_stream s) {
+    if (n_adapters < 0 || (n_adapters > 0 && !adapters)) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_lora: null adapter array");
+    std::vector<gl::TrainLoraAdapter> a((size_t)n_adapters);
+    for (int i = 0; i < n_adapters; ++i)
+        a[i] = {adapters[i].name, adapters[i].down, adapters[i].up, adapters[i].g_down, adapters[i].g_up, adapters[i].rank, adapters[i].scale};
+    return train_step_discrete(ctx, cfg, in, n_params, names, params, grads, a.data(), n_adapters, eps_out, loss, s);
+}
+
+int gl_op_lora_linear(gl_ctx* ctx, int M, int K, int N, int rank, float scale, int down_kr, int up_rn, const float* x, const float* down,
+                      const float* up, const float* dy, float* t, float* y, float* u, float* dx, float* g_down, float* g_up, gl_stream s) {
+    NEED(ctx);
+    if (!x || !down || !up) return gl::set_error(GL_ERR_ARG, "gl_op_lora_linear: null pointer (x, down and up are required)");
+    if (!dy && (u || dx || g_down || g_up)) return gl::set_error(GL_ERR_ARG, "gl_op_lora_linear: a backward output was asked for without dy");
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) return gl::set_error(GL_ERR_ARG, "gl_op_lora_linear: x and dy are 16-byte aligned");
+    GL_API_BEGIN
+    Engine& eng = *ctx->eng;
+    eng.arena().reset();
+    const int rc = gl::train_prim_lora_linear(eng.arena(), eng.splitk_ws(), eng.splitk_ws_bytes(), M, K, N, rank, scale, down_kr, up_rn, x, down, up, dy, t, y,
+                                              u, dx, g_down, g_up, S(s));
+    if (rc != GL_OK) throw GlError(rc, gl::last_error());
+    GL_API_END
+}
+
+int gl_lora_wgrad_chunk_rows(int M) { return M < 1 ? 0 : gl::train::lora_wgrad_chunk_rows(M); }
 
 // gl_unet_train_step_spatial and gl_unet_train_step_spatial_classes: `spi` holds the planes or the class maps
 static int train_step_spatial(const char* what, gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, const gl::TrainSpatialIn& spi, int n_params,

@@ -110,9 +110,25 @@ struct TrainWeightCache;
 TrainWeightCache* train_cache_create();
 void train_cache_destroy(TrainWeightCache* c);      // frees every cached copy
 size_t train_cache_bytes(const TrainWeightCache* c);
+// A LoRA adapter in training (include/gligen_amd_train_lora.h; train_lora.hip): `name` is the state_dict key of a frozen Linear's weight
+// [N][K] -- attn1 / attn2 .to_q / to_k / to_v / to_out.0, ff.net.0.proj, ff.net.2 of a SpatialTransformer's block, or its proj_in /
+// proj_out --, down [rank][K], up [N][rank] fp32 device; g_down / g_up shaped like them (null: not formed). The layer computes
+// x W^T + scale (x down^T) up^T.
+struct TrainLoraAdapter {
+    const char* name;
+    const float* down;
+    const float* up;
+    float* g_down;
+    float* g_up;
+    int rank;
+    float scale;
+};
 int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& cfg, const TrainUNetIn& in, int n_params, const char* const* names,
                     const float* const* params, float* const* grads, const char* const* block_names, float* eps_out, float* loss, hipStream_t s,
-                    hipEvent_t* grad_events = nullptr, int n_grad_events = 0, TrainWeightCache* cache = nullptr, const TrainSpatialIn* spatial = nullptr);
+                    hipEvent_t* grad_events = nullptr, int n_grad_events = 0, TrainWeightCache* cache = nullptr, const TrainSpatialIn* spatial = nullptr,
+                    const TrainLoraAdapter* adapters = nullptr, int n_adapters = 0);
+// adapters (optional): their gradients are final at the milestone of their SpatialTransformer, like that block's fuser gradients. With
+// none, every launch and every bit is the unadapted step's.
 // grad_events (optional): event j is recorded on `s` when the backward of the j-th SpatialTransformer (module order) has written its
 // fuser gradients -- the backward runs from the last block to the first, so high j come early --, event [number of SpatialTransformers]
 // when position_net's, downsample_net's and the first conv's (the last gradients of the step) are written.
@@ -146,6 +162,13 @@ int train_prim_groupnorm(Arena& ar, float* ws, size_t ws_bytes, int B, int HW, i
 int train_prim_geglu(Arena& ar, float* ws, size_t ws_bytes, int R, int I, const float* u, const float* dh, float* h, float* du, hipStream_t s);
 int train_prim_dot(Arena& ar, float* ws, size_t ws_bytes, size_t n, const float* a, const float* b, const float* alpha, float scale, int mode, float* out,
                    hipStream_t s);
+
+// The low-rank part of one adapted Linear by itself (include/gligen_amd_train_lora.h; train_lora.hip)
+int train_prim_lora_linear(Arena& ar, float* ws, size_t ws_bytes, int M, int K, int N, int r, float scale, int down_kr, int up_rn, const float* x,
+                           const float* down, const float* up, const float* dy, float* t, float* y, float* u, float* dx, float* g_down, float* g_up,
+                           hipStream_t s);
+
+namespace train { int lora_wgrad_chunk_rows(int M); }      // rows per partial sum of its weight-gradient kernel
 
 // One AdamW update of a flat fp32 parameter range, in place (torch.optim.AdamW semantics: trainer.py:245, :384 opt.step()); step = 1, 2, ...
 int adamw_step(float* p, const float* g, float* m, float* v, size_t n, double lr, double b1, double b2, double eps, double wd, int step, hipStream_t s);

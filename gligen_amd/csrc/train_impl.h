@@ -1,6 +1,7 @@
 // What the training path's translation units share and nobody else sees (train.h is the interface capi.hip and engine.h see):
 //   train_ops.hip        the primitive kernels, the Ctx methods over them, the frozen-weight operand cache, AdamW
 //   train_attention.hip  the VALU and MFMA attention kernels, Ctx::attn_fwd / attn_bwd
+//   train_lora.hip       the low-rank products of LoRA adapters in training (fp32-input MFMA), lora_fwd / lora_bwd
 //   train_layers.hip     block, SpatialTransformer, ResBlock, resample: *_check / *_forward / *_backward; the four slice entry points
 //   train_spatial.hip    ConvNeXt tokenizer, GroundingDownsampler and the first conv of the spatial-map models
 //   train_unet.hip       the whole iteration: grounding MLPs, time embedding, the layer list, unet_train_step
@@ -48,6 +49,11 @@ inline int isqrt_exact(int n) {
 __device__ __forceinline__ float gelu_cdf(float g) { return 0.5f * (1.f + erff(g * 0.70710678118654752440f)); }
 __device__ __forceinline__ float gelu_pdf(float g) { return 0.3989422804014327f * __expf(-0.5f * g * g); }
 
+// A LoRA adapter of one frozen Linear in training (train_lora.hip): y = x W^T + scale (x down^T) up^T, down [r][K], up [N][r], fp32;
+// a null gradient pointer: that gradient is not formed. The table is keyed by the base weight's address.
+struct LoraAdapter { const float* down; const float* up; float* g_down; float* g_up; int r; float scale; };
+using LoraTable = std::unordered_map<const void*, LoraAdapter>;
+
 // The arena, the stream and every primitive operation as a method. The methods are defined in train_ops.hip, attn_fwd / attn_bwd in
 // train_attention.hip; their comments are with the definitions.
 struct Ctx {
@@ -57,6 +63,7 @@ struct Ctx {
     hipStream_t s;
     TrainWeightCache* wc = nullptr;                            // null: every operand copy is built per product in the arena
     const std::unordered_set<const void*>* frozen = nullptr;   // parameter tensors the caller does not update (no gradient asked for)
+    const LoraTable* lora = nullptr;                           // adapters in training; null: every launch is the unadapted step's
 
     void ck(int rc) const { if (rc != GL_OK) throw GlError(rc, gl::last_error()); }
     void hip(hipError_t e, const char* what) const { if (e != hipSuccess) throw GlError(GL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }
@@ -160,6 +167,18 @@ float* silu_bwd(const Ctx& c, const float* dy, const float* x, size_t n);
 void null_grad(const Ctx& c, const float* g, const float* masks, int R, int ld, int c0, int n, float* out, bool accumulate);
 float* conv3x3_direct(const Ctx& c, const float* x, const float* w, const float* bias, int B, int H, int W, int Cin, int Cout);
 
+// ---- train_lora.hip: the low-rank products on the fp32-input MFMA, and the adapter term of a Linear whose weight is in c.lora
+// (no entry: nothing is launched)
+void lora_check(const char* what, int M, int K, int N, int r);
+int lora_wgrad_chunk_rows(int M);       // rows per partial sum of a weight gradient: a function of M alone
+void lora_down(const Ctx& c, const float* X, int M, int K, const float* A, int r, bool a_kr, float* T);                      // T = X A^T, A [r][K] or [K][r]
+void lora_up(const Ctx& c, const float* T, int M, int r, const float* Bm, int N, bool b_rn, float s, float* Y);              // Y += s T B, B [N][r] or [r][N]
+void lora_wgrad(const Ctx& c, const float* T, const float* Z, int M, int r, int N, float s, bool transposed, float* G);      // G [r][N] (or ^T) = s T^T Z
+const LoraAdapter* lora_find(const Ctx& c, const float* W);
+void lora_fwd(const Ctx& c, const float* W, const float* x, int M, int K, int N, float* y);                                  // y += s (x down^T) up^T
+// dx (optional) += s (dy up) down; the adapter's gradients g_down = s (dy up)^T x, g_up = s dy^T (x down^T)
+void lora_bwd(const Ctx& c, const float* W, const float* dy, const float* x, int M, int K, int N, float* dx);
+
 // ---- train_layers.hip: the UNet's layer kinds. *_forward keeps what the backward needs in the arena; *_backward takes g = dL/dy
 // Everything the backward of a BasicTransformerBlock needs from its forward
 struct BlockSaved {
@@ -172,13 +191,15 @@ struct BlockSaved {
 struct STSaved {
     Ctx::GN n0;
     BlockSaved blk;
+    float* yb = nullptr;        // the block's output, proj_out's input (read by an adapter's backward)
 };
 struct ResSaved {
     Ctx::GN n1, n2;
 };
 void st_check(const TrainBlockDims& d, const float* const* P, float* const* G = nullptr);
 STSaved st_forward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const float* x, const float* objs, const float* context, float* y);
-void st_backward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const STSaved& S, const float* objs, float* g, float* dobjs, float* const* G);
+void st_backward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const STSaved& S, const float* objs, float* g, float* dobjs, float* const* G,
+                 const float* context = nullptr);      // context: read only by adapters on attn2.to_k / to_v
 void res_check(const TrainResDims& d, const float* const* P);
 ResSaved res_forward(const Ctx& c, const TrainResDims& d, const float* const* P, const float* x, const float* silu_emb, float* y);
 float* res_backward(const Ctx& c, const TrainResDims& d, const float* const* P, const ResSaved& S, float* g);

@@ -73,8 +73,14 @@ static BlockSaved block_forward(const Ctx& c, const TrainBlockDims& d, const flo
     S.q1 = c.lin_fwd(S.n1.y, M, C, P[TP_A1_Q], nullptr, C);
     S.k1 = c.lin_fwd(S.n1.y, M, C, P[TP_A1_K], nullptr, C);
     S.v1 = c.lin_fwd(S.n1.y, M, C, P[TP_A1_V], nullptr, C);
+    if (c.lora) {       // the adapters of the frozen SD Linears (train_lora.hip): each adds its low-rank term to the product in place
+        lora_fwd(c, P[TP_A1_Q], S.n1.y, M, C, C, S.q1);
+        lora_fwd(c, P[TP_A1_K], S.n1.y, M, C, C, S.k1);
+        lora_fwd(c, P[TP_A1_V], S.n1.y, M, C, C, S.v1);
+    }
     S.a1 = c.attn_fwd(D, S.q1, S.k1, S.v1, B, H, N, N);
     float* o1 = c.lin_fwd(S.a1.o, M, C, P[TP_A1_O], P[TP_A1_OB], C);
+    if (c.lora) lora_fwd(c, P[TP_A1_O], S.a1.o, M, C, C, o1);
     float* x1 = c.gated_add(x, o1, nullptr, 1.f, nx);
     if (d.fuser_kind == 2) {
         // fuser (gatedCA, attention.py:207-212): x2 = x1 + scale tanh(alpha_attn) attn(norm1(x1), objs, objs): no fuser.linear, to_k / to_v read objs
@@ -126,34 +132,56 @@ static BlockSaved block_forward(const Ctx& c, const TrainBlockDims& d, const flo
     S.q2 = c.lin_fwd(S.n2.y, M, C, P[TP_A2_Q], nullptr, C);
     S.k2 = c.lin_fwd(context, MC, KD, P[TP_A2_K], nullptr, C);
     S.v2 = c.lin_fwd(context, MC, KD, P[TP_A2_V], nullptr, C);
+    if (c.lora) {
+        lora_fwd(c, P[TP_A2_Q], S.n2.y, M, C, C, S.q2);
+        lora_fwd(c, P[TP_A2_K], context, MC, KD, C, S.k2);
+        lora_fwd(c, P[TP_A2_V], context, MC, KD, C, S.v2);
+    }
     S.a2 = c.attn_fwd(D, S.q2, S.k2, S.v2, B, H, N, d.ctx_T);
     float* o2 = c.lin_fwd(S.a2.o, M, C, P[TP_A2_O], P[TP_A2_OB], C);
+    if (c.lora) lora_fwd(c, P[TP_A2_O], S.a2.o, M, C, C, o2);
     float* x4 = c.gated_add(x3, o2, nullptr, 1.f, nx);
     // y = ff(norm3(x4)) + x4
     S.n3 = c.ln_fwd(x4, M, C, P[TP_NORM3_W], P[TP_NORM3_B]);
     S.u3 = c.lin_fwd(S.n3.y, M, C, P[TP_FF1_W], P[TP_FF1_B], 8 * C);
+    if (c.lora) lora_fwd(c, P[TP_FF1_W], S.n3.y, M, C, 8 * C, S.u3);
     float* h3 = c.geglu_fwd(S.u3, M, 4 * C);
     float* ff3 = c.lin_fwd(h3, M, 4 * C, P[TP_FF2_W], P[TP_FF2_B], C);
+    if (c.lora) lora_fwd(c, P[TP_FF2_W], h3, M, 4 * C, C, ff3);
     c.gated_add(x4, ff3, nullptr, 1.f, nx, y);
     return S;
 }
 
 // g: dL/dy on entry, dL/dx on return (the running gradient of the residual stream). dobjs and G[slot] (fuser.* only) are written.
-static void block_backward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const BlockSaved& S, const float* objs, float* g, float* dobjs, float* const* G) {
+static void block_backward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const BlockSaved& S, const float* objs, float* g, float* dobjs, float* const* G,
+                           const float* context = nullptr) {
     hipStream_t s = c.s;
     const int B = d.B, N = d.N, Ng = d.Ng, C = d.C, H = d.heads, D = C / H, T = N + Ng, M = B * N, MT = B * T, KD = d.ctx_dim;
     const size_t nx = (size_t)M * C;
     {   // y = x4 + ff(norm3(x4)): frozen weights, data gradients only
         float* g_h3 = c.lin_dgrad(g, M, C, P[TP_FF2_W], 4 * C);
+        if (lora_find(c, P[TP_FF2_W])) lora_bwd(c, P[TP_FF2_W], g, c.geglu_fwd(S.u3, M, 4 * C), M, 4 * C, C, g_h3);     // (ff.net.2's input is not kept)
         float* g_u3 = c.geglu_bwd(g_h3, S.u3, M, 4 * C);
         float* g_n3 = c.lin_dgrad(g_u3, M, 8 * C, P[TP_FF1_W], C);
+        if (c.lora) lora_bwd(c, P[TP_FF1_W], g_u3, S.n3.y, M, C, 8 * C, g_n3);
         c.ln_bwd(g_n3, S.n3, P[TP_NORM3_W], M, C, g, true, nullptr, nullptr);
     }
     {   // x4 = x3 + attn2(norm2(x3), context): the context comes from the frozen text encoder, no dK / dV
         float* g_a2 = c.lin_dgrad(g, M, C, P[TP_A2_O], C);
+        if (c.lora) lora_bwd(c, P[TP_A2_O], g, S.a2.o, M, C, C, g_a2);
         float* g_q2 = c.f32(nx);
-        c.attn_bwd(D, S.q2, S.k2, S.v2, S.a2, g_a2, B, H, N, d.ctx_T, g_q2, nullptr, nullptr);
+        // adapters on to_k / to_v need dK / dV for their own gradients (weight gradients only: the context still has none)
+        const bool kv = lora_find(c, P[TP_A2_K]) || lora_find(c, P[TP_A2_V]);
+        const int MC = B * d.ctx_T;
+        float* g_k2 = kv ? c.f32((size_t)MC * C) : nullptr;
+        float* g_v2 = kv ? c.f32((size_t)MC * C) : nullptr;
+        c.attn_bwd(D, S.q2, S.k2, S.v2, S.a2, g_a2, B, H, N, d.ctx_T, g_q2, g_k2, g_v2);
+        if (kv) {
+            lora_bwd(c, P[TP_A2_K], g_k2, context, MC, KD, C, nullptr);
+            lora_bwd(c, P[TP_A2_V], g_v2, context, MC, KD, C, nullptr);
+        }
         float* g_n2 = c.lin_dgrad(g_q2, M, C, P[TP_A2_Q], C);
+        if (c.lora) lora_bwd(c, P[TP_A2_Q], g_q2, S.n2.y, M, C, C, g_n2);
         c.ln_bwd(g_n2, S.n2, P[TP_NORM2_W], M, C, g, true, nullptr, nullptr);
     }
     {   // x3 = x2 + g_d ff(norm2(x2)), g_d = scale tanh(alpha_dense): the fuser's feed-forward, TRAINABLE
@@ -233,6 +261,7 @@ static void block_backward(const Ctx& c, const TrainBlockDims& d, const float* c
     }
     {   // x1 = x + attn1(norm1(x)): frozen
         float* g_a1 = c.lin_dgrad(g, M, C, P[TP_A1_O], C);
+        if (c.lora) lora_bwd(c, P[TP_A1_O], g, S.a1.o, M, C, C, g_a1);
         float* g_q1 = c.f32(nx);
         float* g_k1 = c.f32(nx);
         float* g_v1 = c.f32(nx);
@@ -240,6 +269,11 @@ static void block_backward(const Ctx& c, const TrainBlockDims& d, const float* c
         float* g_n1 = c.lin_dgrad(g_q1, M, C, P[TP_A1_Q], C);
         c.add(g_n1, c.lin_dgrad(g_k1, M, C, P[TP_A1_K], C), nx);
         c.add(g_n1, c.lin_dgrad(g_v1, M, C, P[TP_A1_V], C), nx);
+        if (c.lora) {
+            lora_bwd(c, P[TP_A1_Q], g_q1, S.n1.y, M, C, C, g_n1);
+            lora_bwd(c, P[TP_A1_K], g_k1, S.n1.y, M, C, C, g_n1);
+            lora_bwd(c, P[TP_A1_V], g_v1, S.n1.y, M, C, C, g_n1);
+        }
         c.ln_bwd(g_n1, S.n1, P[TP_NORM1_W], M, C, g, true, nullptr, nullptr);
     }
 }
@@ -285,17 +319,25 @@ STSaved train::st_forward(const Ctx& c, const TrainBlockDims& d, const float* co
     STSaved S;
     S.n0 = c.gn_silu_fwd(x, B, N, C, P[ST_NORM_W], P[ST_NORM_B], false, 1e-6f);
     float* t0 = c.lin_fwd(S.n0.a, M, C, P[ST_PIN_W], P[ST_PIN_B], C);
+    if (c.lora) lora_fwd(c, P[ST_PIN_W], S.n0.a, M, C, C, t0);
     float* yb = c.f32(nx);
     S.blk = block_forward(c, d, P + ST_BLOCK0, t0, objs, context, yb);
+    S.yb = yb;
     float* po = c.lin_fwd(yb, M, C, P[ST_POUT_W], P[ST_POUT_B], C);
+    if (c.lora) lora_fwd(c, P[ST_POUT_W], yb, M, C, C, po);
     c.gated_add(x, po, nullptr, 1.f, nx, y);
     return S;
 }
-void train::st_backward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const STSaved& S, const float* objs, float* g, float* dobjs, float* const* G) {
+void train::st_backward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const STSaved& S, const float* objs, float* g, float* dobjs, float* const* G,
+                        const float* context) {
     const int B = d.B, N = d.N, C = d.C, M = B * N;
+    if (c.lora && !context && (lora_find(c, P[ST_BLOCK0 + TP_A2_K]) || lora_find(c, P[ST_BLOCK0 + TP_A2_V])))
+        throw GlError(GL_ERR_ARG, "st_backward: an adapter on attn2.to_k / to_v needs the context in the backward");
     float* g_b = c.lin_dgrad(g, M, C, P[ST_POUT_W], C);                              // through proj_out
-    block_backward(c, d, P + ST_BLOCK0, S.blk, objs, g_b, dobjs, G + ST_BLOCK0);     // g_b: dL/d(block output) -> dL/d(block input)
+    if (c.lora) lora_bwd(c, P[ST_POUT_W], g, S.yb, M, C, C, g_b);
+    block_backward(c, d, P + ST_BLOCK0, S.blk, objs, g_b, dobjs, G + ST_BLOCK0, context);     // g_b: dL/d(block output) -> dL/d(block input)
     float* g_a = c.lin_dgrad(g_b, M, C, P[ST_PIN_W], C);                             // through proj_in
+    if (c.lora) lora_bwd(c, P[ST_PIN_W], g_b, S.n0.a, M, C, C, g_a);
     c.gn_silu_bwd(g_a, S.n0, P[ST_NORM_W], P[ST_NORM_B], B, N, C, g, true, false);   // + the residual x_in: g already holds dL/dy
 }
 

@@ -119,6 +119,35 @@ void check_trainable_set(const TrainUNetCfg& cfg, int n_params, const char* cons
                                   "or both fp32 planes");
 }
 
+// The adapters of a step by the address of their base weight. An adapter is admitted by name: the frozen Linears of a
+// SpatialTransformer outside its fuser (the fuser's own Linears train in full); everything check_trainable_set refuses stays refused.
+LoraTable lora_table(const Names& nm, const TrainLoraAdapter* adapters, int n_adapters) {
+    static const char* const k_sites[] = {".attn1.to_q.weight", ".attn1.to_k.weight", ".attn1.to_v.weight", ".attn1.to_out.0.weight",
+                                          ".attn2.to_q.weight", ".attn2.to_k.weight", ".attn2.to_v.weight", ".attn2.to_out.0.weight",
+                                          ".ff.net.0.proj.weight", ".ff.net.2.weight", ".proj_in.weight", ".proj_out.weight"};
+    LoraTable t;
+    if (n_adapters < 0 || (n_adapters && !adapters)) throw GlError(GL_ERR_ARG, "unet_train_step: null adapter array");
+    for (int i = 0; i < n_adapters; ++i) {
+        const TrainLoraAdapter& a = adapters[i];
+        if (!a.name || !a.down || !a.up) throw GlError(GL_ERR_ARG, fmt("unet_train_step: adapter %d has a null name, down or up", i));
+        const std::string name = a.name;
+        bool site = false;
+        for (const char* sfx : k_sites) {
+            const size_t n = strlen(sfx);
+            site = site || (name.size() > n && !name.compare(name.size() - n, n, sfx));
+        }
+        const bool in_st = name.find(".transformer_blocks.0.") != std::string::npos || name.find(".proj_") != std::string::npos;
+        if (!site || !in_st || name.find(".fuser.") != std::string::npos)
+            throw GlError(GL_ERR_ARG, "unet_train_step: an adapter was given for '" + name + "': adapters go on attn1 / attn2 to_q, to_k, to_v, to_out.0, "
+                                      "ff.net.0.proj, ff.net.2 and proj_in / proj_out of a SpatialTransformer (the fuser's Linears train in full)");
+        if (a.rank < 1 || a.rank > 128) throw GlError(GL_ERR_ARG, fmt("unet_train_step: adapter '%s' has rank %d (1 <= r <= 128)", a.name, a.rank));
+        if (nm.g(name)) throw GlError(GL_ERR_ARG, "unet_train_step: '" + name + "' has an adapter and a gradient of its own");
+        if (!t.emplace(nm.w(name), LoraAdapter{a.down, a.up, a.g_down, a.g_up, a.rank, a.scale}).second)
+            throw GlError(GL_ERR_ARG, "unet_train_step: two adapters for '" + name + "'");
+    }
+    return t;
+}
+
 UNetStep step_dims(const Ctx& c, const Names& nm, const TrainUNetCfg& cfg, const TrainUNetIn& in, const TrainSpatialIn* spatial, const char* const* block_names) {
     UNetStep u{c, nm, cfg, in, spatial, block_names};
     u.B = in.B; u.H0 = in.H; u.W0 = in.W; u.mc = cfg.model_channels; u.ED = 4 * u.mc; u.KD = cfg.context_dim; u.Ng = in.Ng;
@@ -426,7 +455,7 @@ float* layers_backward(const UNetStep& u, std::vector<UNetLayer>& L, const float
             float* d_o = c.f32((size_t)u.MR * u.KD);
             const size_t mk = c.ar.mark();
             if (checkpoint) l.ss = st_forward(c, st_dims(u, l), l.P.data(), l.x_in, objs, u.in.context, c.f32(rows * l.Cout));
-            st_backward(c, st_dims(u, l), l.P.data(), l.ss, objs, g, d_o, l.G.data());      // g in place
+            st_backward(c, st_dims(u, l), l.P.data(), l.ss, objs, g, d_o, l.G.data(), u.in.context);      // g in place
             c.add(g_objs, d_o, (size_t)u.MR * u.KD);
             if (checkpoint) c.ar.release(mk);
             // this block's fuser gradients are final: the caller's communication stream may pick them up (gl_train_wait_grads)
@@ -444,7 +473,7 @@ float* layers_backward(const UNetStep& u, std::vector<UNetLayer>& L, const float
 
 int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& cfg, const TrainUNetIn& in, int n_params, const char* const* names,
                     const float* const* params, float* const* grads, const char* const* block_names, float* eps_out, float* loss, hipStream_t s, hipEvent_t* grad_events, int n_grad_events,
-                    TrainWeightCache* cache, const TrainSpatialIn* spatial) {
+                    TrainWeightCache* cache, const TrainSpatialIn* spatial, const TrainLoraAdapter* adapters, int n_adapters) {
     try {
         Names nm;
         nm.params = params;
@@ -459,6 +488,9 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
             c.wc = cache;
             c.frozen = &frozen;
         }
+        // the adapter tensors are read as fp32 by their own kernels: nothing of them enters the operand cache
+        const LoraTable lora = lora_table(nm, adapters, n_adapters);
+        if (!lora.empty()) c.lora = &lora;
         const UNetStep u = step_dims(c, nm, cfg, in, spatial, block_names);
         // ---- forward; every layer remembers what its backward needs
         PosBranch pb[2];

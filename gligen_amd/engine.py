@@ -1019,7 +1019,8 @@ class Engine:
         return int(n.value)
 
     def unet_train_step(self, cfg: Mapping, state_dict: Mapping[str, torch.Tensor], batch: Mapping[str, torch.Tensor], fuser_scale: float = 1.0,
-                        trainable=None, grads: Optional[Mapping[str, torch.Tensor]] = None, checkpoint: bool = False, use_weight_cache: bool = False):
+                        trainable=None, grads: Optional[Mapping[str, torch.Tensor]] = None, checkpoint: bool = False, use_weight_cache: bool = False,
+                        adapters=None):
         """One training iteration of the reference (trainer.py:353-392: model(input), mse_loss(model_output, noise), backward) on the
         device (gl_unet_train_step). cfg: UNetModel kwargs -- any tokenizer; cfg["fuser_type"] gatedSA (default), gatedSA2 (a square number
         of grounding tokens and H == W) or gatedCA (no fuser.linear.* keys) --; state_dict: the model's parameters (fp32, on this
@@ -1039,7 +1040,12 @@ class Engine:
         trainable set (train.trainable_names: trainer.py:189-245) or the `trainable` names given; `grads`: buffers to
         write into instead of fresh ones (every entry is overwritten); `checkpoint`: keep only block inputs / outputs and recompute each block's
         forward in its backward (the same gradients bit for bit, a fraction of the arena); `use_weight_cache`: keep / reuse the bf16
-        operand copies of the tensors no gradient is asked for (train_weight_cache: only when those tensors never change)."""
+        operand copies of the tensors no gradient is asked for (train_weight_cache: only when those tensors never change).
+        `adapters` (gl_unet_train_step_lora; discrete tokenizers): LoRA adapters in training, a sequence of mappings with name (the
+        state_dict key of a frozen Linear's weight: gligen_amd.lora_train.adapter_sites), down [r, K], up [N, r], scale and optionally
+        g_down / g_up, fp32 tensors on this device used in place; gradients that are not given are created. The layer computes
+        x W^T + scale (x down^T) up^T. The adapters' gradients come back as a fourth value, {name: (g_down, g_up)}; `trainable=[]`
+        trains the adapters alone."""
         dev = self.device
         c = UNetConfig()
         c.in_channels, c.out_channels, c.model_channels = cfg["in_channels"], cfg["out_channels"], cfg["model_channels"]
@@ -1051,6 +1057,8 @@ class Engine:
         for i, v in enumerate(cfg["attention_resolutions"]):
             c.attention_resolutions[i] = int(v)
         sp = spatial_train_config(cfg)          # a spatial-map tokenizer (canny / depth / normal / hed / sem_grounding_net.py)?
+        if sp and adapters is not None:
+            raise ValueError("unet_train_step: adapters are trained on the discrete-tokenizer models (text, text+image, keypoint)")
         ti = sp is None and "image_embeddings" in batch     # the text+image tokenizer (text_image_grounding_net.py)
         kp = sp is None and "points" in batch               # the keypoint tokenizer (keypoint_grounding_net.py); else the text tokenizer
         c.grounding_kind, c.fuser_kind = (3 if sp else 1 if ti else 2 if kp else 0), _lib.fuser_kind(cfg.get("fuser_type", "gatedSA"))
@@ -1137,8 +1145,34 @@ class Engine:
                              keep["ctx"].data_ptr(), keep["boxes"].data_ptr(), keep["masks"].data_ptr(), None if kp else keep["pe"].data_ptr(), keep["target"].data_ptr(),
                              float(fuser_scale), keep["tm"].data_ptr() if ti else None, keep["im"].data_ptr() if ti else None,
                              keep["ie"].data_ptr() if ti else None, int(bool(checkpoint)), int(bool(use_weight_cache)))
+        if adapters is not None:
+            aarr, agrads = self._lora_adapters(adapters, state_dict)
+            check(self.lib.gl_unet_train_step_lora(self._ctx, C.byref(c), C.byref(u), n, narr, parr, garr, aarr, len(aarr), _ptr(eps), _ptr(loss), _stream(dev)))
+            return loss, eps.reshape(B, H, W, c.out_channels).permute(0, 3, 1, 2).contiguous(), grads, agrads
         check(self.lib.gl_unet_train_step(self._ctx, C.byref(c), C.byref(u), n, narr, parr, garr, _ptr(eps), _ptr(loss), _stream(dev)))
         return loss, eps.reshape(B, H, W, c.out_channels).permute(0, 3, 1, 2).contiguous(), grads
+
+    def _lora_adapters(self, adapters, state_dict):
+        """The gl_lora_adapter array of unet_train_step's `adapters`, and {name: (g_down, g_up)}."""
+        dev = torch.device(self.device)
+        arr = (_lib.LoraAdapter * len(adapters))()
+        agrads = {}
+        for i, a in enumerate(adapters):
+            name, down, up = a["name"], a["down"], a["up"]
+            if name not in state_dict:
+                raise ValueError(f"unet_train_step: adapter for '{name}', which is not in the state_dict")
+            w = state_dict[name]
+            N, r = int(w.shape[0]), int(down.shape[0])
+            K = w.numel() // N
+            g_down = a.get("g_down") if a.get("g_down") is not None else torch.zeros_like(down)
+            g_up = a.get("g_up") if a.get("g_up") is not None else torch.zeros_like(up)
+            for what, t, shape in (("down", down, (r, K)), ("up", up, (N, r)), ("g_down", g_down, (r, K)), ("g_up", g_up, (N, r))):
+                if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
+                    raise ValueError(f"unet_train_step: adapter '{name}': {what} is a contiguous fp32 tensor of shape {shape} on {self.device}; got "
+                                     f"{tuple(t.shape)} {t.dtype} on {t.device}")
+            arr[i] = _lib.LoraAdapter(name.encode(), down.data_ptr(), up.data_ptr(), g_down.data_ptr(), g_up.data_ptr(), r, float(a["scale"]))
+            agrads[name] = (g_down, g_up)
+        return arr, agrads
 
     def train_step_inputs(self, z: torch.Tensor, noise: torch.Tensor, timesteps: torch.Tensor, schedule, *, boxes: Optional[torch.Tensor] = None,
                           mask: Optional[torch.Tensor] = None, inpaint: bool = False) -> Dict[str, torch.Tensor]:
@@ -1435,6 +1469,35 @@ class Engine:
         o = self._prim_outs({"out": (1,)}, out, required=("out",))
         check(self.lib.gl_op_train_dot(self._ctx, int(a.numel()), _ptr(a), _ptr(b), _ptr(alpha), C.c_float(scale), int(mode), _ptr(o["out"]), _stream(dev)))
         return o
+
+    # ---- include/gligen_amd_train_lora.h: the low-rank part of one adapted Linear by itself
+    def op_lora_linear(self, x, down, up, scale=1.0, dy=None, down_kr=False, up_rn=False, out=None):
+        """gl_op_lora_linear: x [M, K]; down [r, K] (down_kr: [K, r]); up [N, r] (up_rn: [r, N]). t [M, r] = x down^T and
+        y [M, N] += scale t up^T; with dy [M, N] also u [M, r] = dy up, dx [M, K] += scale u down, g_down = scale u^T x and
+        g_up = scale dy^T t in the layouts of down and up. y and dx are accumulated into: they come in through `out` (out=None starts
+        them at zero)."""
+        dev = self.device
+        x, down, up = (_f32(t, dev) for t in (x, down, up))
+        dy = None if dy is None else _f32(dy, dev)
+        M, K = x.shape
+        r = int(down.shape[1] if down_kr else down.shape[0])
+        N = int(up.shape[1] if up_rn else up.shape[0])
+        if tuple(down.shape) != ((K, r) if down_kr else (r, K)) or tuple(up.shape) != ((r, N) if up_rn else (N, r)) or (dy is not None and dy.shape != (M, N)):
+            raise ValueError("op_lora_linear: x [M, K], down [r, K] (down_kr: [K, r]), up [N, r] (up_rn: [r, N]), dy [M, N]")
+        shapes = {"t": (M, r), "y": (M, N)}
+        if dy is not None:
+            shapes.update(u=(M, r), dx=(M, K), g_down=tuple(down.shape), g_up=tuple(up.shape))
+        if out is None:
+            o = {k: torch.zeros(shape, device=dev, dtype=torch.float32) for k, shape in shapes.items()}
+        else:
+            o = self._prim_outs(shapes, out)
+        check(self.lib.gl_op_lora_linear(self._ctx, int(M), int(K), int(N), r, C.c_float(scale), int(bool(down_kr)), int(bool(up_rn)), _ptr(x), _ptr(down),
+                                         _ptr(up), _ptr(dy), *[_ptr(o.get(n)) for n in ("t", "y", "u", "dx", "g_down", "g_up")], _stream(dev)))
+        return o
+
+    def lora_wgrad_chunk_rows(self, M: int) -> int:
+        """Rows per partial sum of the low-rank weight-gradient kernel over M rows (gl_lora_wgrad_chunk_rows)."""
+        return int(self.lib.gl_lora_wgrad_chunk_rows(int(M)))
 
     def op_conv3x3(self, x0, w_oihw, bias, x1=None, stride=1, ups=0, pad_lo=1, res=None):
         B, H, W, C0 = x0.shape

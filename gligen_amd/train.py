@@ -217,8 +217,7 @@ class TrainStep:
         """One iteration: forward, loss, backward, gradient average over the ranks, AdamW. Returns (loss of this rank, eps)."""
         if self.drop_prob > 0.0 and self.rng.random() < self.drop_prob:      # random drop for guidance (openaimodel.py:428)
             batch = null_grounding(batch)
-        kw = dict(use_weight_cache=True) if self.cache_frozen else {}
-        loss, eps, _ = self.engine.unet_train_step(self.cfg, self.params, batch, fuser_scale=fuser_scale, grads=self.gbuf.views, checkpoint=self.checkpoint, **kw)
+        loss, eps = self._forward_backward(batch, fuser_scale)
         self.steps += 1
         lr = self.lr_at(self.steps)
         if self.ema is None:
@@ -247,6 +246,12 @@ class TrainStep:
                     self.gbuf.all_reduce_bucket(i, average=True, even_alone=alone)
                     upd(i)
             main.wait_stream(self._comm)            # the next forward reads the updated parameters
+        return loss, eps
+
+    def _forward_backward(self, batch, fuser_scale):
+        """Forward, loss and backward into the gradient buckets: (loss, eps). (gligen_amd.lora_train.LoraTrainStep passes its adapters.)"""
+        kw = dict(use_weight_cache=True) if self.cache_frozen else {}
+        loss, eps, _ = self.engine.unet_train_step(self.cfg, self.params, batch, fuser_scale=fuser_scale, grads=self.gbuf.views, checkpoint=self.checkpoint, **kw)
         return loss, eps
 
     def state_dict(self) -> Dict[str, torch.Tensor]:

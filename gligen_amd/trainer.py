@@ -14,7 +14,11 @@ state), which the reference ignores and which makes a resumed run continue bit f
     python -m gligen_amd.trainer --synthetic text --total_iters 20 --enable_ema true --output_dir out
 
 runs on gligen_amd.synthetic weights and batches (no checkpoints or datasets exist offline), prints one line per logged iteration,
-writes the checkpoints and, started again, continues from out/checkpoint_latest.pth."""
+writes the checkpoints and, started again, continues from out/checkpoint_latest.pth.
+
+With lora_rank in the config (--lora_rank, --lora_alpha, --lora_families, --lora_out) the run trains LoRA adapters over the frozen
+model instead (gligen_amd.lora_train.LoraTrainStep; lora_train_base: and the reference's set with them): the checkpoint carries the
+adapter tensors under `lora` next to their optimizer state, and lora_out is rewritten in kohya's format at every save point."""
 from __future__ import annotations
 
 import argparse
@@ -126,10 +130,21 @@ class Trainer:
             raise ValueError(f"scheduler_type {stype!r}: constant or cosine (trainer.py:262-267)")
         self.cosine_total = self.total_iters if stype == "cosine" else None
         self.enable_ema = bool(self.config.get("enable_ema", False))
-        self.ts = TrainStep(engine, cfg, sd, lr=warmup_schedule(self.base_lr, self.warmup_steps, self.cosine_total),
-                            weight_decay=float(self.config.get("weight_decay", 0.0)), bucket_mb=bucket_mb, world=world, checkpoint=checkpoint,
-                            drop_prob=drop_prob, rng=random.Random(seed), overlap=overlap,
-                            ema_rate=float(self.config.get("ema_rate", 0.9999)) if self.enable_ema else None)
+        self.lora_rank = int(self.config.get("lora_rank") or 0)
+        if self.lora_rank:
+            from .lora_train import LoraSpec, LoraTrainStep
+            if self.enable_ema:
+                raise ValueError("Trainer: no EMA is kept of LoRA adapters (enable_ema with lora_rank)")
+            spec = LoraSpec(self.lora_rank, self.config.get("lora_alpha"), tuple(self.config.get("lora_families") or ("attn",)))
+            self.ts = LoraTrainStep(engine, cfg, sd, spec, lr=warmup_schedule(self.base_lr, self.warmup_steps, self.cosine_total),
+                                    weight_decay=float(self.config.get("weight_decay", 0.0)), bucket_mb=bucket_mb, world=world, checkpoint=checkpoint,
+                                    drop_prob=drop_prob, rng=random.Random(seed), overlap=overlap, train_base=bool(self.config.get("lora_train_base", False)),
+                                    seed=seed)
+        else:
+            self.ts = TrainStep(engine, cfg, sd, lr=warmup_schedule(self.base_lr, self.warmup_steps, self.cosine_total),
+                                weight_decay=float(self.config.get("weight_decay", 0.0)), bucket_mb=bucket_mb, world=world, checkpoint=checkpoint,
+                                drop_prob=drop_prob, rng=random.Random(seed), overlap=overlap,
+                                ema_rate=float(self.config.get("ema_rate", 0.9999)) if self.enable_ema else None)
         self.generator = torch.Generator(device=dev).manual_seed(int(seed) + self.rank)
         self.grounding_tokenizer_input = instantiate_from_config(self.config.get("grounding_tokenizer_input") or _plugin(kind, "tokinzer_input.GroundingNetInput"))
         self.grounding_downsampler_input = None
@@ -208,6 +223,8 @@ class Trainer:
                 ckpt[name] = cpu(mod.state_dict())
         if self.enable_ema:
             ckpt["ema"] = cpu(self.ts.ema_state_dict())
+        if self.lora_rank:
+            ckpt["lora"] = cpu(self.ts.adapter_tensors())
         ckpt["rng"] = dict(device=self.generator.get_state().cpu(), python=self.ts.rng.getstate(), torch_cpu=torch.get_rng_state())
         return ckpt
 
@@ -231,6 +248,10 @@ class Trainer:
         except OSError:
             shutil.copyfile(numbered, latest + ".tmp")
         os.replace(latest + ".tmp", latest)
+        if self.lora_rank and self.config.get("lora_out"):
+            out = self.config["lora_out"]
+            self.ts.save_adapter(out + ".tmp", dtype=torch.float32 if self.config.get("lora_dtype", "fp16") == "fp32" else torch.float16)
+            os.replace(out + ".tmp", out)
         return latest
 
     def load(self, path: str) -> None:
@@ -238,6 +259,10 @@ class Trainer:
         the file has it. The optimizer's step count becomes `iters`, which positions the LR schedule."""
         ckpt = read_checkpoint(path)
         self.ts.load_state_dict(ckpt["model"])
+        if self.lora_rank:
+            if "lora" not in ckpt:
+                raise ValueError(f"{path} carries no adapters (`lora`): it was written by a run without lora_rank")
+            self.ts.load_adapter_tensors(ckpt["lora"])
         self.ts.load_torch_optimizer_state_dict(ckpt["opt"])
         if self.enable_ema:
             self.ts.load_ema_state_dict(ckpt["ema"])
@@ -380,6 +405,10 @@ def main(argv=None) -> int:
     ap.add_argument("--save_every_iters", type=int, default=5000)
     ap.add_argument("--enable_ema", type=_bool, default=False)
     ap.add_argument("--ema_rate", type=float, default=0.9999)
+    ap.add_argument("--lora_rank", type=int, default=0, help="train LoRA adapters of this rank over the frozen model instead of the reference's set")
+    ap.add_argument("--lora_alpha", type=float, default=None, help="the adapters' alpha (default: the rank)")
+    ap.add_argument("--lora_families", nargs="+", default=["attn"], choices=["attn", "ff", "proj"])
+    ap.add_argument("--lora_out", default=None, help="the adapter in kohya's format (.safetensors), rewritten at every save point; default output_dir/lora.safetensors")
     ap.add_argument("--resume", action="store_true", help="continue from output_dir/checkpoint_latest.pth (also the default when that file exists)")
     ap.add_argument("--fresh", action="store_true", help="start from iteration 0 even if output_dir holds a checkpoint")
     ap.add_argument("--seed", type=int, default=123)
@@ -393,6 +422,9 @@ def main(argv=None) -> int:
     config = dict(model=cfg, base_learning_rate=a.base_learning_rate, weight_decay=a.weight_decay, warmup_steps=a.warmup_steps, scheduler_type=a.scheduler_type,
                   total_iters=a.total_iters, enable_ema=a.enable_ema, ema_rate=a.ema_rate, inpaint_mode=a.inpaint, save_every_iters=a.save_every_iters,
                   output_dir=a.output_dir, ckpt=None, batch_size=a.batch_size, seed=a.seed, disable_inference_in_training=True)
+    if a.lora_rank:
+        config.update(lora_rank=a.lora_rank, lora_alpha=a.lora_alpha, lora_families=list(a.lora_families),
+                      lora_out=a.lora_out or os.path.join(a.output_dir, "lora.safetensors"))
     latest = os.path.join(a.output_dir, "checkpoint_latest.pth")
     if a.resume and not os.path.exists(latest):
         print(f"--resume: {latest} does not exist", file=sys.stderr)
