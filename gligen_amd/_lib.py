@@ -1,6 +1,6 @@
 """ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
 include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h, include/gligen_amd_train_fusers.h, include/gligen_amd_train_prims.h,
-include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_ffn_rows.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h, include/gligen_amd_lora.h, include/gligen_amd_tiling.h and include/gligen_amd_train_lora.h).
+include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_ffn_rows.h, include/gligen_amd_norm.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h, include/gligen_amd_lora.h, include/gligen_amd_tiling.h and include/gligen_amd_train_lora.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -310,6 +310,17 @@ FFN_ROWS_SYMBOLS = {
     "gl_op_qkv_rows": (_I, [_P, C.POINTER(QkvRowsArgs), _P]),
 }
 
+class LayerNormRowsArgs(C.Structure):   # = gl_layernorm_rows_args
+    _fields_ = [("struct_size", C.c_uint), ("x", _P), ("x2", _P), ("B", _I), ("N1", _I), ("N2", _I), ("Tpad", _I), ("C", _I), ("eps", C.c_float),
+                ("gamma", _P), ("beta", _P), ("y", _P), ("ldx", _I), ("ldy", _I)]
+
+
+# every symbol include/gligen_amd_norm.h declares (the statistics-only GroupNorm and the strided LayerNorm on the caller's buffers)
+NORM_SYMBOLS = {
+    "gl_op_groupnorm_coef": (_I, [_P, _P, _I, _P, _I, _I, _I, _P, _P, C.c_float, _P, C.POINTER(_I), _P]),
+    "gl_op_layernorm_rows": (_I, [_P, C.POINTER(LayerNormRowsArgs), _P]),
+}
+
 # every symbol include/gligen_amd_vae.h declares (the form of the autoencoder's attention, and the operator by itself)
 VAE_SYMBOLS = {
     "gl_vae_set_attention": (_I, [_P, _I]),
@@ -374,7 +385,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS, **TRAIN_PRIM_SYMBOLS,
-                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **FFN_ROWS_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS, **TILING_SYMBOLS, **TRAIN_LORA_SYMBOLS}.items():
+                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **FFN_ROWS_SYMBOLS, **NORM_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS, **TILING_SYMBOLS, **TRAIN_LORA_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

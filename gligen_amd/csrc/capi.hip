@@ -17,6 +17,7 @@
 #include "../../include/gligen_amd_gemm_plans.h"
 #include "../../include/gligen_amd_attention_core.h"
 #include "../../include/gligen_amd_ffn_rows.h"
+#include "../../include/gligen_amd_norm.h"
 #include "../../include/gligen_amd_vae.h"
 #include "../../include/gligen_amd_latent.h"
 #include "../../include/gligen_amd_lora.h"
@@ -1311,9 +1312,23 @@ int gl_op_gn_silu_conv3x3(gl_ctx* ctx, const void* x0, int C0, const void* x1, i
     GL_API_END
 }
 
+static bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
+
+// what gl_op_groupnorm and gl_op_groupnorm_coef refuse before anything is allocated or launched: the kernels read x0, x1 and y in
+// 16-byte pieces and gamma / beta as float4
+static int groupnorm_args(const char* who, const void* x0, int C0, const void* x1, int C1, int B, int HW, const float* gamma, const float* beta,
+                          const void* out) {
+    if (!x0 || !gamma || !beta || !out || (C1 > 0 && !x1)) return gl::set_error(GL_ERR_ARG, "%s: null pointer", who);
+    if (C0 < 0 || C1 < 0 || B < 1 || B > 65535 || HW < 1) return gl::set_error(GL_ERR_ARG, "%s: C0=%d C1=%d B=%d HW=%d", who, C0, C1, B, HW);
+    if (!aligned_to(x0, 16) || (C1 > 0 && !aligned_to(x1, 16)) || !aligned_to(gamma, 16) || !aligned_to(beta, 16) || !aligned_to(out, 16))
+        return gl::set_error(GL_ERR_ARG, "%s: x0, x1, gamma, beta and the output must be 16-byte aligned", who);
+    return GL_OK;
+}
+
 int gl_op_groupnorm(gl_ctx* ctx, const void* x0, int C0, const void* x1, int C1, int B, int HW,
                     const float* gamma, const float* beta, float eps, int silu, void* y, gl_stream s) {
     NEED(ctx);
+    if (int rc = groupnorm_args("gl_op_groupnorm", x0, C0, x1, C1, B, HW, gamma, beta, y)) return rc;
     GL_API_BEGIN
     Arena& ar = ctx->eng->arena();
     ar.reset();
@@ -1326,6 +1341,25 @@ int gl_op_groupnorm(gl_ctx* ctx, const void* x0, int C0, const void* x1, int C1,
     GL_API_END
 }
 
+// include/gligen_amd_norm.h: the statistics-only GroupNorm into the caller's coefficient buffer
+int gl_op_groupnorm_coef(gl_ctx* ctx, const void* x0, int C0, const void* x1, int C1, int B, int HW, const float* gamma, const float* beta,
+                         float eps, float* coef, int* launches, gl_stream s) {
+    NEED(ctx);
+    if (!coef) return gl::set_error(GL_ERR_ARG, "gl_op_groupnorm_coef: no coefficient buffer");
+    if (int rc = groupnorm_args("gl_op_groupnorm_coef", x0, C0, x1, C1, B, HW, gamma, beta, coef)) return rc;
+    GL_API_BEGIN
+    Arena& ar = ctx->eng->arena();
+    ar.reset();
+    GNParams P{};
+    P.x0 = (const bf16*)x0; P.C0 = C0; P.x1 = (const bf16*)x1; P.C1 = C1; P.B = B; P.HW = HW; P.eps = eps;
+    P.gamma = gamma; P.beta = beta; P.coef = coef;
+    P.partial = reinterpret_cast<float*>(ar.alloc(gn_partial_bytes(B, HW)));
+    int r = groupnorm_coef_launch(P, S(s));
+    if (r != GL_OK) throw GlError(r, gl::last_error());
+    if (launches) *launches = groupnorm_coef_launches(HW, C0, C1);
+    GL_API_END
+}
+
 int gl_op_layernorm(gl_ctx* ctx, const void* x, const void* x2, int B, int N1, int N2, int Tpad, int C,
                     const float* gamma, const float* beta, float eps, void* y, gl_stream s) {
     NEED(ctx);
@@ -1333,6 +1367,28 @@ int gl_op_layernorm(gl_ctx* ctx, const void* x, const void* x2, int B, int N1, i
     LNParams P{};
     P.x = (const bf16*)x; P.x2 = (const bf16*)x2; P.B = B; P.N1 = N1; P.N2 = N2; P.Tpad = Tpad; P.C = C; P.eps = eps;
     P.gamma = gamma; P.beta = beta; P.y = (bf16*)y;
+    int r = layernorm_launch(P, S(s));
+    if (r != GL_OK) throw GlError(r, gl::last_error());
+    GL_API_END
+}
+
+// include/gligen_amd_norm.h: ln_kernel with every field of LNParams the caller's (row strides, the no-affine form)
+int gl_op_layernorm_rows(gl_ctx* ctx, const gl_layernorm_rows_args* a, gl_stream s) {
+    NEED(ctx);
+    if (!a) return gl::set_error(GL_ERR_ARG, "gl_op_layernorm_rows: null args");
+    if (a->struct_size != sizeof(gl_layernorm_rows_args))
+        return gl::set_error(GL_ERR_ARG, "gl_op_layernorm_rows: args->struct_size is %u, this library's gl_layernorm_rows_args has %zu bytes",
+                             a->struct_size, sizeof(gl_layernorm_rows_args));
+    if (a->B < 1 || a->N1 < 0 || a->N2 < 0 || a->Tpad < 1 || a->C < 8)
+        return gl::set_error(GL_ERR_ARG, "gl_op_layernorm_rows: B=%d N1=%d N2=%d Tpad=%d C=%d", a->B, a->N1, a->N2, a->Tpad, a->C);
+    if (!a->y || (a->N1 > 0 && !a->x) || (a->N2 > 0 && !a->x2)) return gl::set_error(GL_ERR_ARG, "gl_op_layernorm_rows: null pointer");
+    if ((a->gamma == nullptr) != (a->beta == nullptr)) return gl::set_error(GL_ERR_ARG, "gl_op_layernorm_rows: gamma and beta come together");
+    if (!aligned_to(a->x, 16) || !aligned_to(a->x2, 16) || !aligned_to(a->y, 16) || !aligned_to(a->gamma, 16) || !aligned_to(a->beta, 16))
+        return gl::set_error(GL_ERR_ARG, "gl_op_layernorm_rows: x, x2, y, gamma and beta must be 16-byte aligned");
+    GL_API_BEGIN
+    LNParams P{};
+    P.x = (const bf16*)a->x; P.x2 = (const bf16*)a->x2; P.B = a->B; P.N1 = a->N1; P.N2 = a->N2; P.Tpad = a->Tpad; P.C = a->C; P.eps = a->eps;
+    P.gamma = a->gamma; P.beta = a->beta; P.y = (bf16*)a->y; P.ldx = a->ldx; P.ldy = a->ldy;
     int r = layernorm_launch(P, S(s));
     if (r != GL_OK) throw GlError(r, gl::last_error());
     GL_API_END
@@ -1529,7 +1585,6 @@ int gl_op_proj_attention(gl_ctx* ctx, const void* x, int B, int N, int C, int H,
 // include/gligen_amd_ffn_rows.h: the row-local kernels on the caller's buffers, every field of their parameter blocks the caller's.
 // Folding and packing as gl_op_feedforward / gl_op_ff_chain / gl_op_ff_chain_q / gl_op_proj_attention do them; no other kernel
 // stands in where the row-local one refuses.
-static bool aligned_to(const void* p, uintptr_t a) { return (reinterpret_cast<uintptr_t>(p) & (a - 1)) == 0; }
 
 int gl_op_ff_rows(gl_ctx* ctx, const gl_ff_rows_args* a, gl_stream s) {
     NEED(ctx);

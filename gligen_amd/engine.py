@@ -1594,6 +1594,21 @@ class Engine:
         from ._lib import QkvRowsArgs
         self._rows_call(self.lib.gl_op_qkv_rows, QkvRowsArgs, fields)
 
+    def op_groupnorm_coef(self, x0, C0, gamma, beta, eps, coef, x1=None, C1=0, B=None, HW=None):
+        """The statistics-only GroupNorm on the caller's buffers (gl_op_groupnorm_coef; include/gligen_amd_norm.h): writes coef
+        [B][(C0 + C1) / 8][16] floats and returns the number of kernel launches. x0 [B][HW][C0] (B, HW from its shape unless given)."""
+        B, HW = (x0.shape[0] if B is None else B), (x0.shape[1] if HW is None else HW)
+        launches = C.c_int(0)
+        check(self.lib.gl_op_groupnorm_coef(self._ctx, _ptr(x0), C0, _ptr(x1), C1, B, HW, _ptr(gamma), _ptr(beta), C.c_float(eps), _ptr(coef),
+                                            C.byref(launches), _stream(self.device)))
+        return launches.value
+
+    def op_layernorm_rows(self, **fields):
+        """ln_kernel on the caller's buffers (gl_op_layernorm_rows; include/gligen_amd_norm.h), fields as in op_ff_rows: the members of
+        gl_layernorm_rows_args by name (ldx, ldy, null gamma / beta and the caller's y among them)."""
+        from ._lib import LayerNormRowsArgs
+        self._rows_call(self.lib.gl_op_layernorm_rows, LayerNormRowsArgs, fields)
+
     def _rows_call(self, fn, struct, fields):
         names = {n for n, _ in struct._fields_}
         unknown = set(fields) - names
