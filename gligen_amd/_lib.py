@@ -271,8 +271,17 @@ class AttnProjLayout(C.Structure):   # = gl_attn_proj_layout
     _fields_ = [(n, C.c_int) for n in ("d", "dp", "dpv", "tq", "tk", "tq_pad", "tk_pad", "vt_perm32")]
 
 
+class GemmEpilogueArgs(C.Structure):   # = gl_gemm_epilogue_args
+    _fields_ = [("struct_size", C.c_uint), ("conv", _I), ("M", _I), ("N", _I), ("K", _I), ("x0", _P), ("x1", _P)] + \
+               [(n, _I) for n in ("C0", "C1", "B", "H", "W", "stride", "ups", "pad_lo")] + \
+               [("w", _P), ("bias", _P), ("bias2", _P), ("bias2_ld", _I), ("rows_per_b", _I), ("res", _P), ("ldres", _I), ("gate", _P)] + \
+               [(n, _I) for n in ("act", "out_f32", "mode", "n_real", "remap_in", "remap_out", "remap_off")] + [("out", _P), ("ldo", _I)]
+
+
 # every symbol include/gligen_amd_gemm_plans.h declares (one named GEMM plan at a time, and the log of what ran)
 GEMM_PLAN_SYMBOLS = {
+    "gl_op_attention_project_range": (_I, [_P, _P, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, C.POINTER(AttnProjLayout), _P]),
+    "gl_op_gemm_epilogue": (_I, [_P, C.POINTER(GemmEpilogueArgs), _P]),
     "gl_gemm_force_plan": (_I, [_I, _I, _I, _I]),
     "gl_gemm_force_knobs": (_I, [_I, _I, _I, _I, _I, _I]),
     "gl_gemm_force_clear": (_I, []),

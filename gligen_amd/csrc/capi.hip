@@ -1483,6 +1483,80 @@ int gl_op_attention_project(gl_ctx* ctx, const void* xq, const void* xkv, int B,
     GL_API_END
 }
 
+// include/gligen_amd_gemm_plans.h: the second token range of existing q, k, v^T buffers (the launch of Engine::fuser_kv_fill)
+int gl_op_attention_project_range(gl_ctx* ctx, const void* x, int B, int Tr, int tok_off, int C, int H, const float* wq, const float* wk,
+                                  const float* wv, const float* bias, void* q, void* k, void* vt, const gl_attn_proj_layout* layout, gl_stream s) {
+    NEED(ctx);
+    if (!x || !wq || !wk || !wv || !q || !k || !vt || !layout) return gl::set_error(GL_ERR_ARG, "gl_op_attention_project_range: null pointer");
+    if (B < 1 || Tr < 64 || Tr % 64 || tok_off < 0 || tok_off % 64 || H <= 0 || C % H != 0 || layout->d != C / H)
+        return gl::set_error(GL_ERR_ARG, "gl_op_attention_project_range: B=%d Tr=%d tok_off=%d C=%d H=%d d=%d (Tr, tok_off multiples of 64, d = C / H)", B, Tr, tok_off, C, H, layout->d);
+    if (tok_off + Tr > layout->tq_pad || tok_off + Tr > layout->tk_pad)
+        return gl::set_error(GL_ERR_ARG, "gl_op_attention_project_range: tokens [%d, %d) do not fit tq_pad=%d / tk_pad=%d", tok_off, tok_off + Tr, layout->tq_pad, layout->tk_pad);
+    GL_API_BEGIN
+    Engine& eng = *ctx->eng;
+    int dp, dpv;
+    int r = attn_dims(layout->d, &dp, &dpv);
+    if (r != GL_OK) throw GlError(r, gl::last_error());
+    if (dp != layout->dp || layout->dpv < layout->d) throw GlError(GL_ERR_ARG, "gl_op_attention_project_range: layout->dp / dpv are not this head size's");
+    Arena& ar = eng.arena();
+    ar.reset();
+    auto ck = [&](int rc) { if (rc != GL_OK) throw GlError(rc, gl::last_error()); };
+    bf16* wqkv = ar.get<bf16>((size_t)3 * C * C);
+    ck(cast_f32_bf16_launch(wq, wqkv, (int64_t)C * C, S(s)));
+    ck(cast_f32_bf16_launch(wk, wqkv + (size_t)C * C, (int64_t)C * C, S(s)));
+    ck(cast_f32_bf16_launch(wv, wqkv + (size_t)2 * C * C, (int64_t)C * C, S(s)));
+    Epilogue E = e_heads(EPI_QKV_HEADS, (bf16*)q, (bf16*)k, C, H, layout->d, dp, Tr, layout->tq_pad, layout->tk_pad);
+    E.vt = (bf16*)vt; E.DPV = layout->dpv; E.tok_off = tok_off; E.vt_perm32 = layout->vt_perm32;
+    E.bias = bias;
+    ck(gemm_launch(a_rows((const bf16*)x, C), wqkv, B * Tr, 3 * C, C, E, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s)));
+    GL_API_END
+}
+
+// include/gligen_amd_gemm_plans.h: one gemm_launch with the epilogue the caller describes
+int gl_op_gemm_epilogue(gl_ctx* ctx, const gl_gemm_epilogue_args* a, gl_stream s) {
+    NEED(ctx);
+    if (!a) return gl::set_error(GL_ERR_ARG, "gl_op_gemm_epilogue: null args");
+    if (a->struct_size != sizeof(gl_gemm_epilogue_args))
+        return gl::set_error(GL_ERR_ARG, "gl_op_gemm_epilogue: args->struct_size is %u, this library's gl_gemm_epilogue_args has %zu bytes", a->struct_size,
+                             sizeof(gl_gemm_epilogue_args));
+    if (!a->x0 || !a->w || !a->out || (a->C1 && !a->x1)) return gl::set_error(GL_ERR_ARG, "gl_op_gemm_epilogue: null pointer (x0, w, out; x1 when C1 > 0)");
+    GL_API_BEGIN
+    Engine& eng = *ctx->eng;
+    Arena& ar = eng.arena();
+    ar.reset();
+    AOperand A{};
+    const bf16* w = (const bf16*)a->w;
+    int M = a->M, K = a->K;
+    if (a->conv) {
+        const int Cin = a->C0 + a->C1;
+        if (a->N < 1 || Cin < 1 || a->B < 1 || a->H < 1 || a->W < 1 || a->ups < 0 || a->ups > 1 || (a->stride != 1 && a->stride != 2))
+            throw GlError(GL_ERR_ARG, "gl_op_gemm_epilogue: conv geometry");
+        bf16* wp = ar.get<bf16>((size_t)a->N * 9 * Cin);
+        int r = pack_conv_weight_launch((const float*)a->w, wp, a->N, Cin, 3, 3, a->N, S(s));
+        if (r != GL_OK) throw GlError(r, gl::last_error());
+        w = wp;
+        const int Hup = a->H << a->ups, Wup = a->W << a->ups;
+        const int Ho = a->stride == 1 ? Hup : (a->pad_lo ? (Hup + 2 - 3) / 2 + 1 : (Hup + 1 - 3) / 2 + 1);
+        const int Wo = a->stride == 1 ? Wup : (a->pad_lo ? (Wup + 2 - 3) / 2 + 1 : (Wup + 1 - 3) / 2 + 1);
+        A.p0 = (const bf16*)a->x0; A.C0 = a->C0; A.ld0 = a->C0; A.p1 = (const bf16*)a->x1; A.C1 = a->C1; A.ld1 = a->C1;
+        A.mode = A_CONV3; A.Hin = a->H; A.Win = a->W; A.Ho = Ho; A.Wo = Wo; A.stride = a->stride; A.ups = a->ups; A.pad_lo = a->pad_lo;
+        M = a->B * Ho * Wo; K = 9 * Cin;
+    } else {
+        A = a_rows((const bf16*)a->x0, K);
+    }
+    if (a->mode != EPI_ROWMAJOR && a->mode != EPI_NCHW_F32) throw GlError(GL_ERR_ARG, "gl_op_gemm_epilogue: mode is 0 (row-major) or 3 (NCHW fp32)");
+    Epilogue E;
+    epilogue_defaults(E);
+    E.mode = a->mode; E.act = a->act; E.out = a->out; E.ldo = a->ldo; E.out_f32 = a->out_f32;
+    E.bias = a->bias; E.bias2 = a->bias2; E.bias2_ld = a->bias2_ld; E.rows_per_b = a->rows_per_b;
+    E.res = (const bf16*)a->res; E.ldres = a->ldres; E.gate = a->gate;
+    E.n_real = a->n_real;
+    E.remap_in = a->remap_in; E.remap_out = a->remap_out; E.remap_off = a->remap_off;
+    int r = gemm_launch(A, w, M, a->N, K, E, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s));
+    if (r != GL_OK) throw GlError(r, gl::last_error());
+    GL_API_END
+}
+
 // include/gligen_amd_attention_core.h: one attention kernel on the caller's q, k, v^T (no projection in front, no buffer of the engine's)
 int gl_op_attention_core(gl_ctx* ctx, const void* q, const void* k, const void* vt, const gl_attn_proj_layout* layout, int B, int H, int Nq,
                          int Nk, void* o, int ldo, int o_rows_per_b, int kernel, gl_stream s) {

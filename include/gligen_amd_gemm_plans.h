@@ -1,7 +1,7 @@
 /* gligen_amd_gemm_plans.h -- run the GEMM / conv launcher of libgligen_amd.so with one named plan, and read back what it ran.
  * Which tile, K split, resident grid and XCD item order a problem gets is decided at run time (shipped table, analytic model,
  * on-device tuner); these entries exist so that every plan the planner can choose is held to a reference by itself
- * (tests/test_gemm_candidates_gpu.py) -- the engine does not go through them. They mirror the GL_GEMM_* / GL_CONV_HALO* / GL_WIDE_XCD
+ * (tests/test_gemm_candidates_gpu.py, tests/test_gemm_epilogues_gpu.py) -- the engine does not go through them. They mirror the GL_GEMM_* / GL_CONV_HALO* / GL_WIDE_XCD
  * developer switches (tools/README.md) as calls. Conventions as in gligen_amd.h. The forcing is process-wide: set it before
  * launching, not while other threads launch; the log is per calling thread. */
 #ifndef GLIGEN_AMD_GEMM_PLANS_H
@@ -59,6 +59,49 @@ int gl_gemm_plan_log(gl_gemm_plan_record* out, int max, int* n_written, int* n_l
 typedef struct gl_attn_proj_layout { int d, dp, dpv, tq, tk, tq_pad, tk_pad, vt_perm32; } gl_attn_proj_layout;
 int gl_op_attention_project(gl_ctx* ctx, const void* xq, const void* xkv, int B, int Nq, int Nk, int C, int Ck, int H, const float* wq,
                             const float* wk, const float* wv, void* q, void* k, void* vt, gl_attn_proj_layout* layout, gl_stream s);
+
+/* The second token range of the same buffers (what the fuser's attention does with the grounding tokens behind the visual ones):
+ * the fused q, k, v^T launch of x [B][Tr][C] (bf16; Tr % 64 == 0) whose row t of a sample lands at token tok_off + t
+ * (tok_off % 64 == 0), with an optional bias [3C] (q | k | v order). q, k, vt are buffers in the layouts above that already exist --
+ * typically filled by gl_op_attention_project -- and *layout says how they were laid out (d, dp, dpv, tq_pad, tk_pad, vt_perm32 are read;
+ * tok_off + Tr has to fit tq_pad and tk_pad). Nothing but the Tr token rows of the range is written. */
+int gl_op_attention_project_range(gl_ctx* ctx, const void* x, int B, int Tr, int tok_off, int C, int H, const float* wq, const float* wk,
+                                  const float* wv, const float* bias, void* q, void* k, void* vt, const gl_attn_proj_layout* layout, gl_stream s);
+
+/* One gemm_launch with the engine's split-K workspace and an epilogue filled field by field, so that every epilogue the model's own
+ * launches use can run under every plan. The operand: conv = 0, bf16 rows x0 [M][K] (w: bf16 [N][K], as gl_op_linear takes it); conv = 1,
+ * the 3x3 conv of the NHWC sources x0 [B][H][W][C0] and x1 [..][C1] (x1 NULL, C1 = 0: one source) with stride, ups, pad_lo as in
+ * gl_op_conv3x3, w: fp32 OIHW [N][C0 + C1][3][3], packed as there (M and K follow from the geometry and are not read). The epilogue:
+ *   v = acc + bias[n] + bias2[(m / rows_per_b) * bias2_ld + n];  v = act(v)   (GL_ACT_*)
+ *   mode 0, row-major [..][ldo] bf16 (out_f32: fp32): row r = (m / remap_in) * remap_out + m % remap_in + remap_off when remap_in > 0,
+ *           else m; out[r] = res ? res[r * ldres ..] + (gate ? *gate : 1) * v : v   (gate: a device scalar)
+ *   mode 3, fp32 [M / rows_per_b][n_real][rows_per_b]: the channels n < n_real alone
+ * rows_per_b >= 1 always. What the launcher's validation refuses comes back as its error; this entry itself only looks at struct_size,
+ * null pointers, the mode and the conv geometry it computes M and K from: every size and stride is the caller's to get right. */
+#define GL_ACT_NONE 0
+#define GL_ACT_SILU 1
+#define GL_ACT_GELU 3
+#define GL_ACT_QUICK_GELU 4
+typedef struct gl_gemm_epilogue_args {
+    unsigned struct_size;   /* sizeof(gl_gemm_epilogue_args) */
+    int conv;
+    int M, N, K;
+    const void* x0;
+    const void* x1;
+    int C0, C1, B, H, W, stride, ups, pad_lo;
+    const void* w;
+    const float* bias;
+    const float* bias2;
+    int bias2_ld, rows_per_b;
+    const void* res;
+    int ldres;
+    const float* gate;
+    int act, out_f32, mode, n_real;
+    int remap_in, remap_out, remap_off;
+    void* out;
+    int ldo;
+} gl_gemm_epilogue_args;
+int gl_op_gemm_epilogue(gl_ctx* ctx, const gl_gemm_epilogue_args* args, gl_stream s);
 
 #ifdef __cplusplus
 }

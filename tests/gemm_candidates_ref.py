@@ -224,11 +224,11 @@ def ask_planner(exe, problems=None):
     return out
 
 
-def fixture_payload(answer):
+def fixture_payload(answer, problems=None, provenance=None):
     """The file's form: each distinct answer once (the epilogues of a shape mostly share one), the tuner's caps behind the forced row of
     their (tile, split) -- so every tuner candidate is a forced one, or this raises -- and the problems as indices."""
     answers, index = [], {}
-    for p in PROBLEMS:
+    for p in (PROBLEMS if problems is None else problems):
         a = answer[p["id"]]
         rows = {tuple(f[:3]): f + [[], []] for f in a["forced"]}
         for which, name in enumerate(("tune", "tune_corun")):
@@ -238,8 +238,8 @@ def fixture_payload(answer):
         if c not in answers:
             answers.append(c)
         index[p["id"]] = answers.index(c)
-    return {"_provenance": "tests/gemm_plan_main.hip, mode `candidates`, over tests/gemm_candidates_ref.py PROBLEMS; regenerate with "
-                           "`python tests/gemm_candidates_ref.py --write` (tests/test_gemm_candidates_cpu.py holds it to the planner)",
+    return {"_provenance": provenance or "tests/gemm_plan_main.hip, mode `candidates`, over tests/gemm_candidates_ref.py PROBLEMS; regenerate with "
+                                         "`python tests/gemm_candidates_ref.py --write` (tests/test_gemm_candidates_cpu.py holds it to the planner)",
             "plan_fields": PLAN_FIELDS, "forced_fields": ["tm", "tn", "splits", "n_items", "box", "rm", "rz", "kt_per_split", "tune_caps", "corun_caps"],
             "problems": index, "answers": answers}
 
@@ -252,9 +252,9 @@ def dump_fixture(payload):
     return "\n".join(lines) + "\n]}\n"
 
 
-def load_fixture():
+def load_fixture(path=None):
     """{id: {"plan", "tune", "tune_corun", "forced", "fixed"}}, the file's form expanded again."""
-    with open(FIXTURE) as f:
+    with open(path or FIXTURE) as f:
         data = json.load(f)
     out = {}
     for pid, i in data["problems"].items():

@@ -9,6 +9,8 @@
 //                                                  search space and the 64 x 64 tile), as planned with the XCD boxes on
 //     FIXED halo_splits wide_splits wide_xcd <the line above>   the fixed-tile families under their own knobs
 //     END
+//   gemm_plan_main rpb   stdin: values of rows_per_b; per value `d rpb_magic rpb_shift`, the divide-free m / d gemm_validate prepares
+//                        for the epilogues' div_rpb (tests/test_gemm_epilogues_cpu.py)
 //   gemm_plan_main force_clear   the forcing knobs after gemm_force_cfg / gemm_force_grid / gemm_force_knobs, and after gemm_force_clear
 #include <cstdarg>
 #include <cstdio>
@@ -40,6 +42,20 @@ int main(int argc, char** argv) {
         printf("%d %d %d %d %d %d %d %d %d %d\n", kn.force_tm, kn.force_tn, kn.force_splits, kn.force_grid, kn.halo_splits, kn.wide_splits, kn.wide_xcd, kn.xcd_boxes, kn.halo, kn.wide);
         gemm_force_clear();
         printf("%d %d %d %d %d %d %d %d %d %d\n", kn.force_tm, kn.force_tn, kn.force_splits, kn.force_grid, kn.halo_splits, kn.wide_splits, kn.wide_xcd, kn.xcd_boxes, kn.halo, kn.wide);
+        return 0;
+    }
+    else if (!strcmp(knobs, "rpb")) {   // stdin: divisors; per divisor `d rpb_magic rpb_shift` as gemm_validate fills them for rows_per_b = d
+        for (int d; scanf("%d", &d) == 1;) {
+            static float dummy[4];
+            AOperand A{};
+            A.p0 = (const bf16*)dummy; A.C0 = 64; A.ld0 = 64; A.mode = A_ROWS;
+            Epilogue E{};
+            E.out = dummy; E.rows_per_b = d;
+            GemmPlan p;
+            const int rc = gemm_plan(A, 64, 128, 64, E, false, 0, p);
+            if (rc != GL_OK) { fprintf(stderr, "rows_per_b = %d: error %d\n", d, rc); return 3; }
+            printf("%d %u %d\n", d, E.rpb_magic, E.rpb_shift);
+        }
         return 0;
     }
     else if (list) {

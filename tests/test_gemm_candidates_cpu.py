@@ -98,7 +98,7 @@ def test_entry_points_are_declared_exported_bound_and_strict():
     header = open(os.path.join(ROOT, "include", "gligen_amd_gemm_plans.h")).read()
     declared = set(re.findall(r"\b(gl_[a-z0-9_]+)\s*\(", header))
     assert declared == set(_lib.GEMM_PLAN_SYMBOLS) == {"gl_gemm_force_plan", "gl_gemm_force_knobs", "gl_gemm_force_clear", "gl_gemm_plan_log_clear", "gl_gemm_plan_log",
-                                                           "gl_op_attention_project"}
+                                                           "gl_op_attention_project", "gl_op_attention_project_range", "gl_op_gemm_epilogue"}
     assert not declared & set(_lib.SYMBOLS)
     lib = _lib.load()
     fields = re.search(r"typedef struct gl_gemm_plan_record \{(.*?)\} gl_gemm_plan_record;", header, re.S).group(1)
