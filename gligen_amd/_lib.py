@@ -230,6 +230,8 @@ TRAIN_PRIM_SYMBOLS = {
     "gl_op_train_groupnorm": (_I, [_P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _I] + [_P] * 4 + [_P]),
     "gl_op_train_geglu": (_I, [_P, _I, _I, _P, _P, _P, _P, _P]),
     "gl_op_train_dot": (_I, [_P, C.c_int64, _P, _P, _P, _F, _I, _P, _P]),
+    "gl_op_train_conv3": (_I, [_P] + [_I] * 6 + [_P] * 6 + [_P]),
+    "gl_op_train_conv_direct": (_I, [_P] + [_I] * 7 + [_P] * 7 + [_P]),
 }
 
 class LoraAdapter(C.Structure):   # = gl_lora_adapter

@@ -994,6 +994,22 @@ int gl_op_train_dot(gl_ctx* ctx, int64_t n, const float* a, const float* b, cons
     if (n < 1 || mode < 0 || mode > 1) return gl::set_error(GL_ERR_ARG, "gl_op_train_dot: n = %lld, mode = %d (0 gate gradient, 1 mean squared difference)", (long long)n, mode);
     TRAIN_PRIM(gl::train_prim_dot(ar, ws, ws_bytes, (size_t)n, a, b, alpha, scale, mode, out, S(s)))
 }
+
+int gl_op_train_conv3(gl_ctx* ctx, int B, int H, int W, int Cin, int Cout, int geom, const float* x, const float* w_oihw, const float* bias, const float* dy,
+                      float* y, float* dx, gl_stream s) {
+    NEED(ctx);
+    if (!x || !w_oihw || !y) return gl::set_error(GL_ERR_ARG, "gl_op_train_conv3: null pointer (x, w_oihw and y are required)");
+    if (!dy && dx) return gl::set_error(GL_ERR_ARG, "gl_op_train_conv3: dx was asked for without dy");
+    TRAIN_PRIM(gl::train_prim_conv3(ar, ws, ws_bytes, B, H, W, Cin, Cout, geom, x, w_oihw, bias, dy, y, dx, S(s)))
+}
+
+int gl_op_train_conv_direct(gl_ctx* ctx, int B, int H, int W, int Cin, int Cout, int c0, int n, const float* x, const float* w_oihw, const float* bias,
+                            const float* dy, float* y, float* dx, float* dW, gl_stream s) {
+    NEED(ctx);
+    if (!x || !w_oihw || !y) return gl::set_error(GL_ERR_ARG, "gl_op_train_conv_direct: null pointer (x, w_oihw and y are required)");
+    if (!dy && (dx || dW)) return gl::set_error(GL_ERR_ARG, "gl_op_train_conv_direct: a gradient was asked for without dy");
+    TRAIN_PRIM(gl::train_prim_conv_direct(ar, ws, ws_bytes, B, H, W, Cin, Cout, c0, n, x, w_oihw, bias, dy, y, dx, dW, S(s)))
+}
 #undef TRAIN_PRIM
 
 static_assert(GL_TRAIN_ST_PARAMS == gl::ST_COUNT, "parameter table out of step with train.h");

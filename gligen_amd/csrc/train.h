@@ -150,7 +150,8 @@ int train_step_inputs_launch(const TrainStepInputs& a, hipStream_t s);
 
 // ---- The primitives by themselves (include/gligen_amd_train_prims.h; the argument lists are the entry points'): a Ctx over the arena
 // as the slices above build it -- no weight cache --, the Ctx methods the step is composed of, results copied to the caller on `s`.
-// train_prim_attention is in train_attention.hip, the others in train_ops.hip.
+// train_prim_attention is in train_attention.hip, train_prim_conv3 in train_layers.hip (it reaches the resampling layers),
+// train_prim_conv_direct in train_spatial.hip (next to conv_wgrad), the others in train_ops.hip.
 int train_prim_attention(Arena& ar, float* ws, size_t ws_bytes, int B, int H, int D, int Nq, int Nk, const float* q, const float* k, const float* v,
                          const float* dout, float* o, float* lse, float* dq, float* dk, float* dv, hipStream_t s);
 int train_prim_linear(Arena& ar, float* ws, size_t ws_bytes, int M, int N, int K, const float* x, const float* W, const float* b, const float* dy, float* y,
@@ -162,6 +163,10 @@ int train_prim_groupnorm(Arena& ar, float* ws, size_t ws_bytes, int B, int HW, i
 int train_prim_geglu(Arena& ar, float* ws, size_t ws_bytes, int R, int I, const float* u, const float* dh, float* h, float* du, hipStream_t s);
 int train_prim_dot(Arena& ar, float* ws, size_t ws_bytes, size_t n, const float* a, const float* b, const float* alpha, float scale, int mode, float* out,
                    hipStream_t s);
+int train_prim_conv3(Arena& ar, float* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int geom, const float* x, const float* w_oihw,
+                     const float* bias, const float* dy, float* y, float* dx, hipStream_t s);
+int train_prim_conv_direct(Arena& ar, float* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int c0, int n, const float* x, const float* w_oihw,
+                           const float* bias, const float* dy, float* y, float* dx, float* dW, hipStream_t s);
 
 // The low-rank part of one adapted Linear by itself (include/gligen_amd_train_lora.h; train_lora.hip)
 int train_prim_lora_linear(Arena& ar, float* ws, size_t ws_bytes, int M, int K, int N, int r, float scale, int down_kr, int up_rn, const float* x,

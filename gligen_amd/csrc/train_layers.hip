@@ -433,4 +433,29 @@ int resample_train_step(Arena& ar, float* ws, size_t ws_bytes, int mode, int B, 
         [&](const Ctx& c, float* g) { return resample_backward(c, mode, B, H, W, C, w_oihw, g); });
 }
 
+// Ctx::conv3 (geom 0) or resample_forward / resample_backward (geom 1 Downsample, 2 Upsample) by themselves (train.h): the arena
+// results copied out
+int train_prim_conv3(Arena& ar, float* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int geom, const float* x, const float* w_oihw,
+                     const float* bias, const float* dy, float* y, float* dx, hipStream_t s) {
+    if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return set_error(GL_ERR_ARG, "gl_op_train_conv3: B=%d H=%d W=%d Cin=%d Cout=%d", B, H, W, Cin, Cout);
+    if (geom < 0 || geom > 2) return set_error(GL_ERR_ARG, "gl_op_train_conv3: geom %d (0 stride 1, 1 Downsample, 2 Upsample)", geom);
+    if (Cin % 64 || Cout % 64) return set_error(GL_ERR_ARG, "gl_op_train_conv3: Cin=%d, Cout=%d: multiples of 64 are needed", Cin, Cout);
+    if (geom && Cin != Cout) return set_error(GL_ERR_ARG, "gl_op_train_conv3: a resampling layer keeps its channels (Cin=%d, Cout=%d)", Cin, Cout);
+    if (geom == 1 && ((H | W) & 1)) return set_error(GL_ERR_ARG, "gl_op_train_conv3: Downsample takes even H and W (%d x %d)", H, W);
+    try {
+        Ctx c{ar, ws, ws_bytes, s};
+        const int Ho = geom == 1 ? H / 2 : geom == 2 ? 2 * H : H, Wo = geom == 1 ? W / 2 : geom == 2 ? 2 * W : W;
+        const float* yv = geom ? resample_forward(c, geom - 1, B, H, W, Cin, w_oihw, bias, x) : c.conv3(x, B, H, W, w_oihw, bias, Cin, Cout, false);
+        c.hip(hipMemcpyAsync(y, yv, (size_t)B * Ho * Wo * Cout * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
+        if (dy && dx) {
+            const float* gx = geom ? resample_backward(c, geom - 1, B, H, W, Cin, w_oihw, dy) : c.conv3(dy, B, H, W, w_oihw, nullptr, Cin, Cout, true);
+            c.hip(hipMemcpyAsync(dx, gx, (size_t)B * H * W * Cin * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
+        }
+        c.hip(hipGetLastError(), "training conv kernel launch");
+    } catch (const GlError& e) {
+        return set_error(e.code, "%s", e.what());
+    }
+    return GL_OK;
+}
+
 }  // namespace gl

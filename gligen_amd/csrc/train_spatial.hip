@@ -444,4 +444,27 @@ float* train::conv_in_forward(const UNetStep& u, DsSaved& dsv, const float*& xin
     return conv3x3_direct(c, xin, u.nm.w("input_blocks.0.0.weight"), u.nm.w("input_blocks.0.0.bias"), u.B, u.H0, u.W0, u.Cin0, u.mc);
 }
 
+// The direct conv by itself (train.h): forward, the data gradient of the input channels [c0, c0 + n) as conv_in_backward and the last
+// conv's backward form it, and the weight gradient by conv_wgrad as conv_in_backward calls it
+int train_prim_conv_direct(Arena& ar, float* ws, size_t ws_bytes, int B, int H, int W, int Cin, int Cout, int c0, int n, const float* x, const float* w_oihw,
+                           const float* bias, const float* dy, float* y, float* dx, float* dW, hipStream_t s) {
+    if (B < 1 || H < 1 || W < 1 || Cin < 1 || Cout < 1) return set_error(GL_ERR_ARG, "gl_op_train_conv_direct: B=%d H=%d W=%d Cin=%d Cout=%d", B, H, W, Cin, Cout);
+    if (c0 < 0 || n < 1 || c0 + n > Cin) return set_error(GL_ERR_ARG, "gl_op_train_conv_direct: channels [%d, %d) of %d", c0, c0 + n, Cin);
+    try {
+        Ctx c{ar, ws, ws_bytes, s};
+        const size_t rows = (size_t)B * H * W;
+        c.hip(hipMemcpyAsync(y, conv3x3_direct(c, x, w_oihw, bias, B, H, W, Cin, Cout), rows * Cout * 4, hipMemcpyDeviceToDevice, s), "hipMemcpyAsync");
+        if (dy && dx) {
+            const float* wt = c.conv_dgrad_weight(w_oihw, Cout, Cin);
+            c.hip(hipMemcpyAsync(dx, conv3x3_direct(c, dy, wt + (size_t)c0 * Cout * 9, nullptr, B, H, W, Cout, n), rows * n * 4, hipMemcpyDeviceToDevice, s),
+                  "hipMemcpyAsync");
+        }
+        if (dy && dW) conv_wgrad(c, x, B, Cin, H, W, pixel_rows(Cin, H, W), 3, 1, 1, H, W, dy, Cout, dW, nullptr);
+        c.hip(hipGetLastError(), "training direct conv kernel launch");
+    } catch (const GlError& e) {
+        return set_error(e.code, "%s", e.what());
+    }
+    return GL_OK;
+}
+
 }  // namespace gl

@@ -1470,6 +1470,42 @@ class Engine:
         check(self.lib.gl_op_train_dot(self._ctx, int(a.numel()), _ptr(a), _ptr(b), _ptr(alpha), C.c_float(scale), int(mode), _ptr(o["out"]), _stream(dev)))
         return o
 
+    def op_train_conv3(self, x, w, bias=None, geom=0, dy=None, out=None):
+        """gl_op_train_conv3: pixel rows x [B, H, W, Cin], w [Cout, Cin, 3, 3] -> y [B, Ho, Wo, Cout] (geom 0: stride 1; 1: Downsample,
+        Ho = H / 2; 2: Upsample, Ho = 2 H); with dy (like y) also dx (like x)."""
+        dev = self.device
+        x, w = _f32(x, dev), _f32(w, dev)
+        bias, dy = (None if t is None else _f32(t, dev) for t in (bias, dy))
+        (B, H, W, Cin), Cout = x.shape, w.shape[0]
+        ys = {0: (B, H, W, Cout), 1: (B, H // 2, W // 2, Cout), 2: (B, 2 * H, 2 * W, Cout)}.get(geom, (B, H, W, Cout))
+        if w.shape != (Cout, Cin, 3, 3) or (bias is not None and bias.shape != (Cout,)) or (dy is not None and tuple(dy.shape) != ys):
+            raise ValueError("op_train_conv3: x [B, H, W, Cin], w [Cout, Cin, 3, 3], bias [Cout], dy [B, Ho, Wo, Cout]")
+        shapes = {"y": ys}
+        if dy is not None:
+            shapes.update(dx=x.shape)
+        o = self._prim_outs(shapes, out, required=("y",))
+        check(self.lib.gl_op_train_conv3(self._ctx, int(B), int(H), int(W), int(Cin), int(Cout), int(geom), _ptr(x), _ptr(w), _ptr(bias), _ptr(dy),
+                                         _ptr(o["y"]), _ptr(o.get("dx")), _stream(dev)))
+        return o
+
+    def op_train_conv_direct(self, x, w, bias=None, c0=0, n=None, dy=None, out=None):
+        """gl_op_train_conv_direct: pixel rows x [B, H, W, Cin], w [Cout, Cin, 3, 3] -> y [B, H, W, Cout]; with dy (like y) also dx
+        [B, H, W, n], the gradient of the input channels [c0, c0 + n) (n None: all behind c0), and dW (like w)."""
+        dev = self.device
+        x, w = _f32(x, dev), _f32(w, dev)
+        bias, dy = (None if t is None else _f32(t, dev) for t in (bias, dy))
+        (B, H, W, Cin), Cout = x.shape, w.shape[0]
+        n = Cin - c0 if n is None else n
+        if w.shape != (Cout, Cin, 3, 3) or (bias is not None and bias.shape != (Cout,)) or (dy is not None and dy.shape != (B, H, W, Cout)):
+            raise ValueError("op_train_conv_direct: x [B, H, W, Cin], w [Cout, Cin, 3, 3], bias [Cout], dy [B, H, W, Cout]")
+        shapes = {"y": (B, H, W, Cout)}
+        if dy is not None:
+            shapes.update(dx=(B, H, W, n), dW=w.shape)
+        o = self._prim_outs(shapes, out, required=("y",))
+        check(self.lib.gl_op_train_conv_direct(self._ctx, int(B), int(H), int(W), int(Cin), int(Cout), int(c0), int(n), _ptr(x), _ptr(w), _ptr(bias),
+                                               _ptr(dy), _ptr(o["y"]), _ptr(o.get("dx")), _ptr(o.get("dW")), _stream(dev)))
+        return o
+
     # ---- include/gligen_amd_train_lora.h: the low-rank part of one adapted Linear by itself
     def op_lora_linear(self, x, down, up, scale=1.0, dy=None, down_kr=False, up_rn=False, out=None):
         """gl_op_lora_linear: x [M, K]; down [r, K] (down_kr: [K, r]); up [N, r] (up_rn: [r, N]). t [M, r] = x down^T and

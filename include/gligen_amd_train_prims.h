@@ -1,6 +1,6 @@
 /* gligen_amd_train_prims.h -- the primitives of the training path in libgligen_amd.so, one entry each: attention, the Linear products,
- * LayerNorm, GroupNorm + SiLU, GEGLU and the dot / MSE reduction, forward and backward, exactly as the training step composes them
- * (the same kernels, the same launch helpers, the engine's arena and split-K workspace). They exist so that each primitive can be
+ * LayerNorm, GroupNorm + SiLU, GEGLU, the dot / MSE reduction and the 3x3 convolutions, forward and backward, exactly as the training
+ * step composes them (the same kernels, the same launch helpers, the engine's arena and split-K workspace). They exist so that each primitive can be
  * held to a float64 reference by itself (tests/test_train_prims_gpu.py); the training step does not go through them.
  * Conventions as in gligen_amd.h: fp32 device pointers, work queued on `s`, GL_OK or an error code with gl_last_error(). An output
  * that is NULL is not produced unless it is marked required; a backward output needs the backward's input gradient. */
@@ -39,6 +39,21 @@ int gl_op_train_geglu(gl_ctx* ctx, int R, int I, const float* u, const float* dh
 /* out[0] = scale (1 - tanh(alpha[0])^2) sum a b (mode 0: a tanh gate's gradient) or mean((a - b)^2) (mode 1: the loss; alpha is
  * not read) over n elements; out is required. */
 int gl_op_train_dot(gl_ctx* ctx, int64_t n, const float* a, const float* b, const float* alpha, float scale, int mode, float* out, gl_stream s);
+
+/* The split-precision 3x3 / pad 1 conv of the ResBlocks and of the two resampling layers over pixel rows x [B][H W][Cin], w_oihw
+ * [Cout][Cin][3][3], bias [Cout] (may be NULL). geom 0: stride 1, y [B][H W][Cout]; geom 1: Downsample (stride 2; H and W even), y
+ * [B][H/2 W/2][Cout]; geom 2: Upsample (nearest 2x, then the conv), y [B][2H 2W][Cout]. y is required. With dy (shaped like y): dx
+ * [B][H W][Cin], the input gradient as the step forms it -- the flipped, channel-exchanged filter on dy (geom 0), on dy zero-inserted at
+ * the even positions (geom 1), or on dy followed by 2 x 2 block sums (geom 2). Cin and Cout are multiples of 64; geom 1 and 2 have
+ * Cin == Cout. */
+int gl_op_train_conv3(gl_ctx* ctx, int B, int H, int W, int Cin, int Cout, int geom, const float* x, const float* w_oihw, const float* bias,
+                      const float* dy, float* y, float* dx, gl_stream s);
+
+/* The fp32 direct 3x3 / stride 1 / pad 1 conv of the first and the last conv (any channel counts): y [B][H W][Cout] (required). With dy
+ * [B][H W][Cout]: dx [B][H W][n], the data gradient for the input channels [c0, c0 + n) alone (the direct conv over rows c0 .. c0 + n of
+ * the flipped, channel-exchanged filter), and dW [Cout][Cin][3][3], the weight gradient (im2col of x, then the Linear weight gradient). */
+int gl_op_train_conv_direct(gl_ctx* ctx, int B, int H, int W, int Cin, int Cout, int c0, int n, const float* x, const float* w_oihw,
+                            const float* bias, const float* dy, float* y, float* dx, float* dW, gl_stream s);
 
 #ifdef __cplusplus
 }

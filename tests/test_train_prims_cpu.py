@@ -3,6 +3,7 @@ are held to them (test_train_prims_gpu.py) -- the hand-written float64 attention
 fp32 flavours against float64, the hand-written GroupNorm against F.group_norm --, the guard-zone helper against a write placed
 outside, the summation-chain formulas, and the entry points of include/gligen_amd_train_prims.h (declared, exported, bound)."""
 import ctypes
+import functools
 import os
 import re
 import shutil
@@ -70,6 +71,120 @@ def test_split3_is_three_bf16_passes():
     assert float((ah + al - a).abs().max()) <= 2.0 ** -16 * float(a.abs().max())
     full = (ah + al).double() @ (bh + bl).double()
     assert torch.equal(R.mm_split3(a, b), (full - al.double() @ bl.double()).float())
+
+
+@functools.lru_cache(maxsize=None)
+def conv3_data(c):
+    """(inputs, float64 reference, split3 flavour) of a Conv3Case, computed once for the tests below."""
+    inp = R.conv_inputs(c)
+    return inp, R.conv3_ref(c, *inp), R.conv3_split3(c, *inp)
+
+
+@functools.lru_cache(maxsize=None)
+def direct_data(c):
+    """(inputs, float64 reference with the absolute sums, split3 dW) of a DirectCase."""
+    inp = R.conv_inputs(c)
+    x, _, _, dy = inp
+    return inp, R.direct_ref(c, *inp), R.wgrad_split3(R._nchw(dy), R._nchw(x))
+
+
+def test_conv_references_are_autograd():
+    """conv3_ref's hand-written gradients (flipped, channel-exchanged filter; zero insertion at the even positions; 2 x 2 block sums)
+    and direct_ref's (the filter rows c0 .. c0 + n; dW = dy^T im2col(x) in OIHW order) equal torch.autograd through F.conv2d(stride) and
+    F.interpolate(mode="nearest") in float64 to 1e-12, on every listed case."""
+    for c in R.conv3_cases():
+        inp, ref, _ = conv3_data(c)
+        auto = R.conv3_autograd(c, *inp)
+        for n in ("y", "dx"):
+            assert ref[n].dtype == torch.float64 and ref[n].shape == auto[n].shape and ref[n].is_contiguous(), (c, n)
+            assert close(ref[n], auto[n], 1e-12), (c, n, float((ref[n] - auto[n]).abs().max()))
+        assert ref["dx"].shape == inp[0].shape and ref["y"].shape == inp[3].shape
+    for c in R.direct_cases():
+        inp, ref, _ = direct_data(c)
+        auto = R.direct_autograd(c, *inp)
+        for n in ("y", "dx", "dW"):
+            assert ref[n].dtype == torch.float64 and ref[n].shape == auto[n].shape, (c, n)
+            assert close(ref[n], auto[n], 1e-12), (c, n, float((ref[n] - auto[n]).abs().max()))
+        assert ref["dW"].shape == inp[1].shape and ref["dx"].shape[-1] == c.n
+        assert bool((ref["y_abs"] >= ref["y"].abs()).all()) and bool((ref["dx_abs"] >= ref["dx"].abs()).all())
+
+
+def test_conv_split3_is_three_bf16_passes():
+    """conv_split3 and wgrad_split3 on operands that are bf16 values already are the exact conv / weight gradient; on fp32 operands they
+    miss exactly the lo.lo term; the flavours of every listed case stay within 1e-3 of float64, and the direct conv's worst-case chain bound stays
+    below 1e-2 of the largest value (2881 roundings at 320 channels)."""
+    gen = torch.Generator().manual_seed(11)
+    a, w = torch.randn(2, 8, 5, 7, generator=gen), torch.randn(6, 8, 3, 3, generator=gen)
+    dy = torch.randn(2, 6, 5, 7, generator=gen)
+    ab, wb, dyb = (t.bfloat16().float() for t in (a, w, dy))
+    for stride in (1, 2):
+        assert torch.equal(R.conv_split3(ab, wb, stride), R.conv_f64(ab, wb, stride).float())
+        (ah, al), (wh, wl) = R.bf16_split(a), R.bf16_split(w)
+        full = R.conv_f64(ah.double() + al.double(), wh.double() + wl.double(), stride)
+        assert torch.equal(R.conv_split3(a, w, stride), (full - R.conv_f64(al, wl, stride)).float())
+    assert torch.equal(R.wgrad_split3(dyb, ab), R.wgrad_f64(dyb, ab).float())
+    (dh, dl), (ah, al) = R.bf16_split(dy), R.bf16_split(a)
+    full = R.wgrad_f64(dh.double() + dl.double(), ah.double() + al.double())
+    assert float((R.wgrad_split3(dy, a).double() - (full - R.wgrad_f64(dl, al))).abs().max()) <= 2.0 ** -23 * float(full.abs().max())
+    for c in R.conv3_cases():
+        _, ref, s3 = conv3_data(c)
+        for n in ("y", "dx"):
+            assert s3[n].dtype == torch.float32 and 0 < R.rel_max(s3[n], ref[n]) < 1e-3, (c, n)
+    for c in R.direct_cases():
+        _, ref, dW3 = direct_data(c)
+        assert 0 < R.rel_max(dW3, ref["dW"]) < 1e-3, c
+        for n, bound in R.direct_bounds(c, ref).items():
+            assert float(bound.max()) < 1e-2 * float(ref[n].abs().max()) and float(bound.min()) > 0, (c, n)
+
+
+# mutation -> the tensors it reaches, per kind of case
+CONV3_MUTATIONS = {"lo_hi_last_row": ("y", "dx"), "hi_lo_tap0": ("y", "dx"), "bf16x1": ("y", "dx"), "no_flip": ("dx",), "zero_insert_odd": ("dx",),
+                   "sum2x2_missing": ("dx",)}
+DW_MUTATIONS = ("lo_hi_last_row", "hi_lo_tap0", "bf16x1", "dW_taps_transposed")
+# (mutation, case id, tensor) where the mutation provably changes nothing, so the mutated tensor has to equal the unmutated one:
+#   at 1 x 1 every tap but the centre reads padding -- tap (0, 0) contributes nothing, its im2col columns are zero, the flip keeps the
+#   centre where it is and so does exchanging ky and kx;
+#   the single output of the 2 x 2 Downsample reads rows -1 .. 1: its tap (0, 0) is padding too
+UNCHANGED = {("hi_lo_tap0", "g0-1x1x1-64-64", "y"), ("hi_lo_tap0", "g0-1x1x1-64-64", "dx"), ("no_flip", "g0-1x1x1-64-64", "dx"),
+             ("hi_lo_tap0", "g1-1x2x2-64-64", "y"), ("hi_lo_tap0", "direct-1x1x1-64-4-c0n64", "dW"),
+             ("dW_taps_transposed", "direct-1x1x1-64-4-c0n64", "dW")}
+
+
+def test_conv_mutations_exceed_the_bounds():
+    """What the bounds of the GPU tests see, computed here on the CPU: on every listed case, each way of getting the conv subtly wrong
+    pushes every tensor it reaches over that tensor's bound -- the split-family bound 4 e3 for conv3's y and dx and for dW, the
+    elementwise fp32-chain bound for the direct conv's y and dx. The only tensors let off are those of UNCHANGED, which have to be
+    bit-equal to the unmutated flavour. Prints the table mutation, case, tensor, measure, bound."""
+    seen = set()
+
+    def judge(mut, cid, n, measure, bound, mutated, plain):
+        print(f"[conv mutations] {mut:18s} {cid:26s} {n:3s} measure {measure:.3e}  bound {bound:.3e}  x{measure / bound:.1f}")
+        if (mut, cid, n) in UNCHANGED:
+            seen.add((mut, cid, n))
+            assert torch.equal(mutated, plain), (mut, cid, n)
+        else:
+            assert measure > bound, (mut, cid, n, measure, bound)
+
+    for c in R.conv3_cases():
+        inp, ref, s3 = conv3_data(c)
+        cid = R.conv_case_id(c)
+        for mut, names in CONV3_MUTATIONS.items():
+            if (mut == "zero_insert_odd" and c.geom != 1) or (mut == "sum2x2_missing" and c.geom != 2):
+                continue
+            bad = R.conv3_split3(c, *inp, mut=mut)
+            for n in names:
+                judge(mut, cid, n, R.rel_max(bad[n], ref[n]), R.split_family_bound(R.rel_max(s3[n], ref[n])), bad[n], s3[n])
+    for c in R.direct_cases():
+        (x, w, b, dy), ref, dW3 = direct_data(c)
+        cid = R.conv_case_id(c)
+        for mut in DW_MUTATIONS:
+            bad = R.wgrad_split3(R._nchw(dy), R._nchw(x), mut)
+            judge(mut, cid, "dW", R.rel_max(bad, ref["dW"]), R.split_family_bound(R.rel_max(dW3, ref["dW"])), bad, dW3)
+        bad, bounds = R.direct_ref(c, x, w, b, dy, clamp=True), R.direct_bounds(c, ref)
+        for n in ("y", "dx"):
+            # the measure of an elementwise bound is the worst |error| / bound, against 1
+            judge("clamp_border", cid, n, R._reduction_row(cid, n, bad[n], ref[n], bounds[n])[2], 1.0, bad[n], ref[n])
+    assert seen == UNCHANGED
 
 
 def test_norm_references_are_torchs():
@@ -147,6 +262,23 @@ def test_case_lists():
     assert (100, 96, 384) in R.LINEAR_SHAPES and (100, 384, 96) in R.LINEAR_SHAPES and len(R.LINEAR_SHAPES) == 7
     assert [C // 32 for _, _, C in R.GN_SHAPES] == [1, 2, 10, 3]
     assert R.DOT_SIZES == [1, 1023, 1025, 262144, 262145, 458759]
+    # the convolutions: every form at the smallest shapes at which its path can still go wrong
+    assert R.CONV3_SHAPES == [(2, 32, 32, 64, 128), (8, 16, 16, 128, 128), (1, 64, 64, 64, 128), (1, 12, 20, 192, 128), (3, 8, 8, 128, 320),
+                              (2, 8, 8, 640, 320), (2, 2, 2, 128, 128), (1, 1, 1, 64, 64)]
+    assert R.CONV3_DOWN_SHAPES == [(2, 16, 16, 128), (1, 12, 20, 64), (1, 2, 2, 64), (1, 64, 64, 64)]
+    assert R.CONV3_UP_SHAPES == [(2, 8, 8, 128), (1, 6, 10, 64), (1, 1, 1, 64), (2, 16, 16, 128)]
+    assert R.CONV_DIRECT_SHAPES == [(2, 8, 8, 320, 4, 0, 320), (1, 5, 7, 64, 4, 0, 64), (1, 1, 1, 64, 4, 0, 64), (2, 8, 8, 4, 320, 0, 4),
+                                    (2, 8, 8, 9, 64, 0, 9), (1, 5, 7, 12, 64, 4, 8)]
+    c3 = R.conv3_cases()
+    assert len(c3) == 16 and [c.geom for c in c3] == [0] * 8 + [1] * 4 + [2] * 4 and all(c.Cin == c.Cout for c in c3 if c.geom)
+    assert all(c.Cin % 64 == 0 and c.Cout % 64 == 0 for c in c3) and all(c.H % 2 == 0 and c.W % 2 == 0 for c in c3 if c.geom == 1)
+    assert max(27 * c.Cin for c in c3) == 17280 and len({R.conv_case_id(c) for c in c3 + R.direct_cases()}) == 16 + 6
+    assert all(" " not in R.conv_case_id(c) for c in c3 + R.direct_cases())
+    assert R.CONV_FAMILIES == ("conv_halo_kernel", "gemm_u_kernel(conv)", "gemm_glds_kernel(conv)")
+    assert R.gemm_kernel_family({"kernel": "gemm_u_kernel<2, 2, 5, 1, 2, false> + splitk_reduce_kernel"}) == "gemm_u_kernel(conv)"
+    assert R.gemm_kernel_family({"kernel": "gemm_u_kernel<2, 4, 4, 0, 2, false>"}) == "gemm_u_kernel"
+    assert R.gemm_kernel_family({"kernel": "gemm_glds_kernel<64x64, 1>"}) == "gemm_glds_kernel(conv)"
+    assert R.gemm_kernel_family({"kernel": "conv_halo_kernel<4, 8> + splitk_reduce_kernel"}) == "conv_halo_kernel"
 
 
 # ---- the C ABI
@@ -163,7 +295,7 @@ def test_train_prim_entry_points_are_declared_exported_and_bound():
     lib = table.load()
     declared = _declared("gligen_amd_train_prims.h")
     assert declared == set(table.TRAIN_PRIM_SYMBOLS) == {"gl_op_train_attention", "gl_op_train_linear", "gl_op_train_layernorm", "gl_op_train_groupnorm",
-                                                         "gl_op_train_geglu", "gl_op_train_dot"}
+                                                         "gl_op_train_geglu", "gl_op_train_dot", "gl_op_train_conv3", "gl_op_train_conv_direct"}
     raw = ctypes.CDLL(str(table.LIB_PATH))
     for name in declared:
         assert hasattr(raw, name), f"{name} is declared but not exported"

@@ -6,8 +6,10 @@ The measure is per output tensor max|got - ref64| / max|ref64| -- a maximum, so 
 a view between two 64-float guard zones and starts as NaN: after the call the guards hold their bits and no NaN is left. A second call
 gives the same bits. Every bound is computed at run time from the references on the case's own inputs:
     fp32 family (VALU attention, LayerNorm, GroupNorm, GEGLU)    err <= max(8 e32, 2^-22), e32 the measure of torch's fp32 arithmetic
-    split family (MFMA attention, the Linear products)           err <= 4 e3, e3 the measure of the three-pass bf16 emulation
+    split family (MFMA attention, the Linear products, conv3 in
+                  every geometry, the conv weight gradient)      err <= 4 e3, e3 the measure of the three-pass bf16 emulation
     reductions (dot, and the column sums db, dgamma, dbeta)      |err| <= (L + 1) 2^-24 sum|terms| per element, L the longest chain
+    the direct conv (y, dx)                                      |err| <= (9 Cin_eff + 1) 2^-24 (sum|x||w| + |b|) per element
 Each test prints err / bound of every tensor; profiles/train_prims/ keeps such tables."""
 import os
 import subprocess
@@ -88,8 +90,47 @@ def test_dot(engine, n, mode):
     check(*R.run_dot(engine, n, mode))
 
 
+CONV3_KERNELS = {}      # case id -> kernel families of its launches, filled by test_conv3
+
+
+@pytest.mark.parametrize("case", R.conv3_cases(), ids=R.conv_case_id)
+def test_conv3(engine, case):
+    """y and dx of Ctx::conv3 (geom 0), of Downsample (geom 1: stride 2 forward, zero insertion + the flipped stride-1 conv backward) and
+    of Upsample (geom 2: nearest 2x + conv forward, the dgrad conv at 2H x 2W + 2 x 2 block sums backward) in the aliased two-source
+    one-launch form, K = 27 Cin: split family. Prints the kernel families the GEMM plan log showed."""
+    rows, problems = R.run_conv3(engine, case, CONV3_KERNELS)
+    print("[train prims]", R.conv_case_id(case), "kernels:", ", ".join(CONV3_KERNELS[R.conv_case_id(case)]))
+    check(rows, problems)
+
+
+def test_conv3_kernel_families(engine):
+    """The conv3 list as a whole runs conv_halo_kernel, the conv instantiation of gemm_u_kernel and gemm_glds_kernel, and nothing but the
+    conv kernels: a routing change cannot quietly empty a path. Families only -- tile and split are the tuner's. A case test_conv3 has
+    not run in this process is launched here (without a reference)."""
+    seen = {}
+    for c in R.conv3_cases():
+        cid = R.conv_case_id(c)
+        seen[cid] = CONV3_KERNELS.get(cid) or R.conv3_kernels(engine, c)
+        print("[train prims]", cid, "kernels:", ", ".join(seen[cid]))
+        assert seen[cid], cid
+    families = set().union(*seen.values())
+    assert families >= set(R.CONV_FAMILIES), families
+    assert all(f.endswith("(conv)") or f == "conv_halo_kernel" for f in families), families
+    assert "conv_halo_kernel" in seen["g0-2x32x32-64-128"] and "gemm_glds_kernel(conv)" in seen["g0-2x32x32-64-128"]      # forward; dgrad, N = 64
+    assert "conv_halo_kernel" in seen["g2-2x16x16-128-128"] and "gemm_u_kernel(conv)" in seen["g2-2x16x16-128-128"]      # 32 x 32 dgrad; ups forward
+
+
+@pytest.mark.parametrize("case", R.direct_cases(), ids=R.conv_case_id)
+def test_conv_direct(engine, case):
+    """conv3x3_direct's y and its data gradient for the channels [c0, c0 + n) elementwise against the fp32 chain's bound (err / bound
+    against 1), dW of conv_wgrad (im2col + lin_wgrad_unpad) in the split family."""
+    check(*R.run_conv_direct(engine, case))
+
+
 def test_argument_errors(engine):
-    """A null required pointer, dk without dv, a head dim the tables do not build and C % 32 != 0 are GL_ERR_ARG with a message."""
+    """A null required pointer, dk without dv, a head dim the tables do not build and C % 32 != 0 are GL_ERR_ARG with a message; so
+    are the convs' refusals: channels off the 64-step, a resampling layer that changes its channels, an odd Downsample, a geom outside
+    0 .. 2, dx without dy, a channel range outside the input."""
     import ctypes as C
     import torch
     from gligen_amd._lib import GligenAmdError
@@ -110,13 +151,34 @@ def test_argument_errors(engine):
     refused(lib.gl_op_train_dot(ctx, 4, p, p, null, C.c_float(1.0), 0, p, st), "alpha")
     with pytest.raises(GligenAmdError):
         engine.op_train_attention(t, t, t, 2)                         # 96 / 2 = 48 through the wrapper
+    conv3 = lambda B, H, W, Ci, Co, geom, x=p, w=p, dy=null, y=p, dx=null: lib.gl_op_train_conv3(ctx, B, H, W, Ci, Co, geom, x, w, null, dy, y, dx, st)
+    refused(conv3(1, 2, 2, 96, 64, 0), "multiples of 64")
+    refused(conv3(1, 2, 2, 64, 96, 0), "multiples of 64")
+    refused(conv3(1, 2, 2, 64, 128, 1), "keeps its channels")
+    refused(conv3(1, 2, 2, 64, 128, 2), "keeps its channels")
+    refused(conv3(1, 3, 2, 64, 64, 1), "even H and W")
+    refused(conv3(1, 2, 3, 64, 64, 1), "even H and W")
+    refused(conv3(1, 2, 2, 64, 64, 3), "geom 3")
+    refused(conv3(1, 2, 2, 64, 64, -1), "geom -1")
+    refused(conv3(1, 2, 2, 64, 64, 0, x=null), "required")
+    refused(conv3(1, 2, 2, 64, 64, 0, w=null), "required")
+    refused(conv3(1, 2, 2, 64, 64, 0, y=null), "required")
+    refused(conv3(1, 2, 2, 64, 64, 0, dx=p), "without dy")
+    direct = lambda c0, n, x=p, dy=null, y=p, dx=null, dW=null: lib.gl_op_train_conv_direct(ctx, 1, 2, 2, 4, 8, c0, n, x, p, null, dy, y, dx, dW, st)
+    refused(direct(0, 4, x=null), "required")
+    refused(direct(0, 4, y=null), "required")
+    refused(direct(0, 4, dx=p), "without dy")
+    refused(direct(0, 4, dW=p), "without dy")
+    refused(direct(2, 3), "channels [2, 5) of 4")
+    with pytest.raises(GligenAmdError):
+        engine.op_train_conv3(torch.zeros(1, 3, 2, 64), torch.zeros(64, 64, 3, 3), geom=1)
 
 
 # ---- the other code paths: GL_TRAIN_ATTN_VALU and GL_TRAIN_3LAUNCH are read once per process
 CHILDREN = {
     # switch: (what the child runs, REPORT lines: tensors per case)
     "GL_TRAIN_ATTN_VALU": ("attention", 5 * len(R.attention_cases(R.MFMA_DIMS))),
-    "GL_TRAIN_3LAUNCH": ("linear", 4 * len(R.LINEAR_SHAPES)),
+    "GL_TRAIN_3LAUNCH": ("linear+conv3", 4 * len(R.LINEAR_SHAPES) + 2 * len(R.conv3_cases())),
 }
 
 
@@ -146,7 +208,8 @@ def run_child(switch):
 
 def test_developer_switch_paths():
     """One fresh child per switch, each under its own time limit, the first failure ends the test: the attention list of head dims 32,
-    40, 64, 80 on the VALU kernels (fp32 family), the Linear list in the three-launch form (split family). The number of reports is
+    40, 64, 80 on the VALU kernels (fp32 family), the Linear list and the conv3 list (every geom) in the three-launch form (split family,
+    the same bound). The number of reports is
     asserted, so a child that ran less cannot pass."""
     import torch
     if not torch.cuda.is_available():

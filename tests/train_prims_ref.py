@@ -6,7 +6,10 @@ Every primitive has a float64 reference and an fp32 flavour (torch's own fp32 ar
 products have a third, split3, which forms every product as the kernels do: each fp32 operand x as hi = bf16(x), lo = bf16(x - hi),
 the product as hi.hi + lo.hi + hi.lo (summed in float64 here, rounded to fp32 once). A kernel's error is measured per output tensor as
 max|got - ref64| / max|ref64| and bounded by a multiple of the same measure of the flavour it belongs to, on that case's own inputs;
-reductions get the elementwise bound of their summation tree. No constant in this file was obtained by running a kernel."""
+reductions get the elementwise bound of their summation tree. The convolutions: conv3 in its three geometries and the conv weight
+gradient belong to the split family (three float64 convs of the bf16 halves), the fp32 direct conv gets the elementwise bound of its
+sequential fmaf chain; their gradients are written out by hand from the kernels' comments and held to torch.autograd on the CPU. No
+constant in this file was obtained by running a kernel."""
 import math
 from collections import namedtuple
 
@@ -252,6 +255,157 @@ def geglu_fp32(u, dh):
     return geglu_ref(u, dh, dtype=torch.float32)
 
 
+# ---- the convolutions. Tensors are pixel rows [B, H, W, C] outside and NCHW inside; w is OIHW [Cout, Cin, 3, 3]
+Conv3Case = namedtuple("Conv3Case", "geom B H W Cin Cout")          # geom 0 stride 1, 1 Downsample (stride 2), 2 Upsample (nearest 2x + conv)
+DirectCase = namedtuple("DirectCase", "B H W Cin Cout c0 n")         # dx for the input channels [c0, c0 + n)
+SPLIT_MUTATIONS = ("lo_hi_last_row", "hi_lo_tap0", "bf16x1")         # what conv_split3 / wgrad_split3 can be told to get wrong
+
+
+def _nchw(t):
+    return t.permute(0, 3, 1, 2)
+
+
+def _pixel_rows(t):
+    return t.permute(0, 2, 3, 1).contiguous()
+
+
+def conv_f64(a, w, stride=1):
+    """The 3x3 / pad 1 conv of a [B, C, H, W] with w OIHW in float64."""
+    return F.conv2d(a.double(), w.double(), None, stride, 1)
+
+
+def conv_split3(a, w, stride=1, mut=None):
+    """The conv as Ctx::conv3 forms it: fp32 a and w as hi = bf16(.), lo = bf16(. - hi), three float64 convs hi.hi + lo.hi + hi.lo,
+    rounded to fp32 once. mut (test_train_prims_cpu.py's mutations): lo_hi_last_row drops the lo_a hi_w pass on the last row of each
+    output image, hi_lo_tap0 drops hi_a lo_w for the tap ky = kx = 0, bf16x1 keeps hi.hi alone."""
+    assert a.dtype == torch.float32 and w.dtype == torch.float32 and mut in (None,) + SPLIT_MUTATIONS
+    ah, al = (t.double() for t in bf16_split(a))
+    wh, wl = (t.double() for t in bf16_split(w))
+    cv = lambda p, q: F.conv2d(p, q, None, stride, 1)
+    hh = cv(ah, wh)
+    if mut == "bf16x1":
+        return hh.float()
+    lh, hl = cv(al, wh), cv(ah, wl)
+    if mut == "lo_hi_last_row":
+        lh[:, :, -1, :] = 0
+    elif mut == "hi_lo_tap0":
+        wl0 = torch.zeros_like(wl)
+        wl0[:, :, 0, 0] = wl[:, :, 0, 0]
+        hl = hl - cv(ah, wl0)
+    return (hh + lh + hl).float()
+
+
+def dgrad_weight(w, flip=True):
+    """conv_dgrad_weight_kernel: W'[i][o][ky][kx] = W[o][i][2 - ky][2 - kx], the filter of the data-gradient conv."""
+    return (w.flip(2, 3) if flip else w).transpose(0, 1).contiguous()
+
+
+def _conv3(c, x, w, b, dy, cv, dtype, mut=None):
+    """y and dx of a Conv3Case by the formulas of the kernels' comments, cv the conv of the flavour and dtype what it returns:
+    geom 0  y = conv(x, w) + b,                  dx = conv(dy, W')
+    geom 1  y = conv(x, w, stride 2) + b,        dx = conv(z, W'), z [H, W] = dy at the even positions, zeros elsewhere
+    geom 2  y = conv(nearest2x(x), w) + b,       dx = the 2 x 2 block sums (p00 + p01) + (p10 + p11) of conv(dy, W') at [2H, 2W]
+    mut: no_flip (W' without the flip), zero_insert_odd (dy at the odd positions), sum2x2_missing (p11 left out)."""
+    xn, dyn = _nchw(x), _nchw(dy)
+    a = xn.repeat_interleave(2, dim=2).repeat_interleave(2, dim=3) if c.geom == 2 else xn
+    y = cv(a, w, 2 if c.geom == 1 else 1) + b.to(dtype).view(1, -1, 1, 1)
+    wt = dgrad_weight(w, flip=mut != "no_flip")
+    if c.geom == 0:
+        dx = cv(dyn, wt)
+    elif c.geom == 1:
+        z = torch.zeros(c.B, c.Cin, c.H, c.W)
+        o = 1 if mut == "zero_insert_odd" else 0
+        z[:, :, o::2, o::2] = dyn
+        dx = cv(z, wt)
+    else:
+        gu = cv(dyn, wt)
+        p00, p01, p10, p11 = gu[:, :, 0::2, 0::2], gu[:, :, 0::2, 1::2], gu[:, :, 1::2, 0::2], gu[:, :, 1::2, 1::2]
+        dx = (p00 + p01) + (p10 if mut == "sum2x2_missing" else p10 + p11)
+    assert y.dtype == dtype and dx.dtype == dtype
+    return {"y": _pixel_rows(y), "dx": _pixel_rows(dx)}
+
+
+def conv3_ref(c, x, w, b, dy):
+    return _conv3(c, x, w, b, dy, conv_f64, torch.float64)
+
+
+def conv3_split3(c, x, w, b, dy, mut=None):
+    """The split3 flavour of a Conv3Case: conv_split3, then the code's own fp32 composition (bias add, 2 x 2 sums). mut: one of
+    SPLIT_MUTATIONS goes to every conv, the others to _conv3."""
+    if mut in SPLIT_MUTATIONS:
+        return _conv3(c, x, w, b, dy, lambda a, q, stride=1: conv_split3(a, q, stride, mut), torch.float32)
+    return _conv3(c, x, w, b, dy, conv_split3, torch.float32, mut)
+
+
+def conv3_autograd(c, x, w, b, dy):
+    """torch.autograd through F.conv2d(stride) and F.interpolate(mode="nearest") in float64: what conv3_ref is held to."""
+    xr = _nchw(x).double().clone().requires_grad_(True)
+    a = F.interpolate(xr, scale_factor=2, mode="nearest") if c.geom == 2 else xr
+    y = F.conv2d(a, w.double(), b.double(), 2 if c.geom == 1 else 1, 1)
+    y.backward(_nchw(dy).double())
+    return {"y": _pixel_rows(y.detach()), "dx": _pixel_rows(xr.grad)}
+
+
+def _wgrad_terms(dyn, xn):
+    """(dy [B, Cout, HW], col [B, 9 Cin, HW]): im2col_f32_kernel's columns c 9 + ky 3 + kx, zero for the taps outside the image."""
+    return dyn.reshape(dyn.shape[0], dyn.shape[1], -1), F.unfold(xn, 3, padding=1)
+
+
+def wgrad_f64(dyn, xn):
+    """conv_wgrad: dW [Cout][Cin][3][3] = dy^T col, the sum over every pixel of every sample."""
+    d, col = _wgrad_terms(dyn.double(), xn.double())
+    return torch.einsum("bop,bkp->ok", d, col).reshape(dyn.shape[1], xn.shape[1], 3, 3)
+
+
+def wgrad_split3(dyn, xn, mut=None):
+    """lin_wgrad's three passes: dy is the activation side (hi, lo, hi), the im2col of x the weight side (hi, hi, lo). mut as
+    conv_split3: the lo_dy hi_col pass without the pixels of each image's last row, hi_dy lo_col without the columns of tap 0, or hi.hi
+    alone; dW_taps_transposed exchanges ky and kx in the result."""
+    assert dyn.dtype == torch.float32 and xn.dtype == torch.float32
+    (dh, col_h), (dl, col_l) = (_wgrad_terms(p.double(), q.double()) for p, q in zip(bf16_split(dyn), bf16_split(xn)))
+    mm = lambda p, q: torch.einsum("bop,bkp->ok", p, q)
+    out = mm(dh, col_h)
+    if mut != "bf16x1":
+        if mut == "lo_hi_last_row":
+            dl = dl.clone()
+            dl[:, :, -dyn.shape[3]:] = 0
+        elif mut == "hi_lo_tap0":
+            col_l = col_l.clone()
+            col_l[:, 0::9] = 0
+        out = out + mm(dl, col_h) + mm(dh, col_l)
+    out = out.float().reshape(dyn.shape[1], xn.shape[1], 3, 3)
+    return out.transpose(2, 3).contiguous() if mut == "dW_taps_transposed" else out
+
+
+def direct_ref(c, x, w, b, dy, clamp=False):
+    """conv3x3_direct's y, the data gradient of the channels [c0, c0 + n) (the direct conv of dy over rows c0 .. c0 + n of W') and dW,
+    float64 -- and y_abs, dx_abs: the same sums over absolute values (+ |b|), what the fp32 chain's bound is made of. clamp (a
+    mutation): the taps outside the image read the nearest pixel instead of 0."""
+    def cv(a, q):
+        if clamp:
+            return F.conv2d(F.pad(a.double(), (1, 1, 1, 1), mode="replicate"), q.double())
+        return conv_f64(a, q)
+    xn, dyn = _nchw(x), _nchw(dy)
+    wt = dgrad_weight(w)[c.c0:c.c0 + c.n]
+    bb = b.double().view(1, -1, 1, 1)
+    return {"y": _pixel_rows(cv(xn, w) + bb), "dx": _pixel_rows(cv(dyn, wt)), "dW": wgrad_f64(dyn, xn),
+            "y_abs": _pixel_rows(conv_f64(xn.abs(), w.abs()) + bb.abs()), "dx_abs": _pixel_rows(conv_f64(dyn.abs(), wt.abs()))}
+
+
+def direct_autograd(c, x, w, b, dy):
+    xr, wr = _nchw(x).double().clone().requires_grad_(True), w.double().clone().requires_grad_(True)
+    y = F.conv2d(xr, wr, b.double(), 1, 1)
+    y.backward(_nchw(dy).double())
+    return {"y": _pixel_rows(y.detach()), "dx": _pixel_rows(xr.grad[:, c.c0:c.c0 + c.n]), "dW": wr.grad}
+
+
+def direct_bounds(c, ref):
+    """conv3x3_direct_kernel is one sequential fp32 chain per output element: acc = b, then 9 Cin_eff fmaf in tap and channel order (fewer
+    at the border). Each fmaf rounds once, so |err| <= 9 Cin_eff 2^-24 (sum |x||w| + |b|) to first order, elementwise; tree_bound allows one
+    rounding more. Cin_eff is the contraction's channel count: Cin for y, Cout for dx."""
+    return {"y": tree_bound(9 * c.Cin, ref["y_abs"]), "dx": tree_bound(9 * c.Cout, ref["dx_abs"])}
+
+
 # ---- the cases
 AttnCase = namedtuple("AttnCase", "D Nq Nk B H regime")
 # both tile sizes (32, and the prep pass's 64) crossed on each side, Nk below one tile, a single query
@@ -334,6 +488,55 @@ GN_SHAPES = [(1, 1, 32), (2, 16, 64), (1, 256, 320), (2, 64, 96)]        # chann
 OFFSETS = [0, 8, 30]
 GEGLU_SHAPES = [(1, 1), (3, 255), (5, 257), (188, 1280)]
 DOT_SIZES = [1, 1023, 1025, 1 << 18, (1 << 18) + 1, 3 * (1 << 16) + 7 + (1 << 18)]
+
+
+# Ctx::conv3, stride 1 (B, H, W, Cin, Cout): the halo kernel with 8-row tiles of one image forward and the narrow-output family (N = 64)
+# in dgrad; halo with one whole image per tile in both directions; the widest halo image; no power of two, H != W, M = 240 ragged against
+# every tile; M = 192; the deep contraction K = 27 * 640; the 2 x 2 level; 1 x 1, where every tap but the centre is padding
+CONV3_SHAPES = [(2, 32, 32, 64, 128), (8, 16, 16, 128, 128), (1, 64, 64, 64, 128), (1, 12, 20, 192, 128), (3, 8, 8, 128, 320), (2, 8, 8, 640, 320),
+                (2, 2, 2, 128, 128), (1, 1, 1, 64, 64)]
+CONV3_DOWN_SHAPES = [(2, 16, 16, 128), (1, 12, 20, 64), (1, 2, 2, 64), (1, 64, 64, 64)]        # (B, H, W, C) of the input
+CONV3_UP_SHAPES = [(2, 8, 8, 128), (1, 6, 10, 64), (1, 1, 1, 64), (2, 16, 16, 128)]            # the last: a 32 x 32 dgrad at M = 2048, halo
+# conv3x3_direct (B, H, W, Cin, Cout, c0, n): the last conv (C -> 4) three times, the first conv, the inpainting models' (K = 81, padded to
+# 128 in conv_wgrad), the spatial-map models' downsampler slice
+CONV_DIRECT_SHAPES = [(2, 8, 8, 320, 4, 0, 320), (1, 5, 7, 64, 4, 0, 64), (1, 1, 1, 64, 4, 0, 64), (2, 8, 8, 4, 320, 0, 4), (2, 8, 8, 9, 64, 0, 9),
+                      (1, 5, 7, 12, 64, 4, 8)]
+CONV_FAMILIES = ("conv_halo_kernel", "gemm_u_kernel(conv)", "gemm_glds_kernel(conv)")      # what the conv3 list as a whole has to run
+
+
+def conv3_cases():
+    return ([Conv3Case(0, *s) for s in CONV3_SHAPES] + [Conv3Case(1, *s, s[3]) for s in CONV3_DOWN_SHAPES]
+            + [Conv3Case(2, *s, s[3]) for s in CONV3_UP_SHAPES])
+
+
+def direct_cases():
+    return [DirectCase(*s) for s in CONV_DIRECT_SHAPES]
+
+
+def conv_case_id(c):
+    if isinstance(c, Conv3Case):
+        return f"g{c.geom}-{c.B}x{c.H}x{c.W}-{c.Cin}-{c.Cout}"
+    return f"direct-{c.B}x{c.H}x{c.W}-{c.Cin}-{c.Cout}-c{c.c0}n{c.n}"
+
+
+def conv_inputs(c):
+    """Seeded x [B, H, W, Cin] N(0, 1), w N(0, 1) (9 Cin)^-1/2, a bias N(0, 1), dy (shaped like y) N(0, 1) drawn independently."""
+    geom = getattr(c, "geom", 0)
+    gen = torch.Generator().manual_seed(((c.B * 131 + c.H) * 131 + c.W) * 1009 + c.Cin * 17 + c.Cout * 3 + geom + 29 * getattr(c, "c0", 0))
+    Ho, Wo = {0: (c.H, c.W), 1: (c.H // 2, c.W // 2), 2: (2 * c.H, 2 * c.W)}[geom]
+    x = torch.randn(c.B, c.H, c.W, c.Cin, generator=gen)
+    w = torch.randn(c.Cout, c.Cin, 3, 3, generator=gen) / math.sqrt(9 * c.Cin)
+    return x, w, torch.randn(c.Cout, generator=gen), torch.randn(c.B, Ho, Wo, c.Cout, generator=gen)
+
+
+def gemm_kernel_family(rec):
+    """A gemm_plan_log record's kernel family, "(conv)" behind it when the instantiation is the implicit-GEMM 3x3 conv's (A_CONV3 = 1: the
+    fourth template argument of gemm_u_kernel, the last of gemm_glds_kernel); the halo kernel is a conv by itself."""
+    name = rec["kernel"]
+    fam = name.split("<")[0]
+    args = [a.strip() for a in name.split("<", 1)[1].split(">")[0].split(",")] if "<" in name else []
+    conv = (fam == "gemm_u_kernel" and len(args) > 3 and args[3] == "1") or (fam == "gemm_glds_kernel" and args and args[-1] == "1")
+    return fam + ("(conv)" if conv else "")
 
 
 def linear_inputs(M, K, N):
@@ -480,6 +683,43 @@ def run_dot(engine, n, mode, alpha=0.3, scale=0.5):
     cid = case_id((n, f"mode{mode}"))
     row = _reduction_row(cid, "out", got["out"], terms.sum().reshape(1), tree_bound(dot_chain(n), terms.abs().sum().reshape(1)))
     return [row], [f"{cid} {p}" for p in problems]
+
+
+def run_conv3(engine, c, kernels=None):
+    """y and dx of gl_op_train_conv3 against conv3_ref, split-family bound. kernels (a dict): kernels[case id] = the kernel families of
+    the GEMM plan log for the case's launches."""
+    x, w, b, dy = conv_inputs(c)
+    ref, flav = conv3_ref(c, x, w, b, dy), conv3_split3(c, x, w, b, dy)
+    shapes = {"y": ref["y"].shape, "dx": x.shape}
+    cid = conv_case_id(c)
+    engine.gemm_plan_log_clear()
+    got, problems = _twice(lambda out: engine.op_train_conv3(x, w, b, c.geom, dy=dy, out=out), shapes, device=engine.device)
+    if kernels is not None:
+        kernels[cid] = sorted({gemm_kernel_family(r) for r in engine.gemm_plan_log()[0]})
+    return _rows_of(cid, got, ref, flav, split_family_bound, ("y", "dx")), [f"{cid} {p}" for p in problems]
+
+
+def conv3_kernels(engine, c):
+    """The kernel families one forward + backward of the case launches (no reference is computed)."""
+    x, w, b, dy = conv_inputs(c)
+    engine.gemm_plan_log_clear()
+    engine.op_train_conv3(x, w, b, c.geom, dy=dy)
+    return sorted({gemm_kernel_family(r) for r in engine.gemm_plan_log()[0]})
+
+
+def run_conv_direct(engine, c):
+    """y and dx of gl_op_train_conv_direct elementwise against the fp32 chain's bound (direct_bounds), dW in the split family."""
+    x, w, b, dy = conv_inputs(c)
+    ref = direct_ref(c, x, w, b, dy)
+    bounds = direct_bounds(c, ref)
+    dW3 = wgrad_split3(_nchw(dy), _nchw(x))
+    shapes = {"y": ref["y"].shape, "dx": ref["dx"].shape, "dW": w.shape}
+    call = lambda out: engine.op_train_conv_direct(x, w, b, c0=c.c0, n=c.n, dy=dy, out=out)
+    got, problems = _twice(call, shapes, device=engine.device)
+    cid = conv_case_id(c)
+    rows = [_reduction_row(cid, n, got[n], ref[n], bounds[n]) for n in ("y", "dx")]
+    rows.append((cid, "dW", rel_max(got["dW"], ref["dW"]), split_family_bound(rel_max(dW3, ref["dW"]))))
+    return rows, [f"{cid} {p}" for p in problems]
 
 
 def format_rows(rows):
