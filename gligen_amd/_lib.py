@@ -1,6 +1,6 @@
 """ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
 include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h, include/gligen_amd_train_fusers.h, include/gligen_amd_train_prims.h,
-include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_ffn_rows.h, include/gligen_amd_norm.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h, include/gligen_amd_lora.h, include/gligen_amd_tiling.h and include/gligen_amd_train_lora.h).
+include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_ffn_rows.h, include/gligen_amd_norm.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h, include/gligen_amd_lora.h, include/gligen_amd_tiling.h, include/gligen_amd_train_lora.h and include/gligen_amd_train_run.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -252,6 +252,20 @@ TRAINER_SYMBOLS = {
     "gl_op_adamw_ema_step": (_I, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _I, _P]),
 }
 
+# every symbol include/gligen_amd_train_run.h declares (gradient accumulation, the global norm and its clipping coefficient, the clipped
+# AdamW (+ EMA) update, per-sample loss weights for the next training step)
+_D = C.c_double
+TRAIN_RUN_SYMBOLS = {
+    "gl_op_grad_accumulate": (_I, [_P, _P, _P, C.c_int64, _I, _I, _P]),
+    "gl_grad_sqnorm_partials": (C.c_int64, [C.c_int64]),
+    "gl_op_grad_sqnorm": (_I, [_P, _P, C.c_int64, _P, _P]),
+    "gl_op_clip_coef": (_I, [_P, _P, C.c_int64, C.c_float, _P, _P]),
+    "gl_op_adamw_clip_step": (_I, [_P, _P, _P, _P, _P, C.c_int64, _D, _D, _D, _D, _D, _I, _P, _P]),
+    "gl_op_adamw_ema_clip_step": (_I, [_P, _P, _P, _P, _P, _P, C.c_int64, _D, _D, _D, _D, _D, _D, _I, _P, _P]),
+    "gl_train_set_loss_weights": (_I, [_P, _P, _I]),
+}
+GRAD_ACCUM_MODES = {"first": 0, "middle": 1, "last": 2}   # = GL_GRAD_ACCUM_*
+
 # every symbol include/gligen_amd_sampler.h declares (how the sampler schedules the guidance pair)
 SAMPLER_SYMBOLS = {
     "gl_set_cfg_shared_prefix": (_I, [_I]),
@@ -396,7 +410,8 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS, **TRAIN_PRIM_SYMBOLS,
-                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **FFN_ROWS_SYMBOLS, **NORM_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS, **TILING_SYMBOLS, **TRAIN_LORA_SYMBOLS}.items():
+                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **FFN_ROWS_SYMBOLS, **NORM_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS, **TILING_SYMBOLS, **TRAIN_LORA_SYMBOLS,
+                              **TRAIN_RUN_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res
         fn.argtypes = args

@@ -13,6 +13,8 @@
 #include "../../include/gligen_amd_train_prims.h"
 #include "../../include/gligen_amd_train_lora.h"
 #include "../../include/gligen_amd_trainer.h"
+#include "../../include/gligen_amd_train_run.h"
+#include "train_run.h"
 #include "../../include/gligen_amd_sampler.h"
 #include "../../include/gligen_amd_gemm_plans.h"
 #include "../../include/gligen_amd_attention_core.h"
@@ -843,6 +845,64 @@ int gl_op_adamw_ema_step(gl_ctx* ctx, float* p, const float* g, float* m, float*
     return gl::adamw_ema_step(p, g, m, v, ema, (size_t)n, lr, beta1, beta2, eps, weight_decay, ema_rate, step, S(s));
 }
 
+// ---- include/gligen_amd_train_run.h: accumulation, norm, clipping coefficient, clipped update, loss weights (train_run.hip)
+static_assert(GL_GRAD_NORM_CHUNK == gl::kGradNormChunk && GL_GRAD_NORM_CHAIN == gl::kGradNormChain, "gligen_amd_train_run.h out of step with train_run.h");
+static_assert(GL_GRAD_ACCUM_FIRST == gl::GRAD_ACCUM_FIRST && GL_GRAD_ACCUM_MIDDLE == gl::GRAD_ACCUM_MIDDLE && GL_GRAD_ACCUM_LAST == gl::GRAD_ACCUM_LAST,
+              "gligen_amd_train_run.h out of step with train_run.h");
+
+int gl_op_grad_accumulate(gl_ctx* ctx, float* acc, float* g, int64_t n, int mode, int k, gl_stream s) {
+    NEED(ctx);
+    if (!acc || !g) return gl::set_error(GL_ERR_ARG, "gl_op_grad_accumulate: null pointer");
+    if (n < 0) return gl::set_error(GL_ERR_ARG, "gl_op_grad_accumulate: n = %lld is negative", (long long)n);
+    if (k < 1) return gl::set_error(GL_ERR_ARG, "gl_op_grad_accumulate: k = %d micro-batches, at least 1", k);
+    if (mode < GL_GRAD_ACCUM_FIRST || mode > GL_GRAD_ACCUM_LAST) return gl::set_error(GL_ERR_ARG, "gl_op_grad_accumulate: mode %d (0 first, 1 middle, 2 last)", mode);
+    return gl::grad_accumulate(acc, g, (size_t)n, mode, k, S(s));
+}
+
+int64_t gl_grad_sqnorm_partials(int64_t n) { return n <= 0 ? 0 : (int64_t)gl::grad_sqnorm_partials((size_t)n); }
+
+int gl_op_grad_sqnorm(gl_ctx* ctx, const float* g, int64_t n, float* partials, gl_stream s) {
+    NEED(ctx);
+    if (!g || !partials) return gl::set_error(GL_ERR_ARG, "gl_op_grad_sqnorm: null pointer");
+    if (n < 0) return gl::set_error(GL_ERR_ARG, "gl_op_grad_sqnorm: n = %lld is negative", (long long)n);
+    return gl::grad_sqnorm(g, (size_t)n, partials, S(s));
+}
+
+int gl_op_clip_coef(gl_ctx* ctx, const float* partials, int64_t count, float max_norm, float* out2, gl_stream s) {
+    NEED(ctx);
+    if (!out2 || (!partials && count != 0)) return gl::set_error(GL_ERR_ARG, "gl_op_clip_coef: null pointer");
+    if (count < 0) return gl::set_error(GL_ERR_ARG, "gl_op_clip_coef: count = %lld is negative", (long long)count);
+    if (!(max_norm > 0.f)) return gl::set_error(GL_ERR_ARG, "gl_op_clip_coef: max_norm %g is not > 0", (double)max_norm);
+    return gl::clip_coef(partials, (size_t)count, max_norm, out2, S(s));
+}
+
+int gl_op_adamw_clip_step(gl_ctx* ctx, float* p, const float* g, float* m, float* v, int64_t n, double lr, double beta1, double beta2, double eps,
+                          double weight_decay, int step, const float* coef, gl_stream s) {
+    NEED(ctx);
+    if (!p || !g || !m || !v || !coef) return gl::set_error(GL_ERR_ARG, "gl_op_adamw_clip_step: null pointer");
+    if (n < 0) return gl::set_error(GL_ERR_ARG, "gl_op_adamw_clip_step: n = %lld is negative", (long long)n);
+    if (step < 1) return gl::set_error(GL_ERR_ARG, "gl_op_adamw_clip_step: step = %d, steps count from 1", step);
+    return gl::adamw_clip_step(p, g, m, v, nullptr, coef, (size_t)n, lr, beta1, beta2, eps, weight_decay, 0.0, step, S(s));
+}
+
+int gl_op_adamw_ema_clip_step(gl_ctx* ctx, float* p, const float* g, float* m, float* v, float* ema, int64_t n, double lr, double beta1, double beta2,
+                              double eps, double weight_decay, double ema_rate, int step, const float* coef, gl_stream s) {
+    NEED(ctx);
+    if (!p || !g || !m || !v || !ema || !coef) return gl::set_error(GL_ERR_ARG, "gl_op_adamw_ema_clip_step: null pointer");
+    if (n < 0) return gl::set_error(GL_ERR_ARG, "gl_op_adamw_ema_clip_step: n = %lld is negative", (long long)n);
+    if (step < 1) return gl::set_error(GL_ERR_ARG, "gl_op_adamw_ema_clip_step: step = %d, steps count from 1", step);
+    if (!(ema_rate >= 0.0 && ema_rate <= 1.0)) return gl::set_error(GL_ERR_ARG, "gl_op_adamw_ema_clip_step: ema_rate %g is outside [0, 1]", ema_rate);
+    return gl::adamw_clip_step(p, g, m, v, ema, coef, (size_t)n, lr, beta1, beta2, eps, weight_decay, ema_rate, step, S(s));
+}
+
+int gl_train_set_loss_weights(gl_ctx* ctx, const float* w, int B) {
+    NEED(ctx);
+    if (B < 0 || (!w && B != 0) || (w && B == 0)) return gl::set_error(GL_ERR_ARG, "gl_train_set_loss_weights: w [B] with B >= 1, or NULL and 0 to clear");
+    ctx->eng->loss_weights = w;
+    ctx->eng->loss_weights_B = B;
+    return GL_OK;
+}
+
 static const char* const k_train_block_names[GL_TRAIN_BLOCK_PARAMS] = {
     "norm1.weight", "norm1.bias", "attn1.to_q.weight", "attn1.to_k.weight", "attn1.to_v.weight", "attn1.to_out.0.weight", "attn1.to_out.0.bias",
     "fuser.linear.weight", "fuser.linear.bias", "fuser.norm1.weight", "fuser.norm1.bias", "fuser.attn.to_q.weight", "fuser.attn.to_k.weight",
@@ -1079,12 +1139,31 @@ int gl_op_resample_train(gl_ctx* ctx, int mode, int B, int H, int W, int C, cons
     GL_API_END
 }
 
+// gl_train_set_loss_weights (include/gligen_amd_train_run.h): the weights belong to the next training step, which takes them here --
+// before it checks anything, so that it clears them whether it succeeds or fails
+static const float* take_loss_weights(gl_ctx* ctx, int* B) {
+    Engine& eng = *ctx->eng;
+    const float* w = eng.loss_weights;
+    *B = eng.loss_weights_B;
+    eng.loss_weights = nullptr;
+    eng.loss_weights_B = 0;
+    return w;
+}
+
+static void drop_loss_weights(gl_ctx* ctx) {      // (an entry point that fails in front of the shared step)
+    int B;
+    if (ctx && ctx->eng) take_loss_weights(ctx, &B);
+}
+
 // gl_unet_train_step and gl_unet_train_step_lora (include/gligen_amd_train_lora.h): the same iteration, with or without adapters
 static int train_step_discrete(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, int n_params, const char* const* names,
                                const float* const* params, float* const* grads, const gl::TrainLoraAdapter* adapters, int n_adapters, float* eps_out,
                                float* loss, gl_stream s) {
     NEED(ctx);
+    int lw_B = 0;
+    const float* lw = take_loss_weights(ctx, &lw_B);
     if (!cfg || !in || !names || !params || !grads || !loss || n_params <= 0) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step: null pointer");
+    if (lw && lw_B != in->B) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step: %d loss weights were set, the step's batch is %d", lw_B, in->B);
     if (cfg->grounding_kind < 0 || cfg->grounding_kind > 2 || cfg->fuser_kind < 0 || cfg->fuser_kind > 2 || cfg->extra_channels)
         return gl::set_error(GL_ERR_UNSUPPORTED, "gl_unet_train_step: the training step is built for the text, text+image and keypoint tokenizers with gatedSA, gatedSA2 "
                                                  "or gatedCA fusers (fuser_kind 0 / 1 / 2), with or without inpaint_mode (no downsampler channels: inpaint_mode with "
@@ -1106,7 +1185,7 @@ static int train_step_discrete(gl_ctx* ctx, const gl_unet_config* cfg, const gl_
     gl::TrainUNetIn u{in->B, in->H, in->W, in->ctx_T, cfg->grounding_kind == 1 ? 2 * in->Ng : in->Ng, in->Ng, in->x, in->timesteps, in->context, in->boxes,
                       in->masks, in->positive_embeddings, in->text_masks, in->image_masks, in->image_embeddings, in->target, in->fuser_scale, in->checkpoint};
     int rc = gl::unet_train_step(eng.arena(), eng.splitk_ws(), eng.splitk_ws_bytes(), c, u, n_params, names, params, grads, k_train_block_names, eps_out, loss, S(s),
-                                 eng.train_events(), Engine::kTrainEvents, in->use_weight_cache ? eng.train_cache : nullptr, nullptr, adapters, n_adapters);
+                                 eng.train_events(), Engine::kTrainEvents, in->use_weight_cache ? eng.train_cache : nullptr, nullptr, adapters, n_adapters, lw);
     if (rc != GL_OK) throw GlError(rc, gl::last_error());
     eng.train_events_recorded = true;
     GL_API_END
@@ -1121,7 +1200,10 @@ int gl_unet_train_step(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_un
 int gl_unet_train_step_lora(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, int n_params, const char* const* names,
                             const float* const* params, float* const* grads, const gl_lora_adapter* adapters, int n_adapters, float* eps_out,
                             float* loss, gl_stream s) {
-    if (n_adapters < 0 || (n_adapters > 0 && !adapters)) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_lora: null adapter array");
+    if (n_adapters < 0 || (n_adapters > 0 && !adapters)) {
+        drop_loss_weights(ctx);
+        return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_lora: null adapter array");
+    }
     std::vector<gl::TrainLoraAdapter> a((size_t)n_adapters);
     for (int i = 0; i < n_adapters; ++i)
         a[i] = {adapters[i].name, adapters[i].down, adapters[i].up, adapters[i].g_down, adapters[i].g_up, adapters[i].rank, adapters[i].scale};
@@ -1149,7 +1231,10 @@ int gl_lora_wgrad_chunk_rows(int M) { return M < 1 ? 0 : gl::train::lora_wgrad_c
 static int train_step_spatial(const char* what, gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, const gl::TrainSpatialIn& spi, int n_params,
                               const char* const* names, const float* const* params, float* const* grads, float* eps_out, float* loss, gl_stream s) {
     NEED(ctx);
+    int lw_B = 0;
+    const float* lw = take_loss_weights(ctx, &lw_B);
     if (!cfg || !in || !names || !params || !grads || !loss || n_params <= 0) return gl::set_error(GL_ERR_ARG, "%s: null pointer", what);
+    if (lw && lw_B != in->B) return gl::set_error(GL_ERR_ARG, "%s: %d loss weights were set, the step's batch is %d", what, lw_B, in->B);
     if (cfg->inpaint_mode)
         return gl::set_error(GL_ERR_UNSUPPORTED, "%s: inpaint_mode with a spatial-map tokenizer is undefined in the reference (openaimodel.py:445-446); "
                                                  "gl_unet_train_step trains the inpainting models", what);
@@ -1177,7 +1262,7 @@ static int train_step_spatial(const char* what, gl_ctx* ctx, const gl_unet_confi
     gl::TrainUNetIn u{in->B, in->H, in->W, in->ctx_T, Ng, Ng, in->x, in->timesteps, in->context, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr,
                       in->target, in->fuser_scale, in->checkpoint};
     int rc = gl::unet_train_step(eng.arena(), eng.splitk_ws(), eng.splitk_ws_bytes(), c, u, n_params, names, params, grads, k_train_block_names, eps_out, loss, S(s),
-                                 eng.train_events(), Engine::kTrainEvents, in->use_weight_cache ? eng.train_cache : nullptr, &spi);
+                                 eng.train_events(), Engine::kTrainEvents, in->use_weight_cache ? eng.train_cache : nullptr, &spi, nullptr, 0, lw);
     if (rc != GL_OK) throw GlError(rc, gl::last_error());
     eng.train_events_recorded = true;
     GL_API_END
@@ -1185,7 +1270,10 @@ static int train_step_spatial(const char* what, gl_ctx* ctx, const gl_unet_confi
 
 int gl_unet_train_step_spatial(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, const gl_train_spatial_in* sp, int n_params,
                                const char* const* names, const float* const* params, float* const* grads, float* eps_out, float* loss, gl_stream s) {
-    if (!sp) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial: null pointer");
+    if (!sp) {
+        drop_loss_weights(ctx);
+        return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial: null pointer");
+    }
     gl::TrainSpatialIn spi{sp->map, sp->map_channels, sp->map_h, sp->map_w, sp->mask, sp->extra, sp->extra_in_channels, sp->extra_h, sp->extra_w,
                            sp->ds_resize, sp->ds_mode, sp->ds_n_in, sp->ds_mid};
     return train_step_spatial("gl_unet_train_step_spatial", ctx, cfg, in, spi, n_params, names, params, grads, eps_out, loss, s);
@@ -1195,6 +1283,7 @@ int gl_unet_train_step_spatial(gl_ctx* ctx, const gl_unet_config* cfg, const gl_
 int gl_unet_train_step_spatial_classes(gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, const gl_train_spatial_classes_in* sp,
                                        int n_params, const char* const* names, const float* const* params, float* const* grads, float* eps_out,
                                        float* loss, gl_stream s) {
+    if (!sp || !sp->map || !sp->extra) drop_loss_weights(ctx);
     if (!sp) return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial_classes: null pointer");
     if (!sp->map || !sp->extra)
         return gl::set_error(GL_ERR_ARG, "gl_unet_train_step_spatial_classes: the tokenizer's map and grounding_extra_input are both u8 class maps here; one is NULL");

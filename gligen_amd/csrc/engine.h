@@ -246,6 +246,8 @@ class Engine {
     hipEvent_t* train_events();
     bool train_events_recorded = false;
     TrainWeightCache* train_cache = nullptr;   // gl_train_weight_cache: operand copies of the frozen parameters kept across training steps
+    const float* loss_weights = nullptr;       // gl_train_set_loss_weights: per-sample loss weights [loss_weights_B] of the NEXT training step,
+    int loss_weights_B = 0;                    // which clears them
 
     // ---- per-kernel profile of one eager UNetModel.forward: HIP events around every GEMM / conv / attention /
     // norm launch on the stream it is launched on, aggregated by kernel symbol (bench.py's roofline block)

@@ -126,7 +126,9 @@ struct TrainLoraAdapter {
 int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& cfg, const TrainUNetIn& in, int n_params, const char* const* names,
                     const float* const* params, float* const* grads, const char* const* block_names, float* eps_out, float* loss, hipStream_t s,
                     hipEvent_t* grad_events = nullptr, int n_grad_events = 0, TrainWeightCache* cache = nullptr, const TrainSpatialIn* spatial = nullptr,
-                    const TrainLoraAdapter* adapters = nullptr, int n_adapters = 0);
+                    const TrainLoraAdapter* adapters = nullptr, int n_adapters = 0, const float* loss_weights = nullptr);
+// loss_weights (optional) [B] fp32 device: loss = (1/n) sum_b w_b sum_i (y - target)^2 and its gradient, from train_run.hip
+// (gl_train_set_loss_weights); null: mse_loss, every launch and every bit as before.
 // adapters (optional): their gradients are final at the milestone of their SpatialTransformer, like that block's fuser gradients. With
 // none, every launch and every bit is the unadapted step's.
 // grad_events (optional): event j is recorded on `s` when the backward of the j-th SpatialTransformer (module order) has written its

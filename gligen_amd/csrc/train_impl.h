@@ -64,6 +64,7 @@ struct Ctx {
     TrainWeightCache* wc = nullptr;                            // null: every operand copy is built per product in the arena
     const std::unordered_set<const void*>* frozen = nullptr;   // parameter tensors the caller does not update (no gradient asked for)
     const LoraTable* lora = nullptr;                           // adapters in training; null: every launch is the unadapted step's
+    const float* loss_w = nullptr;                             // per-sample loss weights [B] of the UNet step (train_run.hip); null: mse_loss
 
     void ck(int rc) const { if (rc != GL_OK) throw GlError(rc, gl::last_error()); }
     void hip(hipError_t e, const char* what) const { if (e != hipSuccess) throw GlError(GL_ERR_HIP, std::string(what) + ": " + hipGetErrorString(e)); }

@@ -7,6 +7,7 @@
 // reference (trainer.py:217-245), and no input gradient is needed in front of the first fuser. All activations of the forward stay
 // in the arena (no recomputation at this size; DESIGN.md section 9 has the checkpointing plan for the full model).
 #include "train_impl.h"
+#include "train_run.h"
 
 #include <cstring>
 
@@ -390,7 +391,13 @@ OutSaved out_forward_and_loss(const UNetStep& u, const Act& h, float* eps_out, f
     const size_t ny = u.M0 * Co;
     const float* y = conv3x3_direct(c, o.on.a, u.nm.w("out.2.weight"), u.nm.w("out.2.bias"), u.B, u.H0, u.W0, u.mc, Co);
     if (eps_out) c.hip(hipMemcpyAsync(eps_out, y, ny * 4, hipMemcpyDeviceToDevice, c.s), "hipMemcpyAsync");
-    o.gy = c.mse_loss(y, u.in.target, ny, loss);
+    if (c.loss_w) {     // per-sample weights (gl_train_set_loss_weights): the weighted loss and its gradient, train_run.hip
+        float* part = c.f32((size_t)u.B);
+        o.gy = c.f32(ny);
+        c.ck(weighted_mse(y, u.in.target, c.loss_w, u.B, ny / (size_t)u.B, part, o.gy, loss, c.s));
+    } else {
+        o.gy = c.mse_loss(y, u.in.target, ny, loss);
+    }
     return o;
 }
 // -> dL/d(the stream in front of `out`). The out conv's dgrad: the same direct conv on the flipped / transposed weight
@@ -473,7 +480,7 @@ float* layers_backward(const UNetStep& u, std::vector<UNetLayer>& L, const float
 
 int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& cfg, const TrainUNetIn& in, int n_params, const char* const* names,
                     const float* const* params, float* const* grads, const char* const* block_names, float* eps_out, float* loss, hipStream_t s, hipEvent_t* grad_events, int n_grad_events,
-                    TrainWeightCache* cache, const TrainSpatialIn* spatial, const TrainLoraAdapter* adapters, int n_adapters) {
+                    TrainWeightCache* cache, const TrainSpatialIn* spatial, const TrainLoraAdapter* adapters, int n_adapters, const float* loss_weights) {
     try {
         Names nm;
         nm.params = params;
@@ -481,6 +488,7 @@ int unet_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainUNetCfg& c
         for (int i = 0; i < n_params; ++i) nm.idx[names[i]] = i;
         check_trainable_set(cfg, n_params, names, grads, spatial);
         Ctx c{ar, ws, ws_bytes, s};
+        c.loss_w = loss_weights;
         std::unordered_set<const void*> frozen;
         if (cache) {
             for (int i = 0; i < n_params; ++i)

@@ -993,6 +993,61 @@ class Engine:
         check(self.lib.gl_op_adamw_ema_step(self._ctx, _ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), p.numel(), float(lr), float(betas[0]), float(betas[1]),
                                             float(eps), float(weight_decay), float(ema_rate), int(step), _stream(self.device)))
 
+    # ---- include/gligen_amd_train_run.h: gradient accumulation, the global norm, the clipping coefficient, the clipped update
+    GRAD_NORM_GRID = (16384, 64, 6, 4)   # grad_sqnorm_kernel (train_run.hip): elements per partial, squares per thread chain, wave levels, waves
+
+    @staticmethod
+    def _flat(*ts):
+        for t in ts:
+            assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.numel() == ts[0].numel()
+
+    def op_grad_accumulate(self, acc, g, mode: str, k: int):
+        """One micro-batch of a gradient accumulation over flat fp32 tensors (gl_op_grad_accumulate). mode 'first': acc = g; 'middle':
+        acc = acc + g; 'last': g = (acc + g) * fl(1 / k), acc left alone -- the mean of the k gradients lands in the gradient buffer."""
+        self._flat(acc, g)
+        check(self.lib.gl_op_grad_accumulate(self._ctx, _ptr(acc), _ptr(g), g.numel(), _lib.GRAD_ACCUM_MODES[mode], int(k), _stream(self.device)))
+
+    def grad_sqnorm_partials(self, n: int) -> int:
+        """The number of partial sums op_grad_sqnorm writes for n elements: ceil(n / GRAD_NORM_GRID[0]), a function of n alone."""
+        return int(self.lib.gl_grad_sqnorm_partials(int(n)))
+
+    def op_grad_sqnorm(self, g, partials=None):
+        """The squared L2 norm of a flat fp32 tensor as fp32 partial sums in a fixed order (gl_op_grad_sqnorm), written to `partials`
+        (grad_sqnorm_partials(g.numel()) floats; created when None) and returned."""
+        self._flat(g)
+        count = self.grad_sqnorm_partials(g.numel())
+        if partials is None:
+            partials = torch.empty(count, device=g.device, dtype=torch.float32)
+        assert partials.is_cuda and partials.dtype == torch.float32 and partials.is_contiguous() and partials.numel() == count
+        check(self.lib.gl_op_grad_sqnorm(self._ctx, _ptr(g), g.numel(), _ptr(partials), _stream(self.device)))
+        return partials
+
+    def op_clip_coef(self, partials, max_norm: float, out2=None):
+        """out2 = (norm, min(1, max_norm / (norm + 1e-6))) from the partial sums of one or several ranges (gl_op_clip_coef): what
+        torch.nn.utils.clip_grad_norm_ computes, left on the device. Returns out2 (fp32 [2])."""
+        assert partials.is_cuda and partials.dtype == torch.float32 and partials.is_contiguous()
+        if out2 is None:
+            out2 = torch.empty(2, device=partials.device, dtype=torch.float32)
+        assert out2.is_cuda and out2.dtype == torch.float32 and out2.is_contiguous() and out2.numel() == 2
+        check(self.lib.gl_op_clip_coef(self._ctx, _ptr(partials), partials.numel(), float(max_norm), _ptr(out2), _stream(self.device)))
+        return out2
+
+    def op_adamw_clip_step(self, p, g, m, v, step, *, coef, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        """op_adamw_step on g * coef (gl_op_adamw_clip_step): coef is a one-element fp32 device tensor (op_clip_coef's out2[1:2]) the
+        kernel reads, so nothing waits for the host; g is not written."""
+        self._flat(p, g, m, v)
+        assert coef.is_cuda and coef.dtype == torch.float32 and coef.numel() == 1
+        check(self.lib.gl_op_adamw_clip_step(self._ctx, _ptr(p), _ptr(g), _ptr(m), _ptr(v), p.numel(), float(lr), float(betas[0]), float(betas[1]),
+                                             float(eps), float(weight_decay), int(step), _ptr(coef), _stream(self.device)))
+
+    def op_adamw_ema_clip_step(self, p, g, m, v, ema, step, *, ema_rate, coef, lr=5e-5, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0):
+        """op_adamw_ema_step on g * coef (gl_op_adamw_ema_clip_step), coef as in op_adamw_clip_step."""
+        self._flat(p, g, m, v, ema)
+        assert coef.is_cuda and coef.dtype == torch.float32 and coef.numel() == 1
+        check(self.lib.gl_op_adamw_ema_clip_step(self._ctx, _ptr(p), _ptr(g), _ptr(m), _ptr(v), _ptr(ema), p.numel(), float(lr), float(betas[0]),
+                                                 float(betas[1]), float(eps), float(weight_decay), float(ema_rate), int(step), _ptr(coef),
+                                                 _stream(self.device)))
+
     @staticmethod
     def count_spatial_transformers(cfg: Mapping) -> int:
         """The number of SpatialTransformers of a UNetModel config, walked as gl_unet_train_step numbers them (openaimodel.py:307-383):
@@ -1020,7 +1075,7 @@ class Engine:
 
     def unet_train_step(self, cfg: Mapping, state_dict: Mapping[str, torch.Tensor], batch: Mapping[str, torch.Tensor], fuser_scale: float = 1.0,
                         trainable=None, grads: Optional[Mapping[str, torch.Tensor]] = None, checkpoint: bool = False, use_weight_cache: bool = False,
-                        adapters=None):
+                        *, loss_weights: Optional[torch.Tensor] = None, adapters=None):
         """One training iteration of the reference (trainer.py:353-392: model(input), mse_loss(model_output, noise), backward) on the
         device (gl_unet_train_step). cfg: UNetModel kwargs -- any tokenizer; cfg["fuser_type"] gatedSA (default), gatedSA2 (a square number
         of grounding tokens and H == W) or gatedCA (no fuser.linear.* keys) --; state_dict: the model's parameters (fp32, on this
@@ -1045,7 +1100,10 @@ class Engine:
         state_dict key of a frozen Linear's weight: gligen_amd.lora_train.adapter_sites), down [r, K], up [N, r], scale and optionally
         g_down / g_up, fp32 tensors on this device used in place; gradients that are not given are created. The layer computes
         x W^T + scale (x down^T) up^T. The adapters' gradients come back as a fourth value, {name: (g_down, g_up)}; `trainable=[]`
-        trains the adapters alone."""
+        trains the adapters alone.
+        `loss_weights` (fp32 [B] on this device; gl_train_set_loss_weights, called right before the step, which clears them): the loss
+        becomes (w[:, None, None, None] * (eps - target) ** 2).mean(), e.g. gligen_amd.train.min_snr_weights(...)[t]; None: mse_loss,
+        the launches and bits of a step without weights."""
         dev = self.device
         c = UNetConfig()
         c.in_channels, c.out_channels, c.model_channels = cfg["in_channels"], cfg["out_channels"], cfg["model_channels"]
@@ -1102,6 +1160,13 @@ class Engine:
         garr = (C.c_void_p * n)(*[(grads[k].data_ptr() if k in grads else None) for k in names])
         eps = torch.empty((B, H * W, c.out_channels), device=dev, dtype=torch.float32)
         loss = torch.zeros(1, device=dev, dtype=torch.float32)
+        if loss_weights is not None:
+            lw = loss_weights
+            if not (torch.is_tensor(lw) and lw.is_cuda and lw.device == torch.device(dev) and lw.dtype == torch.float32 and lw.is_contiguous()
+                    and tuple(lw.shape) == (B,)):
+                raise ValueError(f"unet_train_step: loss_weights is a contiguous fp32 tensor of shape ({B},) on {dev}")
+        # (set right before the step's own call: that call takes the weights and clears them, whatever it returns)
+        weigh = (lambda: check(self.lib.gl_train_set_loss_weights(self._ctx, _ptr(loss_weights), B))) if loss_weights is not None else (lambda: None)
         if sp and (batch[sp["map_key"]].dtype == torch.uint8 or (sp["ds"] and batch["grounding_extra_input"].dtype == torch.uint8)):
             # the semantic-map model from u8 class maps (gl_unet_train_step_spatial_classes): both inputs are class maps
             if not sp["ds"]:
@@ -1119,6 +1184,7 @@ class Engine:
                                  int(bool(checkpoint)), int(bool(use_weight_cache)))
             s = _lib.TrainSpatialClassesIn(cm.data_ptr(), int(cm.shape[1]), int(cm.shape[2]), keep["mask"].data_ptr(), ce.data_ptr(), int(ce.shape[1]), int(ce.shape[2]),
                                            ds["resize"], ds["mode"], ds["n_in"], ds["mid"])
+            weigh()
             check(self.lib.gl_unet_train_step_spatial_classes(self._ctx, C.byref(c), C.byref(u), C.byref(s), n, narr, parr, garr, _ptr(eps), _ptr(loss), _stream(dev)))
             return loss, eps.reshape(B, H, W, c.out_channels).permute(0, 3, 1, 2).contiguous(), grads
         if sp:      # batch: the map under the reference's key, mask, grounding_extra_input (gl_unet_train_step_spatial)
@@ -1135,6 +1201,7 @@ class Engine:
             s = _lib.TrainSpatialIn(m.data_ptr(), int(m.shape[1]), int(m.shape[2]), int(m.shape[3]), keep["mask"].data_ptr(),
                                     extra.data_ptr() if ds else None, *((int(extra.shape[1]), int(extra.shape[2]), int(extra.shape[3])) if ds else (0, 0, 0)),
                                     ds["resize"] if ds else 0, ds["mode"] if ds else 0, ds["n_in"] if ds else 0, ds["mid"] if ds else 0)
+            weigh()
             check(self.lib.gl_unet_train_step_spatial(self._ctx, C.byref(c), C.byref(u), C.byref(s), n, narr, parr, garr, _ptr(eps), _ptr(loss), _stream(dev)))
             return loss, eps.reshape(B, H, W, c.out_channels).permute(0, 3, 1, 2).contiguous(), grads
         keep = dict(x=x_rows, t=_f32(batch["timesteps"], dev), ctx=_f32(batch["context"], dev), boxes=_f32(batch["points" if kp else "boxes"], dev),
@@ -1147,8 +1214,10 @@ class Engine:
                              keep["ie"].data_ptr() if ti else None, int(bool(checkpoint)), int(bool(use_weight_cache)))
         if adapters is not None:
             aarr, agrads = self._lora_adapters(adapters, state_dict)
+            weigh()
             check(self.lib.gl_unet_train_step_lora(self._ctx, C.byref(c), C.byref(u), n, narr, parr, garr, aarr, len(aarr), _ptr(eps), _ptr(loss), _stream(dev)))
             return loss, eps.reshape(B, H, W, c.out_channels).permute(0, 3, 1, 2).contiguous(), grads, agrads
+        weigh()
         check(self.lib.gl_unet_train_step(self._ctx, C.byref(c), C.byref(u), n, narr, parr, garr, _ptr(eps), _ptr(loss), _stream(dev)))
         return loss, eps.reshape(B, H, W, c.out_channels).permute(0, 3, 1, 2).contiguous(), grads
 

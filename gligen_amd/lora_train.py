@@ -143,7 +143,8 @@ class LoraTrainStep(TrainStep):
     def __init__(self, engine, cfg: Mapping, state_dict: Mapping[str, torch.Tensor], spec: LoraSpec, lr: Union[float, Callable[[int], float]] = 1e-4,
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, bucket_mb: float = 128.0, world: Optional[int] = None,
                  checkpoint: bool = True, drop_prob: float = 0.0, rng: Optional[random.Random] = None, broadcast: bool = True, overlap: bool = True,
-                 cache_frozen: bool = True, train_base: bool = False, seed: int = 0, adapters: Optional[Mapping[str, torch.Tensor]] = None):
+                 cache_frozen: bool = True, train_base: bool = False, seed: int = 0, adapters: Optional[Mapping[str, torch.Tensor]] = None,
+                 accumulate: int = 1, max_grad_norm: Optional[float] = None):
         self.engine, self.cfg, self.spec = engine, dict(cfg), spec
         self.exchange_even_alone = False
         dev = engine.device
@@ -202,9 +203,12 @@ class LoraTrainStep(TrainStep):
             self.adapters.append(dict(name=w, down=self.pbuf.views[path + DOWN], up=self.pbuf.views[path + UP], g_down=self.gbuf.views[path + DOWN],
                                       g_up=self.gbuf.views[path + UP], scale=spec.scale))
         self._base_grads = {k: self.gbuf.views[k] for k in self.base_names}
+        self._init_run(accumulate, max_grad_norm)     # gradient accumulation and norm clipping, as TrainStep's
 
-    def _forward_backward(self, batch, fuser_scale):
+    def _forward_backward(self, batch, fuser_scale, loss_weights=None):
         kw = dict(use_weight_cache=True) if self.cache_frozen else {}
+        if loss_weights is not None:
+            kw["loss_weights"] = loss_weights
         loss, eps, _, _ = self.engine.unet_train_step(self.cfg, self.params, batch, fuser_scale=fuser_scale, grads=self._base_grads, checkpoint=self.checkpoint,
                                                       adapters=self.adapters, **kw)
         return loss, eps
@@ -227,6 +231,7 @@ class LoraTrainStep(TrainStep):
             if tuple(tensors[k].shape) != tuple(self.pbuf.views[k].shape):
                 raise ValueError(f"load_adapter_tensors: '{k}' is {tuple(tensors[k].shape)}, this step's is {tuple(self.pbuf.views[k].shape)}")
             self.pbuf.views[k].copy_(tensors[k].to(device=self.pbuf.views[k].device, dtype=torch.float32))
+        self.micro = 0          # (an open group of micro-batches belonged to the adapters just replaced)
 
     def adapter_state_dict(self, dtype=torch.float32) -> Dict[str, torch.Tensor]:
         """The adapter in kohya's form (CPU tensors): what gligen_amd.lora.parse_adapter / apply_loras and `--lora` read."""

@@ -52,6 +52,19 @@ def warmup_schedule(base_lr: float, warmup_steps: int, total_iters: Optional[int
     return lr
 
 
+def min_snr_weights(alphas_cumprod, gamma: float, device=None) -> torch.Tensor:
+    """Min-SNR-gamma loss weights for an eps-prediction model (Hang et al. 2023, "Efficient Diffusion Training via Min-SNR Weighting
+    Strategy"; kohya's --min_snr_gamma): one weight per timestep, min(snr, gamma) / snr with snr = a / (1 - a) for a = alphas_cumprod[t],
+    formed in float64 and stored as fp32 (on `device` when given). 1 exactly where snr <= gamma, below 1 at the low-noise timesteps.
+    weights[t] for a batch's timesteps t are Engine.unet_train_step's / TrainStep.step's loss_weights."""
+    if not float(gamma) > 0.0:
+        raise ValueError(f"min_snr_weights: gamma {gamma!r} is not > 0")
+    a = torch.as_tensor(alphas_cumprod).detach().to(device="cpu", dtype=torch.float64).reshape(-1)
+    snr = a / (1.0 - a)
+    w = (torch.clamp(snr, max=float(gamma)) / snr).to(torch.float32)
+    return w if device is None else w.to(device).contiguous()
+
+
 def null_grounding(batch: Mapping[str, torch.Tensor]) -> Dict[str, torch.Tensor]:
     """GroundingNetInput.get_null_input (grounding_input/*_tokinzer_input.py:30-45): every grounding tensor zeroed. A semantic map given
     as a torch.uint8 class map becomes 255 everywhere instead, the "no class" of grounding_input/_base.py: zeros would read as class 0
@@ -148,13 +161,33 @@ class TrainStep:
     parameters (deepcopy(self.model)); every bucket update is then Engine.op_adamw_ema_step, AdamW and the average of the updated
     parameters in one pass on the stream the update ran on before: the same parameter bits, and the same EMA bits from both schedules.
 
+    accumulate = K (1: the calls above and nothing else): step() is called once per MICRO-batch. Calls 1 .. K - 1 of a group run
+    forward + backward and one Engine.op_grad_accumulate per bucket into one more bucket set `self.acc` (allocated only when K > 1) --
+    no collective, as under DDP's no_sync, no update, `steps` does not move --; call K writes the mean (g_1 + .. + g_K) / K into the
+    gradient buckets per bucket in front of that bucket's exchange, so the exchange and the update read what they read without
+    accumulation. `steps`, the LR schedule and AdamW's bias correction count optimizer steps; the guidance drop is drawn per call;
+    `micro` is the position in the group, `at_boundary` whether none is open; the loaders reset the group.
+
+    max_grad_norm (None or 0: off): torch.nn.utils.clip_grad_norm_ over the whole trainable set, after the average over the ranks and
+    the micro-batches. Behind bucket i's exchange, on its stream, Engine.op_grad_sqnorm writes that bucket's partial sums (the zero
+    padding of a bucket included); behind the last bucket Engine.op_clip_coef forms (norm, coefficient) on the device and every bucket's
+    update is Engine.op_adamw_clip_step / op_adamw_ema_clip_step, which reads the coefficient there: no host sync. Under overlap the
+    exchanges and norm passes stay under the backward, the updates wait for the coefficient -- inherent to a global norm.
+    `grad_norm` is the device tensor [1] with the norm before clipping, the same on every rank. The gradient buckets keep the
+    UNCLIPPED average (torch scales .grad in place; nothing here reads it after the update).
+
+    step(..., loss_weights=w): per-sample loss weights, fp32 [B] on the device (Engine.unet_train_step; min_snr_weights).
+
+    Both schedules and the host-side one give the same bits with every combination of these, and two runs give the same bits.
+
     state_dict should be in module order (what UNetModel.state_dict() gives): the order of its trainable names is the parameter
     numbering of torch_optimizer_state_dict."""
 
     def __init__(self, engine, cfg: Mapping, state_dict: Mapping[str, torch.Tensor], lr: Union[float, Callable[[int], float]] = 5e-5,
                  weight_decay: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, bucket_mb: float = 128.0, world: Optional[int] = None,
                  checkpoint: bool = True, drop_prob: float = 0.0, rng: Optional[random.Random] = None, broadcast: bool = True, overlap: bool = True,
-                 cache_frozen: bool = True, exchange_even_alone: bool = False, ema_rate: Optional[float] = None):
+                 cache_frozen: bool = True, exchange_even_alone: bool = False, ema_rate: Optional[float] = None, accumulate: int = 1,
+                 max_grad_norm: Optional[float] = None):
         self.engine, self.cfg = engine, dict(cfg)
         # (a world of one rank issues no collective; True sends the buckets through the collectives anyway -- the one-GPU test of the
         # overlapped schedule with RCCL's kernels on the communication stream, tests/test_ops_gpu.py)
@@ -209,48 +242,113 @@ class TrainStep:
         if self.cache_frozen:
             engine.train_weight_cache(False)       # (copies keyed by the addresses of another TrainStep's tensors must not outlive them)
             engine.train_weight_cache(True)
+        self._init_run(accumulate, max_grad_norm)
 
     def lr_at(self, step: int) -> float:
         return float(self.lr(step)) if callable(self.lr) else self.lr
 
-    def step(self, batch: Mapping[str, torch.Tensor], fuser_scale: float = 1.0):
-        """One iteration: forward, loss, backward, gradient average over the ranks, AdamW. Returns (loss of this rank, eps)."""
+    def _init_run(self, accumulate: int, max_grad_norm: Optional[float]) -> None:
+        """Gradient accumulation and norm clipping (the constructor's accumulate / max_grad_norm; LoraTrainStep shares it): the extra
+        bucket set when K > 1, the partial sums of every bucket side by side and the (norm, coefficient) pair when clipping."""
+        if int(accumulate) != accumulate or int(accumulate) < 1:
+            raise ValueError(f"TrainStep: accumulate {accumulate!r} is not a number of micro-batches >= 1")
+        self.accumulate = int(accumulate)
+        if max_grad_norm is not None and not float(max_grad_norm) >= 0.0:
+            raise ValueError(f"TrainStep: max_grad_norm {max_grad_norm!r} is negative or NaN (None or 0: no clipping)")
+        self.max_grad_norm = float(max_grad_norm) if max_grad_norm else None
+        self.micro = 0                      # micro-batches of the current group already summed
+        self.acc = [torch.zeros_like(b) for b in self.gbuf.buckets] if self.accumulate > 1 else None
+        self.grad_norm = None               # with clipping: the norm BEFORE clipping of the last optimizer step's gradient, a device tensor [1]
+        if self.max_grad_norm is not None:
+            counts = [self.engine.grad_sqnorm_partials(b.numel()) for b in self.gbuf.buckets]
+            self._partials = torch.zeros(sum(counts), device=self.engine.device, dtype=torch.float32)
+            ends = [sum(counts[:i + 1]) for i in range(len(counts))]
+            self._partial_slices = [self._partials[e - c:e] for c, e in zip(counts, ends)]
+            self._clip = torch.zeros(2, device=self.engine.device, dtype=torch.float32)
+            self.grad_norm, self._coef = self._clip[0:1], self._clip[1:2]
+
+    @property
+    def at_boundary(self) -> bool:
+        """No group of micro-batches is open: the last call of step() took an optimizer step (or none was made yet)."""
+        return self.micro == 0
+
+    def step(self, batch: Mapping[str, torch.Tensor], fuser_scale: float = 1.0, loss_weights: Optional[torch.Tensor] = None):
+        """One micro-batch: forward, loss, backward; with accumulate = K the gradients of calls 1 .. K - 1 of a group are summed and
+        nothing else happens; call K (every call when K = 1) averages them, exchanges the average over the ranks and takes the
+        optimizer step, clipped to max_grad_norm when set. Returns (loss of this rank and micro-batch, eps)."""
         if self.drop_prob > 0.0 and self.rng.random() < self.drop_prob:      # random drop for guidance (openaimodel.py:428)
             batch = null_grounding(batch)
-        loss, eps = self._forward_backward(batch, fuser_scale)
+        loss, eps = self._forward_backward(batch, fuser_scale) if loss_weights is None else self._forward_backward(batch, fuser_scale, loss_weights)
+        nb = len(self.gbuf.buckets)
+        K = self.accumulate
+        if K > 1:
+            self.micro += 1
+            if self.micro < K:      # inside a group: the sum alone, behind the backward -- no collective (DDP's no_sync), no update
+                for i in range(nb):
+                    self.engine.op_grad_accumulate(self.acc[i], self.gbuf.buckets[i], "first" if self.micro == 1 else "middle", K)
+                return loss, eps
+            self.micro = 0
         self.steps += 1
         lr = self.lr_at(self.steps)
+        clip = self.max_grad_norm is not None
+        kw = dict(lr=lr, betas=self.betas, eps=self.eps, weight_decay=self.wd)
+        if clip:                    # the same updates on g * coef; coef stays on the device
+            kw["coef"] = self._coef
         if self.ema is None:
-            upd = lambda i: self.engine.op_adamw_step(self.pbuf.buckets[i], self.gbuf.buckets[i], self.m[i], self.v[i], self.steps, lr=lr, betas=self.betas,
-                                                      eps=self.eps, weight_decay=self.wd)
+            op = self.engine.op_adamw_clip_step if clip else self.engine.op_adamw_step
+            upd = lambda i: op(self.pbuf.buckets[i], self.gbuf.buckets[i], self.m[i], self.v[i], self.steps, **kw)
         else:       # AdamW and the EMA of the updated parameters in one pass over the bucket
-            upd = lambda i: self.engine.op_adamw_ema_step(self.pbuf.buckets[i], self.gbuf.buckets[i], self.m[i], self.v[i], self.ema[i], self.steps,
-                                                          ema_rate=self.ema_rate, lr=lr, betas=self.betas, eps=self.eps, weight_decay=self.wd)
-        nb = len(self.gbuf.buckets)
+            op = self.engine.op_adamw_ema_clip_step if clip else self.engine.op_adamw_ema_step
+            upd = lambda i: op(self.pbuf.buckets[i], self.gbuf.buckets[i], self.m[i], self.v[i], self.ema[i], self.steps, ema_rate=self.ema_rate, **kw)
         alone = self.exchange_even_alone
-        if not self.overlap:                        # backward, every collective, every update: one stream
-            for i in range(nb):
-                self.gbuf.all_reduce_bucket(i, average=True, even_alone=alone)
+
+        def exchange(i):            # bucket i: the mean over the group into the gradient buffer, the mean over the ranks, its share of the norm
+            if K > 1:
+                self.engine.op_grad_accumulate(self.acc[i], self.gbuf.buckets[i], "last", K)
+            self.gbuf.all_reduce_bucket(i, average=True, even_alone=alone)
+            if clip:
+                self.engine.op_grad_sqnorm(self.gbuf.buckets[i], self._partial_slices[i])
+
+        def clipped_updates():      # a global norm: every update waits for the last bucket's share
+            self.engine.op_clip_coef(self._partials, self.max_grad_norm, self._clip)
             for i in range(nb):
                 upd(i)
+
+        if not self.overlap:                        # backward, every collective, every update: one stream
+            for i in range(nb):
+                exchange(i)
+            if clip:
+                clipped_updates()
+            else:
+                for i in range(nb):
+                    upd(i)
         elif self._comm is None:                    # (a host-side engine: the same per-bucket order without streams)
             for i in range(nb):
                 self.engine.train_wait_grads(self.bucket_ready[i], None)
-                self.gbuf.all_reduce_bucket(i, average=True, even_alone=alone)
-                upd(i)
+                exchange(i)
+                if not clip:
+                    upd(i)
+            if clip:
+                clipped_updates()
         else:
             main = torch.cuda.current_stream(self.engine.device)
             for i in range(nb):                     # bucket i: wait for its last gradient only, exchange, update -- all behind the backward
                 self.engine.train_wait_grads(self.bucket_ready[i], self._comm)
                 with torch.cuda.stream(self._comm):
-                    self.gbuf.all_reduce_bucket(i, average=True, even_alone=alone)
-                    upd(i)
+                    exchange(i)
+                    if not clip:
+                        upd(i)
+            if clip:                                # (the exchanges and the norm passes ran under the backward; the updates cannot)
+                with torch.cuda.stream(self._comm):
+                    clipped_updates()
             main.wait_stream(self._comm)            # the next forward reads the updated parameters
         return loss, eps
 
-    def _forward_backward(self, batch, fuser_scale):
+    def _forward_backward(self, batch, fuser_scale, loss_weights=None):
         """Forward, loss and backward into the gradient buckets: (loss, eps). (gligen_amd.lora_train.LoraTrainStep passes its adapters.)"""
         kw = dict(use_weight_cache=True) if self.cache_frozen else {}
+        if loss_weights is not None:
+            kw["loss_weights"] = loss_weights
         loss, eps, _ = self.engine.unet_train_step(self.cfg, self.params, batch, fuser_scale=fuser_scale, grads=self.gbuf.views, checkpoint=self.checkpoint, **kw)
         return loss, eps
 
@@ -273,6 +371,7 @@ class TrainStep:
                 mb[off:off + n].view(shape).copy_(state["exp_avg"][name])
                 vb[off:off + n].view(shape).copy_(state["exp_avg_sq"][name])
         self.steps = int(state["steps"])
+        self.micro = 0
 
     def _slices(self, bufs):
         """name -> the view of `bufs` (a buffer set in the bucket layout) that belongs to that trainable tensor."""
@@ -353,6 +452,7 @@ class TrainStep:
         if len(steps) > 1:
             raise ValueError(f"load_torch_optimizer_state_dict: the parameters are at different steps {sorted(steps)}; this step keeps one count")
         self.steps = steps.pop() if steps else 0
+        self.micro = 0
         g0 = groups[0]
         self.betas, self.eps, self.wd = tuple(float(b) for b in g0["betas"]), float(g0["eps"]), float(g0["weight_decay"])
         if not callable(self.lr):
@@ -362,6 +462,7 @@ class TrainStep:
         """Parameters back into the flat buffers (trainable) / the frozen set, in place: the views the engine reads stay the same."""
         for k, t in state_dict.items():
             self.params[k].copy_(t.to(device=self.params[k].device, dtype=torch.float32))
+        self.micro = 0                     # (an open group of micro-batches belonged to the parameters just replaced)
         if self.cache_frozen:              # frozen tensors may have changed under the cached operand copies
             self.engine.train_weight_cache(False)
             self.engine.train_weight_cache(True)

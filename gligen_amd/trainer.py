@@ -18,7 +18,12 @@ writes the checkpoints and, started again, continues from out/checkpoint_latest.
 
 With lora_rank in the config (--lora_rank, --lora_alpha, --lora_families, --lora_out) the run trains LoRA adapters over the frozen
 model instead (gligen_amd.lora_train.LoraTrainStep; lora_train_base: and the reference's set with them): the checkpoint carries the
-adapter tensors under `lora` next to their optimizer state, and lora_out is rewritten in kohya's format at every save point."""
+adapter tensors under `lora` next to their optimizer state, and lora_out is rewritten in kohya's format at every save point.
+
+gradient_accumulation_steps K (--gradient_accumulation_steps), max_grad_norm (--max_grad_norm; 0: off) and min_snr_gamma
+(--min_snr_gamma) are the usual switches of an SD-1.x trainer: an iteration draws K batches and takes one optimizer step on their mean
+gradient (TrainStep's accumulate), clipped to a global norm, with the eps-prediction min-SNR weight of every sample's timestep on its
+loss. total_iters, warmup_steps and save_every_iters count optimizer steps; checkpoints are written between groups only."""
 from __future__ import annotations
 
 import argparse
@@ -31,7 +36,7 @@ from typing import Callable, Dict, Iterator, Mapping, Optional, Union
 
 import torch
 
-from .train import TrainStep, add_input_channels, warmup_schedule
+from .train import TrainStep, add_input_channels, min_snr_weights, warmup_schedule
 
 CKPT_KEYS = ("model", "text_encoder", "autoencoder", "diffusion", "opt", "scheduler", "iters", "config_dict")   # trainer.py:472-480 (+ "ema", "rng")
 SPATIAL = ("canny", "hed", "depth", "normal", "sem")
@@ -84,10 +89,12 @@ class Trainer:
     weight_decay, warmup_steps, scheduler_type (constant | cosine), total_iters, enable_ema, ema_rate, inpaint_mode, save_every_iters,
     output_dir, ckpt (a first-stage checkpoint whose "model" is loaded over model_state_dict, trainer.py:211-213), optionally
     grounding_tokenizer_input / grounding_downsampler_input ({target}; derived from the tokenizer's modality when absent) and
-    disable_inference_in_training. model_state_dict: the starting weights in module order; a first conv narrower than the model's
+    disable_inference_in_training, gradient_accumulation_steps (K, default 1: an iteration draws K batches), max_grad_norm (default
+    and 0: no clipping), min_snr_gamma (default: uniform loss weights). model_state_dict: the starting weights in module order; a first conv narrower than the model's
     (inpaint_mode: 5 channels, a grounding downsampler: its out_dim) is zero-extended (trainer.py:189-193).
     batches: any iterator of dicts with the keys the reference's datasets produce (image or z, caption or context, the grounding
-    tensors), or a callable starting_iter -> iterator, which lets a resumed run continue its data where it stopped.
+    tensors), or a callable n -> iterator, called with the number of batches already consumed (starting_iter * K), which lets a
+    resumed run continue its data where it stopped.
     autoencoder / text_encoder: this package's AutoencoderKL / FrozenCLIPEmbedder on the device; without them the batch carries
     z / context. Every random draw of get_input comes from one torch.Generator on the device seeded seed + rank; the guidance drop
     (10 % of the iterations train on the null grounding input, openaimodel.py:428) from a random.Random(seed).
@@ -131,6 +138,14 @@ class Trainer:
         self.cosine_total = self.total_iters if stype == "cosine" else None
         self.enable_ema = bool(self.config.get("enable_ema", False))
         self.lora_rank = int(self.config.get("lora_rank") or 0)
+        self.accumulate = int(self.config.get("gradient_accumulation_steps") or 1)
+        if self.accumulate < 1:
+            raise ValueError(f"gradient_accumulation_steps {self.accumulate}: at least 1")
+        self.max_grad_norm = float(self.config.get("max_grad_norm") or 0.0) or None
+        self.min_snr_gamma = float(self.config.get("min_snr_gamma") or 0.0) or None
+        # (the checkpoint's config_dict carries the three keys: a resumed run is held to the same K)
+        self.config.update(gradient_accumulation_steps=self.accumulate, max_grad_norm=self.max_grad_norm, min_snr_gamma=self.min_snr_gamma)
+        run = dict(accumulate=self.accumulate, max_grad_norm=self.max_grad_norm)
         if self.lora_rank:
             from .lora_train import LoraSpec, LoraTrainStep
             if self.enable_ema:
@@ -139,12 +154,15 @@ class Trainer:
             self.ts = LoraTrainStep(engine, cfg, sd, spec, lr=warmup_schedule(self.base_lr, self.warmup_steps, self.cosine_total),
                                     weight_decay=float(self.config.get("weight_decay", 0.0)), bucket_mb=bucket_mb, world=world, checkpoint=checkpoint,
                                     drop_prob=drop_prob, rng=random.Random(seed), overlap=overlap, train_base=bool(self.config.get("lora_train_base", False)),
-                                    seed=seed)
+                                    seed=seed, **run)
         else:
             self.ts = TrainStep(engine, cfg, sd, lr=warmup_schedule(self.base_lr, self.warmup_steps, self.cosine_total),
                                 weight_decay=float(self.config.get("weight_decay", 0.0)), bucket_mb=bucket_mb, world=world, checkpoint=checkpoint,
                                 drop_prob=drop_prob, rng=random.Random(seed), overlap=overlap,
-                                ema_rate=float(self.config.get("ema_rate", 0.9999)) if self.enable_ema else None)
+                                ema_rate=float(self.config.get("ema_rate", 0.9999)) if self.enable_ema else None, **run)
+        # min(snr, gamma) / snr per timestep (eps-prediction), indexed with the batch's t in run_one_step
+        self.snr_weights = min_snr_weights(self.diffusion.alphas_cumprod, self.min_snr_gamma, dev) if self.min_snr_gamma else None
+        self._loss_sum = None
         self.generator = torch.Generator(device=dev).manual_seed(int(seed) + self.rank)
         self.grounding_tokenizer_input = instantiate_from_config(self.config.get("grounding_tokenizer_input") or _plugin(kind, "tokinzer_input.GroundingNetInput"))
         self.grounding_downsampler_input = None
@@ -161,7 +179,7 @@ class Trainer:
             resume = os.path.join(self.output_dir, "checkpoint_latest.pth")
         if resume:
             self.load(resume)
-        self.batches = batches(self.starting_iter) if (callable(batches) and not hasattr(batches, "__next__")) else batches
+        self.batches = batches(self.starting_iter * self.accumulate) if (callable(batches) and not hasattr(batches, "__next__")) else batches
 
     # ---- one iteration ---------------------------------------------------------------------------------------------------------
     @torch.no_grad()
@@ -180,28 +198,38 @@ class Trainer:
         return out
 
     def run_one_step(self, batch: Mapping) -> torch.Tensor:
-        """trainer.py:353-371 + 382-391: one iteration on `batch` (`iters` counts it); returns the loss as a device tensor (no host sync)."""
+        """trainer.py:353-371 + 382-391: one micro-batch -- with gradient_accumulation_steps = 1 one iteration -- on `batch`. `iters`
+        counts optimizer steps: it moves when the group is complete. Returns the loss as a device tensor (no host sync): this
+        micro-batch's, and on the call that completes a group the mean over the group."""
         inp = self.get_input(batch)
         inpaint = self.cfg["inpaint_mode"]
         rows = self.engine.train_step_inputs(inp["z"], inp["noise"], inp["t"], self.schedule, boxes=batch["boxes"] if inpaint else None, inpaint=inpaint)
         step_batch = dict(self.grounding_tokenizer_input.prepare(batch), context=inp["context"], **rows)
         if "grounding_extra_input" in inp:
             step_batch["grounding_extra_input"] = inp["grounding_extra_input"]
-        loss, _ = self.ts.step(step_batch)
+        kw = dict(loss_weights=self.snr_weights[inp["t"]].contiguous()) if self.snr_weights is not None else {}
+        loss, _ = self.ts.step(step_batch, **kw)
+        if self.accumulate > 1:         # the mean of the group's losses, formed on the device
+            self._loss_sum = loss if self._loss_sum is None else self._loss_sum + loss
+            if not self.ts.at_boundary:
+                return loss
+            loss, self._loss_sum = self._loss_sum / self.accumulate, None
         self.iters += 1
         self.losses.append(loss)
         return loss
 
     def start_training(self) -> int:
-        """trainer.py:375-404: iterations starting_iter .. total_iters - 1; save() at iteration 0, at every multiple of save_every_iters
-        and at the end. The loss is read back (a host sync) only every 10th iteration, where the reference logs it. Returns the
+        """trainer.py:375-404: iterations starting_iter .. total_iters - 1, each over gradient_accumulation_steps batches; save() at
+        iteration 0, at every multiple of save_every_iters and at the end -- between groups, so that a resumed run is exact. The loss is read back (a host sync) only every 10th iteration, where the reference logs it. Returns the
         number of iterations done in total."""
         for it in range(self.starting_iter, self.total_iters):
-            loss = self.run_one_step(next(self.batches))
-            assert self.iters == it + 1
+            for _ in range(self.accumulate):
+                loss = self.run_one_step(next(self.batches))
+            assert self.iters == it + 1 and self.ts.at_boundary
             if self.rank == 0:
                 if it % 10 == 0:
-                    self.log(f"iter {it + 1} loss {float(loss):.6f} lr {self.ts.lr_at(it + 1):.3e}")
+                    norm = f" grad_norm {float(self.ts.grad_norm):.4f}" if self.max_grad_norm else ""
+                    self.log(f"iter {it + 1} loss {float(loss):.6f} lr {self.ts.lr_at(it + 1):.3e}{norm}")
                 if it == 0 or it % self.save_every == 0 or it == self.total_iters - 1:
                     self.save()
                     if not self.config.get("disable_inference_in_training", True) and self.autoencoder is not None:
@@ -258,6 +286,10 @@ class Trainer:
         """trainer.py:291-304: model, ema, opt and iters of a checkpoint written by save() or by the reference's trainer; `rng` when
         the file has it. The optimizer's step count becomes `iters`, which positions the LR schedule."""
         ckpt = read_checkpoint(path)
+        saved_k = int((ckpt.get("config_dict") or {}).get("gradient_accumulation_steps") or 1)      # (a file without the key: K = 1)
+        if saved_k != self.accumulate:
+            raise ValueError(f"{path} was written with gradient_accumulation_steps = {saved_k}, this run has gradient_accumulation_steps = "
+                             f"{self.accumulate}: iterations and the batch stream would no longer line up")
         self.ts.load_state_dict(ckpt["model"])
         if self.lora_rank:
             if "lora" not in ckpt:
@@ -268,6 +300,7 @@ class Trainer:
             self.ts.load_ema_state_dict(ckpt["ema"])
         self.iters = self.starting_iter = int(ckpt["iters"])
         self.ts.steps = self.iters
+        self._loss_sum = None           # (the loaders dropped an open group of micro-batches: its partial loss goes with it)
         rng = ckpt.get("rng")
         if rng:
             self.generator.set_state(rng["device"])
@@ -405,6 +438,9 @@ def main(argv=None) -> int:
     ap.add_argument("--save_every_iters", type=int, default=5000)
     ap.add_argument("--enable_ema", type=_bool, default=False)
     ap.add_argument("--ema_rate", type=float, default=0.9999)
+    ap.add_argument("--gradient_accumulation_steps", type=int, default=1, help="micro-batches per optimizer step (an iteration draws this many batches)")
+    ap.add_argument("--max_grad_norm", type=float, default=0.0, help="clip the global gradient norm to this (0: off)")
+    ap.add_argument("--min_snr_gamma", type=float, default=0.0, help="min-SNR-gamma loss weights, eps-prediction form (0: off; 5 is customary)")
     ap.add_argument("--lora_rank", type=int, default=0, help="train LoRA adapters of this rank over the frozen model instead of the reference's set")
     ap.add_argument("--lora_alpha", type=float, default=None, help="the adapters' alpha (default: the rank)")
     ap.add_argument("--lora_families", nargs="+", default=["attn"], choices=["attn", "ff", "proj"])
@@ -421,7 +457,8 @@ def main(argv=None) -> int:
     cfg = synthetic_config(a.synthetic, small=a.small, latent=a.latent, inpaint=a.inpaint, fuser=a.fuser)
     config = dict(model=cfg, base_learning_rate=a.base_learning_rate, weight_decay=a.weight_decay, warmup_steps=a.warmup_steps, scheduler_type=a.scheduler_type,
                   total_iters=a.total_iters, enable_ema=a.enable_ema, ema_rate=a.ema_rate, inpaint_mode=a.inpaint, save_every_iters=a.save_every_iters,
-                  output_dir=a.output_dir, ckpt=None, batch_size=a.batch_size, seed=a.seed, disable_inference_in_training=True)
+                  output_dir=a.output_dir, ckpt=None, batch_size=a.batch_size, seed=a.seed, disable_inference_in_training=True,
+                  gradient_accumulation_steps=a.gradient_accumulation_steps, max_grad_norm=a.max_grad_norm or None, min_snr_gamma=a.min_snr_gamma or None)
     if a.lora_rank:
         config.update(lora_rank=a.lora_rank, lora_alpha=a.lora_alpha, lora_families=list(a.lora_families),
                       lora_out=a.lora_out or os.path.join(a.output_dir, "lora.safetensors"))
