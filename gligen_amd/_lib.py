@@ -1,6 +1,6 @@
 """ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
 include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h, include/gligen_amd_train_fusers.h, include/gligen_amd_train_prims.h,
-include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_ffn_rows.h, include/gligen_amd_norm.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h, include/gligen_amd_lora.h, include/gligen_amd_tiling.h, include/gligen_amd_train_lora.h and include/gligen_amd_train_run.h).
+include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_ffn_rows.h, include/gligen_amd_norm.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h, include/gligen_amd_lora.h, include/gligen_amd_tiling.h, include/gligen_amd_train_lora.h, include/gligen_amd_train_lora_conv.h and include/gligen_amd_train_run.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -247,6 +247,11 @@ TRAIN_LORA_SYMBOLS = {
     "gl_lora_wgrad_chunk_rows": (_I, [_I]),
 }
 
+# every symbol include/gligen_amd_train_lora_conv.h declares (one adapted 3 x 3 conv's low-rank part: ResBlock, Downsample, Upsample)
+TRAIN_LORA_CONV_SYMBOLS = {
+    "gl_op_lora_conv3": (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _I] + [_P] * 10 + [_P]),
+}
+
 # every symbol include/gligen_amd_trainer.h declares (the optimizer unit of a training run: AdamW + EMA in one pass)
 TRAINER_SYMBOLS = {
     "gl_op_adamw_ema_step": (_I, [_P, _P, _P, _P, _P, _P, C.c_int64, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, _I, _P]),
@@ -410,7 +415,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS, **TRAIN_PRIM_SYMBOLS,
-                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **FFN_ROWS_SYMBOLS, **NORM_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS, **TILING_SYMBOLS, **TRAIN_LORA_SYMBOLS,
+                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **FFN_ROWS_SYMBOLS, **NORM_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS, **TILING_SYMBOLS, **TRAIN_LORA_SYMBOLS, **TRAIN_LORA_CONV_SYMBOLS,
                               **TRAIN_RUN_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res

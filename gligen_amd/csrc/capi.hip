@@ -12,6 +12,7 @@
 #include "../../include/gligen_amd_train_fusers.h"
 #include "../../include/gligen_amd_train_prims.h"
 #include "../../include/gligen_amd_train_lora.h"
+#include "../../include/gligen_amd_train_lora_conv.h"
 #include "../../include/gligen_amd_trainer.h"
 #include "../../include/gligen_amd_train_run.h"
 #include "train_run.h"
@@ -1226,6 +1227,22 @@ int gl_op_lora_linear(gl_ctx* ctx, int M, int K, int N, int rank, float scale, i
 }
 
 int gl_lora_wgrad_chunk_rows(int M) { return M < 1 ? 0 : gl::train::lora_wgrad_chunk_rows(M); }
+
+// ---- include/gligen_amd_train_lora_conv.h: the low-rank part of one adapted 3 x 3 conv by itself
+int gl_op_lora_conv3(gl_ctx* ctx, int B, int H, int W, int Ci, int Co, int rank, float scale, int geom, const float* x, const float* down,
+                     const float* up, const float* dy, float* t, float* y, float* u, float* dx, float* g_down, float* g_up, gl_stream s) {
+    NEED(ctx);
+    if (!x || !down || !up) return gl::set_error(GL_ERR_ARG, "gl_op_lora_conv3: null pointer (x, down and up are required)");
+    if (!dy && (u || dx || g_down || g_up)) return gl::set_error(GL_ERR_ARG, "gl_op_lora_conv3: a backward output was asked for without dy");
+    if ((reinterpret_cast<uintptr_t>(x) | reinterpret_cast<uintptr_t>(dy)) & 15) return gl::set_error(GL_ERR_ARG, "gl_op_lora_conv3: x and dy are 16-byte aligned");
+    GL_API_BEGIN
+    Engine& eng = *ctx->eng;
+    eng.arena().reset();
+    const int rc = gl::train_prim_lora_conv3(eng.arena(), eng.splitk_ws(), eng.splitk_ws_bytes(), B, H, W, Ci, Co, rank, scale, geom, x, down, up, dy, t, y, u,
+                                             dx, g_down, g_up, S(s));
+    if (rc != GL_OK) throw GlError(rc, gl::last_error());
+    GL_API_END
+}
 
 // gl_unet_train_step_spatial and gl_unet_train_step_spatial_classes: `spi` holds the planes or the class maps
 static int train_step_spatial(const char* what, gl_ctx* ctx, const gl_unet_config* cfg, const gl_train_unet_in* in, const gl::TrainSpatialIn& spi, int n_params,

@@ -175,6 +175,11 @@ int train_prim_lora_linear(Arena& ar, float* ws, size_t ws_bytes, int M, int K, 
                            const float* down, const float* up, const float* dy, float* t, float* y, float* u, float* dx, float* g_down, float* g_up,
                            hipStream_t s);
 
+// The low-rank part of one adapted 3 x 3 conv by itself (include/gligen_amd_train_lora_conv.h; train_lora_conv.hip)
+int train_prim_lora_conv3(Arena& ar, float* ws, size_t ws_bytes, int B, int H, int W, int Ci, int Co, int r, float scale, int geom, const float* x,
+                          const float* down, const float* up, const float* dy, float* t, float* y, float* u, float* dx, float* g_down, float* g_up,
+                          hipStream_t s);
+
 namespace train { int lora_wgrad_chunk_rows(int M); }      // rows per partial sum of its weight-gradient kernel
 
 // One AdamW update of a flat fp32 parameter range, in place (torch.optim.AdamW semantics: trainer.py:245, :384 opt.step()); step = 1, 2, ...

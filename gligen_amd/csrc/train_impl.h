@@ -2,6 +2,7 @@
 //   train_ops.hip        the primitive kernels, the Ctx methods over them, the frozen-weight operand cache, AdamW
 //   train_attention.hip  the VALU and MFMA attention kernels, Ctx::attn_fwd / attn_bwd
 //   train_lora.hip       the low-rank products of LoRA adapters in training (fp32-input MFMA), lora_fwd / lora_bwd
+//   train_lora_conv.hip  the low-rank products of an adapted 3 x 3 conv (the same MFMA over gathered neighbour rows)
 //   train_layers.hip     block, SpatialTransformer, ResBlock, resample: *_check / *_forward / *_backward; the four slice entry points
 //   train_spatial.hip    ConvNeXt tokenizer, GroundingDownsampler and the first conv of the spatial-map models
 //   train_unet.hip       the whole iteration: grounding MLPs, time embedding, the layer list, unet_train_step
@@ -180,6 +181,22 @@ void lora_fwd(const Ctx& c, const float* W, const float* x, int M, int K, int N,
 // dx (optional) += s (dy up) down; the adapter's gradients g_down = s (dy up)^T x, g_up = s dy^T (x down^T)
 void lora_bwd(const Ctx& c, const float* W, const float* dy, const float* x, int M, int K, int N, float* dx);
 
+// ---- train_lora_conv.hip: the low-rank products of an adapted 3 x 3 conv over pixel rows [B H W][C], down [r][Ci][3][3] (OIHW), for
+// the geometries of Ctx::conv3: geom 0 stride 1, 1 Downsample (output H/2 x W/2), 2 Upsample (output 2H x 2W); H, W: the input's
+constexpr size_t kLoraConvWgradWs = (size_t)64 << 20;   // partial sums of all nine taps at once up to this many bytes, else tap by tap
+void lora_conv_check(const char* what, int B, int H, int W, int Ci, int Co, int r, int geom);
+size_t lora_conv_out_rows(int geom, int B, int H, int W);
+int lora_conv_wgrad_taps(int n_chunks, int r, int Ci);  // taps per launch of the weight gradient: 9 or 1, a function of the shape alone
+void lora_conv_down(const Ctx& c, const float* X, int B, int H, int W, int Ci, const float* down, int r, int geom, float* T);             // T [Mo][r] = im2col(X) down^T
+void lora_conv_dgrad(const Ctx& c, const float* U, int B, int H, int W, int Ci, const float* down, int r, int geom, float s, float* dX);  // dX [Mi][Ci] += s (transposed conv of U)
+void lora_conv_wgrad(const Ctx& c, const float* U, const float* X, int B, int H, int W, int Ci, int r, int geom, float s, float* G);      // G (OIHW) = s U^T im2col(X)
+// the adapter term of a 3 x 3 conv whose weight is in c.lora (no entry: nothing is launched): y += s up(down(x)); dx (optional) += its
+// data gradient, and the adapter's gradients g_down, g_up (t is recomputed, as lora_bwd does)
+void lora_conv_fwd(const Ctx& c, const float* W, const float* x, int B, int H, int Wd, int Ci, int Co, int geom, float* y);
+void lora_conv_bwd(const Ctx& c, const float* W, const float* dy, const float* x, int B, int H, int Wd, int Ci, int Co, int geom, float* dx);
+// out [B][C] = the sum of g [B][HW][C] over the HW pixels of each sample, in a fixed order (the gradient of a ResBlock's emb_layers output)
+void lora_sample_colsum(const Ctx& c, const float* g, int B, int HW, int C, float* out);
+
 // ---- train_layers.hip: the UNet's layer kinds. *_forward keeps what the backward needs in the arena; *_backward takes g = dL/dy
 // Everything the backward of a BasicTransformerBlock needs from its forward
 struct BlockSaved {
@@ -196,6 +213,8 @@ struct STSaved {
 };
 struct ResSaved {
     Ctx::GN n1, n2;
+    const float* x = nullptr;           // the block's input and SiLU(emb): read by the backward of adapters on skip_connection / emb_layers.1
+    const float* silu_emb = nullptr;
 };
 void st_check(const TrainBlockDims& d, const float* const* P, float* const* G = nullptr);
 STSaved st_forward(const Ctx& c, const TrainBlockDims& d, const float* const* P, const float* x, const float* objs, const float* context, float* y);
@@ -205,7 +224,8 @@ void res_check(const TrainResDims& d, const float* const* P);
 ResSaved res_forward(const Ctx& c, const TrainResDims& d, const float* const* P, const float* x, const float* silu_emb, float* y);
 float* res_backward(const Ctx& c, const TrainResDims& d, const float* const* P, const ResSaved& S, float* g);
 float* resample_forward(const Ctx& c, int mode, int B, int H, int W, int C, const float* w_oihw, const float* bias, const float* x);
-float* resample_backward(const Ctx& c, int mode, int B, int H, int W, int C, const float* w_oihw, const float* g);
+float* resample_backward(const Ctx& c, int mode, int B, int H, int W, int C, const float* w_oihw, const float* g,
+                        const float* x = nullptr);        // x: the layer's input, read only by an adapter on the conv
 
 // ---- train_unet.hip: the model's state_dict by name, and what the stages of a step share
 struct Names {

@@ -369,24 +369,47 @@ ResSaved train::res_forward(const Ctx& c, const TrainResDims& d, const float* co
     const size_t ny = (size_t)M * Cout;
     ResSaved S;
     S.n1 = c.gn_silu_fwd(x, B, HW, Cin, P[RP_GN1_W], P[RP_GN1_B]);
+    S.x = x;
+    S.silu_emb = silu_emb;
     float* h1 = c.conv3(S.n1.a, B, d.H, d.W, P[RP_C1_W], P[RP_C1_B], Cin, Cout, false);
     float* eo = c.lin_fwd(silu_emb, B, d.emb_dim, P[RP_EMB_W], P[RP_EMB_B], Cout);
+    if (c.lora) {       // adapters on the frozen convs and Linears of the ResBlock (train_lora_conv.hip, train_lora.hip): each adds its term in place
+        lora_conv_fwd(c, P[RP_C1_W], S.n1.a, B, d.H, d.W, Cin, Cout, 0, h1);
+        lora_fwd(c, P[RP_EMB_W], silu_emb, B, d.emb_dim, Cout, eo);
+    }
     float* h2 = c.f32(ny);
     c.ew(add_per_sample_kernel, ny, h1, eo, HW, Cout, ny, h2);
     S.n2 = c.gn_silu_fwd(h2, B, HW, Cout, P[RP_GN2_W], P[RP_GN2_B]);
     float* h3 = c.conv3(S.n2.a, B, d.H, d.W, P[RP_C2_W], P[RP_C2_B], Cout, Cout, false);
+    if (c.lora) lora_conv_fwd(c, P[RP_C2_W], S.n2.a, B, d.H, d.W, Cout, Cout, 0, h3);
     const float* sk = x;
-    if (Cin != Cout) sk = c.lin_fwd(x, M, Cin, P[RP_SKIP_W], P[RP_SKIP_B], Cout);      // the 1 x 1 conv is a Linear over pixel rows
+    if (Cin != Cout) {      // the 1 x 1 conv is a Linear over pixel rows
+        float* sp = c.lin_fwd(x, M, Cin, P[RP_SKIP_W], P[RP_SKIP_B], Cout);
+        if (c.lora) lora_fwd(c, P[RP_SKIP_W], x, M, Cin, Cout, sp);
+        sk = sp;
+    }
     c.gated_add(sk, h3, nullptr, 1.f, ny, y);
     return S;
 }
 float* train::res_backward(const Ctx& c, const TrainResDims& d, const float* const* P, const ResSaved& S, float* g) {
     const int B = d.B, HW = d.H * d.W, Cin = d.Cin, Cout = d.Cout, M = B * HW;
     float* g_a2 = c.conv3(g, B, d.H, d.W, P[RP_C2_W], nullptr, Cout, Cout, true);
+    if (c.lora) lora_conv_bwd(c, P[RP_C2_W], g, S.n2.a, B, d.H, d.W, Cout, Cout, 0, g_a2);
     float* g_h2 = c.f32((size_t)M * Cout);
     c.gn_silu_bwd(g_a2, S.n2, P[RP_GN2_W], P[RP_GN2_B], B, HW, Cout, g_h2, false);    // = dL/dh1 (the emb path has nothing trainable upstream)
     float* g_a1 = c.conv3(g_h2, B, d.H, d.W, P[RP_C1_W], nullptr, Cin, Cout, true);
+    if (c.lora) {
+        lora_conv_bwd(c, P[RP_C1_W], g_h2, S.n1.a, B, d.H, d.W, Cin, Cout, 0, g_a1);
+        if (lora_find(c, P[RP_EMB_W])) {      // dL/d(emb_layers output) [B][Cout]: g_h2 summed over each sample's pixels; only the adapter's gradients are formed
+            const size_t mk = c.ar.mark();
+            float* g_eo = c.f32((size_t)B * Cout);
+            lora_sample_colsum(c, g_h2, B, HW, Cout, g_eo);
+            lora_bwd(c, P[RP_EMB_W], g_eo, S.silu_emb, B, d.emb_dim, Cout, nullptr);
+            c.ar.release(mk);
+        }
+    }
     float* g_x = Cin != Cout ? c.lin_dgrad(g, M, Cout, P[RP_SKIP_W], Cin) : g;         // through the skip connection
+    if (c.lora && Cin != Cout) lora_bwd(c, P[RP_SKIP_W], g, S.x, M, Cin, Cout, g_x);
     c.gn_silu_bwd(g_a1, S.n1, P[RP_GN1_W], P[RP_GN1_B], B, HW, Cin, g_x, true);
     return g_x;
 }
@@ -404,18 +427,27 @@ int resblock_train_step(Arena& ar, float* ws, size_t ws_bytes, const TrainResDim
 // Downsample (mode 0: conv3x3 stride 2, openaimodel.py:99-124) / Upsample (mode 1: nearest 2x + conv3x3, openaimodel.py:64-96) of C
 // channels; the conv is a frozen SD layer: forward, and the gradient w.r.t. the input.
 float* train::resample_forward(const Ctx& c, int mode, int B, int H, int W, int C, const float* w_oihw, const float* bias, const float* x) {
-    return c.conv3(x, B, H, W, w_oihw, bias, C, C, false, mode ? 1 : 2, mode ? 1 : 0);
+    float* y = c.conv3(x, B, H, W, w_oihw, bias, C, C, false, mode ? 1 : 2, mode ? 1 : 0);
+    if (c.lora) lora_conv_fwd(c, w_oihw, x, B, H, W, C, C, mode ? 2 : 1, y);
+    return y;
 }
-float* train::resample_backward(const Ctx& c, int mode, int B, int H, int W, int C, const float* w_oihw, const float* g) {
+float* train::resample_backward(const Ctx& c, int mode, int B, int H, int W, int C, const float* w_oihw, const float* g, const float* x) {
     const size_t nx = (size_t)B * H * W * C;
+    float* dx;
     if (mode == 0) {
         float* z = c.f32(nx);
         c.ew(zero_insert2_kernel, nx, g, H, W, C, nx, z);
-        return c.conv3(z, B, H, W, w_oihw, nullptr, C, C, true);
+        dx = c.conv3(z, B, H, W, w_oihw, nullptr, C, C, true);
+    } else {
+        float* gu = c.conv3(g, B, 2 * H, 2 * W, w_oihw, nullptr, C, C, true);
+        dx = c.f32(nx);
+        c.ew(sum2x2_kernel, nx, gu, H, W, C, nx, dx);
     }
-    float* gu = c.conv3(g, B, 2 * H, 2 * W, w_oihw, nullptr, C, C, true);
-    float* dx = c.f32(nx);
-    c.ew(sum2x2_kernel, nx, gu, H, W, C, nx, dx);
+    // the adapter's data gradient gathers from g on the output grid itself (train_lora_conv.hip): no zero-inserted or enlarged copy
+    if (c.lora && lora_find(c, w_oihw)) {
+        if (!x) throw GlError(GL_ERR_STATE, "resample_backward: an adapter on the conv needs the layer's input");
+        lora_conv_bwd(c, w_oihw, g, x, B, H, W, C, C, mode ? 2 : 1, dx);
+    }
     return dx;
 }
 

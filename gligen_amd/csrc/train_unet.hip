@@ -121,24 +121,32 @@ void check_trainable_set(const TrainUNetCfg& cfg, int n_params, const char* cons
 }
 
 // The adapters of a step by the address of their base weight. An adapter is admitted by name: the frozen Linears of a
-// SpatialTransformer outside its fuser (the fuser's own Linears train in full); everything check_trainable_set refuses stays refused.
+// SpatialTransformer outside its fuser (the fuser's own Linears train in full), and the frozen convs and Linears of a ResBlock, a
+// Downsample and an output block's Upsample (train_lora_conv.hip: down is [r][Ci][3][3] on the 3 x 3 convs, the geometry follows from
+// the site); everything check_trainable_set refuses stays refused.
 LoraTable lora_table(const Names& nm, const TrainLoraAdapter* adapters, int n_adapters) {
     static const char* const k_sites[] = {".attn1.to_q.weight", ".attn1.to_k.weight", ".attn1.to_v.weight", ".attn1.to_out.0.weight",
                                           ".attn2.to_q.weight", ".attn2.to_k.weight", ".attn2.to_v.weight", ".attn2.to_out.0.weight",
                                           ".ff.net.0.proj.weight", ".ff.net.2.weight", ".proj_in.weight", ".proj_out.weight"};
+    static const char* const k_res_sites[] = {".in_layers.2.weight", ".out_layers.3.weight", ".emb_layers.1.weight", ".skip_connection.weight"};
     LoraTable t;
     if (n_adapters < 0 || (n_adapters && !adapters)) throw GlError(GL_ERR_ARG, "unet_train_step: null adapter array");
     for (int i = 0; i < n_adapters; ++i) {
         const TrainLoraAdapter& a = adapters[i];
         if (!a.name || !a.down || !a.up) throw GlError(GL_ERR_ARG, fmt("unet_train_step: adapter %d has a null name, down or up", i));
         const std::string name = a.name;
-        bool site = false;
-        for (const char* sfx : k_sites) {
+        auto ends = [&](const char* sfx) {
             const size_t n = strlen(sfx);
-            site = site || (name.size() > n && !name.compare(name.size() - n, n, sfx));
-        }
+            return name.size() > n && !name.compare(name.size() - n, n, sfx);
+        };
+        auto starts = [&](const char* pfx) { return !name.compare(0, strlen(pfx), pfx); };
+        bool site = false;
+        for (const char* sfx : k_sites) site = site || ends(sfx);
         const bool in_st = name.find(".transformer_blocks.0.") != std::string::npos || name.find(".proj_") != std::string::npos;
-        if (!site || !in_st || name.find(".fuser.") != std::string::npos)
+        bool conv_site = (ends(".op.weight") && starts("input_blocks.")) || (ends(".conv.weight") && starts("output_blocks."));
+        for (const char* sfx : k_res_sites) conv_site = conv_site || (ends(sfx) && (starts("input_blocks.") || starts("middle_block.") || starts("output_blocks.")));
+        conv_site = conv_site && name.find(".transformer_blocks.") == std::string::npos;
+        if ((!(site && in_st) && !conv_site) || name.find(".fuser.") != std::string::npos)
             throw GlError(GL_ERR_ARG, "unet_train_step: an adapter was given for '" + name + "': adapters go on attn1 / attn2 to_q, to_k, to_v, to_out.0, "
                                       "ff.net.0.proj, ff.net.2 and proj_in / proj_out of a SpatialTransformer (the fuser's Linears train in full)");
         if (a.rank < 1 || a.rank > 128) throw GlError(GL_ERR_ARG, fmt("unet_train_step: adapter '%s' has rank %d (1 <= r <= 128)", a.name, a.rank));
@@ -427,7 +435,17 @@ float* layers_backward(const UNetStep& u, std::vector<UNetLayer>& L, const float
     n_st = 0;
     for (size_t i = 0; i < L.size(); ++i)
         if (L[i].kind == K_ST) st_ordinal[i] = n_st++;
-    const int stop = in_grad ? 0 : first_st;
+    int stop = in_grad ? 0 : first_st;
+    if (c.lora)     // a ResBlock or resampling layer with an adapter in front of the first fuser: its backward has to run too
+        for (int i = 0; i < stop; ++i) {
+            const UNetLayer& l = L[i];
+            bool adapted = false;
+            if (l.kind == K_RES)
+                for (int k : {(int)RP_C1_W, (int)RP_EMB_W, (int)RP_C2_W, (int)RP_SKIP_W}) adapted = adapted || lora_find(c, l.P[k]);
+            else if (l.kind == K_DOWN || l.kind == K_UP)
+                adapted = lora_find(c, l.P[0]) != nullptr;
+            if (adapted) { stop = i; break; }
+        }
     float* skip0 = nullptr;
     for (int i = (int)L.size() - 1; i >= 0 && i >= stop; --i) {
         UNetLayer& l = L[i];
@@ -440,7 +458,7 @@ float* layers_backward(const UNetStep& u, std::vector<UNetLayer>& L, const float
             float* gh = c.f32(rows * l.C0);
             split_cols(c, g, l.Cin, 0, l.C0, rows, gh, false);
             const int C1 = l.Cin - l.C0;
-            if (in_grad || l.skip_idx >= first_st) {   // (without in_grad a skip produced in front of the first fuser carries no gradient anybody needs)
+            if (in_grad || l.skip_idx >= stop) {   // (without in_grad a skip produced in front of the first layer that trains carries no gradient anybody needs)
                 float* gs = c.f32(rows * C1);
                 split_cols(c, g, l.Cin, l.C0, C1, rows, gs, false);
                 if (l.skip_idx < 0) skip0 = gs;
@@ -469,7 +487,7 @@ float* layers_backward(const UNetStep& u, std::vector<UNetLayer>& L, const float
             // while the blocks in front of it are still in backward
             if (grad_events && st_ordinal[i] < n_grad_events) c.hip(hipEventRecord(grad_events[st_ordinal[i]], c.s), "hipEventRecord");
         } else {
-            g = resample_backward(c, l.kind == K_UP, B, l.H, l.W, l.Cin, l.P[0], g);
+            g = resample_backward(c, l.kind == K_UP, B, l.H, l.W, l.Cin, l.P[0], g, l.x_in);
         }
     }
     if (in_grad && skip0) c.add(g, skip0, u.M0 * u.mc);      // g = dL/d(conv_in output) through input_blocks.1, plus its skip

@@ -1235,7 +1235,8 @@ class Engine:
             K = w.numel() // N
             g_down = a.get("g_down") if a.get("g_down") is not None else torch.zeros_like(down)
             g_up = a.get("g_up") if a.get("g_up") is not None else torch.zeros_like(up)
-            for what, t, shape in (("down", down, (r, K)), ("up", up, (N, r)), ("g_down", g_down, (r, K)), ("g_up", g_up, (N, r))):
+            dshape = (r, int(w.shape[1]), 3, 3) if (w.dim() == 4 and tuple(w.shape[2:]) == (3, 3)) else (r, K)      # a 3 x 3 conv's down is OIHW
+            for what, t, shape in (("down", down, dshape), ("up", up, (N, r)), ("g_down", g_down, dshape), ("g_up", g_up, (N, r))):
                 if not (t.is_cuda and t.device == dev and t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == shape):
                     raise ValueError(f"unet_train_step: adapter '{name}': {what} is a contiguous fp32 tensor of shape {shape} on {self.device}; got "
                                      f"{tuple(t.shape)} {t.dtype} on {t.device}")
@@ -1598,6 +1599,32 @@ class Engine:
             o = self._prim_outs(shapes, out)
         check(self.lib.gl_op_lora_linear(self._ctx, int(M), int(K), int(N), r, C.c_float(scale), int(bool(down_kr)), int(bool(up_rn)), _ptr(x), _ptr(down),
                                          _ptr(up), _ptr(dy), *[_ptr(o.get(n)) for n in ("t", "y", "u", "dx", "g_down", "g_up")], _stream(dev)))
+        return o
+
+    # ---- include/gligen_amd_train_lora_conv.h: the low-rank part of one adapted 3 x 3 conv by itself
+    def op_lora_conv3(self, x, down, up, scale=1.0, geom=0, dy=None, out=None):
+        """gl_op_lora_conv3: pixel rows x [B, H, W, Ci]; down [r, Ci, 3, 3]; up [Co, r]; geom 0 stride 1 (output H x W), 1 Downsample
+        (H/2 x W/2), 2 Upsample (2H x 2W). t [B, Ho, Wo, r] = im2col(x) down^T and y [B, Ho, Wo, Co] += scale t up^T; with dy (like y)
+        also u [B, Ho, Wo, r] = dy up, dx (like x) += scale (transposed conv of u with down), g_down (like down) and g_up (like up).
+        y and dx are accumulated into: they come in through `out` (out=None starts them at zero)."""
+        dev = self.device
+        x, down, up = (_f32(t, dev) for t in (x, down, up))
+        dy = None if dy is None else _f32(dy, dev)
+        if x.dim() != 4 or down.dim() != 4 or up.dim() != 2:
+            raise ValueError("op_lora_conv3: x [B, H, W, Ci], down [r, Ci, 3, 3], up [Co, r]")
+        (B, H, W, Ci), r, Co = x.shape, int(down.shape[0]), int(up.shape[0])
+        Ho, Wo = (H // 2, W // 2) if geom == 1 else (2 * H, 2 * W) if geom == 2 else (H, W)
+        if tuple(down.shape) != (r, Ci, 3, 3) or tuple(up.shape) != (Co, r) or (dy is not None and tuple(dy.shape) != (B, Ho, Wo, Co)):
+            raise ValueError("op_lora_conv3: x [B, H, W, Ci], down [r, Ci, 3, 3], up [Co, r], dy [B, Ho, Wo, Co]")
+        shapes = {"t": (B, Ho, Wo, r), "y": (B, Ho, Wo, Co)}
+        if dy is not None:
+            shapes.update(u=(B, Ho, Wo, r), dx=tuple(x.shape), g_down=tuple(down.shape), g_up=tuple(up.shape))
+        if out is None:
+            o = {k: torch.zeros(shape, device=dev, dtype=torch.float32) for k, shape in shapes.items()}
+        else:
+            o = self._prim_outs(shapes, out)
+        check(self.lib.gl_op_lora_conv3(self._ctx, int(B), int(H), int(W), int(Ci), int(Co), r, C.c_float(scale), int(geom), _ptr(x), _ptr(down), _ptr(up),
+                                        _ptr(dy), *[_ptr(o.get(n)) for n in ("t", "y", "u", "dx", "g_down", "g_up")], _stream(dev)))
         return o
 
     def lora_wgrad_chunk_rows(self, M: int) -> int:

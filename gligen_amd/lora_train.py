@@ -10,7 +10,13 @@ Everything numeric runs in the library: forward + backward in gl_unet_train_step
 csrc/train_lora.hip), the update in gl_op_adamw_step. The adapter tensors and their gradients are views into GradBuckets, laid out in
 the order the gradients become final, exactly as TrainStep's; an adapter's gradients are final at the milestone of its
 SpatialTransformer. What comes out is kohya's file format (adapter_state_dict / save_adapter), which `--lora` and
-gligen_amd.lora.apply_loras consume."""
+gligen_amd.lora.apply_loras consume.
+
+The convolutional side (kohya's conv_dim / LoCon) comes in through LoraSpec's conv_families: "conv" (a ResBlock's in_layers.2,
+out_layers.3 and skip_connection), "emb" (emb_layers.1) and "sample" (a Downsample's op, an Upsample's conv), meaning what
+synthetic.LORA_FAMILIES means by them. A 3 x 3 site computes conv(x, W) + (conv_alpha / conv_rank) up(down(x)) with down
+[conv_rank, Ci, 3, 3] of the base conv's stride and padding and up 1 x 1 (csrc/train_lora_conv.hip); skip_connection and emb_layers.1
+are Linears and take rank / alpha. Their gradients are final at the last milestone of the step."""
 from __future__ import annotations
 
 import math
@@ -30,29 +36,59 @@ FAMILY_SUFFIXES = {
     "ff": (".transformer_blocks.0.ff.net.0.proj.weight", ".transformer_blocks.0.ff.net.2.weight"),
     "proj": (".proj_in.weight", ".proj_out.weight"),
 }
+CONV_FAMILY_SUFFIXES = {
+    "conv": (".in_layers.2.weight", ".out_layers.3.weight", ".skip_connection.weight"),
+    "emb": (".emb_layers.1.weight",),
+    "sample": (".op.weight", ".conv.weight"),
+}
 MAX_RANK = 128          # the low-rank kernels' limit
 DOWN, UP = ".lora_down.weight", ".lora_up.weight"
 
 
 class LoraSpec:
-    """rank, alpha (None: rank, so that the scale alpha / rank is 1) and the families adapted."""
+    """rank, alpha (None: rank, so that the scale alpha / rank is 1) and the families adapted; conv_families: the ResBlock and
+    resampling sites (CONV_FAMILY_SUFFIXES), whose 3 x 3 convs take conv_rank (None: rank) and conv_alpha (None: conv_rank) while
+    skip_connection and emb_layers.1 take rank / alpha. families may be empty when conv_families is not."""
 
-    def __init__(self, rank: int, alpha: Optional[float] = None, families: Sequence[str] = ("attn",)):
+    def __init__(self, rank: int, alpha: Optional[float] = None, families: Sequence[str] = ("attn",), *, conv_families: Sequence[str] = (),
+                 conv_rank: Optional[int] = None, conv_alpha: Optional[float] = None):
         self.rank = int(rank)
         if not 1 <= self.rank <= MAX_RANK:
             raise ValueError(f"LoraSpec: rank {rank} (1 <= rank <= {MAX_RANK})")
         self.alpha = float(self.rank if alpha is None else alpha)
         self.families = tuple(families)
+        self.conv_families = tuple(conv_families)
         bad = [f for f in self.families if f not in FAMILY_SUFFIXES]
-        if bad or not self.families:
+        if bad or not (self.families or self.conv_families):
             raise ValueError(f"LoraSpec: families {bad or '()'}: some of {sorted(FAMILY_SUFFIXES)}")
+        bad = [f for f in self.conv_families if f not in CONV_FAMILY_SUFFIXES]
+        if bad:
+            raise ValueError(f"LoraSpec: conv_families {bad}: some of {sorted(CONV_FAMILY_SUFFIXES)}")
+        self.conv_rank = int(self.rank if conv_rank is None else conv_rank)
+        if not 1 <= self.conv_rank <= MAX_RANK:
+            raise ValueError(f"LoraSpec: conv_rank {conv_rank} (1 <= conv_rank <= {MAX_RANK})")
+        self.conv_alpha = float(self.conv_rank if conv_alpha is None else conv_alpha)
 
     @property
     def scale(self) -> float:
         return self.alpha / self.rank
 
+    @property
+    def conv_scale(self) -> float:
+        return self.conv_alpha / self.conv_rank
+
+    def of_site(self, w) -> tuple:
+        """(rank, alpha) of the adapter on weight w (anything with .shape): a 3 x 3 conv takes the conv pair."""
+        return (self.conv_rank, self.conv_alpha) if _is_conv3(w) else (self.rank, self.alpha)
+
     def __repr__(self):
-        return f"LoraSpec(rank={self.rank}, alpha={self.alpha:g}, families={self.families})"
+        conv = f", conv_families={self.conv_families}, conv_rank={self.conv_rank}, conv_alpha={self.conv_alpha:g}" if self.conv_families else ""
+        return f"LoraSpec(rank={self.rank}, alpha={self.alpha:g}, families={self.families}{conv})"
+
+
+def _is_conv3(w) -> bool:
+    shape = tuple(int(s) for s in w.shape)
+    return len(shape) == 4 and shape[2:] == (3, 3)
 
 
 def st_prefixes(state_dict: Mapping[str, object]) -> List[str]:
@@ -64,28 +100,33 @@ def adapter_sites(state_dict: Mapping[str, object], spec: LoraSpec) -> List[str]
     """The state_dict keys of the weights `spec` adapts, in the order of the state_dict."""
     sts = set(st_prefixes(state_dict))
     suffixes = tuple(s for f in spec.families for s in FAMILY_SUFFIXES[f])
+    conv_suffixes = tuple(s for f in spec.conv_families for s in CONV_FAMILY_SUFFIXES[f])
     out = []
     for k in state_dict:
-        if ".fuser." in k or not k.endswith(suffixes):
+        if ".fuser." in k:
             continue
-        prefix = k.split(".transformer_blocks.")[0] if ".transformer_blocks." in k else k.rsplit(".", 2)[0]
-        if prefix in sts:
+        if suffixes and k.endswith(suffixes):
+            prefix = k.split(".transformer_blocks.")[0] if ".transformer_blocks." in k else k.rsplit(".", 2)[0]
+            if prefix in sts:
+                out.append(k)
+        elif conv_suffixes and k.endswith(conv_suffixes) and ".transformer_blocks." not in k and k.startswith(("input_blocks.", "middle_block.", "output_blocks.")):
             out.append(k)
     return out
 
 
 def _site_shape(w) -> tuple:
-    """(N, K) of a Linear's [N, K] or a 1 x 1 conv's [N, K, 1, 1] weight."""
+    """(N, K) of a Linear's [N, K] or a 1 x 1 conv's [N, K, 1, 1] weight, (Co, Ci) of a 3 x 3 conv's [Co, Ci, 3, 3]."""
     shape = tuple(int(s) for s in w.shape)
-    if len(shape) not in (2, 4) or any(s != 1 for s in shape[2:]):
-        raise ValueError(f"an adapted weight is [N, K] or [N, K, 1, 1]; got {shape}")
+    if len(shape) not in (2, 4) or (any(s != 1 for s in shape[2:]) and shape[2:] != (3, 3)):
+        raise ValueError(f"an adapted weight is [N, K], [N, K, 1, 1] or [Co, Ci, 3, 3]; got {shape}")
     return shape[0], shape[1]
 
 
 def init_adapters(state_dict: Mapping[str, object], cfg: Optional[Mapping], spec: LoraSpec, seed: int = 0) -> Dict[str, torch.Tensor]:
     """`<module path>.lora_down.weight` [rank, K] and `.lora_up.weight` [N, rank] (fp32, CPU) for every site of `spec`, in module
-    order: down Kaiming-uniform (a = sqrt(5): uniform in +-1 / sqrt(K)), up zero (kohya networks/lora.py). Seeded per module, so a site's
-    start does not depend on which other families are adapted. state_dict: tensors, or anything with .shape."""
+    order: down Kaiming-uniform (a = sqrt(5): uniform in +-1 / sqrt(K)), up zero (kohya networks/lora.py); a 3 x 3 conv's down is
+    [conv_rank, Ci, 3, 3] with fan-in 9 Ci, its up [Co, conv_rank]. Seeded per module, so a site's start does not depend on which other
+    families are adapted. state_dict: tensors, or anything with .shape."""
     out: Dict[str, torch.Tensor] = {}
     for k in adapter_sites(state_dict, spec):
         N, K = _site_shape(state_dict[k])
@@ -93,34 +134,41 @@ def init_adapters(state_dict: Mapping[str, object], cfg: Optional[Mapping], spec
             raise ValueError(f"init_adapters: '{k}' is [{N}, {K}]; the low-rank kernels take K and N that are multiples of 64")
         path = k[:-len(".weight")]
         gen = torch.Generator().manual_seed((zlib.crc32(path.encode()) ^ (int(seed) * 0x9E3779B1)) & 0x7FFFFFFF)
-        bound = 1.0 / math.sqrt(K)
-        out[path + DOWN] = (torch.rand((spec.rank, K), generator=gen, dtype=torch.float32) * 2.0 - 1.0) * bound
-        out[path + UP] = torch.zeros((N, spec.rank), dtype=torch.float32)
+        conv3 = _is_conv3(state_dict[k])
+        rank, _ = spec.of_site(state_dict[k])
+        bound = 1.0 / math.sqrt(9 * K if conv3 else K)
+        out[path + DOWN] = (torch.rand((rank, K, 3, 3) if conv3 else (rank, K), generator=gen, dtype=torch.float32) * 2.0 - 1.0) * bound
+        out[path + UP] = torch.zeros((N, rank), dtype=torch.float32)
     if not out:
-        raise ValueError(f"init_adapters: no weight of the families {spec.families} in this state_dict")
+        raise ValueError(f"init_adapters: no weight of the families {spec.families + spec.conv_families} in this state_dict")
     return out
 
 
-def kohya_state_dict(adapters: Mapping[str, torch.Tensor], state_dict: Mapping[str, object], alpha: float, dtype=torch.float32) -> Dict[str, torch.Tensor]:
+def kohya_state_dict(adapters: Mapping[str, torch.Tensor], state_dict: Mapping[str, object], alpha: float, dtype=torch.float32,
+                     conv_alpha: Optional[float] = None) -> Dict[str, torch.Tensor]:
     """Adapter tensors (init_adapters' keys) in kohya's form: lora_unet_<module path with underscores>.lora_down.weight /
-    .lora_up.weight / .alpha; the factors of a conv (proj_in / proj_out) are 4-D with 1 x 1 tails."""
+    .lora_up.weight / .alpha; the factors of a conv (proj_in / proj_out, skip_connection) are 4-D with 1 x 1 tails; a 3 x 3 conv's
+    down is saved as it is, its up with a (1, 1) tail and conv_alpha (None: alpha) as its .alpha."""
     out: Dict[str, torch.Tensor] = {}
     for key, down in adapters.items():
         if not key.endswith(DOWN):
             continue
         path = key[:-len(DOWN)]
         up = adapters[path + UP]
-        tail = (1, 1) if len(tuple(state_dict[path + ".weight"].shape)) == 4 else ()
+        w = state_dict[path + ".weight"]
+        tail = (1, 1) if len(tuple(w.shape)) == 4 else ()
+        conv3 = _is_conv3(w)
         name = lora.UNET_PREFIX + path.replace(".", "_")
-        out[name + DOWN] = down.detach().reshape(tuple(down.shape) + tail).to(dtype).cpu().contiguous()
+        out[name + DOWN] = down.detach().reshape(tuple(down.shape) + (() if conv3 else tail)).to(dtype).cpu().contiguous()
         out[name + UP] = up.detach().reshape(tuple(up.shape) + tail).to(dtype).cpu().contiguous()
-        out[name + ".alpha"] = torch.tensor(float(alpha), dtype=dtype)
+        out[name + ".alpha"] = torch.tensor(float(alpha if (conv_alpha is None or not conv3) else conv_alpha), dtype=dtype)
     return out
 
 
 def adapter_milestones(names: Sequence[str], state_dict: Mapping[str, object]) -> Dict[str, int]:
     """The gradient milestone of every trainable tensor of a LoraTrainStep: an adapter tensor's and a fuser tensor's is the number of
-    its SpatialTransformer in module order, every other tensor's (position_net, the first conv) the number of SpatialTransformers."""
+    its SpatialTransformer in module order, every other tensor's (position_net, the first conv; the adapters of the conv families, on
+    ResBlocks and resampling layers) the number of SpatialTransformers: the last milestone, recorded behind the whole backward."""
     sts = st_prefixes(state_dict)
     index = {p: i for i, p in enumerate(sts)}
 
@@ -128,7 +176,7 @@ def adapter_milestones(names: Sequence[str], state_dict: Mapping[str, object]) -
         if ".transformer_blocks." in k:
             return index[k.split(".transformer_blocks.")[0]]
         if k.endswith((DOWN, UP)):
-            return index[k.rsplit(".", 3)[0]]       # <st>.proj_in.lora_down.weight
+            return index.get(k.rsplit(".", 3)[0], len(sts))       # <st>.proj_in.lora_down.weight; a conv-family site is in no SpatialTransformer
         return len(sts)
     return {k: of(k) for k in names}
 
@@ -179,7 +227,7 @@ class LoraTrainStep(TrainStep):
                 self.params[k] = t
         for k, t in start.items():
             if tuple(t.shape) != shapes[k]:
-                raise ValueError(f"LoraTrainStep: adapter tensor '{k}' is {tuple(t.shape)}, rank {spec.rank} on this model gives {shapes[k]}")
+                raise ValueError(f"LoraTrainStep: adapter tensor '{k}' is {tuple(t.shape)}, {spec} on this model gives {shapes[k]}")
             self.pbuf.views[k].copy_(t.to(device=dev, dtype=torch.float32))
         if broadcast and tdist.is_available() and tdist.is_initialized() and tdist.get_world_size() > 1:
             for b in self.pbuf.buckets:
@@ -201,7 +249,7 @@ class LoraTrainStep(TrainStep):
         for w in self.sites:
             path = w[:-len(".weight")]
             self.adapters.append(dict(name=w, down=self.pbuf.views[path + DOWN], up=self.pbuf.views[path + UP], g_down=self.gbuf.views[path + DOWN],
-                                      g_up=self.gbuf.views[path + UP], scale=spec.scale))
+                                      g_up=self.gbuf.views[path + UP], scale=spec.conv_scale if _is_conv3(state_dict[w]) else spec.scale))
         self._base_grads = {k: self.gbuf.views[k] for k in self.base_names}
         self._init_run(accumulate, max_grad_norm)     # gradient accumulation and norm clipping, as TrainStep's
 
@@ -235,7 +283,7 @@ class LoraTrainStep(TrainStep):
 
     def adapter_state_dict(self, dtype=torch.float32) -> Dict[str, torch.Tensor]:
         """The adapter in kohya's form (CPU tensors): what gligen_amd.lora.parse_adapter / apply_loras and `--lora` read."""
-        return kohya_state_dict(self.adapter_tensors(), self.params, self.spec.alpha, dtype)
+        return kohya_state_dict(self.adapter_tensors(), self.params, self.spec.alpha, dtype, conv_alpha=self.spec.conv_alpha)
 
     def save_adapter(self, path, dtype=torch.float16) -> None:
         """The adapter as a .safetensors file (gligen_amd.lora.write_safetensors), fp16 as adapters are usually shared, or fp32."""
@@ -243,6 +291,8 @@ class LoraTrainStep(TrainStep):
             raise ValueError("save_adapter: dtype is torch.float16 or torch.float32")
         meta = dict(ss_network_dim=str(self.spec.rank), ss_network_alpha=f"{self.spec.alpha:g}", ss_network_module="networks.lora",
                     families=" ".join(self.spec.families), steps=str(self.steps))
+        if self.spec.conv_families:
+            meta.update(conv_families=" ".join(self.spec.conv_families), ss_network_args=f"conv_dim={self.spec.conv_rank} conv_alpha={self.spec.conv_alpha:g}")
         lora.write_safetensors(path, self.adapter_state_dict(dtype), metadata=meta)
 
     def ema_state_dict(self):

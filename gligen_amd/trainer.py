@@ -150,7 +150,10 @@ class Trainer:
             from .lora_train import LoraSpec, LoraTrainStep
             if self.enable_ema:
                 raise ValueError("Trainer: no EMA is kept of LoRA adapters (enable_ema with lora_rank)")
-            spec = LoraSpec(self.lora_rank, self.config.get("lora_alpha"), tuple(self.config.get("lora_families") or ("attn",)))
+            conv_families = tuple(self.config.get("lora_conv_families") or ())
+            families = self.config.get("lora_families")
+            spec = LoraSpec(self.lora_rank, self.config.get("lora_alpha"), tuple(("attn",) if families is None else families), conv_families=conv_families,
+                            conv_rank=self.config.get("lora_conv_rank"), conv_alpha=self.config.get("lora_conv_alpha"))
             self.ts = LoraTrainStep(engine, cfg, sd, spec, lr=warmup_schedule(self.base_lr, self.warmup_steps, self.cosine_total),
                                     weight_decay=float(self.config.get("weight_decay", 0.0)), bucket_mb=bucket_mb, world=world, checkpoint=checkpoint,
                                     drop_prob=drop_prob, rng=random.Random(seed), overlap=overlap, train_base=bool(self.config.get("lora_train_base", False)),
@@ -290,10 +293,17 @@ class Trainer:
         if saved_k != self.accumulate:
             raise ValueError(f"{path} was written with gradient_accumulation_steps = {saved_k}, this run has gradient_accumulation_steps = "
                              f"{self.accumulate}: iterations and the batch stream would no longer line up")
-        self.ts.load_state_dict(ckpt["model"])
         if self.lora_rank:
             if "lora" not in ckpt:
                 raise ValueError(f"{path} carries no adapters (`lora`): it was written by a run without lora_rank")
+            saved = ckpt.get("config_dict") or {}
+            for key in ("lora_conv_families", "lora_conv_rank", "lora_conv_alpha"):
+                was, now = saved.get(key), self.config.get(key)
+                was, now = (list(was or []), list(now or [])) if key == "lora_conv_families" else (was, now)
+                if was != now:
+                    raise ValueError(f"{path} was written with {key} = {was}, this run has {key} = {now}: the adapters would no longer be the same")
+        self.ts.load_state_dict(ckpt["model"])
+        if self.lora_rank:
             self.ts.load_adapter_tensors(ckpt["lora"])
         self.ts.load_torch_optimizer_state_dict(ckpt["opt"])
         if self.enable_ema:
@@ -444,6 +454,10 @@ def main(argv=None) -> int:
     ap.add_argument("--lora_rank", type=int, default=0, help="train LoRA adapters of this rank over the frozen model instead of the reference's set")
     ap.add_argument("--lora_alpha", type=float, default=None, help="the adapters' alpha (default: the rank)")
     ap.add_argument("--lora_families", nargs="+", default=["attn"], choices=["attn", "ff", "proj"])
+    ap.add_argument("--lora_conv_families", nargs="+", default=[], choices=["conv", "emb", "sample"],
+                    help="also adapt ResBlock convs and skip_connection (conv), emb_layers.1 (emb), Downsample / Upsample convs (sample)")
+    ap.add_argument("--lora_conv_rank", type=int, default=None, help="rank of the adapters on 3 x 3 convs (default: lora_rank)")
+    ap.add_argument("--lora_conv_alpha", type=float, default=None, help="their alpha (default: lora_conv_rank)")
     ap.add_argument("--lora_out", default=None, help="the adapter in kohya's format (.safetensors), rewritten at every save point; default output_dir/lora.safetensors")
     ap.add_argument("--resume", action="store_true", help="continue from output_dir/checkpoint_latest.pth (also the default when that file exists)")
     ap.add_argument("--fresh", action="store_true", help="start from iteration 0 even if output_dir holds a checkpoint")
@@ -460,7 +474,8 @@ def main(argv=None) -> int:
                   output_dir=a.output_dir, ckpt=None, batch_size=a.batch_size, seed=a.seed, disable_inference_in_training=True,
                   gradient_accumulation_steps=a.gradient_accumulation_steps, max_grad_norm=a.max_grad_norm or None, min_snr_gamma=a.min_snr_gamma or None)
     if a.lora_rank:
-        config.update(lora_rank=a.lora_rank, lora_alpha=a.lora_alpha, lora_families=list(a.lora_families),
+        config.update(lora_rank=a.lora_rank, lora_alpha=a.lora_alpha, lora_families=list(a.lora_families), lora_conv_families=list(a.lora_conv_families),
+                      lora_conv_rank=a.lora_conv_rank, lora_conv_alpha=a.lora_conv_alpha,
                       lora_out=a.lora_out or os.path.join(a.output_dir, "lora.safetensors"))
     latest = os.path.join(a.output_dir, "checkpoint_latest.pth")
     if a.resume and not os.path.exists(latest):
