@@ -1,6 +1,6 @@
 """ctypes binding of libgligen_amd.so (C ABI declared in include/gligen_amd.h, include/gligen_amd_image.h, include/gligen_amd_maps.h and
 include/gligen_amd_train_maps.h, include/gligen_amd_train_inputs.h, include/gligen_amd_train_fusers.h, include/gligen_amd_train_prims.h,
-include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_ffn_rows.h, include/gligen_amd_norm.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h, include/gligen_amd_lora.h, include/gligen_amd_tiling.h, include/gligen_amd_train_lora.h, include/gligen_amd_train_lora_conv.h and include/gligen_amd_train_run.h).
+include/gligen_amd_trainer.h, include/gligen_amd_sampler.h, include/gligen_amd_solver.h, include/gligen_amd_gemm_plans.h, include/gligen_amd_attention_core.h, include/gligen_amd_conv8.h, include/gligen_amd_ffn_rows.h, include/gligen_amd_norm.h, include/gligen_amd_vae.h, include/gligen_amd_latent.h, include/gligen_amd_lora.h, include/gligen_amd_tiling.h, include/gligen_amd_train_lora.h, include/gligen_amd_train_lora_conv.h and include/gligen_amd_train_run.h).
 
 The library is the only compute path: if it is missing or a call fails, this module raises —
 there is no PyTorch/CPU fallback anywhere in the package.
@@ -315,6 +315,20 @@ GEMM_PLAN_SYMBOLS = {
 ATTENTION_CORE_SYMBOLS = {
     "gl_op_attention_core": (_I, [_P, _P, _P, _P, C.POINTER(AttnProjLayout), _I, _I, _I, _I, _P, _I, _I, _I, _P]),
 }
+
+
+class Conv8Args(C.Structure):   # = gl_conv8_args
+    _fields_ = [("struct_size", C.c_uint), ("x0", _P), ("x1", _P)] + [(n, _I) for n in ("C0", "C1", "B", "H", "W", "N", "stride", "ups", "pad_lo")] + \
+               [("w", _P), ("bias", _P), ("bias2", _P), ("bias2_ld", _I), ("rows_per_b", _I), ("res", _P), ("ldres", _I), ("act", _I), ("out_f32", _I),
+                ("out", _P), ("ldo", _I), ("bn", _I), ("splits", _I), ("grid_cap", _I), ("slabs", _P), ("slab_bytes", C.c_size_t)]
+
+
+# every symbol include/gligen_amd_conv8.h declares (conv8_kernel by name on the caller's buffers, the router's answer, the family's knobs)
+CONV8_SYMBOLS = {
+    "gl_op_conv8x8": (_I, [_P, C.POINTER(Conv8Args), _P]),
+    "gl_conv8_routed": (_I, [C.POINTER(Conv8Args)]),
+    "gl_conv8_force_knobs": (_I, [_I, _I, _I]),
+}
 ATTN_CORE_KERNELS = {"auto": 0, "attn_kernel": 1, "attn2_kernel_w4": 2, "attn2_kernel_w8": 3, "attn3_kernel": 4}   # = GL_ATTN_CORE_*
 GL_ERR_UNSUPPORTED = 5
 
@@ -415,7 +429,7 @@ def load() -> C.CDLL:
     import torch  # noqa: F401
     lib = C.CDLL(str(LIB_PATH))
     for name, (res, args) in {**SYMBOLS, **IMAGE_SYMBOLS, **MAP_SYMBOLS, **TRAIN_MAP_SYMBOLS, **TRAIN_INPUT_SYMBOLS, **TRAIN_FUSER_SYMBOLS, **TRAIN_PRIM_SYMBOLS,
-                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **FFN_ROWS_SYMBOLS, **NORM_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS, **TILING_SYMBOLS, **TRAIN_LORA_SYMBOLS, **TRAIN_LORA_CONV_SYMBOLS,
+                              **TRAINER_SYMBOLS, **SAMPLER_SYMBOLS, **SOLVER_SYMBOLS, **GEMM_PLAN_SYMBOLS, **ATTENTION_CORE_SYMBOLS, **CONV8_SYMBOLS, **FFN_ROWS_SYMBOLS, **NORM_SYMBOLS, **VAE_SYMBOLS, **LATENT_SYMBOLS, **LORA_SYMBOLS, **TILING_SYMBOLS, **TRAIN_LORA_SYMBOLS, **TRAIN_LORA_CONV_SYMBOLS,
                               **TRAIN_RUN_SYMBOLS}.items():
         fn = getattr(lib, name)  # AttributeError if the symbol is not exported
         fn.restype = res

@@ -16,8 +16,8 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 INCLUDE = HERE.parent / "include"
 LIB = HERE / "libgligen_amd.so"
-# the GEMM: four kernel units and the host unit behind csrc/gemm_impl.h (tools/build_variant.sh and the ISA tests compile these)
-GEMM_UNITS = ["gemm_u.hip", "gemm_halo.hip", "gemm_wide.hip", "gemm_basic.hip", "gemm.hip"]
+# the GEMM: five kernel units and the host unit behind csrc/gemm_impl.h (tools/build_variant.sh and the ISA tests compile these)
+GEMM_UNITS = ["gemm_u.hip", "gemm_halo.hip", "gemm_wide.hip", "gemm_conv8.hip", "gemm_basic.hip", "gemm.hip"]
 SOURCES = [*GEMM_UNITS, "gemm_plan.hip", "ffn.hip", "attention.hip", "vae_attention.hip", "clip.hip", "norm.hip", "misc.hip", "image.hip", "latent.hip", "tile.hip", "lora.hip", "classmap.hip", "convnext.hip",
            "train_ops.hip", "train_attention.hip", "train_layers.hip", "train_spatial.hip", "train_unet.hip", "train_inputs.hip", "train_fusers.hip", "train_optim.hip", "train_lora.hip", "train_lora_conv.hip", "train_run.hip",
            "engine.hip", "engine_unet.hip", "engine_policy.hip", "engine_vae.hip", "engine_clip.hip", "engine_spatial.hip", "engine_sampler.hip", "capi.hip"]

@@ -19,6 +19,7 @@
 #include "../../include/gligen_amd_sampler.h"
 #include "../../include/gligen_amd_gemm_plans.h"
 #include "../../include/gligen_amd_attention_core.h"
+#include "../../include/gligen_amd_conv8.h"
 #include "../../include/gligen_amd_ffn_rows.h"
 #include "../../include/gligen_amd_norm.h"
 #include "../../include/gligen_amd_vae.h"
@@ -573,6 +574,7 @@ int gl_gemm_plan_log(gl_gemm_plan_record* out, int max, int* n_written, int* n_l
         r.family = p.family; r.M = e[i].M; r.N = e[i].N; r.K = e[i].K;
         r.tm = p.tm; r.tn = p.tn; r.splits = p.splits; r.grid = p.grid;
         if (p.family == GEMM_HALO) { r.n_items = p.halo.n_items; r.units_per_split = p.halo.chunks_per_split; }
+        else if (p.family == GEMM_CONV8) { r.n_items = p.conv8.n_items; r.units_per_split = p.conv8.chunks_per_split; }
         else if (p.family == GEMM_WIDE) { r.n_items = p.wide.n_items; r.units_per_split = p.wide.kt_per_split; r.xcd = p.wide.xcd; }
         else {
             r.n_items = p.work.n_items; r.units_per_split = p.work.kt_per_split;
@@ -1675,6 +1677,61 @@ int gl_op_gemm_epilogue(gl_ctx* ctx, const gl_gemm_epilogue_args* a, gl_stream s
     E.n_real = a->n_real;
     E.remap_in = a->remap_in; E.remap_out = a->remap_out; E.remap_off = a->remap_off;
     int r = gemm_launch(A, w, M, a->N, K, E, eng.splitk_ws(), eng.splitk_ws_bytes(), S(s));
+    if (r != GL_OK) throw GlError(r, gl::last_error());
+    GL_API_END
+}
+
+// ---- include/gligen_amd_conv8.h: conv8_kernel by name, the router's answer, the family's knobs
+static bool conv8_describe(const gl_conv8_args* a, AOperand& A, Epilogue& E, int& M, int& K) {
+    if (a->C0 < 1 || a->C1 < 0 || a->B < 1 || a->H < 1 || a->W < 1 || a->N < 1 || a->ups < 0 || a->ups > 1 || (a->stride != 1 && a->stride != 2) ||
+        a->rows_per_b < 1)
+        return false;
+    const int Cin = a->C0 + a->C1;
+    const int Hup = a->H << a->ups, Wup = a->W << a->ups;
+    const int Ho = a->stride == 1 ? Hup : (a->pad_lo ? (Hup + 2 - 3) / 2 + 1 : (Hup + 1 - 3) / 2 + 1);
+    const int Wo = a->stride == 1 ? Wup : (a->pad_lo ? (Wup + 2 - 3) / 2 + 1 : (Wup + 1 - 3) / 2 + 1);
+    A = AOperand{};
+    A.p0 = (const bf16*)a->x0; A.C0 = a->C0; A.ld0 = a->C0; A.p1 = (const bf16*)a->x1; A.C1 = a->C1; A.ld1 = a->C1;
+    A.mode = A_CONV3; A.Hin = a->H; A.Win = a->W; A.Ho = Ho; A.Wo = Wo; A.stride = a->stride; A.ups = a->ups; A.pad_lo = a->pad_lo;
+    M = a->B * Ho * Wo; K = 9 * Cin;
+    epilogue_defaults(E);
+    E.act = a->act; E.out = a->out; E.ldo = a->ldo; E.out_f32 = a->out_f32;
+    E.bias = a->bias; E.bias2 = a->bias2; E.bias2_ld = a->bias2_ld; E.rows_per_b = a->rows_per_b;
+    E.res = (const bf16*)a->res; E.ldres = a->ldres;
+    return true;
+}
+int gl_conv8_routed(const gl_conv8_args* a) {
+    if (!a || a->struct_size != sizeof(gl_conv8_args)) { gl::set_error(GL_ERR_ARG, "gl_conv8_routed: null args or a struct_size that is not this library's"); return -1; }
+    AOperand A;
+    Epilogue E;
+    int M, K;
+    if (!conv8_describe(a, A, E, M, K)) { gl::set_error(GL_ERR_ARG, "gl_conv8_routed: conv geometry"); return -1; }
+    return gemm_conv8_supported(A, M, a->N, K, E) ? 1 : 0;
+}
+int gl_conv8_force_knobs(int on, int bn, int splits) {
+    if (on < 0 || on > 1 || (bn != 0 && bn != 64 && bn != 80) || splits < 0 || splits > 32)
+        return gl::set_error(GL_ERR_ARG, "gl_conv8_force_knobs: on %d, bn %d, splits %d (0 | 1, 0 | 64 | 80, 0..32)", on, bn, splits);
+    gemm_conv8_force_knobs(on, bn, splits);
+    return GL_OK;
+}
+int gl_op_conv8x8(gl_ctx* ctx, const gl_conv8_args* a, gl_stream s) {
+    NEED(ctx);
+    if (!a) return gl::set_error(GL_ERR_ARG, "gl_op_conv8x8: null args");
+    if (a->struct_size != sizeof(gl_conv8_args))
+        return gl::set_error(GL_ERR_ARG, "gl_op_conv8x8: args->struct_size is %u, this library's gl_conv8_args has %zu bytes", a->struct_size, sizeof(gl_conv8_args));
+    if (!a->x0 || !a->w || !a->out || (a->C1 && !a->x1) || (a->splits > 1 && !a->slabs))
+        return gl::set_error(GL_ERR_ARG, "gl_op_conv8x8: null pointer (x0, w, out; x1 when C1 > 0; slabs when splits > 1)");
+    GL_API_BEGIN
+    AOperand A;
+    Epilogue E;
+    int M, K;
+    if (!conv8_describe(a, A, E, M, K)) throw GlError(GL_ERR_ARG, "gl_op_conv8x8: conv geometry");
+    Arena& ar = ctx->eng->arena();
+    ar.reset();
+    bf16* wp = ar.get<bf16>((size_t)a->N * K);
+    int r = pack_conv_weight_launch((const float*)a->w, wp, a->N, a->C0 + a->C1, 3, 3, a->N, S(s));
+    if (r != GL_OK) throw GlError(r, gl::last_error());
+    r = gemm_conv8_launch(A, wp, M, a->N, K, E, a->splits > 1 ? a->slabs : nullptr, a->splits > 1 ? a->slab_bytes : 0, a->bn, a->splits, a->grid_cap, S(s));
     if (r != GL_OK) throw GlError(r, gl::last_error());
     GL_API_END
 }

@@ -503,8 +503,11 @@ void Engine::attention(const bf16* q, const bf16* k, const bf16* vt, bf16* o, in
     ++n_launches;
 }
 
-void Engine::gemm(const AOperand& A, const bf16* W, int M, int N, int K, const Epilogue& E, hipStream_t s) {
+void Engine::gemm(const AOperand& A_in, const bf16* W, int M, int N, int K, const Epilogue& E, hipStream_t s) {
     ProfScope ps(this, s, "gemm", 2.0 * M * N * K, 0.0);
+    AOperand A = A_in;
+    // the stride-1 convs of the 8 x 8 level: conv8_kernel stages an image once per channel chunk (gemm.h A_CONV8; same weights)
+    if (A.mode == A_CONV3 && gemm_conv8_supported(A, M, N, K, E)) A.mode = A_CONV8;
     CK(gemm_launch(A, W, M, N, K, E, ws_, ws_bytes_, s));
     if (profiling_) {
         static const bool by_shape = dev_env("GL_PROF_SHAPES") != nullptr;  // developer aid: one record per problem, not per symbol

@@ -4,7 +4,7 @@
 
 namespace gl {
 
-enum { A_ROWS = 0, A_CONV3 = 1, A_CONV2UP = 2 };
+enum { A_ROWS = 0, A_CONV3 = 1, A_CONV2UP = 2, A_CONV8 = 3 };
 
 // The activation ("rows") operand: logical matrix [M][K], bf16.
 //  A_ROWS : row m = concat(p0[m*ld0 .. +C0), p1[m*ld1 .. +C1)),  K = C0 + C1
@@ -17,6 +17,9 @@ enum { A_ROWS = 0, A_CONV3 = 1, A_CONV2UP = 2 };
 //           in one phase. k = (2a + b)*(C0+C1) + c for source tap (y - 1 + py + a, x - 1 + px + b); W = [4][N][K] from
 //           pack_upconv_phases_launch (misc.h). Ho = 2 Hin, Wo = 2 Win; stride, ups, pad_lo are not read. gemm_u_kernel only, plain
 //           bias epilogue to row-major bf16: ask gemm_upconv_phases_supported() first.
+//  A_CONV8: the A_CONV3 problem with stride 1, pad 1, no upsample on 8 x 8 images, same weights [N][9 (C0+C1)], run by conv8_kernel
+//           (gemm_conv8.hip), which stages every image once per 64-channel chunk instead of once per tap. The caller opts in: ask
+//           gemm_conv8_supported() with the A_CONV3 descriptor first and switch the mode when it says yes (Engine::gemm does).
 struct AOperand {
     const bf16* p0;
     const bf16* p1;
@@ -129,6 +132,11 @@ const char* gemm_last_kernel_name();  // kernel symbol (template arguments inclu
 bool gemm_gn_prologue_supported(const AOperand& A, int M, int N, int K, const Epilogue& E);   // may this launch take AOperand::gn?
 bool gemm_upconv_phases_supported(const AOperand& A, int M, int N, int K, const Epilogue& E);   // may this launch take A_CONV2UP?
 bool gemm_ln_fold_supported(const AOperand& A, int M, int N, int K, const Epilogue& E);   // may this launch take Epilogue::ln_stats?
+bool gemm_conv8_supported(const AOperand& A, int M, int N, int K, const Epilogue& E);   // may this A_CONV3 launch run as A_CONV8?
+// conv8_kernel by name (include/gligen_amd_conv8.h): column tile bn (64 | 80), K split and cap on resident workgroups (0: 256) as given,
+// for every problem the kernel can run whatever the router thinks of it; slabs of a split launch go to ws
+int gemm_conv8_launch(const AOperand& A, const bf16* W, int M, int N, int K, const Epilogue& E, float* ws, size_t ws_bytes, int bn, int splits,
+                      int grid_cap, hipStream_t stream);
 int gemm_last_stats_nb();             // column blocks per row written to Epilogue::stats_out by the most recent gemm_launch (0: none)
 void aoperand_rows(AOperand& A, const bf16* p, int K, int ld);
 

@@ -7,11 +7,12 @@
 // ldm/modules/attention.py:37-64,102-186 projections and GEGLU, ldm/modules/diffusionmodules/
 // model.py:82-141 VAE ResnetBlock).
 //
-// Five files behind one internal header (gemm_impl.h: the helpers the kernels share, Launch, the units' entry functions):
+// Six files behind one internal header (gemm_impl.h: the helpers the kernels share, Launch, the units' entry functions):
 //   gemm_basic.hip  gemm_glds_kernel (N < 128, the independent reference of `kbench check`) and gemm_p_kernel (operands beyond 2 GiB)
 //   gemm_u.hip      gemm_u_kernel, the default: GEMMs and 3x3 convs of every kind
 //   gemm_halo.hip   conv_halo_kernel: stride-1 3x3 convs on power-of-two images, optionally with the GroupNorm + SiLU prologue
 //   gemm_wide.hip   gemm_wide_kernel: long-K, wide-N row GEMMs (FF-out, GEGLU projections)
+//   gemm_conv8.hip  conv8_kernel: the stride-1 3x3 convs of the 8 x 8 level, each image staged once per channel chunk (A_CONV8)
 //   gemm.hip        this file: execute() for a GemmPlan, the split-K reduce, the on-device tuner's timing loop, gemm_launch
 // Which kernel runs a problem (family, tile, K split, resident grid, item order) is decided in gemm_plan.h / gemm_plan.hip, host code
 // without a HIP call.
@@ -162,6 +163,7 @@ int execute(const GemmPlan& p, const AOperand& A, const bf16* W, int M, int N, i
         case GEMM_U: GL_TRY(gemm_exec_u(l, p)); break;
         case GEMM_HALO: GL_TRY(gemm_exec_halo(l, p)); break;
         case GEMM_WIDE: GL_TRY(gemm_exec_wide(l, p)); break;
+        case GEMM_CONV8: GL_TRY(gemm_exec_conv8(l, p)); break;
         default: return gemm_unknown_tile();
     }
     if (p.splits > 1) {
@@ -241,6 +243,18 @@ int gemm_launch(const AOperand& A, const bf16* W, int M, int N, int K, const Epi
     t_last = plan;
     t_log[t_log_n % kGemmLogSize] = GemmLogEntry{plan, M, N, K};
     t_log_n = t_log_n == INT_MAX ? kGemmLogSize : t_log_n + 1;   // (the ring position survives the wrap: kGemmLogSize divides 2^31)
+    return execute(plan, A, W, M, N, K, E, ws, stream);
+}
+
+int gemm_conv8_launch(const AOperand& A_in, const bf16* W, int M, int N, int K, const Epilogue& E_in, float* ws, size_t ws_bytes, int bn, int splits,
+                      int grid_cap, hipStream_t stream) {
+    t_last.stats_nb = 0;
+    AOperand A = A_in;
+    A.mode = A_CONV8;
+    Epilogue E = E_in;
+    GemmPlan plan;
+    GL_TRY(gemm_conv8_plan(A, M, N, K, E, ws != nullptr, ws_bytes, bn, splits, grid_cap, plan));
+    t_last = plan;
     return execute(plan, A, W, M, N, K, E, ws, stream);
 }
 

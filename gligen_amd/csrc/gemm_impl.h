@@ -3,6 +3,7 @@
 //   gemm_u.hip      gemm_u_kernel
 //   gemm_halo.hip   conv_halo_kernel
 //   gemm_wide.hip   gemm_wide_kernel
+//   gemm_conv8.hip  conv8_kernel
 //   gemm.hip        execute() for a GemmPlan, splitk_reduce_kernel, the on-device tuner, gemm_launch
 // Here: the epilogue and LDS-read helpers more than one unit inlines, the two LDS-DMA macros, the host-side Launch and the entry
 // function of every kernel unit. The build has no relocatable device code: a kernel is launched only from the unit that defines it,
@@ -328,6 +329,7 @@ int gemm_exec_basic(const Launch& l, const GemmPlan& p);   // GEMM_GLDS, GEMM_P
 int gemm_exec_u(const Launch& l, const GemmPlan& p);
 int gemm_exec_halo(const Launch& l, const GemmPlan& p);
 int gemm_exec_wide(const Launch& l, const GemmPlan& p);
+int gemm_exec_conv8(const Launch& l, const GemmPlan& p);
 inline int gemm_unknown_tile() { return set_error(GL_ERR_UNSUPPORTED, "gemm: unknown tile candidate"); }
 
 }  // namespace gl

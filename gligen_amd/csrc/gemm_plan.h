@@ -10,7 +10,7 @@
 namespace gl {
 
 // ---- kernel descriptors (the planner fills them, the kernels read them: WorkDesc gemm_u.hip / gemm_basic.hip, HaloDesc gemm_halo.hip,
-// WideDesc gemm_wide.hip)
+// WideDesc gemm_wide.hip, Conv8Desc gemm_conv8.hip)
 struct WorkDesc {
     int tiles_n;
     int splits;
@@ -30,6 +30,10 @@ struct WideDesc {
     int tiles_n, splits, kt_per_split, n_items;
     int xcd;   // 1: every XCD walks a contiguous range of the (tile_m, tile_n) order (see plan_wide)
 };
+struct Conv8Desc {
+    int tiles_n, splits, chunks_per_split, n_items;
+    int tiles_m;   // row groups of four samples (the last one may be partly empty)
+};
 
 // ---- every developer switch of the GEMM (meanings: tools/README.md), read once through dev_env; the gemm_set_* / gemm_force_*
 // functions of gemm.h write into it. Process-wide: set them before launching, not while other threads launch.
@@ -41,12 +45,15 @@ struct GemmKnobs {
     int autotune = 1, tune_reps = 3, corun = 0;   // GL_GEMM_AUTOTUNE / gemm_set_autotune, GL_GEMM_TUNE_REPS, GL_GEMM_TUNE_CORUN
     bool no_table = false, tune_log = false;      // GL_GEMM_NO_TABLE, GL_GEMM_TUNE_LOG (set = on)
     int force_tm = 0, force_tn = 0, force_splits = 0, force_grid = 0;   // gemm_force_cfg / gemm_force_grid (kbench sweeps, gl_gemm_force_plan)
+    int conv8 = 1, conv8_bn = 0, conv8_splits = 0;   // GL_CONV8 (0: A_CONV8 is never offered), GL_CONV8_BN (64 | 80; 0 = automatic), GL_CONV8_SPLITS
 };
 GemmKnobs& gemm_knobs();
 // The knobs a test sets through include/gligen_amd_gemm_plans.h that otherwise only the environment reaches; gemm_force_clear puts
 // them back to what the environment / the defaults say and drops gemm_force_cfg / gemm_force_grid.
 void gemm_force_knobs(int halo_splits, int wide_splits, int wide_xcd, int xcd_boxes, int halo, int wide);
 void gemm_force_clear();
+// conv8_kernel's own knobs (include/gligen_amd_conv8.h); gemm_force_clear puts them back as well
+void gemm_conv8_force_knobs(int on, int bn, int splits);
 
 struct GemmProblem {
     const AOperand& A;
@@ -55,21 +62,22 @@ struct GemmProblem {
     bool has_ws; size_t ws_bytes;   // the split-K workspace the caller passed
 };
 
-enum GemmFamily { GEMM_GLDS, GEMM_P, GEMM_U, GEMM_HALO, GEMM_WIDE };
+enum GemmFamily { GEMM_GLDS, GEMM_P, GEMM_U, GEMM_HALO, GEMM_WIDE, GEMM_CONV8 };
 
 // A tile / split / resident-grid choice of the p / u family: index into the candidate tiles, K split, grid cap (0 = 512)
 struct GemmCand { int c, sp, grid; };
 constexpr int kGemmTiles = 5;
 extern const int kGemmTm[kGemmTiles], kGemmTn[kGemmTiles];   // in units of 32 rows / columns
 
-// Everything a launch needs. The instantiation is (family, tm, tn, amode, qkv, gn); tm, tn in units of 32 (halo / wide: tm = 8).
+// Everything a launch needs. The instantiation is (family, tm, tn, amode, qkv, gn); tm, tn in units of 32 (halo / wide: tm = 8;
+// conv8: tm = 8 and tn in units of 16).
 struct GemmPlan {
     int family;
     int tm, tn, amode;
     bool qkv, gn;         // gemm_u_kernel: the head-layout instantiation (QKV = true); conv_halo_kernel: GroupNorm prologue
     int splits;
     int grid;             // workgroups launched (glds: tiles, times `splits` in z)
-    union { WorkDesc work; HaloDesc halo; WideDesc wide; };
+    union { WorkDesc work; HaloDesc halo; WideDesc wide; Conv8Desc conv8; };
     int stats_nb;         // column blocks of row statistics this launch writes to Epilogue::stats_out (0: none)
     char name[96];
 };
@@ -89,5 +97,10 @@ using GemmTuner = std::function<int(const GemmProblem& pb, bool use_u, const cha
 
 // gemm_validate -> gemm_route -> forced choice | shipped table and earlier winners | analytic model (| tuner) -> plan.
 int gemm_plan(const AOperand& A, int M, int N, int K, Epilogue& E, bool has_ws, size_t ws_bytes, GemmPlan& plan, const GemmTuner& tuner = nullptr);
+
+// conv8_kernel with exactly this column tile (64 | 80), K split and cap on resident workgroups (0: 256) for any problem the KERNEL can
+// run (conv8_kernel_eligible: fewer channels than the router asks for included), whatever the router would do with it: the plan of
+// gemm_conv8_launch (gemm.h). A split that leaves a part without a chunk, or slabs beyond the workspace, is an error here.
+int gemm_conv8_plan(const AOperand& A, int M, int N, int K, Epilogue& E, bool has_ws, size_t ws_bytes, int bn, int splits, int grid_cap, GemmPlan& plan);
 
 }  // namespace gl

@@ -16,7 +16,8 @@ static GemmKnobs read_knobs() {
         {"GL_GEMM_VARIANT", &GemmKnobs::variant}, {"GL_GEMM_WIDE", &GemmKnobs::wide}, {"GL_GEMM_WIDE_SPLITS", &GemmKnobs::wide_splits},
         {"GL_CONV_HALO", &GemmKnobs::halo}, {"GL_CONV_HALO_SPLITS", &GemmKnobs::halo_splits}, {"GL_GEMM_XCD_BOXES", &GemmKnobs::xcd_boxes},
         {"GL_WIDE_XCD", &GemmKnobs::wide_xcd}, {"GL_GEMM_AUTOTUNE", &GemmKnobs::autotune}, {"GL_GEMM_TUNE_REPS", &GemmKnobs::tune_reps},
-        {"GL_GEMM_TUNE_CORUN", &GemmKnobs::corun}};
+        {"GL_GEMM_TUNE_CORUN", &GemmKnobs::corun}, {"GL_CONV8", &GemmKnobs::conv8}, {"GL_CONV8_BN", &GemmKnobs::conv8_bn},
+        {"GL_CONV8_SPLITS", &GemmKnobs::conv8_splits}};
     GemmKnobs k;
     for (const auto& e : kInt)
         if (const char* v = dev_env(e.env)) k.*e.knob = atoi(v);
@@ -37,11 +38,16 @@ void gemm_force_knobs(int halo_splits, int wide_splits, int wide_xcd, int xcd_bo
     GemmKnobs& k = gemm_knobs();
     k.halo_splits = halo_splits; k.wide_splits = wide_splits; k.wide_xcd = wide_xcd; k.xcd_boxes = xcd_boxes; k.halo = halo; k.wide = wide;
 }
+void gemm_conv8_force_knobs(int on, int bn, int splits) {
+    GemmKnobs& k = gemm_knobs();
+    k.conv8 = on; k.conv8_bn = bn; k.conv8_splits = splits;
+}
 void gemm_force_clear() {
     const GemmKnobs d = read_knobs();
     gemm_force_cfg(0, 0, 0);
     gemm_force_grid(0);
     gemm_force_knobs(d.halo_splits, d.wide_splits, d.wide_xcd, d.xcd_boxes, d.halo, d.wide);
+    gemm_conv8_force_knobs(d.conv8, d.conv8_bn, d.conv8_splits);
 }
 static thread_local int t_no_split = 0;
 void gemm_set_no_split(int on) { t_no_split = on; }
@@ -82,6 +88,27 @@ static bool halo_eligible(const AOperand& A, int M, int N, int K, const Epilogue
     if (E.bias2 && (E.rows_per_b != A.Hin * A.Win)) return false;
     return fits_buffer_offsets(A, M, N, K);
 }
+// What conv8_kernel (gemm_conv8.hip) can run: 3x3, stride 1, pad 1 on 8 x 8 images, whole 64-channel chunks per source, whole 64- or
+// 80-wide column tiles, a row-major epilogue (its unsplit form is epi_finish4, the split form splitk_reduce_kernel: bias, per-sample
+// bias, residual, SiLU, bf16 or fp32 out). The mode may be A_CONV3 (a question) or A_CONV8 (a launch).
+static bool conv8_kernel_eligible(const AOperand& A, int M, int N, int K, const Epilogue& E) {
+    if ((A.mode != A_CONV3 && A.mode != A_CONV8) || A.stride != 1 || A.ups || A.pad_lo != 1 || A.gn) return false;
+    if (A.Hin != 8 || A.Win != 8 || A.Ho != 8 || A.Wo != 8 || M <= 0 || M % 64) return false;
+    if (A.C0 <= 0 || A.C0 % 64 || A.C1 % 64 || K != 9 * (A.C0 + A.C1) || (N % 64 && N % 80)) return false;
+    if (E.mode != EPI_ROWMAJOR || E.remap_in || E.gate || (E.act != ACT_NONE && E.act != ACT_SILU) || E.ln_stats) return false;
+    return fits_buffer_offsets(A, M, N, K);
+}
+// The router's answer (the caller switches A_CONV3 to A_CONV8 on a yes; GL_CONV8=0: never): the kernel's problems with at least ten
+// chunks of input channels -- below that the K split that fills the chip leaves a workgroup one or two chunks, all prologue -- and
+// what gemm_u_kernel's conv instantiations take otherwise (v5 main loop, no per-sample bias next to a residual, no forced tile)
+bool gemm_conv8_supported(const AOperand& A, int M, int N, int K, const Epilogue& E) {
+    const GemmKnobs& kn = gemm_knobs();
+    if (!kn.conv8 || kn.variant != 4 || kn.force_tm || A.C0 + A.C1 < 640 || N < 128 || (E.bias2 && E.res)) return false;
+    if (kn.conv8_bn && (kn.conv8_bn != 64 && kn.conv8_bn != 80)) return false;
+    if (kn.conv8_bn && N % kn.conv8_bn) return false;
+    return conv8_kernel_eligible(A, M, N, K, E);
+}
+
 // The wide kernel's problems: row-major activations, whole 256 x BN tiles, plain / residual / SiLU / GEGLU row-major epilogues.
 static bool wide_eligible(const AOperand& A, int M, int N, int K, const Epilogue& E) {
     if (A.mode != A_ROWS || M % 256 || (N % 160 && N % 128)) return false;
@@ -95,6 +122,7 @@ static bool wide_eligible(const AOperand& A, int M, int N, int K, const Epilogue
 // The kernel family a (valid) problem goes to. honour_force = false: as if no gemm_force_cfg override were set.
 static int gemm_route(const AOperand& A, int M, int N, int K, const Epilogue& E, bool honour_force = true) {
     const GemmKnobs& kn = gemm_knobs();
+    if (A.mode == A_CONV8) return GEMM_CONV8;   // (gemm_validate has asked conv8_kernel_eligible)
     // the phase form of the upsample convs exists in gemm_u_kernel only, narrow outputs included (gemm_validate refuses every other family)
     if (A.mode == A_CONV2UP) return kn.variant == 4 && fits_buffer_offsets(A, M, N, K) ? GEMM_U : GEMM_P;
     // gemm_glds_kernel: narrow outputs, and everything under variant 1
@@ -161,6 +189,9 @@ static int gemm_validate(const AOperand& A, int M, int N, int K, Epilogue& E) {
     if (A.mode == A_CONV2UP) {
         if (!gemm_upconv_phases_supported(A, M, N, K, E))
             return set_error(GL_ERR_UNSUPPORTED, "conv3x3: no phase form of the upsample conv for this launch (gemm_u_kernel, bias-only bf16 epilogue, K = 4 Cin, N %% 8 == 0)");
+    } else if (A.mode == A_CONV8) {
+        if (!conv8_kernel_eligible(A, M, N, K, E))
+            return set_error(GL_ERR_UNSUPPORTED, "conv3x3: A_CONV8 is the 3x3 / stride 1 / pad 1 conv of 8 x 8 images (channels %% 64, N %% 64 or 80, plain row-major epilogue)");
     } else if (A.mode == A_CONV3) {
         if ((A.C0 + A.C1) % 64 != 0 || A.C0 % 64 != 0 || K != 9 * (A.C0 + A.C1))
             return set_error(GL_ERR_ARG, "conv3x3: channels (%d,%d) must be multiples of 64 and K=9*Cin (K=%d)", A.C0, A.C1, K);
@@ -271,6 +302,51 @@ void plan_wide(const GemmProblem& pb, const GemmProblem& ph, GemmPlan& p) {
     p.tm = 8; p.tn = tn; p.splits = wd.splits;
     p.grid = std::min(wd.n_items, 256);
     snprintf(p.name, sizeof p.name, "gemm_wide_kernel<%d>%s", tn, reduce_suffix(p.splits));
+}
+
+// conv8_kernel: column tile (64 | 80) and K split in whole chunks. One work item per CU and launch: the items of a second round
+// would start behind a full first one. In units of one chunk at a 64-wide tile, a launch costs
+//   rounds x (chunks per split x BN / 64 + 1 for an item's prologue and store) + (split: 0.5 + 0.25 per slab for the reduce pass)
+// and the cheapest (BN, split) is taken: for batch 8 that is four or five chunks per workgroup on 200-240 CUs. Measured choices for
+// the benchmark's two shapes (profiles/conv8/) come first; GL_CONV8_BN / GL_CONV8_SPLITS (gemm_conv8_force_knobs) override both.
+void plan_conv8_choice(const GemmProblem& ph, int& bn, int& splits) {
+    const int N = ph.N, chunks = (ph.A.C0 + ph.A.C1) / 64, groups = cdiv(ph.M, 256);
+    const GemmKnobs& kn = gemm_knobs();
+    static const struct { int M, N, chunks, bn, sp; } kMeasured[] = {{512, 1280, 20, 64, 5}, {512, 1280, 40, 80, 8}};
+    int want_bn = kn.conv8_bn, want_sp = kn.conv8_splits;
+    if (!kn.no_table)
+        for (const auto& e : kMeasured)
+            if (e.M == ph.M && e.N == N && e.chunks == chunks) {
+                if (!want_bn && !want_sp) { want_bn = e.bn; want_sp = e.sp; }
+            }
+    double best = 1e300;
+    bn = 0; splits = 1;
+    for (int b = 64; b <= 80; b += 16) {
+        if (N % b || (want_bn && want_bn != b)) continue;
+        const int tiles = groups * (N / b);
+        for (int sp = 1; sp <= std::min(chunks, 32); ++sp) {
+            const int per = cdiv(chunks, sp);
+            if (cdiv(chunks, per) != sp) continue;                 // (not a split count of its own: the same launch as a smaller one)
+            if (want_sp && sp != cdiv(chunks, cdiv(chunks, std::min(want_sp, chunks)))) continue;
+            if (sp > 1 && (!ph.has_ws || (size_t)sp * ph.M * N * sizeof(float) > ph.ws_bytes)) continue;
+            const double t = cdiv(tiles * sp, 256) * (per * b / 64.0 + 1.0) + (sp > 1 ? 0.5 + 0.25 * sp : 0.0);
+            if (t < best) { best = t; bn = b; splits = sp; }
+        }
+    }
+    if (!bn) { bn = N % 64 == 0 ? 64 : 80; splits = 1; }   // (a wanted split the workspace cannot hold: unsplit)
+}
+void plan_conv8_fill(const GemmProblem& pb, int bn, int splits, int grid_cap, GemmPlan& p) {
+    const int chunks = (pb.A.C0 + pb.A.C1) / 64;
+    Conv8Desc& cd = p.conv8;
+    cd.tiles_m = cdiv(pb.M, 256);
+    cd.tiles_n = pb.N / bn;
+    cd.chunks_per_split = cdiv(chunks, splits);
+    cd.splits = cdiv(chunks, cd.chunks_per_split);
+    cd.n_items = cd.tiles_m * cd.tiles_n * cd.splits;
+    p.family = GEMM_CONV8;
+    p.tm = 8; p.tn = bn / 16; p.amode = A_CONV8; p.splits = cd.splits;
+    p.grid = std::min(cd.n_items, grid_cap > 0 ? grid_cap : 256);
+    snprintf(p.name, sizeof p.name, "conv8_kernel<%d>%s", bn, reduce_suffix(p.splits));
 }
 
 }  // namespace
@@ -466,6 +542,13 @@ int gemm_plan(const AOperand& A, int M, int N, int K, Epilogue& E, bool has_ws, 
     if (p.family == GEMM_GLDS) { plan_glds(pb, ph, p); return GL_OK; }
     if (p.family == GEMM_HALO) { plan_halo(pb, ph, p); return GL_OK; }
     if (p.family == GEMM_WIDE) { plan_wide(pb, ph, p); return GL_OK; }
+    if (p.family == GEMM_CONV8) {
+        if (!gemm_conv8_supported(A, M, N, K, E)) return set_error(GL_ERR_UNSUPPORTED, "conv3x3: A_CONV8 without gemm_conv8_supported()");
+        int bn, splits;
+        plan_conv8_choice(ph, bn, splits);
+        plan_conv8_fill(pb, bn, splits, gemm_knobs().force_grid, p);
+        return GL_OK;
+    }
     const bool use_u = p.family == GEMM_U;
     GemmCand pick;
     if (forced_choice(pb, use_u, pick)) return gemm_plan_tile(pb, use_u, pick, p);
@@ -486,6 +569,20 @@ int gemm_plan(const AOperand& A, int M, int N, int K, Epilogue& E, bool has_ws, 
         }
     }
     return gemm_plan_tile(pb, use_u, pick, p);
+}
+
+int gemm_conv8_plan(const AOperand& A, int M, int N, int K, Epilogue& E, bool has_ws, size_t ws_bytes, int bn, int splits, int grid_cap, GemmPlan& p) {
+    if (A.mode != A_CONV8) return set_error(GL_ERR_ARG, "gemm_conv8_plan: the operand is not A_CONV8");
+    GL_TRY(gemm_validate(A, M, N, K, E));
+    const int chunks = (A.C0 + A.C1) / 64;
+    if ((bn != 64 && bn != 80) || N % bn || splits < 1 || splits > chunks || cdiv(chunks, cdiv(chunks, splits)) != splits || grid_cap < 0)
+        return set_error(GL_ERR_ARG, "conv8: column tile %d / %d splits of %d chunks / cap %d (tile 64 | 80 dividing N, every part with a chunk, cap >= 0)", bn, splits, chunks, grid_cap);
+    if (splits > 1 && (!has_ws || (size_t)splits * M * N * sizeof(float) > ws_bytes))
+        return set_error(GL_ERR_ARG, "conv8: %d slabs of %d x %d do not fit the workspace", splits, M, N);
+    const GemmProblem pb{A, M, N, K, E, has_ws, ws_bytes};
+    p = GemmPlan{GEMM_CONV8, 0, 0, A.mode};
+    plan_conv8_fill(pb, bn, splits, grid_cap, p);
+    return GL_OK;
 }
 
 }  // namespace gl

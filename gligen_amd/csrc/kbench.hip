@@ -477,6 +477,24 @@ int main(int argc, char** argv) {
                 } else {
                     us = time_us(relaunch, reps, s);
                 }
+            } else if (gemm_conv8_supported(A, M, Cout, K, E)) {
+                // The 8 x 8 level: the shape's own line is the launcher's choice for A_CONV3 (gemm_u_kernel), the CONV8 line behind it
+                // conv8_kernel (gemm.h A_CONV8, what the engine launches) on the same weights, both with their reduce pass; outputs compared
+                AOperand A8 = A;
+                A8.mode = A_CONV8;
+                Epilogue E8 = E;
+                if (!C1) E8.out = a1;
+                auto conv8 = [=] { GC(gemm_launch(A8, w, M, Cout, K, E8, cur_s == s ? ws : ws2, ws_bytes, cur_s)); };
+                const float us8 = time_us(conv8, reps, s);
+                int ptm, ptn, psp;
+                gemm_last_cfg(&ptm, &ptn, &psp);
+                us = time_us(relaunch, reps, s);
+                float d = 0.f, m = 0.f;
+                if (!C1) maxdiff(a2, a1, (size_t)M * Cout, s, &d, &m);
+                const bool ok = d <= 0.02f * m + 1e-6f;
+                if (!ok) ++n_bad;
+                printf("CONV8  %-51s %9.1f %9.1f  conv8_kernel<%d>/%d (%.2fx of gemm_u_kernel's %.1f us) maxdiff %g of %g %s\n", line, us8, flop / us8 * 1e-6,
+                       ptn * 16, psp, us8 / us, us, d, m, ok ? "ok" : "MISMATCH");
             } else {
                 us = time_us(relaunch, reps, s);
             }

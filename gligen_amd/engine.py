@@ -919,6 +919,29 @@ class Engine:
         out = [{f: (getattr(r, f).decode() if f == "kernel" else getattr(r, f)) for f, _ in GemmPlanRecord._fields_} for r in recs[:n.value]]
         return out, total.value
 
+    # ---- conv8_kernel by name (include/gligen_amd_conv8.h)
+    def conv8_force_knobs(self, on=1, bn=0, splits=0) -> None:
+        """gl_conv8_force_knobs: the 8 x 8 level's stride-1 convs on conv8_kernel or not, their column tile and K split (0: shipped / model)."""
+        check(self.lib.gl_conv8_force_knobs(int(on), int(bn), int(splits)))
+
+    def op_conv8x8(self, x0, w, out, bn, splits, *, x1=None, bias=None, bias2=None, rows_per_b=64, res=None, act=0, slabs=None, grid_cap=0,
+                   B=None, ldo=None):
+        """gl_op_conv8x8 on the caller's tensors: x0 [B][8][8][C0] (x1 [..][C1]) bf16, w fp32 OIHW [N][C0 + C1][3][3], out [B 64][ldo] bf16
+        or fp32 (by its dtype; it may be a view into a larger guarded buffer), slabs fp32 with room for splits x B 64 x N values."""
+        from ._lib import Conv8Args
+        a = Conv8Args()
+        a.struct_size = C.sizeof(Conv8Args)
+        a.x0 = _ptr(x0); a.x1 = _ptr(x1)
+        a.C0 = x0.shape[-1]; a.C1 = 0 if x1 is None else x1.shape[-1]
+        a.B = x0.shape[0] if B is None else B
+        a.H = a.W = 8; a.N = w.shape[0]; a.stride = 1; a.ups = 0; a.pad_lo = 1
+        a.w = _ptr(w); a.bias = _ptr(bias); a.bias2 = _ptr(bias2); a.bias2_ld = a.N; a.rows_per_b = rows_per_b
+        a.res = _ptr(res); a.ldres = a.N; a.act = act; a.out_f32 = int(out.dtype == torch.float32)
+        a.out = _ptr(out); a.ldo = a.N if ldo is None else ldo
+        a.bn = bn; a.splits = splits; a.grid_cap = grid_cap
+        a.slabs = _ptr(slabs); a.slab_bytes = 0 if slabs is None else slabs.numel() * 4
+        check(self.lib.gl_op_conv8x8(self._ctx, C.byref(a), _stream(self.device)))
+
     def ff_rows_policy_report(self) -> str:
         buf = C.create_string_buffer(4096)
         check(self.lib.gl_ff_rows_policy_report(buf, 4096))

@@ -30,14 +30,14 @@ int gl_gemm_force_clear(void);
 
 typedef struct gl_gemm_plan_record {
     char kernel[96];      /* kernel name with template arguments, " + splitk_reduce_kernel" behind a split launch */
-    int family;           /* 0 gemm_glds_kernel, 1 gemm_p_kernel, 2 gemm_u_kernel, 3 conv_halo_kernel, 4 gemm_wide_kernel */
+    int family;           /* 0 gemm_glds_kernel, 1 gemm_p_kernel, 2 gemm_u_kernel, 3 conv_halo_kernel, 4 gemm_wide_kernel, 5 conv8_kernel */
     int M, N, K;
-    int tm, tn;           /* tile in units of 32 (halo / wide: tm = 8) */
+    int tm, tn;           /* tile in units of 32 (halo / wide: tm = 8; conv8_kernel: tm = 8, tn in units of 16) */
     int splits;
     int grid;             /* workgroups launched (gemm_glds_kernel: tiles, times splits in z) */
     int n_items;          /* work items: tiles x splits (gemm_glds_kernel: tiles) */
     int box, rm, rz;      /* p / u: XCD partition (box < 0: linear ranges; else lgm | lgn << 4, rows and splits per box); else 0 */
-    int units_per_split;  /* K tiles of 64 per split; conv_halo_kernel: chunks of 64 channels per split */
+    int units_per_split;  /* K tiles of 64 per split; conv_halo_kernel, conv8_kernel: chunks of 64 channels per split */
     int xcd;              /* gemm_wide_kernel: item order (1: contiguous ranges per XCD); else 0 */
 } gl_gemm_plan_record;
 
